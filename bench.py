@@ -2,13 +2,17 @@
 """Headline benchmark: real-time factor of the RVC hot path (IVF retrieval + NSF-HiFi-GAN decode)
 on 10 s clips, v2 / 48 kHz, synthetic data, one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one pass of the hot path over one batch of B clips per rank: 599 HuBERT-shaped queries per
 clip through search(k=8)+blend against the index, then the generator on T=1198 frames (what a 10 s
 clip costs inside the pipeline with x_pad=1).  Inputs are resident in HBM before
 the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes its outputs (``--dump-outputs DIR``) and prints the headline line.
+Everything else the line can carry -- the repeat loops, the roofline and whole-infer legs, the CPU and stock PyTorch-ROCm
+baselines, the batch64 / stream / bf16 legs -- runs only with ``--full`` (each still switchable off by its ``--no-*`` option).
 
 What is imported from ``oracle/`` and why: ``oracle.synth`` / the config dataclasses only GENERATE the seeded synthetic
 weights, features, f0 and index (no checkpoints or datasets exist offline); nothing under ``oracle/`` executes inside a
@@ -42,7 +46,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
-    p.add_argument("--repeats", type=int, default=10, help="extra repetitions of the K-step loop for the median / spread report")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline, run every other leg of the line: repeats, roofline, whole infer, CPU / stock PyTorch-ROCm "
+                        "baselines, batch64 / stream / bf16 (each still switchable off by its --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    p.add_argument("--repeats", type=int, default=10, help="(--full) extra repetitions of the K-step loop for the median / spread report")
     p.add_argument("--batch", type=int, default=None, help="clips per rank per step (default 1 = BASELINE configs[1]; 64 = configs[2])")
     p.add_argument("--config", type=int, default=None, choices=[1, 2, 3],
                    help="BASELINE configs[N] preset: 1 = one clip, 10000x768 index; 2 = 64 clips, one GPU; 3 = 64 clips PER RANK against a "
@@ -61,7 +70,7 @@ def parse():
     p.add_argument("--no-gpu-torch-baseline", action="store_true")
     p.add_argument("--torch-gpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--no-roofline", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the batch64 / stream / bf16 objects of the default N=1 line")
+    p.add_argument("--no-extra", action="store_true", help="skip the batch64 / stream / bf16 objects of the --full N=1 line")
     p.add_argument("--e2e", action="store_true",
                    help="end-to-end Pipeline.convert_files with HuBERT / RMVPE architecture proxies on PyTorch-ROCm: wall per clip and its split, 1 and N files")
     p.add_argument("--e2e-files", type=int, default=64)
@@ -77,8 +86,9 @@ def parse():
 
 def ensure_world(a):
     """``--gpus N`` MEANS N ranks.  Under a launcher (WORLD_SIZE set) the two must agree; without one and N > 1 this process
-    replaces itself with ``python -m torch.distributed.run --nproc-per-node N ... bench.py <same args>`` (one rank per GPU,
-    rendezvous on 127.0.0.1); with fewer than N GPUs visible it exits non-zero.  It never silently measures one GPU."""
+    runs ``python -m torch.distributed.run --nproc-per-node N ... bench.py <same args>`` as a fresh child (one rank per GPU,
+    rendezvous on 127.0.0.1) and exits with its status; with fewer than N GPUs visible it exits non-zero.  It never silently
+    measures one GPU."""
     ws = os.environ.get("WORLD_SIZE")
     if ws is not None:
         if int(ws) != a.gpus:
@@ -95,7 +105,11 @@ def ensure_world(a):
     argv = torchrun_argv(os.path.abspath(__file__), sys.argv[1:], a.gpus)
     print("[bench] self-launching %d ranks: %s" % (a.gpus, " ".join(argv)), file=sys.stderr)
     sys.stderr.flush()
-    os.execv(argv[0], argv)
+    import subprocess
+
+    # a child process, not exec: this one may already have opened the GPU runtime (device_count above)
+    rc = subprocess.run(argv).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)
 
 
 def dist_selftest(a):
@@ -794,6 +808,22 @@ def emit(line: dict) -> None:
     out.flush()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``--dump-outputs``: each array as ``path/<name>.npy`` in float32, at most DUMP_MAX_BYTES in all.  An array larger than its
+    even share of that budget is stored as a fixed sample of its flattened elements: the sorted indices that
+    ``np.random.default_rng(0).choice(n, share, replace=False)`` draws, which depend on nothing but the array's size."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) // 4
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        if x.size > share:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
 def _list_major_bytes(sizes, asg, d, ms_per_search):
     """What the list-major launches move for THIS assignment of queries to lists (host arithmetic, outside every timed region): a work
     item = (list, 32 sorted queries, 32 rows) stages its 32 query rows and its 32 list rows, so a list's rows are read once per
@@ -817,7 +847,7 @@ def main():
     if a.torch_gpu_baseline_worker:
         return torch_gpu_baseline_worker(a)
     if not a.stream and not a.e2e:
-        ensure_world(a)  # may replace this process with the N-rank launcher (before fd 1 is touched)
+        ensure_world(a)  # may run the N-rank launcher as a child and exit with its status (before fd 1 is touched)
     if _REAL_STDOUT is None:
         # libraries write banners to fd 1 (RCCL prints its version block at the first communicator): keep stdout for the JSON line
         sys.stdout.flush()
@@ -959,10 +989,16 @@ def main():
         dt = float(tt.item())
     # (timing ablations -- RVCMI_DBG / RVCMI_POST_DBG, wrong results by construction -- set RVCMI_BENCH_ABLATION=1; such a line is never a result)
     assert os.environ.get("RVCMI_BENCH_ABLATION") == "1" or torch.isfinite(out_holder["o"]).all(), "non-finite generator output"
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the waveform and (hot path) the blended features
+        outs = {"audio": out_holder["o"]}
+        if front is None:
+            outs["blended_features"] = feats
+        dump_outputs(a.dump_outputs, outs)
 
     # ---- stability report: R more repetitions of the same K-step loop (same step, same graph), per-rank wall clock ----
     rep_stats = None
-    if a.repeats > 0:
+    if a.full and a.repeats > 0:
         rt = []
         for _ in range(a.repeats):
             torch.cuda.synchronize()
@@ -983,7 +1019,7 @@ def main():
 
     # ---- roofline leg: the same step, eager, every kernel bracketed by HIP events --------------
     roof = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         gen.profile(True)
         index.profile(True)
         if front is not None:
@@ -1105,7 +1141,7 @@ def main():
 
     # ---- whole net_g.infer leg: retrieval -> x2 frames -> enc_p -> z_p -> flow^-1 -> decode, one graph ----
     whole = None
-    if rank == 0 and not a.no_roofline and not a.whole and a.index_d == 768 and a.operand != "fp32":
+    if rank == 0 and a.full and not a.no_roofline and not a.whole and a.index_d == 768 and a.operand != "fp32":
         from oracle.front_oracle import FrontConfig
 
         fcfg = FrontConfig()
@@ -1153,14 +1189,14 @@ def main():
 
     cpu = None
     oracle_out = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and idx is not None:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and idx is not None:
         cpu = cpu_baseline(cfg, w, idx, phone, z, f0, g, noise, a.index_rate)
         oracle_out = cpu.pop("_oracle_out", None)
 
     # ---- the other BASELINE configurations under the same clock (N = 1, default line only): configs[2] = batch64, configs[4] = stream,
     #      configs[1] as written = bf16 operands + what each operand type costs in parity ----
     extra = {}
-    if rank == 0 and world == 1 and not a.no_extra and not a.whole and B == 1 and a.operand == "fp16" and T == T_CLIP and a.index_d == 768:
+    if rank == 0 and world == 1 and a.full and not a.no_extra and not a.whole and B == 1 and a.operand == "fp16" and T == T_CLIP and a.index_d == 768:
         for name, fn in (("bf16", lambda: leg_operands(a, dev, cfg, w, index, phone_d, zd, f0d, gd, nd, out_holder["o"], oracle_out)),
                          ("batch64", lambda: leg_batch64(a, dev, cfg, w, index)),
                          ("stream", lambda: (lambda l_: {"what": l_["config"]["workload"] + "; v1/40k generator (configs/v1/40k.json + v2 encoder), 20 warm-ups + 200 chunks, hipGraph replay",
@@ -1173,7 +1209,7 @@ def main():
             except Exception as e:  # noqa
                 extra[name] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
     tgpu = None
-    if rank == 0 and world == 1 and not a.no_gpu_torch_baseline and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_gpu_torch_baseline and not a.no_cpu_baseline:
         tgpu = torch_gpu_baseline(a)
 
     if rank == 0:

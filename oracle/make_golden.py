@@ -9,6 +9,7 @@ noise + outputs are stored.  Weights are NOT stored (63 MB): tests regenerate th
 oracle/synth.py and verify the sha256 recorded here.
 
     python -m oracle.make_golden            # regenerate every fixture
+    GOLDEN_ONLY_STRUCTURE=1 python -m oracle.make_golden   # only tests/golden/reference_structure.json
 """
 from __future__ import annotations
 
@@ -575,6 +576,84 @@ def mute_case(name: str = "mute_hubert"):
     print("%-28s 149 real HuBERT rows x {256, 768}  (%d KB)" % (name, os.path.getsize(os.path.join(GOLD, name + ".npz")) // 1024))
 
 
+def _layers(net):
+    """The geometry the introspection helpers read, per conv / linear layer (weight norm removed), and the state dict's shapes."""
+    layers = {}
+    for n, m in net.named_modules():
+        if isinstance(m, (torch.nn.Conv1d, torch.nn.ConvTranspose1d, torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
+            layers[n] = {"type": type(m).__name__, "in": m.in_channels, "out": m.out_channels, "kernel": list(m.kernel_size),
+                         "stride": list(m.stride), "dilation": list(m.dilation)}
+        elif isinstance(m, torch.nn.Linear):
+            layers[n] = {"type": "Linear", "in": m.in_features, "out": m.out_features}
+    return layers
+
+
+def _weight_normed(net):
+    return sorted(n for n, m in net.named_modules() if hasattr(m, "parametrizations") or hasattr(m, "weight_g"))
+
+
+def structure_case(name: str = "reference_structure"):
+    """The reference's module STRUCTURE, as data, for the tests that check the introspection helpers (config_from_reference,
+    front_config_from_reference, FrontHIP.from_reference's weight-norm guard) and the RMVPE architecture proxy without a reference
+    checkout: layer geometry, state-dict shapes, which layers carry weight norm, the scalars the helpers read, and E2E's
+    parameter / FLOP counts.  No source and no weights are stored."""
+    import json
+
+    from torch.utils.flop_counter import FlopCounterMode
+
+    sys.path.insert(0, REF)
+    if "numba" not in sys.modules:
+        try:
+            import numba  # noqa: F401
+        except ImportError:  # rvc/f0 imports it for a decorator only
+            stub = type(sys)("numba")
+            stub.jit = stub.njit = lambda *a, **k: (lambda f: f)
+            sys.modules["numba"] = stub
+    from rvc.f0.e2e import E2E
+    from rvc.layers.nsf import NSFGenerator
+    from rvc.layers.synthesizers import SynthesizerTrnMsNSFsid
+
+    from rvc_amd.front import front_config_from_reference
+    from rvc_amd.nsf import config_from_reference
+
+    out = {}
+    cfg = CONFIGS["v1_40k"]
+    net = NSFGenerator(cfg.inter_channels, "1", cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes, cfg.upsample_rates,
+                       cfg.upsample_initial_channel, cfg.upsample_kernel_sizes, cfg.gin_channels, cfg.sr)
+    wn, sd_wn = _weight_normed(net), sorted(net.state_dict())
+    net.remove_weight_norm()
+    out["nsf_v1_40k"] = {"weight_norm_layers": wn, "state_dict_keys_with_weight_norm": sd_wn,
+                         "state_dict": {k: list(v.shape) for k, v in net.state_dict().items()}, "layers": _layers(net),
+                         "num_kernels": int(net.num_kernels), "num_upsamples": int(net.num_upsamples), "upp": int(net.upp),
+                         "sampling_rate": int(net.m_source.l_sin_gen.sampling_rate), "config": config_from_reference(net)}
+    cl = [1025, 32, 192, 192, 768, 2, 6, 3, 0, "1", [3, 7, 11], [[1, 3, 5]] * 3, [10, 10, 2, 2], 512, [16, 16, 4, 4], 109, 256, 40000]
+    syn = SynthesizerTrnMsNSFsid(*cl, encoder_dim=256, use_f0=True)
+    front_keys = lambda sd: {k: list(v.shape) for k, v in sd.items() if k.startswith(("enc_p.", "flow."))}
+    out["synth_v1_40k_enc256"] = {"config_list": cl, "weight_norm_layers": [n for n in _weight_normed(syn) if n.startswith(("enc_p.", "flow."))],
+                                  "front_state_dict_with_weight_norm": front_keys(syn.state_dict()),
+                                  "front_config": front_config_from_reference(syn)}
+    syn.remove_weight_norm()
+    out["synth_v1_40k_enc256"]["front_state_dict"] = front_keys(syn.state_dict())
+    e2e = E2E(4, 1, (2, 2)).eval()
+    with FlopCounterMode(display=False) as fc, torch.no_grad():
+        y = e2e(torch.randn(1, 128, 64))
+    g = e2e.fc[0].gru
+    per_type = {}
+    for m in e2e.modules():
+        n_ = sum(p.numel() for p in m.parameters(recurse=False))
+        if n_:
+            per_type[type(m).__name__] = per_type.get(type(m).__name__, 0) + n_
+    out["rmvpe_e2e_4_1_2_2"] = {"parameters": sum(p.numel() for p in e2e.parameters()), "parameters_by_type": per_type,
+                                "flops_mel_1x128x64": int(fc.get_total_flops()), "output_shape_mel_1x128x64": list(y.shape),
+                                "gru": {"path": "fc.0.gru", "input_size": g.input_size, "hidden_size": g.hidden_size, "num_layers": g.num_layers,
+                                        "bidirectional": g.bidirectional, "batch_first": g.batch_first}}
+    sys.path.remove(REF)
+    with open(os.path.join(GOLD, name + ".json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("%-28s reference module structure  (%d KB)" % (name, os.path.getsize(os.path.join(GOLD, name + ".json")) // 1024))
+
+
 def main_front():
     glue_case()
     front_case("front_v2_B2_T50", 2, 50, [50, 43])
@@ -587,6 +666,8 @@ def main_front():
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
+    if os.environ.get("GOLDEN_ONLY_STRUCTURE"):
+        return structure_case()
     if os.environ.get("GOLDEN_ONLY_FULL"):
         return dec_full_case()
     if os.environ.get("GOLDEN_ONLY_MUTE"):
@@ -597,6 +678,7 @@ def main():
         pipeline_case()
         pipeline_webui_case()
         return front_full_case()
+    structure_case()
     mute_case()
     main_front()
     if os.environ.get("GOLDEN_ONLY_FRONT"):

@@ -275,26 +275,72 @@ def test_ranks_agree_detects_a_one_ulp_difference_gloo():
     mp.spawn(_agree_worker, args=(2, _free_port()), nprocs=2, join=True)
 
 
-def test_reference_module_introspection_when_reference_is_present():
-    """config_from_reference / _plain_state_dict against the REAL reference classes (skipped on the GPU box)."""
-    ref = os.environ.get("RVC_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref, "rvc")):
-        pytest.skip("reference checkout not mounted")
+def _reference_structure():
+    """tests/golden/reference_structure.json: the reference's module structure as data (oracle/make_golden.py, structure_case)."""
+    import json
+
+    with open(os.path.join(ROOT, "tests", "golden", "reference_structure.json")) as f:
+        return json.load(f)
+
+
+def _skeleton_import(modname):
+    """A module of tests/skeleton (the stand-in of an RVC checkout: the reference's names and shapes, no compute)."""
+    import importlib
     import sys
 
-    sys.path.insert(0, ref)
-    from rvc.layers.nsf import NSFGenerator
+    skel = os.path.join(ROOT, "tests", "skeleton")
+    for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "infer")]:
+        del sys.modules[m]
+    sys.path.insert(0, skel)
+    try:
+        return importlib.import_module(modname)
+    finally:
+        sys.path.remove(skel)
+        for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "infer")]:
+            del sys.modules[m]
 
+
+def _shapes(sd):
+    return {k: list(v.shape) for k, v in sd.items()}
+
+
+def _attach_weight_norm(net, names):
+    from torch.nn.utils.parametrizations import weight_norm
+
+    for n in names:
+        weight_norm(net.get_submodule(n))
+
+
+def _remove_weight_norm(net, names):
+    from torch.nn.utils.parametrize import remove_parametrizations
+
+    for n in names:
+        remove_parametrizations(net.get_submodule(n), "weight")
+
+
+def test_reference_module_introspection_when_reference_is_present():
+    """config_from_reference / _plain_state_dict on a module with the REFERENCE's structure: the skeleton's NSFGenerator, checked
+    layer for layer (geometry, state-dict shapes, the scalars the helper reads) against the reference's own module as recorded in
+    tests/golden/reference_structure.json, with weight norm attached to the same layers as the reference attaches it."""
+    from oracle.make_golden import _layers
     from oracle.nsf_oracle import CONFIGS
     from rvc_amd.nsf import _plain_state_dict, config_from_reference
 
+    ref = _reference_structure()["nsf_v1_40k"]
+    NSFGenerator = _skeleton_import("rvc.layers.nsf").NSFGenerator
     cfg = CONFIGS["v1_40k"]
     net = NSFGenerator(cfg.inter_channels, "1", cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes, cfg.upsample_rates,
                        cfg.upsample_initial_channel, cfg.upsample_kernel_sizes, cfg.gin_channels, cfg.sr)
+    assert _layers(net) == ref["layers"] and _shapes(net.state_dict()) == ref["state_dict"]
+    assert (net.num_kernels, net.num_upsamples, net.upp, net.m_source.l_sin_gen.sampling_rate) == (
+        ref["num_kernels"], ref["num_upsamples"], ref["upp"], ref["sampling_rate"])
+    _attach_weight_norm(net, ref["weight_norm_layers"])
+    assert sorted(net.state_dict()) == ref["state_dict_keys_with_weight_norm"]
     with pytest.raises(ValueError):
         _plain_state_dict(net)  # weight norm still attached
-    net.remove_weight_norm()
+    _remove_weight_norm(net, ref["weight_norm_layers"])
     got = config_from_reference(net)
+    assert got == ref["config"]
     for k in ("inter_channels", "upsample_rates", "upsample_kernel_sizes", "upsample_initial_channel", "gin_channels", "sr",
               "resblock_kernel_sizes", "resblock_dilation_sizes", "use_f0"):
         assert got[k] == getattr(cfg, k), k
@@ -303,23 +349,25 @@ def test_reference_module_introspection_when_reference_is_present():
 
 
 def test_front_introspection_and_infer_patch_when_reference_is_present():
-    """front_config_from_reference against the REAL reference synthesizer (skipped on the GPU box)."""
-    ref = os.environ.get("RVC_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref, "rvc")):
-        pytest.skip("reference checkout not mounted")
-    import sys
-
-    sys.path.insert(0, ref)
-    from rvc.layers.synthesizers import SynthesizerTrnMsNSFsid
-
+    """front_config_from_reference / FrontHIP.from_reference's weight-norm guard on a synthesizer with the REFERENCE's structure:
+    the skeleton's SynthesizerTrnMsNSFsid, its enc_p / flow checked against the reference's own as recorded in
+    tests/golden/reference_structure.json, with weight norm attached to the same layers as the reference attaches it."""
     from oracle.front_oracle import FrontConfig
 
+    ref = _reference_structure()["synth_v1_40k_enc256"]
+    SynthesizerTrnMsNSFsid = _skeleton_import("rvc.layers.synthesizers").SynthesizerTrnMsNSFsid
     cl = [1025, 32, 192, 192, 768, 2, 6, 3, 0, "1", [3, 7, 11], [[1, 3, 5]] * 3, [10, 10, 2, 2], 512, [16, 16, 4, 4], 109, 256, 40000]
+    assert cl == ref["config_list"]
     net = SynthesizerTrnMsNSFsid(*cl, encoder_dim=256, use_f0=True)
+    front = lambda sd: {k: v for k, v in _shapes(sd).items() if k.startswith(("enc_p.", "flow."))}
+    assert front(net.state_dict()) == ref["front_state_dict"]
     got = rvc_amd.front_config_from_reference(net)
+    assert got == ref["front_config"]
     want = vars(FrontConfig(in_channels=256))
     for k, v in got.items():
         assert want[k] == v, k
+    _attach_weight_norm(net, ref["weight_norm_layers"])
+    assert front(net.state_dict()) == ref["front_state_dict_with_weight_norm"]
     with pytest.raises(ValueError):
         rvc_amd.FrontHIP.from_reference(net, device="cuda:0")  # weight norm still attached
 
@@ -368,9 +416,8 @@ def test_install_rebinds_names_without_editing_the_callers():
     import sys
 
     skel = os.path.join(os.path.dirname(os.path.abspath(__file__)), "skeleton")
-    if os.path.isdir(os.path.join(os.environ.get("RVC_REFERENCE", "/root/reference"), "rvc")):
-        for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "infer")]:
-            del sys.modules[m]  # a previous test imported the real reference package
+    for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "infer")]:
+        del sys.modules[m]  # a previous test imported another rvc / infer package
     had_faiss = sys.modules.get("faiss")
     sys.path.insert(0, skel)
     try:
@@ -592,42 +639,42 @@ def test_index_cache_of_the_rebound_pipeline(monkeypatch, tmp_path):
 
 
 def test_e2e_rmvpe_proxy_has_the_reference_architecture():
-    """``tools/e2e_proxies.py`` (the stand-in ``bench.py --e2e`` times for the RMVPE network): same parameter count and the same FLOPs as the
-    reference's own ``E2E(4, 1, (2, 2))`` (rvc/f0/e2e.py, rvc/f0/models.py), output [1, T, 360] in (0, 1).  Skipped on the GPU box."""
-    ref = os.environ.get("RVC_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref, "rvc")):
-        pytest.skip("reference checkout not mounted")
+    """``tools/e2e_proxies.py`` (the stand-in ``bench.py --e2e`` times for the RMVPE network): same parameter count (per layer type too)
+    and the same FLOPs as the reference's own ``E2E(4, 1, (2, 2))`` (rvc/f0/e2e.py, rvc/f0/models.py) as recorded in
+    tests/golden/reference_structure.json, output [1, T, 360] in (0, 1)."""
     import sys
-    import types
 
     from torch.utils.flop_counter import FlopCounterMode
 
+    ref = _reference_structure()["rmvpe_e2e_4_1_2_2"]
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    sys.path.insert(0, ref)
-    sys.modules.setdefault("numba", types.SimpleNamespace(jit=lambda *a, **k: (lambda f: f), njit=lambda *a, **k: (lambda f: f)))
     try:
         from e2e_proxies import _SalienceNet
-        from rvc.f0.e2e import E2E
 
-        theirs, ours = E2E(4, 1, (2, 2)).eval(), _SalienceNet().eval()
-        assert sum(p.numel() for p in ours.parameters()) == sum(p.numel() for p in theirs.parameters()) == 90423165
+        ours = _SalienceNet().eval()
+        assert sum(p.numel() for p in ours.parameters()) == ref["parameters"] == 90423165
+        per_type = {}
+        for m in ours.modules():
+            n_ = sum(p.numel() for p in m.parameters(recurse=False))
+            if n_:
+                per_type[type(m).__name__] = per_type.get(type(m).__name__, 0) + n_
+        assert per_type == ref["parameters_by_type"]
         mel = torch.randn(1, 128, 64)
-        fl = []
-        for m in (theirs, ours):
-            with FlopCounterMode(display=False) as fc, torch.no_grad():
-                y = m(mel)
-            fl.append(fc.get_total_flops())
-            assert y.shape == (1, 64, 360) and float(y.min()) > 0 and float(y.max()) < 1
-        assert fl[0] == fl[1]
-        # the one layer that runs on csrc/gru.hip: the reference's own E2E holds it where accelerate_rmvpe looks (fc[0].gru), in a shape GRUHIP
+        with FlopCounterMode(display=False) as fc, torch.no_grad():
+            y = ours(mel)
+        assert fc.get_total_flops() == ref["flops_mel_1x128x64"]
+        assert list(y.shape) == ref["output_shape_mel_1x128x64"] == [1, 64, 360] and float(y.min()) > 0 and float(y.max()) < 1
+        # the one layer that runs on csrc/gru.hip: the reference's E2E holds it where accelerate_rmvpe looks (fc[0].gru), in a shape GRUHIP
         # supports; on a CPU model nothing is swapped
         from rvc_amd.gru import accelerate_rmvpe, supports
 
-        g = theirs.fc[0].gru
-        assert supports(g) and (g.input_size, g.hidden_size) == (384, 256) and supports(ours.gru)
-        assert accelerate_rmvpe(theirs) == 0 and theirs.fc[0].gru is g
+        gd = ref["gru"]
+        g = torch.nn.GRU(gd["input_size"], gd["hidden_size"], num_layers=gd["num_layers"], batch_first=gd["batch_first"],
+                         bidirectional=gd["bidirectional"])
+        assert gd["path"] == "fc.0.gru" and supports(g) and (g.input_size, g.hidden_size) == (384, 256) and supports(ours.gru)
+        g0 = ours.gru
+        assert accelerate_rmvpe(ours) == 0 and ours.gru is g0
     finally:
-        sys.path.remove(ref)
         sys.path.remove(os.path.join(ROOT, "tools"))
-        for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "e2e_proxies")]:
+        for m in [m for m in sys.modules if m.split(".")[0] == "e2e_proxies"]:
             del sys.modules[m]

@@ -3,16 +3,17 @@
 # nothing).  usage: tools/gpu_ab.sh NAME "ENV_A" "ENV_B" [rounds]   e.g.  tools/gpu_ab.sh y16 "RVCMI_Y_F16=0" "RVCMI_Y_F16=1" 3
 # Prints per run: ms_per_step (K timed steps), the repeat median, and the per-kernel event times of the eager profiling pass.
 name=$1; ea=$2; eb=$3; rounds=${4:-3}
-mkdir -p gpurun_out
+export BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p $BENCH_OUT
 for r in $(seq 1 $rounds); do
   for v in A B; do
     if [ $v = A ]; then e="$ea"; else e="$eb"; fi
-    env $e python bench.py --no-cpu-baseline --no-gpu-torch-baseline --no-extra --repeats 5 > gpurun_out/ab_${name}_${v}${r}.json 2> gpurun_out/ab_${name}_${v}${r}.err
+    env $e python bench.py --full --no-cpu-baseline --no-gpu-torch-baseline --no-extra --repeats 5 > $BENCH_OUT/ab_${name}_${v}${r}.json 2> $BENCH_OUT/ab_${name}_${v}${r}.err
     python - "$name" $v $r "$e" <<'PY'
-import json, sys
+import json, os, sys
 name, v, r, e = sys.argv[1:5]
 try:
-    d = json.load(open("gpurun_out/ab_%s_%s%s.json" % (name, v, r)))
+    d = json.load(open(os.path.join(os.environ["BENCH_OUT"], "ab_%s_%s%s.json") % (name, v, r)))
 except Exception as ex:
     print(name, v, r, "FAILED", ex); sys.exit(0)
 k = {s["name"]: round(s["ms"], 4) for s in d.get("kernels", [])} if "kernels" in d else {}

@@ -2,7 +2,7 @@
 # Launcher penalty: the same 1-GPU step single-process vs under torch.distributed.run at world 1 (RCCL
 # initialised, one broadcast of the index), interleaved on ONE lease.  Prints ms_per_step, repeat median and the dominant kernel's time.
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-gpu-torch-baseline --repeats 5"
+B="--full --no-cpu-baseline --no-gpu-torch-baseline --repeats 5"
 show() { python - "$1" "$2" <<'PY'
 import json, sys
 try:
