@@ -80,8 +80,8 @@ struct rvcmi_nsf {
     size_t ws_bytes = 0;
     Profiler prof;
     // dev / test options (common.hpp Options): RB_STREAM (absent = auto, 1 = streaming resblock kernels whenever supported, 0 = never),
-    // NO_RBFULL, NO_RB_SPLIT, RB_ORDER (1 = resblock-major pair launches), UPS_NJ, NB (weight-ring depth of k_rb_full), DBG (timing-ablation bit
-    // mask: results are WRONG when non-zero) and the rb_stream keys (rb_stream.hpp).  Read from RVCMI_<KEY> once, in rvcmi_nsf_create.
+    // NO_RB_SPLIT, Y_F16, X0_F16, X0_F16_NOSTREAM, POST_DMA, POST_DBG, DBG (timing-ablation bit mask: results are WRONG when non-zero) and
+    // the rb_stream keys (rb_stream.hpp).  Read from RVCMI_<KEY> once, in rvcmi_nsf_create.
     rvcmi::Options opt;
 };
 
@@ -99,6 +99,101 @@ static int rb_rows(int C) { return C == 256 ? 32 * RB256_NJ : RB_ROWS; }
 constexpr int RB_SPLIT_MAX_ROWS = 1024;      // C = 256
 constexpr int RB_SPLIT_MAX_ROWS_128 = 4096;  // C = 128 (a chunk's second stage: 3100 rows = 75 pair tiles of 3 x 40 us)
 
+// Weights of upsampling stage i: ups[i], noise_convs[i] and its resblocks.
+static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& wm, int i) {
+    const int op = cfg->operand, C0 = cfg->upsample_initial_channel;
+    s.cin = C0 >> i;
+    s.cout = C0 >> (i + 1);
+    s.u = cfg->upsample_rates[i];
+    s.k = cfg->upsample_kernel_sizes[i];
+    s.pad = (s.k - s.u) / 2;
+    if (s.u > 16) RVCMI_FAIL(RVCMI_ERR_INVALID, "upsample rate %d > 16 unsupported", s.u);
+    if (s.cout < 4 || (s.cout & 3)) RVCMI_FAIL(RVCMI_ERR_INVALID, "stage %d has %d channels", i, s.cout);
+    // The reference requires len(ups) == len(noise_convs): (L-1)*u - 2*pad + k == u*L  <=>  k - 2*pad == u
+    if (s.k - 2 * s.pad != s.u) RVCMI_FAIL(RVCMI_ERR_INVALID, "stage %d: k-u must be even (k=%d,u=%d)", i, s.k, s.u);
+    {  // ups[i]: ConvTranspose1d(cin, cout, k, u, padding=(k-u)//2)   nsf.py:92-102
+        // out[q*u + r] = sum_j x[q + off_r - j] * W[:, :, cm_r + j*u],  c = r + pad, off_r = c / u, cm_r = c % u
+        const rvcmi_tensor& w = wm.get("ups." + std::to_string(i) + ".weight", {s.cin, s.cout, s.k});
+        const rvcmi_tensor& b = wm.get("ups." + std::to_string(i) + ".bias", {s.cout});
+        int nt[16], off[16], cm[16];
+        for (int r = 0; r < s.u; ++r) {
+            const int c = r + s.pad;
+            off[r] = c / s.u;
+            cm[r] = c % s.u;
+            nt[r] = (s.k - cm[r] + s.u - 1) / s.u;
+        }
+        const float* wd = w.data;
+        const int cout = s.cout, k = s.k, u = s.u;
+        std::vector<int> cmv(cm, cm + s.u);
+        build_conv(s.up, s.cin, s.cout, s.u, nt, off, -1,
+                   [=](int co, int ci, int p, int tap) { return wd[((size_t)ci * cout + co) * k + cmv[p] + tap * u]; },
+                   b.data, op);
+    }
+    if (cfg->use_f0) {  // noise_convs[i]   nsf.py:103-115
+        int sf = 1;
+        for (int j = i + 1; j < cfg->n_ups; ++j) sf *= cfg->upsample_rates[j];
+        const bool last = i + 1 == cfg->n_ups;
+        s.nk = last ? 1 : 2 * sf;
+        s.ns = last ? 1 : sf;
+        s.npad = last ? 0 : sf / 2;
+        const rvcmi_tensor& w = wm.get("noise_convs." + std::to_string(i) + ".weight", {s.cout, 1, s.nk});
+        const rvcmi_tensor& b = wm.get("noise_convs." + std::to_string(i) + ".bias", {s.cout});
+        std::vector<float> wt((size_t)s.nk * s.cout);
+        for (int co = 0; co < s.cout; ++co)
+            for (int j = 0; j < s.nk; ++j) wt[(size_t)j * s.cout + co] = w.data[(size_t)co * s.nk + j];
+        upload(s.noise_w, wt);
+        upload(s.noise_b, std::vector<float>(b.data, b.data + s.cout));
+        if (op != RVCMI_OPERAND_F32 && !last && s.ns % 8 == 0 && s.ns <= 64) {
+            const int cinp = s.ns <= 16 ? 16 : (s.ns <= 32 ? 32 : 64);
+            int nt = 2, off = 0;
+            const float* wd = w.data;
+            const int ns = s.ns, nkk = s.nk;
+            build_conv(s.nz, cinp, s.cout, 1, &nt, &off, 1,
+                       [=](int co, int ci, int, int tap) { return ci < ns ? wd[(size_t)co * nkk + tap * ns + ci] : 0.f; }, b.data, op);
+            s.nz_mfma = true;
+        } else if (op != RVCMI_OPERAND_F32 && s.nk >= 2 && s.nk <= 16 && s.ns % 2 == 0) {
+            const int ctiles = (s.cout + 31) / 32;
+            std::vector<uint16_t> pk((size_t)ctiles * 512, 0);
+            for (int ct = 0; ct < ctiles; ++ct)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int co = ct * 32 + (lane & 31), kk = 8 * (lane >> 5) + e;
+                        if (co < s.cout && kk < s.nk) {
+                            const float v = w.data[(size_t)co * s.nk + kk];
+                            pk[(size_t)ct * 512 + lane * 8 + e] = op == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
+                        }
+                    }
+            s.nz_k1_w.alloc(pk.size() * 2);
+            HIP_CHECK(hipMemcpy(s.nz_k1_w.p, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
+            s.nz_k1 = true;
+        }
+    }
+    s.rb.resize(cfg->n_resblock_kernels);
+    for (int j = 0; j < cfg->n_resblock_kernels; ++j) {  // ResBlock1   residuals.py:19-58
+        const int n = i * cfg->n_resblock_kernels + j;
+        const int k = cfg->resblock_kernel_sizes[j];
+        const int nd = cfg->n_dilations[j];
+        if (nd < 1 || nd > RVCMI_MAX_DIL || !(k & 1)) RVCMI_FAIL(RVCMI_ERR_INVALID, "bad resblock %d", j);
+        s.rb[j].resize(nd);
+        for (int m = 0; m < nd; ++m) {
+            const int d = cfg->resblock_dilation_sizes[j][m];
+            const std::string base = "resblocks." + std::to_string(n);
+            const int C = s.cout;
+            for (int which = 0; which < 2; ++which) {
+                const std::string nm = base + (which ? ".convs2." : ".convs1.") + std::to_string(m);
+                const rvcmi_tensor& w = wm.get(nm + ".weight", {C, C, k});
+                const rvcmi_tensor& b = wm.get(nm + ".bias", {C});
+                const int dil = which ? 1 : d;
+                int nt = k, off = -((k * dil - dil) / 2);  // get_padding, rvc/layers/utils.py:14
+                const float* wd = w.data;
+                ConvLayer& L2 = which ? s.rb[j][m].second : s.rb[j][m].first;
+                build_conv(L2, C, C, 1, &nt, &off, dil,
+                           [=](int co, int ci, int, int tap) { return wd[((size_t)co * C + ci) * k + tap]; }, b.data, op);
+            }
+        }
+    }
+}
+
 static void nsf_create(const rvcmi_nsf_config* cfg, const rvcmi_tensor* weights, int n_weights, int device, int max_B,
                        int max_T, rvcmi_nsf** out) {
     if (!cfg || !out || (!weights && n_weights)) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
@@ -112,7 +207,7 @@ static void nsf_create(const rvcmi_nsf_config* cfg, const rvcmi_tensor* weights,
     rb_stream_prepare();
 
     std::unique_ptr<rvcmi_nsf> h(new rvcmi_nsf());
-    h->opt.load_env({"RB_STREAM", "NO_RBFULL", "NO_RB_SPLIT", "NO_RB_SPLIT128", "RB_ORDER", "UPS_NJ", "UPS_TW", "PRE_OP", "POST_DMA", "POST_DMA_OCC", "POST_DBG", "NB", "DBG", "Y_F16", "X0_F16", "UPS_TR", "UPS_BL", "X0_F16_NOSTREAM", "CONV_KS", "RBF_SMALL"});
+    h->opt.load_env({"RB_STREAM", "NO_RB_SPLIT", "POST_DMA", "POST_DBG", "DBG", "Y_F16", "X0_F16", "X0_F16_NOSTREAM"});
     rb_stream_load_env(h->opt);
     h->cfg = *cfg;
     h->device = device;
@@ -150,99 +245,9 @@ static void nsf_create(const rvcmi_nsf_config* cfg, const rvcmi_tensor* weights,
     size_t S = (size_t)max_T * C0;
     long L = max_T;
     for (int i = 0; i < cfg->n_ups; ++i) {
-        Stage& s = h->stages[i];
-        s.cin = C0 >> i;
-        s.cout = C0 >> (i + 1);
-        s.u = cfg->upsample_rates[i];
-        s.k = cfg->upsample_kernel_sizes[i];
-        s.pad = (s.k - s.u) / 2;
-        if (s.u > 16) RVCMI_FAIL(RVCMI_ERR_INVALID, "upsample rate %d > 16 unsupported", s.u);
-        if (s.cout < 4 || (s.cout & 3)) RVCMI_FAIL(RVCMI_ERR_INVALID, "stage %d has %d channels", i, s.cout);
-        // The reference requires len(ups) == len(noise_convs): (L-1)*u - 2*pad + k == u*L  <=>  k - 2*pad == u
-        if (s.k - 2 * s.pad != s.u) RVCMI_FAIL(RVCMI_ERR_INVALID, "stage %d: k-u must be even (k=%d,u=%d)", i, s.k, s.u);
-        L *= s.u;
-        S = std::max(S, (size_t)L * s.cout);
-        {  // ups[i]: ConvTranspose1d(cin, cout, k, u, padding=(k-u)//2)   nsf.py:92-102
-            // out[q*u + r] = sum_j x[q + off_r - j] * W[:, :, cm_r + j*u],  c = r + pad, off_r = c / u, cm_r = c % u
-            const rvcmi_tensor& w = wm.get("ups." + std::to_string(i) + ".weight", {s.cin, s.cout, s.k});
-            const rvcmi_tensor& b = wm.get("ups." + std::to_string(i) + ".bias", {s.cout});
-            int nt[16], off[16], cm[16];
-            for (int r = 0; r < s.u; ++r) {
-                const int c = r + s.pad;
-                off[r] = c / s.u;
-                cm[r] = c % s.u;
-                nt[r] = (s.k - cm[r] + s.u - 1) / s.u;
-            }
-            const float* wd = w.data;
-            const int cout = s.cout, k = s.k, u = s.u;
-            std::vector<int> cmv(cm, cm + s.u);
-            build_conv(s.up, s.cin, s.cout, s.u, nt, off, -1,
-                       [=](int co, int ci, int p, int tap) { return wd[((size_t)ci * cout + co) * k + cmv[p] + tap * u]; },
-                       b.data, op);
-        }
-        if (cfg->use_f0) {  // noise_convs[i]   nsf.py:103-115
-            int sf = 1;
-            for (int j = i + 1; j < cfg->n_ups; ++j) sf *= cfg->upsample_rates[j];
-            const bool last = i + 1 == cfg->n_ups;
-            s.nk = last ? 1 : 2 * sf;
-            s.ns = last ? 1 : sf;
-            s.npad = last ? 0 : sf / 2;
-            const rvcmi_tensor& w = wm.get("noise_convs." + std::to_string(i) + ".weight", {s.cout, 1, s.nk});
-            const rvcmi_tensor& b = wm.get("noise_convs." + std::to_string(i) + ".bias", {s.cout});
-            std::vector<float> wt((size_t)s.nk * s.cout);
-            for (int co = 0; co < s.cout; ++co)
-                for (int j = 0; j < s.nk; ++j) wt[(size_t)j * s.cout + co] = w.data[(size_t)co * s.nk + j];
-            upload(s.noise_w, wt);
-            upload(s.noise_b, std::vector<float>(b.data, b.data + s.cout));
-            if (op != RVCMI_OPERAND_F32 && !last && s.ns % 8 == 0 && s.ns <= 64) {
-                const int cinp = s.ns <= 16 ? 16 : (s.ns <= 32 ? 32 : 64);
-                int nt = 2, off = 0;
-                const float* wd = w.data;
-                const int ns = s.ns, nkk = s.nk;
-                build_conv(s.nz, cinp, s.cout, 1, &nt, &off, 1,
-                           [=](int co, int ci, int, int tap) { return ci < ns ? wd[(size_t)co * nkk + tap * ns + ci] : 0.f; }, b.data, op);
-                s.nz_mfma = true;
-            } else if (op != RVCMI_OPERAND_F32 && s.nk >= 2 && s.nk <= 16 && s.ns % 2 == 0) {
-                const int ctiles = (s.cout + 31) / 32;
-                std::vector<uint16_t> pk((size_t)ctiles * 512, 0);
-                for (int ct = 0; ct < ctiles; ++ct)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = ct * 32 + (lane & 31), kk = 8 * (lane >> 5) + e;
-                            if (co < s.cout && kk < s.nk) {
-                                const float v = w.data[(size_t)co * s.nk + kk];
-                                pk[(size_t)ct * 512 + lane * 8 + e] = op == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
-                            }
-                        }
-                s.nz_k1_w.alloc(pk.size() * 2);
-                HIP_CHECK(hipMemcpy(s.nz_k1_w.p, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-                s.nz_k1 = true;
-            }
-        }
-        s.rb.resize(cfg->n_resblock_kernels);
-        for (int j = 0; j < cfg->n_resblock_kernels; ++j) {  // ResBlock1   residuals.py:19-58
-            const int n = i * cfg->n_resblock_kernels + j;
-            const int k = cfg->resblock_kernel_sizes[j];
-            const int nd = cfg->n_dilations[j];
-            if (nd < 1 || nd > RVCMI_MAX_DIL || !(k & 1)) RVCMI_FAIL(RVCMI_ERR_INVALID, "bad resblock %d", j);
-            s.rb[j].resize(nd);
-            for (int m = 0; m < nd; ++m) {
-                const int d = cfg->resblock_dilation_sizes[j][m];
-                const std::string base = "resblocks." + std::to_string(n);
-                const int C = s.cout;
-                for (int which = 0; which < 2; ++which) {
-                    const std::string nm = base + (which ? ".convs2." : ".convs1.") + std::to_string(m);
-                    const rvcmi_tensor& w = wm.get(nm + ".weight", {C, C, k});
-                    const rvcmi_tensor& b = wm.get(nm + ".bias", {C});
-                    const int dil = which ? 1 : d;
-                    int nt = k, off = -((k * dil - dil) / 2);  // get_padding, rvc/layers/utils.py:14
-                    const float* wd = w.data;
-                    ConvLayer& L2 = which ? s.rb[j][m].second : s.rb[j][m].first;
-                    build_conv(L2, C, C, 1, &nt, &off, dil,
-                               [=](int co, int ci, int, int tap) { return wd[((size_t)co * C + ci) * k + tap]; }, b.data, op);
-                }
-            }
-        }
+        build_stage(h->stages[i], cfg, wm, i);
+        L *= h->stages[i].u;
+        S = std::max(S, (size_t)L * h->stages[i].cout);
     }
     h->c_last = C0 >> cfg->n_ups;
     {  // conv_post: Conv1d(ch, 1, 7, padding=3, bias=False)   nsf.py:126
@@ -374,18 +379,8 @@ static void launch_rb_inst(const RbPairArgs& ra, int tiles, int nj, int B, int r
 template <typename OpT>
 static void launch_rb_pair_t(int C, const RbPairArgs& ra, int tiles, int nj, int B, int rows, hipStream_t st) {
     switch (C) {
-#ifdef RB_MI1  // experiment: 32-channel waves (64 accumulator registers) -> more waves per SIMD
-        case 256: return launch_rb_inst<OpT, 256, 1, 8, RB_KG>(ra, tiles, nj, B, rows, st);
-        case 128: return launch_rb_inst<OpT, 128, 1, 4, RB_KG>(ra, tiles, nj, B, rows, st);
-#else
-#ifdef RB_TSPLIT  // experiment: 128 rows split over 2 time slabs (NJ = 2, 64 accumulator registers) -> 2x the waves per tile
-        case 256: return launch_rb_inst<OpT, 256, 2, 4, RB_KG, 2, 2, 2>(ra, tiles, nj, B, rows, st);
-        case 128: return launch_rb_inst<OpT, 128, 2, 2, RB_KG, 2, 2, RB_TSPLIT>(ra, tiles, nj, B, rows, st);
-#else
         case 256: return launch_rb_inst<OpT, 256, 2, 4, RB_KG, RB256_NJ>(ra, tiles, nj, B, rows, st);
         case 128: return launch_rb_inst<OpT, 128, 2, 2, RB_KG>(ra, tiles, nj, B, rows, st);
-#endif
-#endif
         case 64: return launch_rb_inst<OpT, 64, 2, 1, RB_KG>(ra, tiles, nj, B, rows, st);
         case 32: return launch_rb_inst<OpT, 32, 1, 1, RB_KG>(ra, tiles, nj, B, rows, st);
         case 16: return launch_rb_inst<OpT, 16, 1, 1, RB_KG>(ra, tiles, nj, B, rows, st);
@@ -401,21 +396,9 @@ static void set_lds_rb() {
 #define RB_ATTR(C_, MI_, NW_)                                                                                   \
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_pair<OpT, C_, MI_, NW_, RB_KG>),           \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#ifdef RB_MI1
-    RB_ATTR(256, 1, 8) RB_ATTR(128, 1, 4)
-#else
-#ifdef RB_TSPLIT
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_pair<OpT, 256, 2, 4, RB_KG, 2, 2, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_pair<OpT, 128, 2, 2, RB_KG, 2, 2, RB_TSPLIT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#else
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_pair<OpT, 256, 2, 4, RB_KG, RB256_NJ>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RB_ATTR(128, 2, 2)
-#endif
-#endif
-    RB_ATTR(64, 2, 1) RB_ATTR(32, 1, 1) RB_ATTR(16, 1, 1)
+    RB_ATTR(128, 2, 2) RB_ATTR(64, 2, 1) RB_ATTR(32, 1, 1) RB_ATTR(16, 1, 1)
 #undef RB_ATTR
 }
 
@@ -423,7 +406,7 @@ template <typename OpT, int CIN, int MI, int WV>
 static void launch_ups_inst(UpsArgs a, int nj, int B, hipStream_t st) {
     const int TQ = 32 * nj * (4 / WV);
     size_t smem = (size_t)a.tile_rows * Tile<CIN>::STRIDE + (a.nz_k1 ? (size_t)(TQ * a.u * a.ns + 16) * 2 : 0);
-    // option UPS_BL: [2][cout] fp32 LDS copy of bias / bn.  Reserved FIRST so that both bounds below see it (appended after
+    // a.bias_off: [2][cout] fp32 LDS copy of bias / bn.  Reserved FIRST so that both bounds below see it (appended after
     // the checks, a 52 KB block became 54 KB -- two resident blocks instead of three -- and a tile near 160 KB would have failed at launch);
     // dropped where it would break the 160 KB limit
     if (a.bias_off && a.cout % 4 == 0 && (smem + 15) / 16 * 16 + (size_t)2 * a.cout * 4 <= 160 * 1024) {
@@ -450,7 +433,7 @@ static void launch_ups_inst(UpsArgs a, int nj, int B, hipStream_t st) {
         }
     }
     // ... else, for one-tile waves writing fp16 (stage 1 of v2/48k: 10 phases x 128 channels, the block's output tile would be 87 KB): wave-private
-    // transposition tiles, so that the stores are whole 128-byte lines (option UPS_TW)
+    // transposition tiles, so that the stores are whole 128-byte lines (a.out_tw_off)
     if (a.out_tw_off && !a.out_tr && a.out_half && nj == 1 && MI == 2 && a.cout % 64 == 0) {
         smem = (smem + 15) / 16 * 16;
         a.out_tw_off = (int)smem;
@@ -515,19 +498,15 @@ template <> struct RbFullGeom<64> { static constexpr int MI = 2, NJ = 3, KG = 4,
 template <> struct RbFullGeom<32> { static constexpr int MI = 1, NJ = RBF32_NJ, KG = 4, OCC = RBF32_OCC, NWV = RBF32_NWV; };
 template <> struct RbFullGeom<16> { static constexpr int MI = 1, NJ = RBF32_NJ, KG = 4, OCC = RBF32_OCC, NWV = RBF32_NWV; };
 static int rbf_rows(int C) { return C == 64 ? RbFullGeom<64>::NWV * 32 * RbFullGeom<64>::NJ : RBF32_NWV * 32 * RBF32_NJ; }
-static int rbf_nb(const Options& opt, int dflt) {  // weight-prefetch depth (register buffers); option NB overrides for A/B experiments
-    const int v = opt.geti("NB", dflt);
-    return v < 2 ? 2 : (v > 4 ? 4 : v);
-}
+// weight-prefetch depth (register buffers): the 8-wave geometry has 256 registers per wave, a 2-deep ring fits without spills
+template <int C>
+constexpr int rbf_nb() { return RbFullGeom<C>::NWV == 8 ? 2 : 3; }
 template <typename OpT, int C>
-static void launch_rbf_inst(const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st, const Options& opt) {
+static void launch_rbf_inst(const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st) {
     using G = RbFullGeom<C>;
     constexpr int R = G::NWV * 32 * G::NJ;
     const size_t smem = (size_t)(R + 2 * RBF_G + R + 2 * RBF_G2) * Tile<C>::STRIDE + 3 * 2 * 32 * G::MI * 4 + 512;  // + bias vectors + dev phase stamps
-    const int nb = rbf_nb(opt, G::NWV == 8 ? 2 : 3);  // the 8-wave geometry has 256 registers per wave: a 2-deep ring fits without spills
-    if (nb == 2) hipLaunchKernelGGL((k_rb_full<OpT, C, G::MI, G::NJ, G::KG, 2, G::OCC, G::NWV>), dim3(tiles, nj, B), dim3(64 * G::NWV), smem, st, ra);
-    else if (nb == 3) hipLaunchKernelGGL((k_rb_full<OpT, C, G::MI, G::NJ, G::KG, 3, G::OCC, G::NWV>), dim3(tiles, nj, B), dim3(64 * G::NWV), smem, st, ra);
-    else hipLaunchKernelGGL((k_rb_full<OpT, C, G::MI, G::NJ, G::KG, 4, G::OCC, G::NWV>), dim3(tiles, nj, B), dim3(64 * G::NWV), smem, st, ra);
+    hipLaunchKernelGGL((k_rb_full<OpT, C, G::MI, G::NJ, G::KG, rbf_nb<C>(), G::OCC, G::NWV>), dim3(tiles, nj, B), dim3(64 * G::NWV), smem, st, ra);
 }
 // C = 64 on a launch of a few tiles (a realtime chunk's 6200 rows = 44 tiles of 512 rows on 256 CUs, the launch as long as ONE k = 11 tile:
 // 50 us): 256-row tiles of four waves -- 107 blocks, each half as long.  Two accumulator sets of 64 registers + a 3-deep ring: no spills.
@@ -540,32 +519,29 @@ static void launch_rbf_small(const RbFullArgs& ra, int tiles, int nj, int B, hip
     hipLaunchKernelGGL((k_rb_full<OpT, C, MI, RBF64S_NJ, 4, 3, OCCS, RBF64S_NWV>), dim3(tiles, nj, B), dim3(64 * RBF64S_NWV), smem, st, ra);
 }
 template <typename OpT>
-static void launch_rbf_t(int C, const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st, const Options& opt, bool small64 = false) {
+static void launch_rbf_t(int C, const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st, bool small64) {
     if (small64 && C == 64) return launch_rbf_small<OpT, 64>(ra, tiles, nj, B, st);
     if (small64 && C == 32) return launch_rbf_small<OpT, 32>(ra, tiles, nj, B, st);
     switch (C) {
-        case 64: return launch_rbf_inst<OpT, 64>(ra, tiles, nj, B, st, opt);
-        case 32: return launch_rbf_inst<OpT, 32>(ra, tiles, nj, B, st, opt);
-        case 16: return launch_rbf_inst<OpT, 16>(ra, tiles, nj, B, st, opt);
+        case 64: return launch_rbf_inst<OpT, 64>(ra, tiles, nj, B, st);
+        case 32: return launch_rbf_inst<OpT, 32>(ra, tiles, nj, B, st);
+        case 16: return launch_rbf_inst<OpT, 16>(ra, tiles, nj, B, st);
         default: RVCMI_FAIL(RVCMI_ERR_INVALID, "fused resblock: unsupported channel count %d", C);
     }
 }
 template <typename OpT>
 static void set_lds_rbf() {
-#define RBF_ATTR1(C_, NB_)                                                                                                  \
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, C_, RbFullGeom<C_>::MI, RbFullGeom<C_>::NJ, RbFullGeom<C_>::KG, NB_, RbFullGeom<C_>::OCC, RbFullGeom<C_>::NWV>), \
+#define RBF_ATTR(C_)                                                                                                        \
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, C_, RbFullGeom<C_>::MI, RbFullGeom<C_>::NJ, RbFullGeom<C_>::KG, rbf_nb<C_>(), RbFullGeom<C_>::OCC, RbFullGeom<C_>::NWV>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define RBF_ATTR(C_) RBF_ATTR1(C_, 2) RBF_ATTR1(C_, 3) RBF_ATTR1(C_, 4)
     RBF_ATTR(64) RBF_ATTR(32) RBF_ATTR(16)
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, 64, 2, RBF64S_NJ, 4, 3, 1, RBF64S_NWV>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, 32, 1, RBF64S_NJ, 4, 3, 2, RBF64S_NWV>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#undef RBF_ATTR1
 #undef RBF_ATTR
 }
 
-// Fill the common part of ConvArgs for `L` and launch it in the handle's operand mode.
 // option RB_STREAM: absent = auto (streaming kernel when the strips are long enough), 1 = always when supported, 0 = never.
 static int rb_stream_mode(const rvcmi_nsf* h) {
     if (!h->opt.has("RB_STREAM")) return 2;
@@ -577,67 +553,6 @@ static int rb_stream_mode(const rvcmi_nsf* h) {
 // and the next stage's k_ups / k_post read them as such (nsf_kernels.hpp pack4_h).  0 = fp32 streams (round 3).
 static bool y_f16(const rvcmi_nsf* h) {
     return h->cfg.operand != RVCMI_OPERAND_F32 && h->opt.geti("Y_F16", 1) != 0;
-}
-
-// Option X0_F16 (default 1, only together with Y_F16): at the stages whose ResBlocks run on k_rb_full (C <= 64: the two HBM-heaviest
-// stages of every shipped config) the ups output X0 -- read three times, once per ResBlock -- is stored as fp16 too.  Unlike the Y
-// streams this rounds the START of the fp32 residual stream (relative 2^-11 once per stage; the stream itself stays fp32 inside the
-// kernels): +1.1e-4 RMS on the full-clip golden, measured on the oracle and gated by the same 5e-4 test.  0 = fp32 X0.
-static bool x0_f16(const rvcmi_nsf* h, int C, size_t maxnd) {
-    return y_f16(h) && h->opt.geti("X0_F16", 1) != 0 && C <= 64 && maxnd <= 3 && !h->opt.on("NO_RBFULL");
-}
-
-// Whole resblocks of a stage on the streaming kernel (ND = 3).  Fills src[j] with the output streams on success.
-// `xhalf`: X0 is an fp16 stream (round 5).  `dry`: plan only -- would this stage stream?  (decides BEFORE the upsampler runs whether it
-// may write X0 as fp16: the tile kernels a short clip falls back to read fp32 rows)
-static bool try_rb_stream_full(rvcmi_nsf* h, const Stage& s, int op, int C, int L, int B, int nk, const float** src, hipStream_t st,
-                               const int* lens, int lm, bool xhalf = false, bool dry = false) {
-    const bool yh = y_f16(h);
-    const int mode = rb_stream_mode(h);
-    if (mode == 0 || op == RVCMI_OPERAND_F32 || nk > 3) return false;
-    for (int j = 0; j < nk; ++j)
-        if (s.rb[j].size() != 3) return false;
-    if (!rb_stream_supported(op, C, 3)) return false;
-    RbStreamDesc sd[3];
-    int order[3];
-    for (int j = 0; j < nk; ++j) order[j] = j;
-    std::sort(order, order + nk, [&](int a1, int b1) { return s.rb[a1][0].first.ntaps[0] > s.rb[b1][0].first.ntaps[0]; });
-    double flops = 0, bytes = 0;
-    for (int oj = 0; oj < nk; ++oj) {
-        const int j = order[oj];
-        RbStreamDesc& d = sd[oj];
-        memset(&d, 0, sizeof(d));
-        d.src = h->X0.as<float>();
-        d.dst = h->Ya[j].as<float>();
-        d.y_half = yh ? 1 : 0;
-        d.x_half = xhalf ? 1 : 0;
-        d.lens = lens;
-        d.lmul = lm;
-        d.k = s.rb[j][0].first.ntaps[0];
-        d.k_p = s.rb[j][0].first.ntaps_p;
-        d.ct1 = s.rb[j][0].first.ct_stride;
-        d.ct2 = s.rb[j][0].second.ct_stride;
-        for (int m = 0; m < 3; ++m) {
-            const ConvLayer& c1 = s.rb[j][m].first;
-            const ConvLayer& c2 = s.rb[j][m].second;
-            d.w1[m] = c1.w_pack.p;
-            d.w2[m] = c2.w_pack.p;
-            d.b1[m] = c1.bias.as<float>();
-            d.b2[m] = c2.bias.as<float>();
-            d.dil[m] = c1.dstep;
-            flops += (c1.flops_per_pos + c2.flops_per_pos) * (double)L * B;
-            bytes += 2.0 * d.k * C * C * 2;
-        }
-        bytes += (double)B * L * C * ((yh ? 2 : 4) + (xhalf ? 2 : 4));
-    }
-    char nm[48];
-    snprintf(nm, sizeof(nm), "rb_stream_c%d", C);
-    if (!rb_stream_launch(op, C, 3, sd, nk, L, B, (long)L * C, mode == 1, st, h->opt, true)) return false;
-    if (dry) return true;
-    h->prof.launch(nm, flops, bytes, st, [&] { rb_stream_launch(op, C, 3, sd, nk, L, B, (long)L * C, mode == 1, st, h->opt); });
-    HIP_CHECK(hipGetLastError());
-    for (int j = 0; j < nk; ++j) src[j] = h->Ya[j].as<float>();
-    return true;
 }
 
 static void run_conv(rvcmi_nsf* h, const ConvLayer& L, ConvArgs a, int B, const char* name, hipStream_t st) {
@@ -694,21 +609,8 @@ static void run_conv(rvcmi_nsf* h, const ConvLayer& L, ConvArgs a, int B, const 
     HIP_CHECK(hipGetLastError());
 }
 
-// Up to three independent convs of the same shape class (C_in = C_out = 256) in ONE launch of k_conv_mfma_jobs, blocks of
-// 32 output channels x 128 rows (MI = 1, NJ = 1, waves split time): grid = row tiles x 8 channel tiles x (jobs x batch).
-template <typename OpT, int C>
-static void launch_conv_jobs(const ConvJobs& js, int Lq, int B, size_t smem, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    auto kern = &k_conv_mfma_jobs<OpT, C, 1, 1, 1>;
-    if (!(attr_done.load() & (1ull << (dev & 63)))) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done.fetch_or(1ull << (dev & 63));
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((Lq + 127) / 128), C / 32, (unsigned)(B * js.njobs)), dim3(256), smem, st, js);
-}
-// K-split form (nsf_kernels.hpp conv_ks_body): 32 rows x 32 channels per block, the four waves split the taps.
+// Up to three independent convs of the same shape class (C_in = C_out = 256 or 128) in ONE launch of k_conv_ks_jobs
+// (nsf_kernels.hpp conv_ks_body): 32 NJ rows x 32 channels per block, the four waves split the taps.
 constexpr int conv_ks_nj(int C) { return C == 256 ? 1 : 3; }  // rows per block / 32 (C = 128: 96-row tiles = 396 blocks for a chunk's 3100 rows)
 template <typename OpT, int C>
 static void launch_conv_ks_jobs(const ConvJobs& js, int Lq, int B, size_t smem, hipStream_t st) {
@@ -723,16 +625,15 @@ static void launch_conv_ks_jobs(const ConvJobs& js, int Lq, int B, size_t smem, 
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)((Lq + 32 * NJ - 1) / (32 * NJ)), C / 32, (unsigned)(B * js.njobs)), dim3(256), smem, st, js);
 }
+// Realtime chunk, ABAB, against blocks that run all the taps of 128 rows: C = 256 (310 rows, 32-row tiles = 240 blocks) six launches
+// 134 -> 107 us; C = 128 (3100 rows) 113 -> 107 us with 96-row tiles (396 blocks) -- with 32-row tiles it LOST (155 us: 1164 blocks that
+// each stage 82 rows for 32 outputs).
 static void run_conv_jobs(rvcmi_nsf* h, const ConvLayer* const* Ls, const ConvArgs* as, int nj, int B, const char* name, hipStream_t st) {
     ConvJobs js;
     memset(&js, 0, sizeof(js));
     js.njobs = nj;
     double flops = 0, bytes = 0;
     size_t smem = 0;
-    // K-split blocks (taps over the four waves, option CONV_KS, default on).  Realtime chunk, ABAB: C = 256 (310 rows, 32-row tiles = 240
-    // blocks) six launches 134 -> 107 us; C = 128 (3100 rows) 113 -> 107 us with 96-row tiles (396 blocks) -- with 32-row tiles it LOST
-    // (155 us: 1164 blocks that each stage 82 rows for 32 outputs).
-    const bool ks = h->opt.geti("CONV_KS", 1) != 0;
     for (int j = 0; j < nj; ++j) {
         const ConvLayer& L = *Ls[j];
         ConvArgs a = as[j];
@@ -749,8 +650,8 @@ static void run_conv_jobs(rvcmi_nsf* h, const ConvLayer* const* Ls, const ConvAr
         a.ntaps = L.ntaps_p;
         a.roff = 0;
         const int ksr = 32 * conv_ks_nj(L.cin);
-        a.tile_rows = (ks ? ksr : 128) + (L.ntaps_p - 1) * L.dstep;
-        smem = std::max(smem, (size_t)a.tile_rows * (2 * L.cin + 16) + (ks ? (size_t)3 * (ksr / 32) * 16 * 64 * 4 : 0));  // (+ the partial sums of 3 waves)
+        a.tile_rows = ksr + (L.ntaps_p - 1) * L.dstep;
+        smem = std::max(smem, (size_t)a.tile_rows * (2 * L.cin + 16) + (size_t)3 * (ksr / 32) * 16 * 64 * 4);  // (+ the partial sums of 3 waves)
         flops += L.flops_per_pos * (double)a.Lq * B;
         bytes += (double)B * a.Lq * L.cin * (a.in_mode == IN_OP_RAW ? 2 : 4) + (double)B * a.Lq * L.cin * (a.out_mode == OUT_ACT ? 2 : 4) +
                  (a.res ? (double)B * a.Lq * L.cin * 4 : 0) + (double)L.ntaps[0] * L.cin * L.cin * 2;
@@ -758,20 +659,12 @@ static void run_conv_jobs(rvcmi_nsf* h, const ConvLayer* const* Ls, const ConvAr
     }
     const bool c256 = Ls[0]->cin == 256;
     h->prof.launch(name, flops, bytes, st, [&] {
-        if (ks) {
-            if (h->cfg.operand == RVCMI_OPERAND_BF16) {
-                if (c256) launch_conv_ks_jobs<__bf16, 256>(js, as[0].Lq, B, smem, st);
-                else launch_conv_ks_jobs<__bf16, 128>(js, as[0].Lq, B, smem, st);
-            } else {
-                if (c256) launch_conv_ks_jobs<_Float16, 256>(js, as[0].Lq, B, smem, st);
-                else launch_conv_ks_jobs<_Float16, 128>(js, as[0].Lq, B, smem, st);
-            }
-        } else if (h->cfg.operand == RVCMI_OPERAND_BF16) {
-            if (c256) launch_conv_jobs<__bf16, 256>(js, as[0].Lq, B, smem, st);
-            else launch_conv_jobs<__bf16, 128>(js, as[0].Lq, B, smem, st);
+        if (h->cfg.operand == RVCMI_OPERAND_BF16) {
+            if (c256) launch_conv_ks_jobs<__bf16, 256>(js, as[0].Lq, B, smem, st);
+            else launch_conv_ks_jobs<__bf16, 128>(js, as[0].Lq, B, smem, st);
         } else {
-            if (c256) launch_conv_jobs<_Float16, 256>(js, as[0].Lq, B, smem, st);
-            else launch_conv_jobs<_Float16, 128>(js, as[0].Lq, B, smem, st);
+            if (c256) launch_conv_ks_jobs<_Float16, 256>(js, as[0].Lq, B, smem, st);
+            else launch_conv_ks_jobs<_Float16, 128>(js, as[0].Lq, B, smem, st);
         }
     });
     HIP_CHECK(hipGetLastError());
@@ -813,6 +706,642 @@ static void copy_tap_cl(rvcmi_nsf* h, const float* src_cl, int B, int L, int C, 
     tr->done = true;
 }
 
+// dev only (DBG & 32, RVCMI_DEV_STAMPS builds): a zeroed buffer of `n` per-wave phase stamps for the fused resblock kernels ...
+static unsigned long long* stamp_buffer(rvcmi_nsf* h, size_t n, hipStream_t st) {
+    if (h->dbg.bytes < n * 8) h->dbg.alloc(n * 8);
+    HIP_CHECK(hipMemsetAsync(h->dbg.p, 0, n * 8, st));
+    return h->dbg.as<unsigned long long>();
+}
+// ... and its readback: the cycles between consecutive stamps of batch item 0's blocks, averaged per job (resblock kernel size).
+// Stamps [job][tile][wave][nst]; a wave that wrote no first stamp, or a phase it never reached, counts nothing.
+template <typename Args>
+static void print_stamps(rvcmi_nsf* h, const char* nm, const Args& ra, int njobs, int max_tiles, int nwv, int nst, size_t nblk,
+                         hipStream_t st) {
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<unsigned long long> ts(nblk * nwv * nst);
+    HIP_CHECK(hipMemcpy(ts.data(), h->dbg.p, ts.size() * 8, hipMemcpyDeviceToHost));
+    for (int oj = 0; oj < njobs; ++oj) {
+        double sum[16] = {0};
+        long cnt = 0;
+        for (int t = 0; t < ra.job[oj].ntiles; ++t)
+            for (int w = 0; w < nwv; ++w) {
+                const unsigned long long* p = &ts[(((size_t)oj * max_tiles + t) * nwv + w) * nst];
+                if (!p[0]) continue;
+                for (int i = 1; i < nst; ++i) sum[i] += p[i] ? (double)(p[i] - p[i - 1]) : 0.0;
+                ++cnt;
+            }
+        fprintf(stderr, "[rvcmi ts] %s k=%d tiles=%d:", nm, ra.job[oj].k, ra.job[oj].ntiles);
+        for (int i = 1; i < nst; ++i) fprintf(stderr, " %.0f", cnt ? sum[i] / cnt : 0.0);
+        fprintf(stderr, "\n");
+    }
+}
+
+// ---- forward ------------------------------------------------------------------------------------
+
+// What every step of one forward call shares.
+struct Fwd {
+    rvcmi_nsf* h;
+    int op, B, Te;       // Te: frames after the realtime interpolation (n_res)
+    const int* lens;     // ragged batch: valid frames per item (device [B]) or nullptr
+    const float* har;    // excitation [B][Te * upp] (use_f0)
+    hipStream_t st;
+    TapRequest* tr;
+    bool want(const char* w) const { return tr && strcmp(tr->what, w) == 0; }
+};
+
+// The running activation ((y[0] + y[1]) + y[2]) / div, [B][L][C] rows (nsf.py:177-186); stage 0 reads conv_pre's P alone.
+struct Act {
+    const float* y[3];
+    bool half;  // y[] are fp16 streams (written by k_rb_stream ND = 3 / k_rb_full under option Y_F16)
+    bool raw;   // y[0] holds the activated operands already (conv_pre on the MFMA path)
+    float div;
+    long L;
+    int C;
+    int lm;     // rows per frame (ragged batches: item rows = lens[b] * lm)
+};
+
+using RbLevels = std::vector<std::pair<ConvLayer, ConvLayer>>;  // one resblock: {conv1, conv2} per dilation
+
+// How a stage's resblocks run, in order of precedence (plan_stage):
+//   F32_CHAIN  fp32 operands: conv by conv
+//   SPLIT      a handful of rows (realtime chunk): conv1 / conv2 of all resblocks as output-channel-split launches per pair level
+//   STREAM     whole resblocks on the streaming kernel (rb_stream_kernels.hpp): persistent blocks walk strips of the time axis
+//   FULL       whole resblocks fused, x resident in registers (C <= 64): ONE launch for the stage   residuals.py:68-85
+//   PAIR       one launch per pair level (k_rb_pair, or at C = 256 the streaming kernel with ND = 1 where its planner takes it)
+enum class RbPath { F32_CHAIN, SPLIT, STREAM, FULL, PAIR };
+struct StagePlan {
+    RbPath path;
+    bool x0_half;     // the upsampler writes X0 as fp16
+    bool stage_half;  // the resblocks write their output streams as fp16
+    bool small64;     // FULL: 256-row tiles (launch_rbf_small)
+};
+
+static float* ydst(rvcmi_nsf* h, size_t j, size_t m) { return (m & 1) ? h->Yb[j].as<float>() : h->Ya[j].as<float>(); }
+
+static size_t max_levels(const Stage& s) {
+    size_t n = 0;
+    for (const RbLevels& rb : s.rb) n = std::max(n, rb.size());
+    return n;
+}
+
+// The stage's resblocks, heaviest kernel size first (the long blocks are dispatched first).
+static void rb_order(const Stage& s, int* order) {
+    const int nk = (int)s.rb.size();
+    for (int j = 0; j < nk; ++j) order[j] = j;
+    std::sort(order, order + nk, [&](int a, int b) { return s.rb[a][0].first.ntaps[0] > s.rb[b][0].first.ntaps[0]; });
+}
+
+// One-sided halo of a whole resblock in the fused kernel.
+static int rbf_halo(const RbLevels& rb) {
+    int dsum = 0;
+    for (const auto& pr : rb) dsum += pr.first.dstep;
+    return (rb[0].first.ntaps[0] - 1) / 2 * (dsum + (int)rb.size());
+}
+
+// Job descriptor (RbStreamDesc, RbFullJob) of pair levels [m0, m0 + nd) of one resblock; adds their flops and weight bytes over B x L rows.
+template <typename D>
+static void fill_rb_job(D& d, const RbLevels& rb, int m0, int nd, long L, int B, int C, double& flops, double& bytes) {
+    d.k = rb[m0].first.ntaps[0];
+    d.k_p = rb[m0].first.ntaps_p;
+    d.ct1 = rb[m0].first.ct_stride;
+    d.ct2 = rb[m0].second.ct_stride;
+    for (int m = 0; m < nd; ++m) {
+        const ConvLayer& c1 = rb[m0 + m].first;
+        const ConvLayer& c2 = rb[m0 + m].second;
+        d.w1[m] = c1.w_pack.p;
+        d.w2[m] = c2.w_pack.p;
+        d.b1[m] = c1.bias.as<float>();
+        d.b2[m] = c2.bias.as<float>();
+        d.dil[m] = c1.dstep;
+        flops += (c1.flops_per_pos + c2.flops_per_pos) * (double)L * B;
+        bytes += 2.0 * d.k * C * C * 2;
+    }
+}
+
+// Whole resblocks of a stage as jobs of the streaming kernel (ND = 3): X0 -> Ya[j], heaviest first.
+static void stream_jobs(const Fwd& f, const Stage& s, long L, int lm, bool xhalf, bool yhalf, RbStreamDesc* sd, double& flops,
+                        double& bytes) {
+    rvcmi_nsf* h = f.h;
+    const int C = s.cout;
+    int order[RVCMI_MAX_RB];
+    rb_order(s, order);
+    for (size_t oj = 0; oj < s.rb.size(); ++oj) {
+        const int j = order[oj];
+        RbStreamDesc& d = sd[oj];
+        memset(&d, 0, sizeof(d));
+        d.src = h->X0.as<float>();
+        d.dst = h->Ya[j].as<float>();
+        d.y_half = yhalf ? 1 : 0;
+        d.x_half = xhalf ? 1 : 0;
+        d.lens = f.lens;
+        d.lmul = lm;
+        fill_rb_job(d, s.rb[j], 0, 3, L, f.B, C, flops, bytes);
+        bytes += (double)f.B * L * C * ((yhalf ? 2 : 4) + (xhalf ? 2 : 4));
+    }
+}
+
+// Everything that decides how stage `s` (L rows per item, lm rows per frame) runs, decided once, before anything of it is launched:
+// the upsampler's X0 dtype must match the resblock path that reads it.
+static StagePlan plan_stage(const Fwd& f, const Stage& s, long L, int lm) {
+    rvcmi_nsf* h = f.h;
+    const int op = f.op, C = s.cout, nk = (int)s.rb.size();
+    const bool yh = y_f16(h);
+    // Option X0_F16 (default 1, only together with Y_F16): X0 -- read once per resblock -- is stored as fp16 where its consumer reads
+    // fp16 rows: k_rb_full (C <= 64: the two HBM-heaviest stages of every shipped config) and -- round 5, unless X0_F16_NOSTREAM -- the
+    // streaming kernel with its coalesced step IO.  Unlike the Y streams this rounds the START of the fp32 residual stream (relative 2^-11
+    // once per stage; the stream itself stays fp32 inside the kernels): +1.1e-4 RMS on the full-clip golden, measured on the oracle and
+    // gated by the same 5e-4 test.  0 = fp32 X0.
+    const bool x0h = yh && h->opt.geti("X0_F16", 1) != 0;
+    StagePlan p = {RbPath::PAIR, false, false, false};
+    if (op == RVCMI_OPERAND_F32) {
+        p.path = RbPath::F32_CHAIN;
+        return p;
+    }
+    const long rows = (long)f.B * L;
+    const int mode = rb_stream_mode(h);
+    // (round 6, review item 4: the same conv-by-conv launches for a FULL-length stage 0 with 64-channel x 256-row blocks -- 684 blocks per launch,
+    //  no halo recompute -- were built as a dev option, parity-green, and measured 0.61 ms against k_rb_pair<256>'s 0.284 ms; removed)
+    if (((C == 256 && rows <= RB_SPLIT_MAX_ROWS) || (C == 128 && rows <= RB_SPLIT_MAX_ROWS_128)) && nk <= 3 && !h->opt.on("NO_RB_SPLIT") &&
+        mode != 1) {
+        p.path = RbPath::SPLIT;
+        return p;
+    }
+    bool stream = mode != 0 && nk <= 3 && rb_stream_supported(op, C, 3);
+    for (int j = 0; j < nk; ++j) stream = stream && s.rb[j].size() == 3;
+    if (stream) {
+        // a dry run of the planner: it refuses short strips, and fp16 input rows outside the kernel form that reads them (option RS_KL)
+        auto plans = [&](bool xhalf) {
+            RbStreamDesc sd[3];
+            double flops = 0, bytes = 0;
+            stream_jobs(f, s, L, lm, xhalf, yh, sd, flops, bytes);
+            return rb_stream_launch(op, C, 3, sd, nk, (int)L, f.B, L * C, mode == 1, f.st, h->opt, true);
+        };
+        const bool xh = x0h && !h->opt.on("X0_F16_NOSTREAM") && plans(true);
+        if (xh || plans(false)) return {RbPath::STREAM, xh, yh, false};
+    }
+    if (C <= 64 && max_levels(s) <= 3) {
+        p = {RbPath::FULL, x0h, yh, false};
+        // (C = 64) short launches take 256-row tiles: at 512 rows they would be fewer blocks than half the CUs (halo of the k = 11
+        // resblock: 120 rows either way -- the small tiles keep 136 of 256 rows)
+        if (C == 64 || C == 32) {
+            long blocks512 = 0;
+            for (int j = 0; j < nk; ++j) {
+                const int HL = rbf_halo(s.rb[j]);
+                blocks512 += (L + (rbf_rows(C) - 2 * HL) - 1) / (rbf_rows(C) - 2 * HL) * f.B;
+                if (RBF64S_ROWS - 2 * HL < RBF64S_ROWS / 4) blocks512 = 1 << 30;  // (halo too large for the small tile)
+            }
+            p.small64 = blocks512 < num_cus() / 2 * (C == 64 ? 1 : 2);
+        }
+    }
+    return p;
+}
+
+// ---- excitation: har[B][Te*upp]                                           nsf.py:152-159
+// Returns true when the "har" tap has been served (the forward ends there).
+static bool excitation(Fwd& f, int T, const float* f0, const float* noise) {
+    rvcmi_nsf* h = f.h;
+    const rvcmi_nsf_config& c = h->cfg;
+    const int B = f.B, Te = f.Te, upp = h->upp;
+    hipStream_t st = f.st;
+    const int* lens = f.lens;
+    h->prof.launch("phase_scan", 0, (double)B * T * 8, st, [&] {
+        hipLaunchKernelGGL(k_phase_scan, dim3(B), dim3(256), 0, st, f0, h->phase.as<float>(), T, (float)c.sr, (float)upp, lens);
+    });
+    const size_t total = (size_t)B * T * upp;
+    h->prof.launch("sine_source", 0, (double)total * (noise ? 8 : 4), st, [&] {
+        hipLaunchKernelGGL(k_sine_source, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, f0,
+                           h->phase.as<float>(), noise, h->har.as<float>(), T, upp, (float)c.sr, h->lin_w, h->lin_b, total);
+    });
+    f.har = h->har.as<float>();
+    if (Te != T) {  // nsf.py:155-159
+        const size_t tot2 = (size_t)B * Te * upp;
+        hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, st, f.har,
+                           h->har2.as<float>(), T * upp, Te * upp, tot2);
+        f.har = h->har2.as<float>();
+    }
+    HIP_CHECK(hipGetLastError());
+    if (!f.want("har")) return false;
+    TapRequest* tr = f.tr;
+    const size_t n = (size_t)B * Te * upp;
+    if (n > tr->capacity) RVCMI_FAIL(RVCMI_ERR_NOMEM, "tap capacity");
+    HIP_CHECK(hipMemcpyAsync(tr->out_host, f.har, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    tr->shape[0] = B; tr->shape[1] = 1; tr->shape[2] = (int64_t)Te * upp;
+    tr->done = true;
+    return true;
+}
+
+// ---- conv_pre + cond                                                       nsf.py:164-166
+static Act conv_pre(const Fwd& f, const float* x, int T, const float* g) {
+    rvcmi_nsf* h = f.h;
+    const rvcmi_nsf_config& c = h->cfg;
+    const int B = f.B, Te = f.Te, inter = c.inter_channels, C0 = h->C0;
+    hipStream_t st = f.st;
+    if (Te != T) {  // nsf.py:160-162 / generators.py:76-79
+        const size_t tot = (size_t)B * inter * Te;
+        hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, h->x2.as<float>(), T, Te, tot);
+        x = h->x2.as<float>();
+    }
+    if (g && c.gin_channels) {
+        hipLaunchKernelGGL(k_cond, dim3((C0 + 3) / 4, B), dim3(256), 0, st, g, h->cond_w.as<float>(),
+                           h->cond_b.as<float>(), h->condv.as<float>(), c.gin_channels, C0);
+    }
+    float* P = h->P.as<float>();
+    // round 6: on the MFMA path conv_pre writes the ACTIVATED OPERANDS to_op(lrelu(conv + bias + cond, 0.1)) -- the only thing stage 0's upsampler does
+    // with P is to compute exactly that while staging (12 blocks per time tile each re-read and re-converted the fp32 rows) -- unless the fp32 "pre" tap is asked for
+    const bool pre_op = f.op != RVCMI_OPERAND_F32 && !f.want("pre");
+    ConvArgs a = base_args();
+    a.in = x;
+    a.in_bstride = (long)inter * Te;
+    a.Lin = Te;
+    a.in_mode = IN_F32_CF;
+    a.Lq = Te;
+    a.out_mode = pre_op ? OUT_ACT : OUT_F32;
+    a.out = P;
+    a.out_bstride = (long)Te * C0;
+    a.out_C = C0;
+    a.cb = (g && c.gin_channels) ? h->condv.as<float>() : nullptr;
+    a.lens = f.lens;
+    a.lmul_in = a.lmul_q = 1;
+    run_conv(h, h->pre, a, B, "conv_pre", st);
+    return Act{{P, nullptr, nullptr}, false, pre_op, 1.f, Te, C0, 1};
+}
+
+// ---- x = ups[i](leaky_relu(x, 0.1)) + noise_convs[i](har) -> X0 (L rows)    nsf.py:171-174
+static void ups_f32(const Fwd& f, const Stage& s, const Act& x, long L, int lm) {
+    rvcmi_nsf* h = f.h;
+    const int C = s.cout, B = f.B;
+    char nm[48];
+    ConvArgs a = base_args();
+    a.in = x.y[0];
+    a.in_b = x.y[1];
+    a.in_c = x.y[2];
+    a.in_bstride = x.L * x.C;
+    a.Lin = (int)x.L;
+    a.in_mode = IN_F32_ACT;
+    a.div_in = x.div;
+    a.Lq = (int)x.L;
+    a.out_mode = OUT_F32;
+    a.out = h->X0.p;
+    a.out_bstride = L * C;
+    a.out_C = C;
+    a.out_mul = s.u;
+    a.lens = f.lens;
+    a.lmul_in = a.lmul_q = x.lm;
+    snprintf(nm, sizeof(nm), "ups_c%d", s.cin);
+    run_conv(h, s.up, a, B, nm, f.st);
+    if (h->cfg.use_f0) {
+        const size_t n = (size_t)L * C;
+        snprintf(nm, sizeof(nm), "noise_conv_c%d", C);
+        h->prof.launch(nm, 2.0 * s.nk * n * B, (double)B * n * 8, f.st, [&] {
+            hipLaunchKernelGGL(k_noise_add, dim3((unsigned)((n + 255) / 256), 1, B), dim3(256), 0, f.st, h->X0.as<float>(), f.har,
+                               s.noise_w.as<float>(), s.noise_b.as<float>(), (int)L, C, f.Te * h->upp, s.nk, s.ns, s.npad, f.lens, lm, h->upp);
+        });
+    }
+}
+
+// ups + bias + noise conv in one MFMA kernel, X0 written once
+static void ups_mfma(const Fwd& f, const Stage& s, const Act& x, const StagePlan& p, long L, int lm) {
+    rvcmi_nsf* h = f.h;
+    const int C = s.cout, B = f.B, upp = h->upp;
+    const long Lin = x.L;
+    const ConvLayer& U = s.up;
+    char nm[48];
+    UpsArgs ua;
+    memset(&ua, 0, sizeof(ua));
+    ua.dbg = dbg_flags(h);
+    ua.bias_off = 1;    // LDS copy of bias / bn (the launcher turns it into the LDS offset where it fits)
+    ua.in_a = x.y[0];
+    ua.in_b = x.y[1];
+    ua.in_c = x.y[2];
+    ua.in_half = x.half ? 1 : 0;
+    ua.in_raw = x.raw ? 1 : 0;
+    ua.lens = f.lens;
+    ua.lmul = x.lm;
+    ua.lhmul = upp;
+    ua.Lh_stride = f.Te * upp;
+    ua.div = x.div;
+    ua.Lin = (int)Lin;
+    ua.cin = s.cin;
+    ua.in_bstride = Lin * x.C;
+    ua.w = U.w_pack.p;
+    ua.ct_stride = U.ct_stride;
+    int lo = 1 << 30, hi = -(1 << 30);
+    for (int r = 0; r < s.u; ++r) {
+        ua.ph_w_off[r] = U.pack_off[r];
+        ua.ph_in_off[r] = U.in_off[r];
+        lo = std::min(lo, U.in_off[r] - (U.ntaps_p - 1));
+        hi = std::max(hi, U.in_off[r]);
+    }
+    ua.ntaps_p = U.ntaps_p;
+    ua.u = s.u;
+    ua.cout = C;
+    ua.lo = lo;
+    ua.bias = U.bias.as<float>();
+    ua.out = h->X0.as<float>();
+    ua.out_half = p.x0_half ? 1 : 0;
+    ua.out_tr = 1;      // row-wise stores (the launcher clears it where the block does not own whole rows)
+    ua.out_tw_off = 1;  // wave-private transposition tiles (the launcher turns it into the LDS offset where it applies)
+    ua.out_bstride = L * C;
+    if (h->cfg.use_f0 && s.nz_mfma) {  // noise_convs[i](har) as a 2-tap MFMA conv over frames -> NZ, added in k_ups' epilogue
+        ConvArgs na = base_args();
+        na.in = f.har;
+        na.in_bstride = (long)f.Te * upp;
+        na.Lin = f.Te * upp;
+        na.in_mode = IN_HAR;
+        na.hs = s.ns;
+        na.hpad = s.npad;
+        na.Lq = (int)L;
+        na.out_mode = OUT_F32;
+        na.out = h->NZ.p;
+        na.out_bstride = L * C;
+        na.out_C = C;
+        na.lens = f.lens;
+        na.lmul_in = upp;
+        na.lmul_q = lm;
+        snprintf(nm, sizeof(nm), "noise_mfma_c%d", C);
+        run_conv(h, s.nz, na, B, nm, f.st);
+        ua.addend = h->NZ.as<float>();
+    } else if (h->cfg.use_f0) {
+        ua.nz_k1 = s.nz_k1 ? 1 : 0;
+        ua.wnz = s.nz_k1_w.p;
+        ua.har = f.har;
+        ua.Lh = f.Te * upp;
+        ua.Wn = s.noise_w.as<float>();
+        ua.bn = s.noise_b.as<float>();
+        ua.nk = s.nk;
+        ua.ns = s.ns;
+        ua.npad = s.npad;
+    }
+    const int MIu = C >= 64 ? 2 : 1;
+    ua.cog = (C + 32 * MIu - 1) / (32 * MIu);
+    ua.nvt = s.u * ua.cog;
+    const int wv = ua.nvt >= 4 ? 4 : (ua.nvt >= 2 ? 2 : 1);
+    // time-tile height: blocks have equal duration, so a launch of ~1.1 x (resident blocks) runs two rounds for one
+    // round of work; pick the largest tile that still gives >= 4 rounds of blocks (2 resident blocks per CU)
+    // (measured at B = 1, same box, us: C_in 512: 52 / 36 / 37 for NJ 4 / 2 / 1; 256: 94 / 95 / 85; 128: 131 / 118 / 110;
+    //  64 -> 32 channels: 98 / 102 / 150 -- with one 32-channel tile per wave, short tiles starve the MFMA of columns)
+    int nj = 4;
+    const long blocks4 = (long)((Lin + 128 * (4 / wv) - 1) / (128 * (4 / wv))) * B;
+    if (blocks4 < 2048 && s.cin >= 128) nj = s.cin >= 512 ? 2 : 1;
+    else if (blocks4 < 2048 && s.cin == 64) nj = 2;  // (us at B = 1 after the staging fix: 84 / 75 / 89 for NJ 4 / 2 / 1)
+    // large grids (round 4, fp16 inputs + row-wise stores; us per clip at B = 16 for NJ 4 / 1 / 2, ABAB: C_in 128: 77 / 67 / 83,
+    // 64: 70 / 73 / 55): the short tiles win there too -- they also keep the output tile inside the row-wise store's LDS budget
+    else if (s.cin >= 512) nj = 2;   // (C_in 512: 22 vs 29 us for NJ 2 / 4; C_in 256 keeps NJ = 4: 52 vs 57)
+    else if (s.cin == 128) nj = 1;
+    else if (s.cin == 64) nj = 2;
+    // (round 6: NJ 2 / 4 and vpw 1 / 2 for the C_in = 256 stage alone, 8 variants x 2, ABAB: 72-110 us against 60 -- every one loses)
+    const int TQ = 32 * nj * (4 / wv);
+    ua.tile_rows = TQ + (hi - lo);
+    const long qtiles = (Lin + TQ - 1) / TQ;
+    int vpw = (ua.nvt + wv - 1) / wv;  // everything in one block ...
+    while (vpw > 1 && qtiles * B * ((ua.nvt + wv * vpw - 1) / (wv * vpw)) < 300) --vpw;  // ... unless the grid would starve
+    ua.vpw = vpw;
+    snprintf(nm, sizeof(nm), "ups_c%d", s.cin);
+    const double flops = U.flops_per_pos * (double)Lin * B + 2.0 * s.nk * (double)L * C * B;
+    const double bytes = (double)B * Lin * x.C * (x.half ? 2 : 4) * (x.y[1] ? (x.y[2] ? 3 : 2) : 1) + (double)B * L * C * (p.x0_half ? 2 : 4);
+    h->prof.launch(nm, flops, bytes, f.st, [&] {
+        if (f.op == RVCMI_OPERAND_BF16) launch_ups_t<__bf16>(ua, wv, nj, B, f.st);
+        else launch_ups_t<_Float16>(ua, wv, nj, B, f.st);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+// ---- resblocks[i*nk + j](x), j < nk: X0 -> src[j]                         nsf.py:175-185
+
+// conv1 / conv2 of one resblock pair as two convs: hbuf = to_op(lrelu(conv1(lrelu(src)))), dst = src + conv2(hbuf)   residuals.py:73-82
+static void rb_pair_args(const Fwd& f, long L, int C, int lm, const float* src, void* hbuf, float* dst, ConvArgs& a1, ConvArgs& a2) {
+    a1 = base_args();
+    a1.in = src;
+    a1.in_mode = IN_F32_ACT;
+    a1.out_mode = OUT_ACT;
+    a1.out = hbuf;
+    a2 = base_args();
+    a2.in = hbuf;
+    a2.in_mode = IN_OP_RAW;
+    a2.out_mode = OUT_F32;
+    a2.out = dst;
+    a2.res = src;
+    a2.res_bstride = L * C;
+    for (ConvArgs* a : {&a1, &a2}) {
+        a->in_bstride = L * C;
+        a->Lin = (int)L;
+        a->Lq = (int)L;
+        a->lens = f.lens;
+        a->lmul_in = a->lmul_q = lm;
+        a->out_bstride = L * C;
+        a->out_C = C;
+    }
+}
+
+static void rb_f32_chain(const Fwd& f, const Stage& s, long L, int lm, const float** src) {
+    rvcmi_nsf* h = f.h;
+    char nm[48];
+    snprintf(nm, sizeof(nm), "rb_c%d", s.cout);
+    for (size_t j = 0; j < s.rb.size(); ++j)
+        for (size_t m = 0; m < s.rb[j].size(); ++m) {
+            float* dst = ydst(h, j, m);
+            ConvArgs a1, a2;
+            rb_pair_args(f, L, s.cout, lm, src[j], h->H.p, dst, a1, a2);
+            run_conv(h, s.rb[j][m].first, a1, f.B, nm, f.st);
+            run_conv(h, s.rb[j][m].second, a2, f.B, nm, f.st);
+            src[j] = dst;
+        }
+}
+
+static void rb_split(const Fwd& f, const Stage& s, long L, int lm, const float** src) {
+    rvcmi_nsf* h = f.h;
+    char nm[48];
+    snprintf(nm, sizeof(nm), "rb_split_c%d", s.cout);
+    for (size_t m = 0; m < max_levels(s); ++m) {
+        const ConvLayer* L1[3];
+        const ConvLayer* L2[3];
+        ConvArgs a1[3], a2[3];
+        int nj = 0;
+        for (size_t j = 0; j < s.rb.size(); ++j) {
+            if (m >= s.rb[j].size()) continue;
+            float* dst = ydst(h, j, m);
+            void* hbuf = (char*)h->H.p + (size_t)nj * (h->H.bytes / 3);
+            rb_pair_args(f, L, s.cout, lm, src[j], hbuf, dst, a1[nj], a2[nj]);
+            L1[nj] = &s.rb[j][m].first;
+            L2[nj] = &s.rb[j][m].second;
+            src[j] = dst;
+            ++nj;
+        }
+        run_conv_jobs(h, L1, a1, nj, f.B, nm, f.st);
+        run_conv_jobs(h, L2, a2, nj, f.B, nm, f.st);
+    }
+}
+
+static void rb_stream(const Fwd& f, const Stage& s, const StagePlan& p, long L, int lm, const float** src) {
+    rvcmi_nsf* h = f.h;
+    const int C = s.cout, nk = (int)s.rb.size();
+    RbStreamDesc sd[3];
+    double flops = 0, bytes = 0;
+    stream_jobs(f, s, L, lm, p.x0_half, p.stage_half, sd, flops, bytes);
+    char nm[48];
+    snprintf(nm, sizeof(nm), "rb_stream_c%d", C);
+    h->prof.launch(nm, flops, bytes, f.st, [&] {
+        rb_stream_launch(f.op, C, 3, sd, nk, (int)L, f.B, L * C, rb_stream_mode(h) == 1, f.st, h->opt);
+    });
+    HIP_CHECK(hipGetLastError());
+    for (int j = 0; j < nk; ++j) src[j] = h->Ya[j].as<float>();
+}
+
+static void rb_full(const Fwd& f, const Stage& s, const StagePlan& p, long L, int lm, const float** src) {
+    rvcmi_nsf* h = f.h;
+    const int C = s.cout, nk = (int)s.rb.size(), B = f.B;
+    char nm[48];
+    snprintf(nm, sizeof(nm), "rb_full_c%d", C);
+    RbFullArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.L = (int)L;
+    ra.lens = f.lens;
+    ra.lmul = lm;
+    ra.bstride = L * C;
+    ra.dbg = dbg_flags(h);
+    ra.yh = p.stage_half ? 1 : 0;
+    ra.xh = p.x0_half ? 1 : 0;
+    const int R = p.small64 ? RBF64S_ROWS : rbf_rows(C);
+    int order[RVCMI_MAX_RB];
+    rb_order(s, order);
+    int max_tiles = 0;
+    double flops = 0, bytes = 0;
+    for (int oj = 0; oj < nk; ++oj) {
+        const int j = order[oj];
+        RbFullJob& J = ra.job[oj];
+        J.src = h->X0.as<float>();
+        J.dst = h->Ya[j].as<float>();
+        J.nd = (int)s.rb[j].size();
+        fill_rb_job(J, s.rb[j], 0, J.nd, L, B, C, flops, bytes);
+        for (int m = 0; m < J.nd; ++m)
+            if (J.dil[m] * (J.k - 1) / 2 + J.dil[m] > RBF_G) RVCMI_FAIL(RVCMI_ERR_INVALID, "dilation too large for the fused resblock");
+        J.HL = rbf_halo(s.rb[j]);
+        J.tvalid = R - 2 * J.HL;
+        if (J.tvalid < R / 4) RVCMI_FAIL(RVCMI_ERR_INVALID, "resblock halo too large for the fused kernel");
+        J.ntiles = (int)((L + J.tvalid - 1) / J.tvalid);
+        max_tiles = std::max(max_tiles, J.ntiles);
+        bytes += (double)B * L * C * ((p.stage_half ? 2 : 4) + (p.x0_half ? 2 : 4));
+        src[j] = J.dst;
+    }
+    const size_t nblk = (size_t)max_tiles * nk * B;
+    if (ra.dbg & 32) ra.ts = stamp_buffer(h, nblk * 8 * 16, f.st);
+    h->prof.launch(nm, flops, bytes, f.st, [&] {
+        if (f.op == RVCMI_OPERAND_BF16) launch_rbf_t<__bf16>(C, ra, max_tiles, nk, B, f.st, p.small64);
+        else launch_rbf_t<_Float16>(C, ra, max_tiles, nk, B, f.st, p.small64);
+    });
+    HIP_CHECK(hipGetLastError());
+    if (ra.dbg & 32) {  // waves per block: the stamp rows of a tile
+        const int nwv = p.small64 ? RBF64S_NWV : (C == 64 ? RbFullGeom<64>::NWV : RBF32_NWV);
+        print_stamps(h, nm, ra, nk, max_tiles, nwv, 16, nblk, f.st);
+    }
+}
+
+// One launch per pair level, heaviest kernel size first.  At C = 256 the streaming kernel (ND = 1) takes a level where its planner accepts it.
+static void rb_pair(const Fwd& f, const Stage& s, long L, int lm, const float** src) {
+    rvcmi_nsf* h = f.h;
+    const int op = f.op, C = s.cout, nk = (int)s.rb.size(), B = f.B;
+    const int mode = rb_stream_mode(h);
+    char nm[48], nms[48];
+    snprintf(nm, sizeof(nm), "rb_pair_c%d", C);
+    snprintf(nms, sizeof(nms), "rb_stream1_c%d", C);
+    int order[RVCMI_MAX_RB];
+    rb_order(s, order);
+    constexpr int NWp = 8;  // upper bound of waves per block across the pair-kernel geometries (stamp rows)
+    for (size_t m = 0; m < max_levels(s); ++m) {
+        RbPairArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.lens = f.lens;
+        ra.lmul = lm;
+        ra.L = (int)L;
+        ra.bstride = L * C;
+        ra.dbg = dbg_flags(h);
+        RbStreamDesc sd[RVCMI_MAX_RB];
+        float* dsts[RVCMI_MAX_RB] = {nullptr};
+        int nj = 0, max_tiles = 0, max_rows = 0;
+        double flops = 0, bytes = 0;
+        for (int oj = 0; oj < nk; ++oj) {
+            const int j = order[oj];
+            if (m >= s.rb[j].size()) continue;
+            RbStreamDesc& d = sd[nj];
+            memset(&d, 0, sizeof(d));
+            d.src = src[j];
+            d.dst = dsts[j] = ydst(h, j, m);
+            d.lens = f.lens;
+            d.lmul = lm;
+            fill_rb_job(d, s.rb[j], (int)m, 1, L, B, C, flops, bytes);
+            bytes += (double)B * L * C * 8;
+            RbJob& J = ra.job[nj++];
+            J.src = d.src; J.dst = d.dst; J.w1 = d.w1[0]; J.w2 = d.w2[0]; J.b1 = d.b1[0]; J.b2 = d.b2[0];
+            J.ct1 = d.ct1; J.ct2 = d.ct2; J.k = d.k; J.k_p = d.k_p; J.dil = d.dil[0];
+            J.tt2 = rb_rows(C) - (J.k - 1);
+            J.ntiles = (int)((L + J.tt2 - 1) / J.tt2);
+            max_tiles = std::max(max_tiles, J.ntiles);
+            max_rows = std::max(max_rows, rb_rows(C) + (J.k_p - 1) * J.dil);
+        }
+        const size_t nblk = (size_t)max_tiles * nj * B;
+        if (ra.dbg & 32) ra.ts = stamp_buffer(h, nblk * NWp * 8, f.st);
+        bool streamed = false;
+        if (mode != 0 && rb_stream_supported(op, C, 1) && rb_stream_launch(op, C, 1, sd, nj, (int)L, B, L * C, mode == 1, f.st, h->opt, true))
+            h->prof.launch(nms, flops, bytes, f.st, [&] { streamed = rb_stream_launch(op, C, 1, sd, nj, (int)L, B, L * C, mode == 1, f.st, h->opt); });
+        if (!streamed) h->prof.launch(nm, flops, bytes, f.st, [&] { launch_rb_pair(op, C, ra, max_tiles, nj, B, max_rows, f.st); });
+        if ((ra.dbg & 32) && m == 0) print_stamps(h, nm, ra, nj, max_tiles, NWp, 8, nblk, f.st);  // (pair level 0)
+        for (int j = 0; j < nk; ++j)
+            if (dsts[j]) src[j] = dsts[j];
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// ---- x = tanh(conv_post(leaky_relu(x)))                                    nsf.py:187-189
+static void conv_post(const Fwd& f, const Act& x, float* out) {
+    rvcmi_nsf* h = f.h;
+    const int B = f.B, C = x.C, L = (int)x.L;
+    hipStream_t st = f.st;
+    const int dbg = h->opt.geti("POST_DBG", 0);
+    h->prof.launch("conv_post", 2.0 * 7 * C * (double)x.L * B, (double)B * x.L * (C * h->cfg.n_resblock_kernels * (x.half ? 2 : 4) + 4), st, [&] {
+        // round 6: three fp16 streams (every shipped config) through the LDS-DMA kernel: persistent blocks (3 per CU), next tile in flight
+        // (option POST_DMA = 0: k_post)
+        if (x.half && x.y[1] && x.y[2] && x.div == 3.f && (C == 32 || C == 16) && h->opt.geti("POST_DMA", 1) != 0) {
+            const int ntiles = (L + POSTD_TT - 1) / POSTD_TT;
+            const dim3 grid((unsigned)std::min(ntiles, std::max(1, num_cus() * 3 / B)), B);
+            const _Float16* y0 = (const _Float16*)x.y[0];
+            const _Float16* y1 = (const _Float16*)x.y[1];
+            const _Float16* y2 = (const _Float16*)x.y[2];
+            if (C == 32)
+                hipLaunchKernelGGL(k_post_dma<32>, grid, dim3(POSTD_TT), post_dma_smem<32>(), st, y0, y1, y2, h->post_w.as<float>(), out, L, f.lens, x.lm, dbg);
+            else
+                hipLaunchKernelGGL(k_post_dma<16>, grid, dim3(POSTD_TT), post_dma_smem<16>(), st, y0, y1, y2, h->post_w.as<float>(), out, L, f.lens, x.lm, dbg);
+            return;
+        }
+        const size_t smem = (size_t)(7 * C + (POST_TT + 6) * (C + 4)) * 4;
+        hipLaunchKernelGGL(k_post, dim3((unsigned)((L + POST_TT - 1) / POST_TT), B), dim3(256), smem, st, x.y[0], x.y[1], x.y[2],
+                           h->post_w.as<float>(), out, L, C, x.div, x.half ? 1 : 0, f.lens, x.lm, dbg);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+// The fp32 [B][L][C] rows of X0 (the "up<i>" tap): an fp16 X0 is widened first.
+static void tap_x0(const Fwd& f, const StagePlan& p, long L, int C) {
+    rvcmi_nsf* h = f.h;
+    if (!p.x0_half) return copy_tap_cl(h, h->X0.as<float>(), f.B, (int)L, C, f.tr, f.st);
+    const size_t n = (size_t)f.B * L * C;
+    hipLaunchKernelGGL(k_h2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, f.st, (const _Float16*)h->X0.p, h->Ya[0].as<float>(), n);
+    copy_tap_cl(h, h->Ya[0].as<float>(), f.B, (int)L, C, f.tr, f.st);
+}
+
+// The un-divided sum of the stage's resblock outputs (the "stage<i>" tap).
+static void tap_stage(const Fwd& f, const Act& x) {
+    rvcmi_nsf* h = f.h;
+    const size_t n = (size_t)f.B * x.L * x.C;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (x.half)
+        hipLaunchKernelGGL(k_sum3h, grid, dim3(256), 0, f.st, (const _Float16*)x.y[0], (const _Float16*)x.y[1], (const _Float16*)x.y[2],
+                           h->X0.as<float>(), n);
+    else
+        hipLaunchKernelGGL(k_sum3, grid, dim3(256), 0, f.st, x.y[0], x.y[1], x.y[2], h->X0.as<float>(), n);
+    copy_tap_cl(h, h->X0.as<float>(), f.B, (int)x.L, x.C, f.tr, f.st);
+}
+
 // `lens`: optional device array [B] of valid frames per item (1 <= lens[b] <= T): a ragged batch, every item computed exactly as
 // a separate call of its own length (nsf_kernels.hpp item_rows); the output rows behind an item's end are zero.
 static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float* x, const float* f0, const float* g,
@@ -828,578 +1357,37 @@ static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float
         RVCMI_FAIL(RVCMI_ERR_NOMEM, "shape B=%d T=%d n_res=%d exceeds handle limits (max_B=%d max_T=%d)", B, T, n_res,
                    h->max_B, h->max_T);
     HIP_CHECK(hipSetDevice(h->device));
-    const int upp = h->upp, inter = c.inter_channels, C0 = h->C0;
-    const int op = c.operand;
-    auto want = [&](const char* w) { return tr && strcmp(tr->what, w) == 0; };
-
-    // ---- excitation: har[B][Te*upp]                                           nsf.py:152-153
-    const float* har = nullptr;
-    if (c.use_f0) {
-        h->prof.launch("phase_scan", 0, (double)B * T * 8, st, [&] {
-            hipLaunchKernelGGL(k_phase_scan, dim3(B), dim3(256), 0, st, f0, h->phase.as<float>(), T, (float)c.sr, (float)upp, lens);
-        });
-        const size_t total = (size_t)B * T * upp;
-        h->prof.launch("sine_source", 0, (double)total * (noise ? 8 : 4), st, [&] {
-            hipLaunchKernelGGL(k_sine_source, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, f0,
-                               h->phase.as<float>(), noise, h->har.as<float>(), T, upp, (float)c.sr, h->lin_w, h->lin_b, total);
-        });
-        har = h->har.as<float>();
-        if (n_res >= 0 && Te != T) {  // nsf.py:155-159
-            const size_t tot2 = (size_t)B * Te * upp;
-            hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, st, har,
-                               h->har2.as<float>(), T * upp, Te * upp, tot2);
-            har = h->har2.as<float>();
-        }
-        HIP_CHECK(hipGetLastError());
-        if (want("har")) {
-            const size_t n = (size_t)B * Te * upp;
-            if (n > tr->capacity) RVCMI_FAIL(RVCMI_ERR_NOMEM, "tap capacity");
-            HIP_CHECK(hipMemcpyAsync(tr->out_host, har, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            tr->shape[0] = B; tr->shape[1] = 1; tr->shape[2] = (int64_t)Te * upp;
-            tr->done = true;
-            return;
-        }
-    }
-    if (n_res >= 0 && Te != T) {  // nsf.py:160-162 / generators.py:76-79
-        const size_t tot = (size_t)B * inter * Te;
-        hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, h->x2.as<float>(), T, Te, tot);
-        x = h->x2.as<float>();
-    }
-    // ---- conv_pre + cond                                                       nsf.py:164-166
-    if (g && c.gin_channels) {
-        hipLaunchKernelGGL(k_cond, dim3((C0 + 3) / 4, B), dim3(256), 0, st, g, h->cond_w.as<float>(),
-                           h->cond_b.as<float>(), h->condv.as<float>(), c.gin_channels, C0);
-    }
-    float* P = h->P.as<float>();
-    // round 6: on the MFMA path conv_pre writes the ACTIVATED OPERANDS to_op(lrelu(conv + bias + cond, 0.1)) -- the only thing stage 0's upsampler does
-    // with P is to compute exactly that while staging (12 blocks per time tile each re-read and re-converted the fp32 rows) -- unless the fp32 "pre" tap is asked for
-    const bool pre_op = op != RVCMI_OPERAND_F32 && !want("pre") && h->opt.geti("PRE_OP", 1) != 0;
-    {
-        ConvArgs a = base_args();
-        a.in = x;
-        a.in_bstride = (long)inter * Te;
-        a.Lin = Te;
-        a.in_mode = IN_F32_CF;
-        a.Lq = Te;
-        a.out_mode = pre_op ? OUT_ACT : OUT_F32;
-        a.out = P;
-        a.out_bstride = (long)Te * C0;
-        a.out_C = C0;
-        a.cb = (g && c.gin_channels) ? h->condv.as<float>() : nullptr;
-        a.lens = lens;
-        a.lmul_in = a.lmul_q = 1;
-        run_conv(h, h->pre, a, B, "conv_pre", st);
-    }
-    if (want("pre")) return copy_tap_cl(h, P, B, Te, C0, tr, st);
-
-    // The running activation is ((y[0] + y[1]) + y[2]) / div  (nsf.py:177-186); stage 0 reads P alone.
-    const float* y[3] = {P, nullptr, nullptr};
-    bool yhalf = false;  // y[] are fp16 streams (written by k_rb_stream ND = 3 / k_rb_full under option Y_F16)
-    float div = 1.f;
-    long L = Te;
-    int Cprev = C0;
-    int lm = 1;  // rows per frame at the current stage (ragged batches: item rows = lens[b] * lm)
+    Fwd f{h, c.operand, B, Te, lens, nullptr, st, tr};
+    if (c.use_f0 && excitation(f, T, f0, noise)) return;
+    Act a = conv_pre(f, x, T, g);
+    if (f.want("pre")) return copy_tap_cl(h, a.y[0], B, Te, h->C0, tr, st);
+    char nm[48];
     for (int i = 0; i < c.n_ups; ++i) {
-        Stage& s = h->stages[i];
-        const long Lin = L;
-        const int lm_prev = lm;
-        lm *= s.u;
-        L = Lin * s.u;
-        const int C = s.cout;
-        const int nk = (int)s.rb.size();
-        size_t maxnd0 = 0;
-        for (int j = 0; j < nk; ++j) maxnd0 = std::max(maxnd0, s.rb[j].size());
-        // X0 of this stage is fp16: where the consumer is k_rb_full (C <= 64), and -- round 5 -- where the whole resblocks WILL run on the
-        // streaming kernel with its coalesced step IO (C = 128 on clips long enough for strips; decided by a dry run of the planner)
-        // ... decided HERE, once, together with the branch the ResBlocks will take below: the conv-by-conv path for a handful of rows reads X0
-        // as fp32 (IN_F32_ACT) and comes BEFORE the streaming kernel in that chain, so it must veto the fp16 X0 explicitly (ADVICE round 5:
-        // the two could not coincide only because the planner happens to refuse such short launches)
-        const bool rb_split = op != RVCMI_OPERAND_F32 &&
-                              ((C == 256 && (long)B * L <= RB_SPLIT_MAX_ROWS) || (C == 128 && (long)B * L <= RB_SPLIT_MAX_ROWS_128 && !h->opt.on("NO_RB_SPLIT128"))) &&
-                              nk <= 3 && !h->opt.on("NO_RB_SPLIT") && rb_stream_mode(h) != 1;
-        // (round 6, review item 4: the same conv-by-conv launches for a FULL-length stage 0 with 64-channel x 256-row blocks -- 684 blocks per launch, no halo
-        //  recompute -- were built as a dev option, parity-green, and measured 0.61 ms against k_rb_pair<256>'s 0.284 ms; removed)
-        const bool x0h_stream = op != RVCMI_OPERAND_F32 && !rb_split && C > 64 && y_f16(h) && h->opt.geti("X0_F16", 1) != 0 && !h->opt.on("X0_F16_NOSTREAM") &&
-                                try_rb_stream_full(h, s, op, C, (int)L, B, nk, nullptr, st, lens, lm, true, true);
-        const bool x0h = op != RVCMI_OPERAND_F32 && (x0_f16(h, C, maxnd0) || x0h_stream);
-        char nm[48];
-        if (op == RVCMI_OPERAND_F32) {
-            {  // x = ups[i](leaky_relu(x, 0.1))                                nsf.py:171-172
-                ConvArgs a = base_args();
-                a.in = y[0];
-                a.in_b = y[1];
-                a.in_c = y[2];
-                a.in_bstride = Lin * Cprev;
-                a.Lin = (int)Lin;
-                a.in_mode = IN_F32_ACT;
-                a.div_in = div;
-                a.Lq = (int)Lin;
-                a.out_mode = OUT_F32;
-                a.out = h->X0.p;
-                a.out_bstride = L * C;
-                a.out_C = C;
-                a.out_mul = s.u;
-                a.lens = lens;
-                a.lmul_in = a.lmul_q = lm_prev;
-                snprintf(nm, sizeof(nm), "ups_c%d", s.cin);
-                run_conv(h, s.up, a, B, nm, st);
-            }
-            if (c.use_f0) {  // x = x + noise_convs[i](har)                       nsf.py:173-174
-                const size_t n = (size_t)L * C;
-                snprintf(nm, sizeof(nm), "noise_conv_c%d", C);
-                h->prof.launch(nm, 2.0 * s.nk * n * B, (double)B * n * 8, st, [&] {
-                    hipLaunchKernelGGL(k_noise_add, dim3((unsigned)((n + 255) / 256), 1, B), dim3(256), 0, st, h->X0.as<float>(),
-                                       har, s.noise_w.as<float>(), s.noise_b.as<float>(), (int)L, C, Te * upp, s.nk, s.ns, s.npad, lens, lm, upp);
-                });
-            }
-        } else {  // ups + bias + noise conv in one MFMA kernel, X0 written once      nsf.py:171-174
-            const ConvLayer& U = s.up;
-            UpsArgs ua;
-            memset(&ua, 0, sizeof(ua));
-            ua.dbg = dbg_flags(h);
-            ua.bias_off = h->opt.geti("UPS_BL", 1) != 0 ? 1 : 0;  // (the launcher turns it into the LDS offset)
-            ua.in_a = y[0];
-            ua.in_b = y[1];
-            ua.in_c = y[2];
-            ua.in_half = yhalf ? 1 : 0;
-            ua.in_raw = (i == 0 && pre_op) ? 1 : 0;  // (stage 0: y[0] = P holds operands already)
-            ua.lens = lens;
-            ua.lmul = lm_prev;
-            ua.lhmul = upp;
-            ua.Lh_stride = Te * upp;
-            ua.div = div;
-            ua.Lin = (int)Lin;
-            ua.cin = s.cin;
-            ua.in_bstride = Lin * Cprev;
-            ua.w = U.w_pack.p;
-            ua.ct_stride = U.ct_stride;
-            int lo = 1 << 30, hi = -(1 << 30);
-            for (int r = 0; r < s.u; ++r) {
-                ua.ph_w_off[r] = U.pack_off[r];
-                ua.ph_in_off[r] = U.in_off[r];
-                lo = std::min(lo, U.in_off[r] - (U.ntaps_p - 1));
-                hi = std::max(hi, U.in_off[r]);
-            }
-            ua.ntaps_p = U.ntaps_p;
-            ua.u = s.u;
-            ua.cout = C;
-            ua.lo = lo;
-            ua.bias = U.bias.as<float>();
-            ua.out = h->X0.as<float>();
-            ua.out_half = x0h ? 1 : 0;
-            ua.out_tr = h->opt.geti("UPS_TR", 1) != 0 ? 1 : 0;  // (the launcher clears it where the block does not own whole rows)
-            ua.out_tw_off = h->opt.geti("UPS_TW", 1) != 0 ? 1 : 0;  // (the launcher turns it into the LDS offset where it applies)
-            ua.out_bstride = L * C;
-            if (c.use_f0 && s.nz_mfma) {  // noise_convs[i](har) as a 2-tap MFMA conv over frames -> NZ, added in k_ups' epilogue
-                ConvArgs na = base_args();
-                na.in = har;
-                na.in_bstride = (long)Te * upp;
-                na.Lin = Te * upp;
-                na.in_mode = IN_HAR;
-                na.hs = s.ns;
-                na.hpad = s.npad;
-                na.Lq = (int)L;
-                na.out_mode = OUT_F32;
-                na.out = h->NZ.p;
-                na.out_bstride = L * C;
-                na.out_C = C;
-                na.lens = lens;
-                na.lmul_in = upp;
-                na.lmul_q = lm;
-                snprintf(nm, sizeof(nm), "noise_mfma_c%d", C);
-                run_conv(h, s.nz, na, B, nm, st);
-                ua.addend = h->NZ.as<float>();
-            } else if (c.use_f0) {
-                ua.nz_k1 = s.nz_k1 ? 1 : 0;
-                ua.wnz = s.nz_k1_w.p;
-                ua.har = har;
-                ua.Lh = Te * upp;
-                ua.Wn = s.noise_w.as<float>();
-                ua.bn = s.noise_b.as<float>();
-                ua.nk = s.nk;
-                ua.ns = s.ns;
-                ua.npad = s.npad;
-            }
-            const int MIu = C >= 64 ? 2 : 1;
-            ua.cog = (C + 32 * MIu - 1) / (32 * MIu);
-            ua.nvt = s.u * ua.cog;
-            const int wv = ua.nvt >= 4 ? 4 : (ua.nvt >= 2 ? 2 : 1);
-            // time-tile height: blocks have equal duration, so a launch of ~1.1 x (resident blocks) runs two rounds for one
-            // round of work; pick the largest tile that still gives >= 4 rounds of blocks (2 resident blocks per CU)
-            // (measured at B = 1, same box, us: C_in 512: 52 / 36 / 37 for NJ 4 / 2 / 1; 256: 94 / 95 / 85; 128: 131 / 118 / 110;
-            //  64 -> 32 channels: 98 / 102 / 150 -- with one 32-channel tile per wave, short tiles starve the MFMA of columns)
-            int nj = 4;
-            const long blocks4 = (long)((Lin + 128 * (4 / wv) - 1) / (128 * (4 / wv))) * B;
-            if (blocks4 < 2048 && s.cin >= 128) nj = s.cin >= 512 ? 2 : 1;
-            else if (blocks4 < 2048 && s.cin == 64) nj = 2;  // (us at B = 1 after the staging fix: 84 / 75 / 89 for NJ 4 / 2 / 1)
-            // large grids (round 4, fp16 inputs + row-wise stores; us per clip at B = 16 for NJ 4 / 1 / 2, ABAB: C_in 128: 77 / 67 / 83,
-            // 64: 70 / 73 / 55): the short tiles win there too -- they also keep the output tile inside the row-wise store's LDS budget
-            else if (s.cin >= 512) nj = 2;   // (C_in 512: 22 vs 29 us for NJ 2 / 4; C_in 256 keeps NJ = 4: 52 vs 57)
-            else if (s.cin == 128) nj = 1;
-            else if (s.cin == 64) nj = 2;
-            if (h->opt.has("UPS_NJ")) {
-                const int v = h->opt.geti("UPS_NJ", nj);
-                if (v == 1 || v == 2 || v == 4) nj = v;
-            }
-            // (round 6: NJ 2 / 4 and vpw 1 / 2 for the C_in = 256 stage alone, 8 variants x 2, ABAB: 72-110 us against 60 -- every one loses)
-            const int TQ = 32 * nj * (4 / wv);
-            ua.tile_rows = TQ + (hi - lo);
-            const long qtiles = (Lin + TQ - 1) / TQ;
-            int vpw = (ua.nvt + wv - 1) / wv;  // everything in one block ...
-            while (vpw > 1 && qtiles * B * ((ua.nvt + wv * vpw - 1) / (wv * vpw)) < 300) --vpw;  // ... unless the grid would starve
-            ua.vpw = vpw;
-            snprintf(nm, sizeof(nm), "ups_c%d", s.cin);
-            const double flops = U.flops_per_pos * (double)Lin * B + 2.0 * s.nk * (double)L * C * B;
-            const double bytes = (double)B * Lin * Cprev * (yhalf ? 2 : 4) * (y[1] ? (y[2] ? 3 : 2) : 1) + (double)B * L * C * (x0h ? 2 : 4);
-            h->prof.launch(nm, flops, bytes, st, [&] {
-                if (op == RVCMI_OPERAND_BF16) launch_ups_t<__bf16>(ua, wv, nj, B, st);
-                else launch_ups_t<_Float16>(ua, wv, nj, B, st);
-            });
-            HIP_CHECK(hipGetLastError());
-        }
+        const Stage& s = h->stages[i];
+        const long L = a.L * s.u;
+        const int lm = a.lm * s.u, C = s.cout;
+        const StagePlan p = plan_stage(f, s, L, lm);
+        if (f.op == RVCMI_OPERAND_F32) ups_f32(f, s, a, L, lm);
+        else ups_mfma(f, s, a, p, L, lm);
         snprintf(nm, sizeof(nm), "up%d", i);
-        if (want(nm)) {
-            if (x0h) {  // widen the fp16 X0 for the tap
-                const size_t n = (size_t)B * L * C;
-                hipLaunchKernelGGL(k_h2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const _Float16*)h->X0.p, h->Ya[0].as<float>(), n);
-                return copy_tap_cl(h, h->Ya[0].as<float>(), B, (int)L, C, tr, st);
-            }
-            return copy_tap_cl(h, h->X0.as<float>(), B, (int)L, C, tr, st);
-        }
-
-        // resblocks[i*nk + j](x), j < nk                                         nsf.py:175-185
-        size_t maxnd = 0;
-        for (int j = 0; j < nk; ++j) maxnd = std::max(maxnd, s.rb[j].size());
+        if (f.want(nm)) return tap_x0(f, p, L, C);
         const float* src[RVCMI_MAX_RB];
-        for (int j = 0; j < nk; ++j) src[j] = h->X0.as<float>();
-        bool stage_half = false;  // this stage's resblock outputs are fp16 streams
-        if (op == RVCMI_OPERAND_F32) {
-            snprintf(nm, sizeof(nm), "rb_c%d", C);
-            for (int j = 0; j < nk; ++j)
-                for (size_t m = 0; m < s.rb[j].size(); ++m) {  // residuals.py:73-82
-                    float* dst = (m & 1) ? h->Yb[j].as<float>() : h->Ya[j].as<float>();
-                    ConvArgs a = base_args();
-                    a.in = src[j];
-                    a.in_bstride = L * C;
-                    a.Lin = (int)L;
-                    a.in_mode = IN_F32_ACT;
-                    a.Lq = (int)L;
-                    a.lens = lens;
-                    a.lmul_in = a.lmul_q = lm;
-                    a.out_mode = OUT_ACT;
-                    a.out = h->H.p;
-                    a.out_bstride = L * C;
-                    a.out_C = C;
-                    run_conv(h, s.rb[j][m].first, a, B, nm, st);
-                    a = base_args();
-                    a.in = h->H.p;
-                    a.in_bstride = L * C;
-                    a.Lin = (int)L;
-                    a.in_mode = IN_OP_RAW;
-                    a.Lq = (int)L;
-                    a.lens = lens;
-                    a.lmul_in = a.lmul_q = lm;
-                    a.out_mode = OUT_F32;
-                    a.out = dst;
-                    a.out_bstride = L * C;
-                    a.out_C = C;
-                    a.res = src[j];
-                    a.res_bstride = L * C;
-                    run_conv(h, s.rb[j][m].second, a, B, nm, st);
-                    src[j] = dst;
-                }
-        } else if (rb_split) {
-            // a handful of rows (realtime chunk): conv1 / conv2 of all resblocks as two output-channel-split launches per pair level
-            snprintf(nm, sizeof(nm), "rb_split_c%d", C);
-            for (size_t m = 0; m < maxnd; ++m) {
-                const ConvLayer* L1[3];
-                const ConvLayer* L2[3];
-                ConvArgs a1[3], a2[3];
-                int nj = 0;
-                for (int j = 0; j < nk; ++j) {
-                    if (m >= s.rb[j].size()) continue;
-                    float* dst = (m & 1) ? h->Yb[j].as<float>() : h->Ya[j].as<float>();
-                    void* hbuf = (char*)h->H.p + (size_t)nj * (h->H.bytes / 3);
-                    ConvArgs a = base_args();
-                    a.in = src[j];
-                    a.in_bstride = L * C;
-                    a.Lin = (int)L;
-                    a.in_mode = IN_F32_ACT;
-                    a.Lq = (int)L;
-                    a.lens = lens;
-                    a.lmul_in = a.lmul_q = lm;
-                    a.out_mode = OUT_ACT;
-                    a.out = hbuf;
-                    a.out_bstride = L * C;
-                    a.out_C = C;
-                    a1[nj] = a;
-                    L1[nj] = &s.rb[j][m].first;
-                    a = base_args();
-                    a.in = hbuf;
-                    a.in_bstride = L * C;
-                    a.Lin = (int)L;
-                    a.in_mode = IN_OP_RAW;
-                    a.Lq = (int)L;
-                    a.lens = lens;
-                    a.lmul_in = a.lmul_q = lm;
-                    a.out_mode = OUT_F32;
-                    a.out = dst;
-                    a.out_bstride = L * C;
-                    a.out_C = C;
-                    a.res = src[j];
-                    a.res_bstride = L * C;
-                    a2[nj] = a;
-                    L2[nj] = &s.rb[j][m].second;
-                    src[j] = dst;
-                    ++nj;
-                }
-                if (!nj) continue;
-                run_conv_jobs(h, L1, a1, nj, B, nm, st);
-                run_conv_jobs(h, L2, a2, nj, B, nm, st);
-            }
-        } else if (try_rb_stream_full(h, s, op, C, (int)L, B, nk, src, st, lens, lm, x0h_stream)) {
-            // streaming fused resblocks (rb_stream_kernels.hpp): persistent blocks walk strips of the time axis
-            stage_half = y_f16(h);
-        } else if (C <= 64 && maxnd <= 3 && !h->opt.on("NO_RBFULL")) {
-            // whole resblocks fused (x resident in registers): ONE launch for the stage   residuals.py:68-85
-            snprintf(nm, sizeof(nm), "rb_full_c%d", C);
-            RbFullArgs ra;
-            memset(&ra, 0, sizeof(ra));
-            ra.L = (int)L;
-            ra.lens = lens;
-            ra.lmul = lm;
-            ra.bstride = L * C;
-            ra.dbg = dbg_flags(h);
-            stage_half = y_f16(h);
-            ra.yh = stage_half ? 1 : 0;
-            ra.xh = x0h ? 1 : 0;
-            // (C = 64) short launches take 256-row tiles: at 512 rows they would be fewer blocks than half the CUs (halo of the k = 11
-            // resblock: 120 rows either way -- the small tiles keep 136 of 256 rows; option RBF_SMALL 0 / 1 pins the choice)
-            bool small64 = false;
-            if (C == 64 || C == 32) {
-                long blocks512 = 0;
-                for (int j = 0; j < nk; ++j) {
-                    int dsum = 0;
-                    for (size_t m = 0; m < s.rb[j].size(); ++m) dsum += s.rb[j][m].first.dstep;
-                    const int k = s.rb[j][0].first.ntaps[0];
-                    const int HL = (k - 1) / 2 * (dsum + (int)s.rb[j].size());
-                    blocks512 += (L + (rbf_rows(C) - 2 * HL) - 1) / (rbf_rows(C) - 2 * HL) * B;
-                    if (RBF64S_ROWS - 2 * HL < RBF64S_ROWS / 4) blocks512 = 1 << 30;  // (halo too large for the small tile)
-                }
-                small64 = h->opt.has("RBF_SMALL") ? h->opt.geti("RBF_SMALL", 0) != 0 && blocks512 < (1 << 30) : blocks512 < num_cus() / 2 * (C == 64 ? 1 : 2);
-            }
-            const int R = small64 ? RBF64S_ROWS : rbf_rows(C);
-            int order[RVCMI_MAX_RB];
-            for (int j = 0; j < nk; ++j) order[j] = j;
-            std::sort(order, order + nk, [&](int a1, int b1) { return s.rb[a1][0].first.ntaps[0] > s.rb[b1][0].first.ntaps[0]; });
-            int max_tiles = 0;
-            double flops = 0, bytes = 0;
-            for (int oj = 0; oj < nk; ++oj) {
-                const int j = order[oj];
-                RbFullJob& J = ra.job[oj];
-                J.src = h->X0.as<float>();
-                J.dst = h->Ya[j].as<float>();
-                J.nd = (int)s.rb[j].size();
-                J.k = s.rb[j][0].first.ntaps[0];
-                J.k_p = s.rb[j][0].first.ntaps_p;
-                J.ct1 = s.rb[j][0].first.ct_stride;
-                J.ct2 = s.rb[j][0].second.ct_stride;
-                int dsum = 0;
-                for (int m = 0; m < J.nd; ++m) {
-                    const ConvLayer& c1 = s.rb[j][m].first;
-                    const ConvLayer& c2 = s.rb[j][m].second;
-                    J.w1[m] = c1.w_pack.p;
-                    J.w2[m] = c2.w_pack.p;
-                    J.b1[m] = c1.bias.as<float>();
-                    J.b2[m] = c2.bias.as<float>();
-                    J.dil[m] = c1.dstep;
-                    dsum += c1.dstep;
-                    flops += (c1.flops_per_pos + c2.flops_per_pos) * (double)L * B;
-                    bytes += 2.0 * J.k * C * C * 2;
-                    if (c1.dstep * (J.k - 1) / 2 + c1.dstep > RBF_G) RVCMI_FAIL(RVCMI_ERR_INVALID, "dilation too large for the fused resblock");
-                }
-                J.HL = (J.k - 1) / 2 * (dsum + J.nd);
-                J.tvalid = R - 2 * J.HL;
-                if (J.tvalid < R / 4) RVCMI_FAIL(RVCMI_ERR_INVALID, "resblock halo too large for the fused kernel");
-                J.ntiles = (int)((L + J.tvalid - 1) / J.tvalid);
-                max_tiles = std::max(max_tiles, J.ntiles);
-                bytes += (double)B * L * C * ((stage_half ? 2 : 4) + (x0h ? 2 : 4));
-                src[j] = J.dst;
-            }
-            const size_t nblk = (size_t)max_tiles * nk * B;
-            if (ra.dbg & 32) {
-                if (h->dbg.bytes < nblk * 8 * 16 * 8) h->dbg.alloc(nblk * 8 * 16 * 8);
-                HIP_CHECK(hipMemsetAsync(h->dbg.p, 0, nblk * 8 * 16 * 8, st));
-                ra.ts = h->dbg.as<unsigned long long>();
-            }
-            h->prof.launch(nm, flops, bytes, st, [&] {
-                if (op == RVCMI_OPERAND_BF16) launch_rbf_t<__bf16>(C, ra, max_tiles, nk, B, st, h->opt, small64);
-                else launch_rbf_t<_Float16>(C, ra, max_tiles, nk, B, st, h->opt, small64);
-            });
-            HIP_CHECK(hipGetLastError());
-            if (ra.dbg & 32) {  // dev only: per-phase cycle breakdown, averaged per resblock kernel size
-                HIP_CHECK(hipStreamSynchronize(st));
-                const int nwv = small64 ? RBF64S_NWV : (C == 64 ? RbFullGeom<64>::NWV : RBF32_NWV);  // waves per block: the stamp rows of a tile
-                std::vector<unsigned long long> ts(nblk * nwv * 16);
-                HIP_CHECK(hipMemcpy(ts.data(), h->dbg.p, ts.size() * 8, hipMemcpyDeviceToHost));
-                for (int oj = 0; oj < nk; ++oj) {
-                    double sum[16] = {0};
-                    long cnt = 0;
-                    for (int t = 0; t < ra.job[oj].ntiles; ++t)
-                        for (int w = 0; w < nwv; ++w) {
-                            const unsigned long long* p = &ts[(((size_t)(0 * nk + oj) * max_tiles + t) * nwv + w) * 16];
-                            if (!p[0]) continue;
-                            for (int i = 1; i < 16; ++i) sum[i] += p[i] ? (double)(p[i] - p[i - 1]) : 0.0;
-                            ++cnt;
-                        }
-                    fprintf(stderr, "[rvcmi ts] %s k=%d tiles=%d:", nm, ra.job[oj].k, ra.job[oj].ntiles);
-                    for (int i = 1; i < 16; ++i) fprintf(stderr, " %.0f", cnt ? sum[i] / cnt : 0.0);
-                    fprintf(stderr, "\n");
-                }
-            }
-        } else {
-            snprintf(nm, sizeof(nm), "rb_pair_c%d", C);
-            // Launch order.  Level-major (one launch = pair level m of all resblocks) maximises the grid; resblock-major
-            // (one launch = one pair of ONE resblock, chains run back to back) keeps a chain's src+dst (2 x L*C*4 B) inside
-            // the 256 MB Infinity Cache when L*C*4*6 does not fit -- chosen per stage by working-set size.
-            const double ws_level = 6.0 * (double)B * L * C * 4;
-            const bool jmajor = h->opt.on("RB_ORDER");
-            (void)ws_level;
-            const size_t npass = jmajor ? (size_t)nk * maxnd : maxnd;
-            for (size_t pass = 0; pass < npass; ++pass) {
-                const size_t m = jmajor ? pass % maxnd : pass;
-                const int only_j = jmajor ? (int)(pass / maxnd) : -1;
-                RbPairArgs ra;
-                memset(&ra, 0, sizeof(ra));
-                ra.lens = lens;
-                ra.lmul = lm;
-                ra.L = (int)L;
-                ra.bstride = L * C;
-                ra.dbg = dbg_flags(h);
-                int nj = 0, max_tiles = 0, max_rows = 0;
-                double flops = 0, bytes = 0;
-                // heaviest kernel size first so that the long blocks are dispatched first
-                int order[RVCMI_MAX_RB];
-                for (int j = 0; j < nk; ++j) order[j] = j;
-                std::sort(order, order + nk, [&](int a1, int b1) {
-                    return s.rb[a1][0].first.ntaps[0] > s.rb[b1][0].first.ntaps[0];
-                });
-                float* dsts[RVCMI_MAX_RB] = {nullptr};
-                for (int oj = 0; oj < nk; ++oj) {
-                    const int j = order[oj];
-                    if (m >= s.rb[j].size()) continue;
-                    if (only_j >= 0 && j != only_j) continue;
-                    const ConvLayer& c1 = s.rb[j][m].first;
-                    const ConvLayer& c2 = s.rb[j][m].second;
-                    RbJob& J = ra.job[nj++];
-                    float* dst = (m & 1) ? h->Yb[j].as<float>() : h->Ya[j].as<float>();
-                    dsts[j] = dst;
-                    J.src = src[j];
-                    J.dst = dst;
-                    J.w1 = c1.w_pack.p;
-                    J.w2 = c2.w_pack.p;
-                    J.b1 = c1.bias.as<float>();
-                    J.b2 = c2.bias.as<float>();
-                    J.ct1 = c1.ct_stride;
-                    J.ct2 = c2.ct_stride;
-                    J.k = c1.ntaps[0];
-                    J.k_p = c1.ntaps_p;
-                    J.dil = c1.dstep;
-                    J.tt2 = rb_rows(C) - (J.k - 1);
-                    J.ntiles = (int)((L + J.tt2 - 1) / J.tt2);
-                    max_tiles = std::max(max_tiles, J.ntiles);
-                    max_rows = std::max(max_rows, rb_rows(C) + (J.k_p - 1) * J.dil);
-                    flops += (c1.flops_per_pos + c2.flops_per_pos) * (double)L * B;
-                    bytes += (double)B * L * C * 8 + 2.0 * J.k * C * C * 2;
-                }
-                if (nj == 0) continue;
-                const int NWp = 8;  // upper bound of waves per block across the pair-kernel geometries
-                const size_t nblk = (size_t)max_tiles * nj * B;
-                if (ra.dbg & 32) {
-                    if (h->dbg.bytes < nblk * NWp * 64) h->dbg.alloc(nblk * NWp * 64);
-                    HIP_CHECK(hipMemsetAsync(h->dbg.p, 0, nblk * NWp * 64, st));
-                    ra.ts = h->dbg.as<unsigned long long>();
-                }
-                bool streamed = false;
-                if (rb_stream_mode(h) != 0 && rb_stream_supported(op, C, 1)) {
-                    RbStreamDesc sd[RVCMI_MAX_RB];
-                    for (int q = 0; q < nj; ++q) {
-                        const RbJob& J = ra.job[q];
-                        memset(&sd[q], 0, sizeof(sd[q]));
-                        sd[q].src = J.src; sd[q].dst = J.dst; sd[q].w1[0] = J.w1; sd[q].w2[0] = J.w2; sd[q].b1[0] = J.b1; sd[q].b2[0] = J.b2;
-                        sd[q].ct1 = J.ct1; sd[q].ct2 = J.ct2; sd[q].k = J.k; sd[q].k_p = J.k_p; sd[q].dil[0] = J.dil;
-                        sd[q].lens = lens; sd[q].lmul = lm;
-                    }
-                    char nms[48];
-                    snprintf(nms, sizeof(nms), "rb_stream1_c%d", C);
-                    const bool force = rb_stream_mode(h) == 1;
-                    if (rb_stream_launch(op, C, 1, sd, nj, (int)L, B, L * C, force, st, h->opt, true))
-                        h->prof.launch(nms, flops, bytes, st, [&] { streamed = rb_stream_launch(op, C, 1, sd, nj, (int)L, B, L * C, force, st, h->opt); });
-                }
-                if (!streamed) h->prof.launch(nm, flops, bytes, st, [&] { launch_rb_pair(op, C, ra, max_tiles, nj, B, max_rows, st); });
-                if ((ra.dbg & 32) && m == 0) {  // dev only: per-phase cycles of pair level 0, per kernel size
-                    HIP_CHECK(hipStreamSynchronize(st));
-                    std::vector<unsigned long long> ts(nblk * NWp * 8);
-                    HIP_CHECK(hipMemcpy(ts.data(), h->dbg.p, ts.size() * 8, hipMemcpyDeviceToHost));
-                    for (int oj = 0; oj < nj; ++oj) {
-                        double sum[8] = {0};
-                        long cnt = 0;
-                        for (int t = 0; t < ra.job[oj].ntiles; ++t)
-                            for (int w = 0; w < NWp; ++w) {
-                                const unsigned long long* p = &ts[(((size_t)oj * max_tiles + t) * NWp + w) * 8];
-                                if (!p[0]) continue;
-                                for (int i = 1; i < 8; ++i) sum[i] += (double)(p[i] - p[i - 1]);
-                                ++cnt;
-                            }
-                        fprintf(stderr, "[rvcmi ts] %s k=%d tiles=%d:", nm, ra.job[oj].k, ra.job[oj].ntiles);
-                        for (int i = 1; i < 8; ++i) fprintf(stderr, " %.0f", cnt ? sum[i] / cnt : 0.0);
-                        fprintf(stderr, "\n");
-                    }
-                }
-                for (int j = 0; j < nk; ++j)
-                    if (dsts[j]) src[j] = dsts[j];
-            }
-            HIP_CHECK(hipGetLastError());
+        for (auto& v : src) v = h->X0.as<float>();
+        switch (p.path) {
+            case RbPath::F32_CHAIN: rb_f32_chain(f, s, L, lm, src); break;
+            case RbPath::SPLIT: rb_split(f, s, L, lm, src); break;
+            case RbPath::STREAM: rb_stream(f, s, p, L, lm, src); break;
+            case RbPath::FULL: rb_full(f, s, p, L, lm, src); break;
+            case RbPath::PAIR: rb_pair(f, s, L, lm, src); break;
         }
-        for (int j = 0; j < 3; ++j) y[j] = j < nk ? src[j] : nullptr;
-        yhalf = stage_half;
-        div = (float)nk;  // x = xs / num_kernels (nsf.py:186) is applied by the consumer
-        Cprev = C;
+        const int nk = (int)s.rb.size();
+        // x = xs / num_kernels (nsf.py:186) is applied by the consumer
+        a = Act{{src[0], nk > 1 ? src[1] : nullptr, nk > 2 ? src[2] : nullptr}, p.stage_half, false, (float)nk, L, C, lm};
         snprintf(nm, sizeof(nm), "stage%d", i);
-        if (want(nm)) {  // the un-divided sum
-            const size_t n = (size_t)B * L * C;
-            if (yhalf)
-                hipLaunchKernelGGL(k_sum3h, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const _Float16*)y[0], (const _Float16*)y[1],
-                                   (const _Float16*)y[2], h->X0.as<float>(), n);
-            else
-            hipLaunchKernelGGL(k_sum3, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, y[0], y[1], y[2], h->X0.as<float>(), n);
-            return copy_tap_cl(h, h->X0.as<float>(), B, (int)L, C, tr, st);
-        }
+        if (f.want(nm)) return tap_stage(f, a);
     }
     if (tr) RVCMI_FAIL(RVCMI_ERR_INVALID, "unknown tap '%s'", tr->what);
-    // ---- x = tanh(conv_post(leaky_relu(x)))                                    nsf.py:187-189
-    const int nkk = c.n_resblock_kernels;
-    h->prof.launch("conv_post", 2.0 * 7 * Cprev * (double)L * B, (double)B * L * (Cprev * nkk * (yhalf ? 2 : 4) + 4), st, [&] {
-        // round 6: three fp16 streams (every shipped config) through the LDS-DMA kernel: persistent blocks, next tile in flight (option POST_DMA = 0: k_post)
-        if (yhalf && y[1] && y[2] && div == 3.f && (Cprev == 32 || Cprev == 16) && h->opt.geti("POST_DMA", 1) != 0) {
-            const int ntiles = (int)((L + POSTD_TT - 1) / POSTD_TT);
-            const int slots = std::max(1, num_cus() * h->opt.geti("POST_DMA_OCC", 3) / B);
-            const dim3 grid((unsigned)std::min(ntiles, slots), B);
-            const int dbg = h->opt.geti("POST_DBG", 0);
-            if (Cprev == 32)
-                hipLaunchKernelGGL(k_post_dma<32>, grid, dim3(POSTD_TT), post_dma_smem<32>(), st, (const _Float16*)y[0], (const _Float16*)y[1],
-                                   (const _Float16*)y[2], h->post_w.as<float>(), out, (int)L, lens, lm, dbg);
-            else
-                hipLaunchKernelGGL(k_post_dma<16>, grid, dim3(POSTD_TT), post_dma_smem<16>(), st, (const _Float16*)y[0], (const _Float16*)y[1],
-                                   (const _Float16*)y[2], h->post_w.as<float>(), out, (int)L, lens, lm, dbg);
-            return;
-        }
-        const size_t smem = (size_t)(7 * Cprev + (POST_TT + 6) * (Cprev + 4)) * 4;
-        hipLaunchKernelGGL(k_post, dim3((unsigned)((L + POST_TT - 1) / POST_TT), B), dim3(256), smem, st, y[0], y[1], y[2],
-                           h->post_w.as<float>(), out, (int)L, Cprev, div, yhalf ? 1 : 0, lens, lm, h->opt.geti("POST_DBG", 0));
-    });
-    HIP_CHECK(hipGetLastError());
+    conv_post(f, a, out);
 }
 
 }  // namespace rvcmi

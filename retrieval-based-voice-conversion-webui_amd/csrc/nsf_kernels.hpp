@@ -1119,9 +1119,9 @@ static __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
     conv_mfma_body<OpT, CIN, MI, NJ, WCO>(a, (int)blockIdx.z, smem);
 }
 
-// The same conv for up to three independent jobs in ONE launch (grid.z = batch x jobs).  Used where a fused resblock launch would
+// Up to three independent convs of one shape in ONE launch (grid.z = batch x jobs).  Used where a fused resblock launch would
 // be a handful of blocks (the realtime chunk: 310 rows at C = 256 = 9 pair tiles, each streaming 2.9 MB of weights through one
-// CU): conv1 / conv2 of all the stage's resblocks as separate, output-channel-split launches of ~70 blocks.
+// CU): conv1 / conv2 of all the stage's resblocks as separate, output-channel-split launches (k_conv_ks_jobs).
 struct ConvJobs {
     ConvArgs job[3];
     int njobs;
@@ -1244,15 +1244,6 @@ static __global__ void __launch_bounds__(256) k_conv_ks_jobs(ConvJobs js) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int j = (int)blockIdx.z % js.njobs, b = (int)blockIdx.z / js.njobs;
     conv_ks_body<OpT, CIN, MI, NJ>(js.job[j], b, smem);
-}
-
-template <typename OpT, int CIN, int MI, int NJ, int WCO>
-static __global__ void __launch_bounds__(256) k_conv_mfma_jobs(ConvJobs js) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int j = (int)blockIdx.z % js.njobs, b = (int)blockIdx.z / js.njobs;
-    // a weight ring of 4 groups (12 k-steps in flight): with one MFMA per k-step (NJ = 1) the default 2 groups cover 4 k-steps =
-    // ~260 cycles, less than one L2 round trip, and the K loop ran at the latency of the weight loads (28 us per launch)
-    conv_mfma_body<OpT, CIN, MI, NJ, WCO, 4, true>(js.job[j], b, smem);
 }
 
 // Branch-free helpers.  lrelu as max(x, slope*x) (0 < slope < 1); row masking by AND-ing the value bits so that
@@ -1380,13 +1371,7 @@ static __global__ void __launch_bounds__(64 * NW * NWT, OCC) k_rb_pair(RbPairArg
     constexpr int CP = 32 * MI * NW;  // padded channel count
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-#ifdef RVCMI_RB_INTERLEAVE
-    // dev experiment: co-resident blocks take different jobs (kernel sizes) so their load / MFMA phases drift apart
-    const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int bjob = lin % gridDim.y, btile = lin / gridDim.y;
-#else
     const int bjob = blockIdx.y, btile = blockIdx.x;
-#endif
     const RbJob& J = a.job[bjob];
     if (btile >= J.ntiles) return;
     const int b = blockIdx.z;
@@ -1631,12 +1616,7 @@ static __global__ void __launch_bounds__(256, UPS_OCC) k_ups(UpsArgs a) {  // 2 
     const long hbase = (long)q0 * us - a.npad;
     const int hspan = TQ * us + 16;
     float hpre[2] = {0.f, 0.f};
-#ifdef UPS_NO_PRELOAD  // dev A/B: the round-3 order (har and bias loads behind the tile staging / the K loop)
-    constexpr bool UPS_PRE = false;
-#else
-    constexpr bool UPS_PRE = true;
-#endif
-    if (a.nz_k1 && UPS_PRE) {
+    if (a.nz_k1) {
         const float* hp = a.har + (size_t)b * a.Lh_stride;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -1787,12 +1767,10 @@ static __global__ void __launch_bounds__(256, UPS_OCC) k_ups(UpsArgs a) {  // 2 
     OpT* har16 = (OpT*)(smem + (size_t)a.tile_rows * STRIDE);
     if (a.nz_k1) {
         const float* hp = a.har + (size_t)b * a.Lh_stride;
-        if (UPS_PRE) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if ((int)threadIdx.x + 256 * j < hspan) har16[threadIdx.x + 256 * j] = to_op<OpT>(hpre[j]);
-        }
-        for (int i = threadIdx.x + (UPS_PRE ? 512 : 0); i < hspan; i += 256) {  // (spans beyond 512 samples: large noise strides)
+        for (int j = 0; j < 2; ++j)
+            if ((int)threadIdx.x + 256 * j < hspan) har16[threadIdx.x + 256 * j] = to_op<OpT>(hpre[j]);
+        for (int i = threadIdx.x + 512; i < hspan; i += 256) {  // (spans beyond 512 samples: large noise strides)
             const long idx = hbase + i;
             har16[i] = (idx >= 0 && idx < Lhb) ? to_op<OpT>(hp[idx]) : (OpT)0.f;
         }

@@ -151,6 +151,9 @@ def test_handle_rejects_bad_shapes_and_grows_its_workspace(gpu):
         gen(z.to(gpu), None, g.to(gpu))
     out = gen(z.to(gpu), f0.to(gpu), g.to(gpu), noise=torch.zeros(2, 20 * cfg.upp, device=gpu))  # beyond max_B/max_T: re-created
     assert out.shape == (2, 1, 20 * cfg.upp)
+    for key in ("NB", "UPS_NJ", "CONV_KS", "RBF_SMALL"):  # retired A/B options: an error, never a silent no-op
+        with pytest.raises(rvc_amd.RvcmiError, match="unknown option"):
+            gen.set_option(key, 2)
     bad = dict(w)
     bad.pop("ups.1.bias")
     with pytest.raises(rvc_amd.RvcmiError, match="missing weight"):
