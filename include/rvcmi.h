@@ -346,6 +346,32 @@ int rvcmi_glue_sola(const float* infer_wav_dev, int64_t n, float* sola_buffer_de
                     const float* fade_in_dev, const float* fade_out_dev, int block_frame, float* out_block_dev,
                     int* offset_out_dev, void* stream);
 
+/* The GUI's phase-vocoder cross-fade (gui.py:27-49): out [n] <- phase_vocoder(a, b, fade_out, fade_in), all [n] fp32:
+ *   w = sqrt(fade_out * fade_in);  Fa, Fb = rfft(a * w), rfft(b * w);  absab = |Fa| + |Fb| (doubled except DC / Nyquist);
+ *   d = angle(Fb) - angle(Fa) wrapped by 2 pi floor(d / 2 pi + 0.5);
+ *   out[t] = a fade_out^2 + b fade_in^2 + w / n * sum_k absab[k] cos((2 pi k + d[k]) t / n + angle(Fa)[k]).
+ * Spectrum and synthesis in fp64 (an O(n * (n/2+1)) sum, not an inverse DFT).  A bin whose real and imaginary parts are both
+ * exactly zero has phase 0.  n <= 4096, else RVCMI_ERR_INVALID.  scratch_dev: 3 * (n/2 + 1) doubles.
+ * out_dev may not alias the inputs.                                                                                         */
+int rvcmi_glue_phase_vocoder(const float* a_dev, const float* b_dev, const float* fade_out_dev, const float* fade_in_dev, int n,
+                             float* out_dev, double* scratch_dev, void* stream);
+
+/* rvcmi_glue_sola with the GUI's use_pv branch (gui.py:1076-1087): the same search (first maximum), then
+ * infer_wav[off : off + Lb] is cross-faded with sola_buffer by rvcmi_glue_phase_vocoder instead of the sin^2 fade; out_block_dev
+ * and the new tail (sola_buffer_dev, in place) are cut from the result as in rvcmi_glue_sola, block_frame < Lb included.  The
+ * offset stays on the device.  Lb <= 4096.  scratch_dev: 3 * (Lb/2 + 1) + Lb/2 + 1 doubles.                                  */
+int rvcmi_glue_sola_pv(const float* infer_wav_dev, int64_t n, float* sola_buffer_dev, int Lb, int Ls,
+                       const float* fade_in_dev, const float* fade_out_dev, int block_frame, float* out_block_dev,
+                       int* offset_out_dev, double* scratch_dev, void* stream);
+
+/* The realtime GUI's envelope mix (gui.py:1023-1056), IN PLACE on wav_dev [n]:
+ *   rms1, rms2 = frame RMS of input_dev[:n] and wav_dev (librosa.feature.rms, frame_length 4 zc, hop zc, centred, zero padded),
+ *   both linearly interpolated with align_corners=True to n + 1 points, the last dropped;  rms2 = max(rms2, 1e-3);
+ *   wav *= pow(rms1 / rms2, float32(1 - rate)).
+ * scratch_dev: 2 * (1 + n / zc) floats.  Not the offline change_rms (half-second frames, align_corners=False, 1e-6).           */
+int rvcmi_glue_envelope_mix(const float* input_dev, float* wav_dev, int64_t n, int zc, double rate, float* scratch_dev,
+                            void* stream);
+
 /* The formant-shift resample of the realtime path (rtrvc.py:248-259, torchaudio.transforms.Resample(orig_freq = upp_res,
  * new_freq = tgt_sr / 100)): out[j * new + p] = sum_{k < K} kernel[p][k] * xpad[j * orig + k], xpad = x with `width` zeros in
  * front and zeros behind; orig / new already divided by their gcd; kernel_dev [new][K] (K = 2 * width + orig) is torchaudio's

@@ -109,6 +109,9 @@ SYMBOLS = [
     ("rvcmi_glue_scale_int16_range", C.c_int, [_P, C.c_int64, _P, _P]),
     ("rvcmi_glue_resample_poly", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     ("rvcmi_glue_sola", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    ("rvcmi_glue_phase_vocoder", C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    ("rvcmi_glue_sola_pv", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
+    ("rvcmi_glue_envelope_mix", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P]),
     ("rvcmi_gru_create", C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(_P)]),
     ("rvcmi_gru_destroy", C.c_int, [_P]),
     ("rvcmi_gru_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -18,7 +18,19 @@ static void ensure_dyn_lds(K kernel, int bytes, std::atomic<unsigned long long>&
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     done_mask.fetch_or(bit, std::memory_order_release);
 }
-static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0};
+static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0};
+
+// The phase-vocoder launches on a device-resident b (b_off: optional device offset into b); out [n] may not alias a or b.
+static void launch_phase_vocoder(const float* a, const float* b, const int* b_off, const float* fade_out, const float* fade_in, int n, float* out,
+                                 double* bins, hipStream_t st) {
+    const int nb = n / 2 + 1;
+    ensure_dyn_lds(k_pv_spectrum, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec);
+    ensure_dyn_lds(k_pv_synth, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth);
+    hipLaunchKernelGGL(k_pv_spectrum, dim3((unsigned)std::min(256, (nb + 3) / 4)), dim3(256), (size_t)32 * n, st, a, b, b_off, fade_out,
+                       fade_in, n, bins);
+    hipLaunchKernelGGL(k_pv_synth, dim3((unsigned)((n + 63) / 64)), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st, a, b, b_off, fade_out,
+                       fade_in, n, (const double*)bins, out);
+}
 
 extern "C" {
 
@@ -95,6 +107,58 @@ int rvcmi_glue_sola(const float* infer_wav, int64_t n, float* sola_buffer, int L
         ensure_dyn_lds(k_sola, 150 * 1024, g_attr_sola);  // + 2 KB static
         hipLaunchKernelGGL(k_sola, dim3(1), dim3(256), smem, (hipStream_t)stream, infer_wav, sola_buffer, Lb, Ls, fade_in, fade_out,
                            block_frame, out_block, offset_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out, double* scratch,
+                             void* stream) {
+    return guarded([&] {
+        if (!a || !b || !fade_out || !fade_in || !out || !scratch || n < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "phase_vocoder: bad argument");
+        if (n > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "phase_vocoder: n = %d exceeds %d", n, RVCMI_PV_MAX_N);
+        launch_phase_vocoder(a, b, nullptr, fade_out, fade_in, n, out, scratch, (hipStream_t)stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_sola_pv(const float* infer_wav, int64_t n, float* sola_buffer, int Lb, int Ls, const float* fade_in, const float* fade_out,
+                       int block_frame, float* out_block, int* offset_out, double* scratch, void* stream) {
+    return guarded([&] {
+        if (!infer_wav || !sola_buffer || !fade_in || !fade_out || !out_block || !scratch || Lb < 1 || Ls < 0 || block_frame < 1)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv: bad argument");
+        if ((int64_t)Ls + block_frame + Lb > n)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv: chunk of %lld samples is shorter than search %d + block %d + buffer %d", (long long)n, Ls,
+                       block_frame, Lb);
+        if (Lb > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv: cross-fade buffer of %d samples exceeds %d", Lb, RVCMI_PV_MAX_N);
+        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
+        if (smem > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "sola_pv: buffer + search window too large");
+        // scratch: bins [3 * (Lb/2 + 1)] doubles | pv result [Lb] floats | offset (when offset_out is NULL)
+        const int nb = Lb / 2 + 1;
+        float* pv = reinterpret_cast<float*>(scratch + 3 * nb);
+        int* off = offset_out ? offset_out : reinterpret_cast<int*>(pv + Lb);
+        hipStream_t st = (hipStream_t)stream;
+        ensure_dyn_lds(k_sola_search, 150 * 1024, g_attr_sola_search);
+        hipLaunchKernelGGL(k_sola_search, dim3(1), dim3(256), smem, st, infer_wav, (const float*)sola_buffer, Lb, Ls, off);
+        launch_phase_vocoder(sola_buffer, infer_wav, off, fade_out, fade_in, Lb, pv, scratch, st);
+        hipLaunchKernelGGL(k_sola_pv_stitch, dim3((unsigned)((block_frame + Lb + 255) / 256)), dim3(256), 0, st, infer_wav, (const int*)off,
+                           (const float*)pv, Lb, block_frame, out_block, sola_buffer);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_envelope_mix(const float* input, float* wav, int64_t n, int zc, double rate, float* scratch, void* stream) {
+    return guarded([&] {
+        if (!input || !wav || !scratch || n < 1 || zc < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix: bad argument");
+        const int64_t nf64 = 1 + n / zc;
+        if (nf64 > (1 << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix: too many frames");
+        const int nf = (int)nf64;
+        hipStream_t st = (hipStream_t)stream;
+        hipLaunchKernelGGL(k_frame_rms, dim3(nf), dim3(256), 0, st, input, n, 4 * zc, zc, nf, scratch);
+        hipLaunchKernelGGL(k_frame_rms, dim3(nf), dim3(256), 0, st, (const float*)wav, n, 4 * zc, zc, nf, scratch + nf);
+        // torch.pow(rms1 / rms2, torch.tensor(1 - rate)): the exponent is the python double rounded to float32
+        const float e = (float)(1.0 - rate);
+        hipLaunchKernelGGL(k_envelope_mix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wav, n, (const float*)scratch,
+                           (const float*)(scratch + nf), nf, e);
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -256,18 +256,11 @@ static __global__ void __launch_bounds__(256) k_scale_int16_range(float* __restr
 //   y = x[offset:];  y[:Lb] = y[:Lb] * fade_in + buf * fade_out;  buf <- y[block : block + Lb];  out <- y[:block]
 // The two sums are accumulated in fp64 and rounded once (the reference's F.conv1d leaves the fp32 summation order to the
 // backend); everything after the argmax is the reference's fp32 expression, unfused.  One block.
-static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
-                                                     const float* __restrict__ fade_in, const float* __restrict__ fade_out,
-                                                     int block, float* __restrict__ out, int* __restrict__ offset_out) {
+//
+// The offset search shared by k_sola and k_sola_search (256 threads): xs [Lb + Ls] and bs [Lb] staged in LDS, rv / ri 256
+// entries of LDS for the block's argmax.  Every thread gets the offset.
+__device__ __forceinline__ int sola_search(const float* xs, const float* bs, int Lb, int Ls, float* rv, int* ri) {
 #pragma clang fp contract(off)
-    extern __shared__ float sl[];
-    float* xs = sl;             // [Lb + Ls]
-    float* bs = sl + Lb + Ls;   // [Lb]
-    __shared__ float rv[256];
-    __shared__ int ri[256];
-    for (int i = threadIdx.x; i < Lb + Ls; i += 256) xs[i] = x[i];
-    for (int i = threadIdx.x; i < Lb; i += 256) bs[i] = buf[i];
-    __syncthreads();
     float best = -INFINITY;
     int bo = 0;
     for (int o = threadIdx.x; o <= Ls; o += 256) {
@@ -297,7 +290,22 @@ static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x
         }
         __syncthreads();
     }
-    const int off = ri[0];
+    return ri[0];
+}
+
+static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
+                                                     const float* __restrict__ fade_in, const float* __restrict__ fade_out,
+                                                     int block, float* __restrict__ out, int* __restrict__ offset_out) {
+#pragma clang fp contract(off)
+    extern __shared__ float sl[];
+    float* xs = sl;             // [Lb + Ls]
+    float* bs = sl + Lb + Ls;   // [Lb]
+    __shared__ float rv[256];
+    __shared__ int ri[256];
+    for (int i = threadIdx.x; i < Lb + Ls; i += 256) xs[i] = x[i];
+    for (int i = threadIdx.x; i < Lb; i += 256) bs[i] = buf[i];
+    __syncthreads();
+    const int off = sola_search(xs, bs, Lb, Ls, rv, ri);
     if (threadIdx.x == 0 && offset_out) *offset_out = off;
     auto y = [&](int p) {  // the shifted, cross-faded chunk at position p
         const float v = x[off + p];
@@ -305,6 +313,170 @@ static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x
     };
     for (int i = threadIdx.x; i < block; i += 256) out[i] = y(i);
     for (int i = threadIdx.x; i < Lb; i += 256) buf[i] = y(block + i);  // old tail is in LDS: safe to overwrite
+}
+
+// ------------------------------------------------------------------------------------------------
+// The GUI's use_pv branch (gui.py:1076-1087): the same search, then x[off : off + Lb] is cross-faded with the previous tail by
+// the phase vocoder below instead of the sin^2 fade.  Four launches: search -> pv spectrum -> pv synthesis (into scratch) ->
+// stitch; the offset stays in device memory between them.
+static __global__ void __launch_bounds__(256) k_sola_search(const float* __restrict__ x, const float* __restrict__ buf, int Lb, int Ls,
+                                                            int* __restrict__ offset_out) {
+    extern __shared__ float sl[];
+    float* xs = sl;             // [Lb + Ls]
+    float* bs = sl + Lb + Ls;   // [Lb]
+    __shared__ float rv[256];
+    __shared__ int ri[256];
+    for (int i = threadIdx.x; i < Lb + Ls; i += 256) xs[i] = x[i];
+    for (int i = threadIdx.x; i < Lb; i += 256) bs[i] = buf[i];
+    __syncthreads();
+    const int off = sola_search(xs, bs, Lb, Ls, rv, ri);
+    if (threadIdx.x == 0) *offset_out = off;
+}
+
+// out <- y[:block], buf <- y[block : block + Lb] with y = x[off:], y[:Lb] = pv.  buf is not read here (the pv launches have
+// consumed it), so any number of blocks may write it.
+static __global__ void __launch_bounds__(256) k_sola_pv_stitch(const float* __restrict__ x, const int* __restrict__ offset, const float* __restrict__ pv,
+                                                               int Lb, int block, float* __restrict__ out, float* __restrict__ buf) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= block + Lb) return;
+    const int off = *offset;
+    const float v = i < Lb ? pv[i] : x[off + i];
+    if (i < block) out[i] = v;
+    else buf[i - block] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// phase_vocoder(a, b, fade_out, fade_in) of gui.py:27-49, n = len(a) <= RVCMI_PV_MAX_N:
+//   w = sqrt(fade_out * fade_in);  Fa, Fb = rfft(a * w), rfft(b * w)                     (nb = n/2 + 1 bins)
+//   absab = |Fa| + |Fb|, doubled for 0 < k < n/2 (even n) / 0 < k (odd n)
+//   d = angle(Fb) - angle(Fa);  d -= 2 pi floor(d / 2 / pi + 0.5)
+//   out[t] = a[t] fade_out[t]^2 + b[t] fade_in[t]^2 + w[t] / n * sum_k absab[k] cos((2 pi k + d[k]) t / n + angle(Fa)[k])
+// The synthesis is not an inverse DFT (d[k] t / n couples bin and sample): an O(n * nb) sum, 1.85 M terms at n = 1920.
+// Spectrum and synthesis run in fp64 from the fp32 inputs (the reference's own fp32 run is less faithful to its formula:
+// its w * t reaches ~6000 rad); the cosine is fp32 on an argument reduced exactly into [-pi, pi].
+// A bin whose real and imaginary sums are both exactly zero has phase 0 (the reference's angle there depends on the signed
+// zeros its FFT backend returns).
+#define RVCMI_PV_MAX_N 4096
+
+// Spectrum: one wave per bin (grid-strided), lanes over samples.  LDS: the twiddle table (cos, sin)(2 pi m / n) built with
+// sincospi (the quarter points are exact) and the windowed inputs, 32 n bytes.  bins: absab [nb] | phia [nb] | d / n [nb].
+// b_off (optional): b is read at b + *b_off (the SOLA offset, which never leaves the device).
+static __global__ void __launch_bounds__(256) k_pv_spectrum(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
+                                                            const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                            double* __restrict__ bins) {
+    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+    double2* tw = reinterpret_cast<double2*>(pv_sm);   // [n]
+    double2* xy = tw + n;                              // [n]: (a w, b w)
+    const float* bp = b + (b_off ? *b_off : 0);
+    const int nb = n / 2 + 1;
+    for (int m = threadIdx.x; m < n; m += 256) {
+        double s, c;
+        sincospi((double)(2 * m) / (double)n, &s, &c);
+        tw[m] = make_double2(c, s);
+        const double w = sqrt((double)fade_out[m] * (double)fade_in[m]);
+        xy[m] = make_double2((double)a[m] * w, (double)bp[m] * w);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < nb; k += gridDim.x * 4) {
+        double ra = 0.0, ia = 0.0, rb = 0.0, ib = 0.0;
+        int m = (k * lane) % n;              // (k * i) mod n, i = lane + 64 j   (k * i < 2^31 for n <= 4096)
+        const int step = (k * 64) % n;
+        for (int i = lane; i < n; i += 64) {
+            const double2 t = tw[m], x = xy[i];
+            ra += x.x * t.x;
+            ia -= x.x * t.y;
+            rb += x.y * t.x;
+            ib -= x.y * t.y;
+            m += step;
+            if (m >= n) m -= n;
+        }
+        for (int o = 32; o >= 1; o >>= 1) {
+            ra += __shfl_xor(ra, o, 64);
+            ia += __shfl_xor(ia, o, 64);
+            rb += __shfl_xor(rb, o, 64);
+            ib += __shfl_xor(ib, o, 64);
+        }
+        if (lane == 0) {
+            double ab = sqrt(ra * ra + ia * ia) + sqrt(rb * rb + ib * ib);
+            if (k >= 1 && (k < nb - 1 || (n & 1))) ab *= 2.0;
+            const double pa = (ra == 0.0 && ia == 0.0) ? 0.0 : atan2(ia, ra);
+            const double pb = (rb == 0.0 && ib == 0.0) ? 0.0 : atan2(ib, rb);
+            double d = pb - pa;
+            d = d - 2.0 * M_PI * floor(d / 2.0 / M_PI + 0.5);
+            bins[k] = ab;
+            bins[nb + k] = pa;
+            bins[2 * nb + k] = d / (double)n;
+        }
+    }
+}
+
+// Synthesis: a block owns 64 consecutive samples (one per lane); its 16 waves split the bins, staged in LDS, and their
+// partial sums are added in a fixed order.  Argument per term: 2 pi ((k t) mod n) / n + (d[k] / n) t + phia[k] in fp64,
+// reduced by 2 pi rint(arg / 2 pi) into [-pi, pi] before the fp32 cosine; products and sums in fp64, one rounding at the end.
+static __global__ void __launch_bounds__(1024) k_pv_synth(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
+                                                          const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                          const double* __restrict__ bins, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+    const int nb = n / 2 + 1;
+    double* ab = pv_sm;             // [nb]
+    double* ph = ab + nb;           // [nb]
+    double* dn = ph + nb;           // [nb]
+    double* red = dn + nb;          // [16][64]
+    for (int i = threadIdx.x; i < 3 * nb; i += 1024) pv_sm[i] = bins[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t = blockIdx.x * 64 + lane;
+    const int tt = t < n ? t : 0;
+    const double two_pi = 2.0 * M_PI, inv_two_pi = 1.0 / (2.0 * M_PI), w_n = 2.0 * M_PI / (double)n, td = (double)tt;
+    int m = (wv * tt) % n;                  // (k * t) mod n for k = wv + 16 j
+    const int step = (16 * tt) % n;
+    double acc = 0.0;
+    for (int k = wv; k < nb; k += 16) {
+        double arg = (double)m * w_n + (dn[k] * td + ph[k]);
+        arg -= two_pi * rint(arg * inv_two_pi);
+        acc += ab[k] * (double)cosf((float)arg);
+        m += step;
+        if (m >= n) m -= n;
+    }
+    red[wv * 64 + lane] = acc;
+    __syncthreads();
+    if (wv == 0 && t < n) {
+        double s = 0.0;
+        for (int j = 0; j < 16; ++j) s += red[j * 64 + lane];
+        const float* bp = b + (b_off ? *b_off : 0);
+        const double fo = (double)fade_out[t], fi = (double)fade_in[t];
+        const double w = sqrt(fo * fi);
+        out[t] = (float)(((double)a[t] * (fo * fo) + (double)bp[t] * (fi * fi)) + s * w / (double)n);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The realtime GUI's envelope mix (gui.py:1023-1056), in place on wav [n]:
+//   rms1, rms2 = librosa.feature.rms(input[:n] / wav, frame_length = 4 zc, hop_length = zc)   (k_frame_rms below)
+//   both -> F.interpolate(linear, align_corners=True, size=n+1)[:-1];  rms2 = max(rms2, 1e-3);
+//   wav *= pow(rms1 / rms2, float32(1 - rate))
+// The interpolation is torch's CPU kernel: scale = (in-1)/(out-1) in fp32, src = scale * o, floor, clamp.
+__device__ __forceinline__ float interp_linear_ac(const float* __restrict__ r, int nin, int64_t nout, int64_t o) {
+#pragma clang fp contract(off)
+    if ((int64_t)nin == nout) return r[o];
+    const float scale = nout > 1 ? div_rn((float)(nin - 1), (float)(nout - 1)) : 0.f;
+    const float src = mul_rn(scale, (float)o);
+    int i0 = (int)floorf(src);
+    if (i0 > nin - 1) i0 = nin - 1;
+    const int i1 = i0 + (i0 < nin - 1 ? 1 : 0);
+    const float l1 = fminf(fmaxf(sub_rn(src, (float)i0), 0.f), 1.f);
+    const float l0 = sub_rn(1.f, l1);
+    return add_rn(mul_rn(l0, r[i0]), mul_rn(l1, r[i1]));
+}
+
+static __global__ void __launch_bounds__(256) k_envelope_mix(float* __restrict__ wav, int64_t n, const float* __restrict__ rms1,
+                                                             const float* __restrict__ rms2, int nf, float e) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const float r1 = interp_linear_ac(rms1, nf, n + 1, t);
+    const float r2 = fmaxf(interp_linear_ac(rms2, nf, n + 1, t), 1e-3f);
+    wav[t] = mul_rn(wav[t], powf(div_rn(r1, r2), e));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,6 +7,12 @@ row 2), so that nothing between the PyTorch-ROCm feature extractors and ``net_g.
     change_rms(audio16k, 16000, audio_opt, tgt_sr, rms_mix_rate)              pipeline.py:26-46,351
     scale_int16_range(audio)                                                  pipeline.py:355-359
 
+and of the realtime GUI's block (gui.py:934-1090, assembled by ``realtime.RealtimeStream``):
+
+    envelope_mix(input_wav, infer_wav, zc, rms_mix_rate)                      gui.py:1023-1056
+    sola(infer_wav, sola_buffer, fade_in, fade_out, block, search, use_pv)    gui.py:1057-1090
+    phase_vocoder(a, b, fade_out, fade_in)                                    gui.py:27-49
+
 All take and return CUDA (ROCm) tensors and enqueue on the current stream; a CPU tensor raises (no fallback).
 """
 from __future__ import annotations
@@ -143,9 +149,11 @@ def scale_int16_range(audio: torch.Tensor) -> torch.Tensor:
 
 
 def sola(infer_wav: torch.Tensor, sola_buffer: torch.Tensor, fade_in: torch.Tensor, fade_out: torch.Tensor, block_frame: int,
-         search_frame: int, return_offset: bool = False):
+         search_frame: int, return_offset: bool = False, use_pv: bool = False):
     """The SOLA stitch of gui.py:1057-1090 in one launch: returns the ``block_frame`` output samples and updates
-    ``sola_buffer`` in place (``return_offset=True`` also returns the chosen offset as a 1-element int32 tensor)."""
+    ``sola_buffer`` in place (``return_offset=True`` also returns the chosen offset as a 1-element int32 tensor).
+    ``use_pv=True`` is the GUI's phase-vocoder branch (gui.py:1081-1087): the same search, then the ``len(sola_buffer)``
+    samples at the offset are cross-faded by ``phase_vocoder`` (four launches; the offset never leaves the device)."""
     dev = _dev(infer_wav, "infer_wav")
     for t, nm in ((infer_wav, "infer_wav"), (sola_buffer, "sola_buffer"), (fade_in, "fade_in"), (fade_out, "fade_out")):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
@@ -154,6 +162,48 @@ def sola(infer_wav: torch.Tensor, sola_buffer: torch.Tensor, fade_in: torch.Tens
     out = torch.empty(int(block_frame), device=dev, dtype=torch.float32)
     off = torch.empty(1, device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_sola(_ptr(infer_wav), infer_wav.numel(), _ptr(sola_buffer), Lb, int(search_frame), _ptr(fade_in),
-                                              _ptr(fade_out), int(block_frame), _ptr(out), _ptr(off), _stream(dev)))
+        if use_pv:
+            scratch = torch.empty(3 * (Lb // 2 + 1) + Lb // 2 + 1, device=dev, dtype=torch.float64)
+            _lib.check(_lib.lib().rvcmi_glue_sola_pv(_ptr(infer_wav), infer_wav.numel(), _ptr(sola_buffer), Lb, int(search_frame), _ptr(fade_in),
+                                                     _ptr(fade_out), int(block_frame), _ptr(out), _ptr(off), _ptr(scratch), _stream(dev)))
+        else:
+            _lib.check(_lib.lib().rvcmi_glue_sola(_ptr(infer_wav), infer_wav.numel(), _ptr(sola_buffer), Lb, int(search_frame), _ptr(fade_in),
+                                                  _ptr(fade_out), int(block_frame), _ptr(out), _ptr(off), _stream(dev)))
     return (out, off) if return_offset else out
+
+
+def phase_vocoder(a: torch.Tensor, b: torch.Tensor, fade_out: torch.Tensor, fade_in: torch.Tensor) -> torch.Tensor:
+    """``phase_vocoder(a, b, fade_out, fade_in)`` of gui.py:27-49 on the device (n = len(a) <= 4096): the windowed spectra of
+    both signals, their summed magnitudes and wrapped phase difference, and the O(n^2 / 2) phase-interpolating synthesis, in
+    fp64.  A bin whose spectrum is exactly zero has phase 0.  Returns a new float32 tensor [n]."""
+    dev = _dev(a, "a")
+    n = int(a.numel())
+    for t, nm in ((a, "a"), (b, "b"), (fade_out, "fade_out"), (fade_in, "fade_in")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.dim() != 1 or t.numel() != n:
+            raise ValueError("%s must be a contiguous 1-D float32 tensor of %d samples on %s" % (nm, n, dev))
+    out = torch.empty(n, device=dev, dtype=torch.float32)
+    scratch = torch.empty(3 * (n // 2 + 1), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_phase_vocoder(_ptr(a), _ptr(b), _ptr(fade_out), _ptr(fade_in), n, _ptr(out), _ptr(scratch),
+                                                       _stream(dev)))
+    return out
+
+
+def envelope_mix(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int, rms_mix_rate: float) -> torch.Tensor:
+    """The realtime GUI's volume-envelope mix (gui.py:1023-1056), IN PLACE on ``infer_wav`` (returned): frame RMS of
+    ``input_wav[:len(infer_wav)]`` and of ``infer_wav`` (frame 4 zc, hop zc), both interpolated with ``align_corners=True``,
+    ``infer_wav *= pow(rms1 / max(rms2, 1e-3), 1 - rms_mix_rate)``.  Not ``change_rms``: that is the offline formula."""
+    dev = _dev(infer_wav, "infer_wav")
+    for t, nm in ((input_wav, "input_wav"), (infer_wav, "infer_wav")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1 or t.device != dev:
+            raise ValueError("%s must be a contiguous 1-D float32 tensor on %s" % (nm, dev))
+    n, zc = int(infer_wav.numel()), int(zc)
+    if input_wav.numel() < n:
+        raise ValueError("input_wav has %d samples, infer_wav %d" % (input_wav.numel(), n))
+    if zc < 1:
+        raise ValueError("zc must be positive")
+    scratch = torch.empty(2 * (1 + n // zc), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_envelope_mix(_ptr(input_wav), _ptr(infer_wav), n, zc, float(rms_mix_rate), _ptr(scratch),
+                                                      _stream(dev)))
+    return infer_wav

@@ -15,6 +15,7 @@ from __future__ import annotations
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib, glue
@@ -170,6 +171,126 @@ class RealtimeVC:
                 self._resample[upp_res] = SincResample(upp_res, self.tgt_sr // 100, self.device)
             audio = self._resample[upp_res](audio[:, : return_length * upp_res].contiguous())
         return audio.squeeze()
+
+
+def stream_geometry(samplerate: int, block_time: float = 0.25, crossfade_time: float = 0.05, extra_time: float = 2.5) -> dict:
+    """The realtime GUI's block geometry (gui.py:783-840), in samples at ``samplerate`` unless named ``_16k``; no device needed."""
+    sr = int(samplerate)
+    zc = sr // 100
+    block = int(np.round(block_time * sr / zc)) * zc
+    crossfade = int(np.round(crossfade_time * sr / zc)) * zc
+    sola_buffer = min(crossfade, 4 * zc)
+    search = zc
+    extra = int(np.round(extra_time * sr / zc)) * zc
+    n_in = extra + crossfade + search + block
+    return dict(zc=zc, block_frame=block, block_frame_16k=160 * block // zc, crossfade_frame=crossfade, sola_buffer_frame=sola_buffer,
+                sola_search_frame=search, extra_frame=extra, skip_head=extra // zc, return_length=(block + sola_buffer + search) // zc,
+                input_wav_len=n_in, input_wav_res_len=160 * n_in // zc)
+
+
+def frame_rms_np(y: np.ndarray, frame_length: int, hop_length: int) -> np.ndarray:
+    """``librosa.feature.rms(y=y, frame_length, hop_length)[0]`` (librosa >= 0.10.2: centred, zero padding) in numpy; the float32
+    squares are summed in float64 and the mean rounded to float32, as the device's k_frame_rms does."""
+    y = np.asarray(y, dtype=np.float32)
+    pad = frame_length // 2
+    yp = np.pad(y, (pad, pad), mode="constant")
+    n_frames = 1 + (len(yp) - frame_length) // hop_length
+    sq = (yp * yp).astype(np.float64)
+    sums = np.array([sq[i * hop_length: i * hop_length + frame_length].sum() for i in range(n_frames)], dtype=np.float64)
+    return np.sqrt((sums / frame_length).astype(np.float32))
+
+
+def amplitude_to_db(s: np.ndarray, amin: float = 1e-5, top_db: float = 80.0) -> np.ndarray:
+    """``librosa.amplitude_to_db(s, ref=1.0, amin=1e-5, top_db=80.0)`` in float32: ``10 log10(max(amin^2, s^2))``, clipped at
+    ``max - top_db``."""
+    power = np.square(np.abs(np.asarray(s, dtype=np.float32)))
+    log_spec = (np.float32(10.0) * np.log10(np.maximum(np.float32(amin * amin), power))).astype(np.float32)
+    if log_spec.size:
+        log_spec = np.maximum(log_spec, log_spec.max() - np.float32(top_db))
+    return log_spec
+
+
+def input_gate(indata: np.ndarray, rms_buffer: np.ndarray, zc: int, threhold: float) -> np.ndarray:
+    """The GUI's input gate (gui.py:950-963), on the host where the block arrives: frame RMS over the last ``4 zc`` samples of
+    the previous block and this one, frames below ``threhold`` dB zeroed ``zc`` samples at a time.  Updates ``rms_buffer``
+    [4 zc] in place and returns ``block + 2 zc`` samples (the GUI rewrites the last ``2 zc`` of the previous block too)."""
+    x = np.append(rms_buffer, np.asarray(indata, dtype=np.float32))
+    rms = frame_rms_np(x, 4 * zc, zc)[2:]
+    rms_buffer[:] = x[-4 * zc:]
+    x = x[2 * zc - zc // 2:]
+    quiet = amplitude_to_db(rms) < threhold
+    for i in np.flatnonzero(quiet):
+        x[i * zc: (i + 1) * zc] = 0
+    return x[zc // 2:]
+
+
+class RealtimeStream:
+    """The per-block audio path of the realtime GUI (``audio_infer``, gui.py:934-1090) around any ``rtrvc.RVC``-like object
+    (``.tgt_sr`` and ``.infer(input_wav_res, block_frame_16k, skip_head, return_length, f0method)``; the reference's own after
+    ``rvc_amd.install()``), without the PySimpleGUI front end:
+
+        rt = RealtimeStream(rvc, samplerate=48000, use_pv=True)
+        out = rt.process(block)        # host float32 [block_frame] or [block_frame, channels] -> device float32 [block_frame]
+
+    Per block: the input gate (host, when ``threhold > -60``), rolling ``input_wav`` / ``input_wav_res`` buffers and the 16 kHz
+    resample, ``rvc.infer``, the ``tgt_sr -> samplerate`` resample, the envelope mix (``rms_mix_rate < 1``) and the SOLA stitch
+    (sin^2 or phase-vocoder fade), all on the device: one host-to-device copy (the block), none back.  The keyword names are the
+    GUI's ``GUIConfig`` fields; ``samplerate=None`` is the model rate.  Not covered: noise reduction (TorchGate) and the "im"
+    monitor mode."""
+
+    def __init__(self, rvc, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05, extra_time: float = 2.5,
+                 threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe", device=None):
+        self.rvc = rvc
+        self.tgt_sr = int(rvc.tgt_sr)
+        self.samplerate = self.tgt_sr if samplerate is None else int(samplerate)
+        self.block_time, self.crossfade_time, self.extra_time = block_time, crossfade_time, extra_time
+        self.threhold, self.rms_mix_rate, self.use_pv, self.f0method = threhold, float(rms_mix_rate), bool(use_pv), f0method
+        if device is None:
+            device = getattr(rvc, "device", None) or "cuda:0"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.RvcmiError("RealtimeStream runs on the GPU (got %s); there is no CPU fallback" % self.device)
+        g = stream_geometry(self.samplerate, block_time, crossfade_time, extra_time)
+        for k, v in g.items():
+            setattr(self, k, v)
+        self.input_wav = torch.zeros(self.input_wav_len, device=self.device, dtype=torch.float32)
+        self.input_wav_res = torch.zeros(self.input_wav_res_len, device=self.device, dtype=torch.float32)
+        self.rms_buffer = np.zeros(4 * self.zc, dtype="float32")
+        self.sola_buffer = torch.zeros(self.sola_buffer_frame, device=self.device, dtype=torch.float32)
+        # the GUI's fp32 expression (gui.py:841-855), on the CPU and uploaded once
+        fade_in = torch.sin(0.5 * np.pi * torch.linspace(0.0, 1.0, steps=self.sola_buffer_frame, dtype=torch.float32)) ** 2
+        self.fade_in_window = fade_in.to(self.device)
+        self.fade_out_window = (1 - fade_in).to(self.device)
+        self.resampler = SincResample(self.samplerate, 16000, self.device)
+        self.resampler2 = SincResample(self.tgt_sr, self.samplerate, self.device) if self.tgt_sr != self.samplerate else None
+        self.last_offset = None  # device int32 [1]: the SOLA offset of the last block
+
+    def process(self, indata) -> torch.Tensor:
+        x = np.asarray(indata, dtype=np.float32)
+        if x.ndim == 2:
+            x = np.mean(x.T, axis=0)       # librosa.to_mono(indata.T)
+        if x.shape[0] != self.block_frame:
+            raise ValueError("a block has %d samples, got %d" % (self.block_frame, x.shape[0]))
+        if self.threhold > -60:
+            x = input_gate(x, self.rms_buffer, self.zc, self.threhold)
+        m = int(x.shape[0])
+        blk, blk16 = self.block_frame, self.block_frame_16k
+        self.input_wav[:-blk] = self.input_wav[blk:].clone()
+        self.input_wav[-m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        self.input_wav_res[:-blk16] = self.input_wav_res[blk16:].clone()
+        self.input_wav_res[-160 * (m // self.zc + 1):] = self.resampler(self.input_wav[-m - 2 * self.zc:])[160:]
+        infer_wav = self.rvc.infer(self.input_wav_res, blk16, self.skip_head, self.return_length, self.f0method)
+        if self.resampler2 is not None:
+            infer_wav = self.resampler2(infer_wav)
+        infer_wav = infer_wav.reshape(-1)
+        if infer_wav.dtype != torch.float32 or not infer_wav.is_contiguous():
+            infer_wav = infer_wav.float().contiguous()
+        if self.rms_mix_rate < 1:
+            n = int(infer_wav.numel())
+            glue.envelope_mix(self.input_wav[self.extra_frame: self.extra_frame + n], infer_wav, self.zc, self.rms_mix_rate)
+        out, self.last_offset = glue.sola(infer_wav, self.sola_buffer, self.fade_in_window, self.fade_out_window, blk, self.sola_search_frame,
+                                          return_offset=True, use_pv=self.use_pv)
+        return out
 
 
 RT_GRAPH_AFTER = 3  # eager calls of one (window length, key) before its f0 chain is captured (MIOpen / rocFFT pick their algorithms and plans first)
