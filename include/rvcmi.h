@@ -372,6 +372,28 @@ int rvcmi_glue_sola_pv(const float* infer_wav_dev, int64_t n, float* sola_buffer
 int rvcmi_glue_envelope_mix(const float* input_dev, float* wav_dev, int64_t n, int zc, double rate, float* scratch_dev,
                             void* stream);
 
+/* The realtime GUI's noise reduction (gui.py:869-871, 974-992, 1015-1022): TorchGate.forward(x, xn) of
+ * infer/modules/gui/torchgate.py for B rows at once.  x_dev [B][n], xn_dev [B][nn] (NULL: the noise statistics come from x, the
+ * reference's xn=None), all fp32; out_dev [B][hop * (n / hop)] fp32.  Per row:
+ *   X = stft(x, n_fft, hop, window, center=True, zero padding, onesided);  X_db = amp_to_db(X) = max(20 log10(|X| + eps64), max_f - 40)
+ *   stationary:      mask = X_db > mean_f(XN_db) + n_std_thresh * std_f(XN_db)   (unbiased std over the noise frames, per bin)
+ *   non-stationary:  s = conv1d(|X|, ones(n_movemean), padding="same") / n_movemean over frames (xn unused);
+ *                    mask = sigmoid(((|X| - s) / (s + 1e-6) - n_thresh_ns) / temp_coeff)
+ *   mask = prop_decrease * (float(mask) - 1) + 1 (fp32);  filter_dev [nf][nt] fp32 (NULL: none): conv2d over (bin, frame),
+ *   padding="same";  out = istft(X * mask): window * irfft, overlap-add, / sum of squared windows, n_fft / 2 trimmed at each end.
+ * window_dev [n_fft] fp64 is torch.hann_window(win_length) zero-padded to the centre.  Spectra, dB, statistics, comparison and
+ * overlap-add in fp64 (direct DFTs with exact (k m) mod n_fft twiddle reduction), one rounding at the end; the mask is fp32 like
+ * the reference's.  n_fft even and <= 4096 (an odd n_fft, which torch accepts, is RVCMI_ERR_INVALID), 1 <= hop <= n_fft,
+ * 0 <= prop_decrease <= 1.  Where the window envelope vanishes (torch.istft raises) the quotient is written as it falls.
+ * Enqueue-only: no allocation, synchronisation or host read-back (graph-capturable); rows are independent, so a row's output
+ * does not depend on B.  scratch_dev: rvcmi_glue_spectral_gate_scratch_bytes(B, n, xn_dev ? nn : 0, n_fft, hop) bytes.       */
+int rvcmi_glue_spectral_gate(const float* x_dev, int B, int64_t n, const float* xn_dev, int64_t nn, int n_fft, int hop,
+                             const double* window_dev, const float* filter_dev, int nf, int nt, int nonstationary,
+                             double n_std_thresh, double n_thresh_ns, double temp_coeff, int n_movemean, double prop_decrease,
+                             float* out_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+/* Bytes of scratch rvcmi_glue_spectral_gate needs (nn = 0: no noise signal); 0 when the arguments are out of range. */
+size_t rvcmi_glue_spectral_gate_scratch_bytes(int B, int64_t n, int64_t nn, int n_fft, int hop);
+
 /* The formant-shift resample of the realtime path (rtrvc.py:248-259, torchaudio.transforms.Resample(orig_freq = upp_res,
  * new_freq = tgt_sr / 100)): out[j * new + p] = sum_{k < K} kernel[p][k] * xpad[j * orig + k], xpad = x with `width` zeros in
  * front and zeros behind; orig / new already divided by their gcd; kernel_dev [new][K] (K = 2 * width + orig) is torchaudio's

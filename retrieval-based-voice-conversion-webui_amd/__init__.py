@@ -14,10 +14,11 @@ from .gru import GRUHIP, accelerate_rmvpe
 from .synthesizer import accelerate_synthesizer, get_synthesizer, load_synthesizer
 from . import dist
 from .install import install, uninstall
+from .gate import TorchGateHIP
 from .realtime import PitchCache, RealtimeStream, RealtimeVC, SincResample, f0_extractor_frame, sinc_resample_kernel, stream_geometry
 
 __all__ = [
     "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "GeneratorHIP", "NSFGeneratorHIP",
     "config_from_reference", "FrontHIP", "front_config_from_reference", "infer_hip", "retrieve_blend", "accelerate_synthesizer", "get_synthesizer", "load_synthesizer", "dist", "glue", "install", "uninstall", "RealtimeVC", "PitchCache", "f0_extractor_frame", "SincResample", "sinc_resample_kernel", "GRUHIP", "accelerate_rmvpe",
-    "RealtimeStream", "stream_geometry",
+    "RealtimeStream", "stream_geometry", "TorchGateHIP",
 ]

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "gate_kernels.hpp"
 #include "glue_kernels.hpp"
 
 using namespace rvcmi;
@@ -18,7 +19,8 @@ static void ensure_dyn_lds(K kernel, int bytes, std::atomic<unsigned long long>&
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     done_mask.fetch_or(bit, std::memory_order_release);
 }
-static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0};
+static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0},
+    g_attr_gate_stft{0}, g_attr_gate_idft{0};
 
 // The phase-vocoder launches on a device-resident b (b_off: optional device offset into b); out [n] may not alias a or b.
 static void launch_phase_vocoder(const float* a, const float* b, const int* b_off, const float* fade_out, const float* fade_in, int n, float* out,
@@ -32,7 +34,86 @@ static void launch_phase_vocoder(const float* a, const float* b, const int* b_of
                        fade_in, n, (const double*)bins, out);
 }
 
+// Scratch of rvcmi_glue_spectral_gate, in this order (each part 256-byte aligned):
+//   X [B][F][K] double2 | XN [B][Fn][K] double2 (nn > 0) | xmax, thresh [B][K] double | mask [B][F][K] float | frames [B][F][n_fft] double
+struct GateLayout {
+    size_t x, xn, xmax, thresh, mask, frames, total;
+};
+static bool gate_layout(int B, int64_t n, int64_t nn, int n_fft, int hop, GateLayout* g) {
+    if (B < 1 || n < 1 || nn < 0 || n_fft < 2 || (n_fft & 1) || n_fft > RVCMI_GATE_MAX_NFFT || hop < 1 || hop > n_fft) return false;
+    const int64_t F = 1 + n / hop, Fn = nn > 0 ? 1 + nn / hop : 0, K = n_fft / 2 + 1;
+    const int64_t tiles = (F + GATE_FT - 1) / GATE_FT + (Fn + GATE_FT - 1) / GATE_FT;
+    if (F > 65535 || tiles > 65535 || (int64_t)B > 65535) return false;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t o = 0;
+    g->x = o;       o = up(o + (size_t)B * F * K * 16);
+    g->xn = o;      o = up(o + (size_t)B * Fn * K * 16);
+    g->xmax = o;    o = up(o + (size_t)B * K * 8);
+    g->thresh = o;  o = up(o + (size_t)B * K * 8);
+    g->mask = o;    o = up(o + (size_t)B * F * K * 4);
+    g->frames = o;  o = up(o + (size_t)B * F * n_fft * 8);
+    g->total = o;
+    return true;
+}
+
 extern "C" {
+
+size_t rvcmi_glue_spectral_gate_scratch_bytes(int B, int64_t n, int64_t nn, int n_fft, int hop) {
+    GateLayout g;
+    return gate_layout(B, n, nn, n_fft, hop, &g) ? g.total : 0;
+}
+
+int rvcmi_glue_spectral_gate(const float* x, int B, int64_t n, const float* xn, int64_t nn, int n_fft, int hop, const double* window,
+                             const float* filter, int nf, int nt, int nonstationary, double n_std_thresh, double n_thresh_ns,
+                             double temp_coeff, int n_movemean, double prop_decrease, float* out, void* scratch, size_t scratch_bytes,
+                             void* stream) {
+    return guarded([&] {
+        if (!x || !window || !out || !scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: null pointer");
+        if (n_fft < 2 || n_fft > RVCMI_GATE_MAX_NFFT || (n_fft & 1))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: n_fft = %d must be even and in [2, %d]", n_fft, RVCMI_GATE_MAX_NFFT);
+        if (hop < 1 || hop > n_fft) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: hop = %d outside [1, n_fft = %d]", hop, n_fft);
+        if (B < 1 || n < 1 || (xn && nn < 1)) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: empty input");
+        if (filter && (nf < 1 || nt < 1 || (int64_t)nf * nt > (1 << 20)))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: smoothing filter %d x %d", nf, nt);
+        if (!(prop_decrease >= 0.0 && prop_decrease <= 1.0)) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: prop_decrease outside [0, 1]");
+        if (nonstationary && n_movemean < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: n_movemean < 1");
+        const bool use_xn = xn && !nonstationary;  // the non-stationary mask looks at x alone (torchgate.py:246-247)
+        GateLayout g;
+        if (!gate_layout(B, n, use_xn ? nn : 0, n_fft, hop, &g)) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: too many frames");
+        if (scratch_bytes < g.total)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate: scratch of %zu bytes, %zu needed", scratch_bytes, g.total);
+        char* s = static_cast<char*>(scratch);
+        double2* X = reinterpret_cast<double2*>(s + g.x);
+        double2* XN = use_xn ? reinterpret_cast<double2*>(s + g.xn) : nullptr;
+        double* xmax = reinterpret_cast<double*>(s + g.xmax);
+        double* thresh = reinterpret_cast<double*>(s + g.thresh);
+        float* mraw = reinterpret_cast<float*>(s + g.mask);
+        double* z = reinterpret_cast<double*>(s + g.frames);
+        const int F = (int)(1 + n / hop), Fn = use_xn ? (int)(1 + nn / hop) : 0, K = n_fft / 2 + 1;
+        const int tiles_x = (F + GATE_FT - 1) / GATE_FT, tiles_n = (Fn + GATE_FT - 1) / GATE_FT;
+        const int64_t Lout = (int64_t)hop * (n / hop);
+        const int lds = gate_lds_bytes(n_fft);
+        hipStream_t st = (hipStream_t)stream;
+        ensure_dyn_lds(k_gate_stft, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_stft);
+        ensure_dyn_lds(k_gate_idft, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_idft);
+        hipLaunchKernelGGL(k_gate_stft, dim3((unsigned)((K + 63) / 64), (unsigned)(tiles_x + tiles_n), (unsigned)B), dim3(256), (size_t)lds, st,
+                           x, n, F, X, use_xn ? xn : x, use_xn ? nn : n, Fn, XN, tiles_x, n_fft, hop, window);
+        hipLaunchKernelGGL(k_gate_stats, dim3((unsigned)((K + 63) / 64), (unsigned)B), dim3(1024), 0, st, (const double2*)X, F,
+                           (const double2*)XN, Fn, K, nonstationary ? 0 : 1, n_std_thresh, xmax, thresh);
+        hipLaunchKernelGGL(k_gate_mask, dim3((unsigned)((K + 255) / 256), (unsigned)F, (unsigned)B), dim3(256), 0, st, (const double2*)X, F, K,
+                           (const double*)xmax, (const double*)thresh, nonstationary ? 1 : 0, n_thresh_ns, temp_coeff, n_movemean,
+                           (float)prop_decrease, mraw);
+        hipLaunchKernelGGL(k_gate_smooth, dim3((unsigned)((K + 255) / 256), (unsigned)F, (unsigned)B), dim3(256), 0, st, X, F, K,
+                           (const float*)mraw, filter, nf, nt);
+        hipLaunchKernelGGL(k_gate_idft, dim3((unsigned)((n_fft + 63) / 64), (unsigned)tiles_x, (unsigned)B), dim3(256), (size_t)lds, st,
+                           (const double2*)X, F, n_fft, window, z);
+        if (Lout > 0)
+            hipLaunchKernelGGL(k_gate_ola, dim3((unsigned)((Lout + 255) / 256), (unsigned)B), dim3(256), 0, st, (const double*)z, F, n_fft, hop,
+                               window, Lout, out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 
 int rvcmi_glue_expand_protect(const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
                               float* out, void* stream) {

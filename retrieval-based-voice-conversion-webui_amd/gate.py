@@ -1,0 +1,100 @@
+"""``TorchGate`` (infer/modules/gui/torchgate.py), the realtime GUI's noise reduction, on the device: the same constructor,
+defaults, ``smoothing_filter`` buffer and ``forward(x, xn=None)``, computed by one ``glue.spectral_gate`` call (rvcmi.h).
+
+    tg = TorchGateHIP(sr=48000, n_fft=4 * 480, prop_decrease=0.9).to("cuda:0")     # gui.py:869-871
+    y = tg(x[None], xn[None])                                                        # gui.py:983-985, 1020-1022
+
+Divergences from the reference: an odd ``n_fft`` raises ``RvcmiError`` (torch accepts it); a ``freq_mask_smooth_hz`` below one bin
+raises the ``ValueError`` the reference means to raise (its message formats the missing ``self._n_fft``, so it raises
+``AttributeError``, torchgate.py:94-96); the DirectML ``STFT`` branch is not reproduced (the input must be a ROCm tensor).
+"""
+from __future__ import annotations
+
+from typing import Optional, Union
+
+import torch
+
+from . import _lib, glue
+
+
+def _linspace(start, stop, num: int = 50, endpoint: bool = True) -> torch.Tensor:
+    """utils.py:46-71"""
+    if endpoint:
+        return torch.linspace(start, stop, num)
+    return torch.linspace(start, stop, num + 1)[:-1]
+
+
+class TorchGateHIP(torch.nn.Module):
+    @torch.no_grad()
+    def __init__(self, sr: int, nonstationary: bool = False, n_std_thresh_stationary: float = 1.5, n_thresh_nonstationary: float = 1.3,
+                 temp_coeff_nonstationary: float = 0.1, n_movemean_nonstationary: int = 20, prop_decrease: float = 1.0, n_fft: int = 1024,
+                 win_length: bool = None, hop_length: int = None, freq_mask_smooth_hz: float = 500, time_mask_smooth_ms: float = 50):
+        super().__init__()
+        self.sr = sr
+        self.nonstationary = nonstationary
+        assert 0.0 <= prop_decrease <= 1.0
+        self.prop_decrease = prop_decrease
+        self.n_fft = n_fft
+        self.win_length = self.n_fft if win_length is None else win_length
+        self.hop_length = self.win_length // 4 if hop_length is None else hop_length
+        self.n_std_thresh_stationary = n_std_thresh_stationary
+        self.temp_coeff_nonstationary = temp_coeff_nonstationary
+        self.n_movemean_nonstationary = n_movemean_nonstationary
+        self.n_thresh_nonstationary = n_thresh_nonstationary
+        self.freq_mask_smooth_hz = freq_mask_smooth_hz
+        self.time_mask_smooth_ms = time_mask_smooth_ms
+        self.register_buffer("smoothing_filter", self._generate_mask_smoothing_filter())
+        self._windows = {}
+
+    @torch.no_grad()
+    def _generate_mask_smoothing_filter(self) -> Union[torch.Tensor, None]:
+        """torchgate.py:75-127, in the default dtype as there."""
+        if self.freq_mask_smooth_hz is None and self.time_mask_smooth_ms is None:
+            return None
+        n_grad_freq = 1 if self.freq_mask_smooth_hz is None else int(self.freq_mask_smooth_hz / (self.sr / (self.n_fft / 2)))
+        if n_grad_freq < 1:
+            raise ValueError(f"freq_mask_smooth_hz needs to be at least {int((self.sr / (self.n_fft / 2)))} Hz")
+        n_grad_time = 1 if self.time_mask_smooth_ms is None else int(self.time_mask_smooth_ms / ((self.hop_length / self.sr) * 1000))
+        if n_grad_time < 1:
+            raise ValueError(f"time_mask_smooth_ms needs to be at least {int((self.hop_length / self.sr) * 1000)} ms")
+        if n_grad_time == 1 and n_grad_freq == 1:
+            return None
+        v_f = torch.cat([_linspace(0, 1, n_grad_freq + 1, endpoint=False), _linspace(1, 0, n_grad_freq + 2)])[1:-1]
+        v_t = torch.cat([_linspace(0, 1, n_grad_time + 1, endpoint=False), _linspace(1, 0, n_grad_time + 2)])[1:-1]
+        smoothing_filter = torch.outer(v_f, v_t).unsqueeze(0).unsqueeze(0)
+        return smoothing_filter / smoothing_filter.sum()
+
+    def _window(self, dev: torch.device) -> torch.Tensor:
+        """torch.stft's window: torch.hann_window(win_length) (periodic) zero-padded to n_fft at the centre, in fp64."""
+        w = self._windows.get(dev)
+        if w is None:
+            if not 0 < self.win_length <= self.n_fft:
+                raise ValueError("win_length = %d must be in [1, n_fft = %d]" % (self.win_length, self.n_fft))
+            w = torch.zeros(self.n_fft, dtype=torch.float64)
+            left = (self.n_fft - self.win_length) // 2
+            w[left: left + self.win_length] = torch.hann_window(self.win_length, dtype=torch.float64)
+            w = self._windows[dev] = w.to(dev)
+        return w
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B, L] or [L] (``xn`` shaped alike, or None: the noise statistics come from x) on the GPU -> the gated signal,
+        ``hop_length * (L // hop_length)`` samples in x's dtype (computed from x rounded to float32)."""
+        if x.device.type != "cuda" or (xn is not None and xn.device.type != "cuda"):
+            raise _lib.RvcmiError("TorchGateHIP runs on the GPU (got %s); there is no CPU fallback" % x.device)
+        squeeze = x.dim() == 1
+        x32 = (x[None] if squeeze else x).to(torch.float32).contiguous()
+        xn32 = None
+        if xn is not None:
+            xn32 = (xn[None] if xn.dim() == 1 else xn).to(torch.float32)
+            if xn32.shape[0] == 1 and x32.shape[0] > 1:
+                xn32 = xn32.expand(x32.shape[0], -1)
+            xn32 = xn32.contiguous()
+        filt = self.smoothing_filter
+        if filt is not None:
+            filt = filt.reshape(filt.shape[-2], filt.shape[-1]).to(device=x.device, dtype=torch.float32).contiguous()
+        y = glue.spectral_gate(x32, xn32, self.n_fft, self.hop_length, self._window(x.device), filt, nonstationary=self.nonstationary,
+                               n_std_thresh=self.n_std_thresh_stationary, n_thresh_ns=self.n_thresh_nonstationary,
+                               temp_coeff=self.temp_coeff_nonstationary, n_movemean=self.n_movemean_nonstationary,
+                               prop_decrease=self.prop_decrease)
+        return (y[0] if squeeze else y).to(x.dtype)

@@ -12,6 +12,7 @@ and of the realtime GUI's block (gui.py:934-1090, assembled by ``realtime.Realti
     envelope_mix(input_wav, infer_wav, zc, rms_mix_rate)                      gui.py:1023-1056
     sola(infer_wav, sola_buffer, fade_in, fade_out, block, search, use_pv)    gui.py:1057-1090
     phase_vocoder(a, b, fade_out, fade_in)                                    gui.py:27-49
+    spectral_gate(x, xn, n_fft, hop, window, smoothing_filter, ...)           torchgate.py (gui.py:974-992, 1015-1022)
 
 All take and return CUDA (ROCm) tensors and enqueue on the current stream; a CPU tensor raises (no fallback).
 """
@@ -207,3 +208,44 @@ def envelope_mix(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int, rms_
         _lib.check(_lib.lib().rvcmi_glue_envelope_mix(_ptr(input_wav), _ptr(infer_wav), n, zc, float(rms_mix_rate), _ptr(scratch),
                                                       _stream(dev)))
     return infer_wav
+
+
+def spectral_gate(x: torch.Tensor, xn: Optional[torch.Tensor], n_fft: int, hop: int, window: torch.Tensor,
+                  smoothing_filter: Optional[torch.Tensor] = None, nonstationary: bool = False, n_std_thresh: float = 1.5,
+                  n_thresh_ns: float = 1.3, temp_coeff: float = 0.1, n_movemean: int = 20, prop_decrease: float = 1.0) -> torch.Tensor:
+    """``TorchGate.forward(x, xn)`` (infer/modules/gui/torchgate.py) in one enqueue-only call: x [B, L] and xn [B, Ln] (or None)
+    contiguous float32, ``window`` [n_fft] float64 (the hann window zero-padded to the centre), ``smoothing_filter`` [nf, nt]
+    float32 or None.  Returns a new float32 tensor [B, hop * (L // hop)].  STFT, statistics and overlap-add in fp64
+    (rvcmi.h); n_fft must be even and <= 4096."""
+    dev = _dev(x, "x")
+    tensors = [(x, "x", torch.float32), (window, "window", torch.float64)]
+    if xn is not None:
+        tensors.append((xn, "xn", torch.float32))
+    if smoothing_filter is not None:
+        tensors.append((smoothing_filter, "smoothing_filter", torch.float32))
+    for t, nm, dt in tensors:
+        _dev(t, nm)
+        if t.device != dev:
+            raise _lib.RvcmiError("%s lives on %s, x on %s" % (nm, t.device, dev))
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor" % (nm, dt))
+    if x.dim() != 2 or (xn is not None and (xn.dim() != 2 or xn.shape[0] != x.shape[0])):
+        raise ValueError("x must be [B, L] and xn [B, Ln]")
+    if window.dim() != 1 or window.numel() != int(n_fft):
+        raise ValueError("window must have n_fft = %d samples" % int(n_fft))
+    B, n = int(x.shape[0]), int(x.shape[1])
+    nn = int(xn.shape[1]) if xn is not None else 0
+    hop = int(hop)
+    nf, nt = (int(smoothing_filter.shape[-2]), int(smoothing_filter.shape[-1])) if smoothing_filter is not None else (0, 0)
+    L = _lib.lib()
+    nbytes = int(L.rvcmi_glue_spectral_gate_scratch_bytes(B, n, nn, int(n_fft), hop))
+    if nbytes == 0:
+        raise _lib.RvcmiError("spectral_gate: n_fft = %d (even, <= 4096), hop = %d (1..n_fft) or the shapes %s / %s are out of range"
+                              % (int(n_fft), hop, tuple(x.shape), tuple(xn.shape) if xn is not None else None), code=_lib.ERR_INVALID)
+    out = torch.empty(B, hop * (n // hop) if hop > 0 else 0, device=dev, dtype=torch.float32)
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(L.rvcmi_glue_spectral_gate(_ptr(x), B, n, _ptr(xn), nn, int(n_fft), hop, _ptr(window), _ptr(smoothing_filter), nf, nt,
+                                              1 if nonstationary else 0, float(n_std_thresh), float(n_thresh_ns), float(temp_coeff),
+                                              int(n_movemean), float(prop_decrease), _ptr(out), _ptr(scratch), nbytes, _stream(dev)))
+    return out

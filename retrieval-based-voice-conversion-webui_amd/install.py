@@ -18,6 +18,9 @@ rebinds the two names the reference resolves its hot path through:
   the GPU through retrieval, x2, protect mix, ``net_g.infer``, RMS mix and int16 scaling (one copy to the host at the end).
   The originals stay reachable (an index object the HIP reader cannot serve is handed back to them).
 
+* with ``patch_gui=True`` (opt-in): ``TorchGate`` as ``infer.modules.gui`` and ``infer.modules.gui.torchgate`` export it -> ``TorchGateHIP``,
+  so the realtime GUI's noise reduction (gui.py:869-871) runs on the device.
+
 Nothing of the reference is edited; ``uninstall()`` restores the original bindings.
 """
 from __future__ import annotations
@@ -37,6 +40,7 @@ _state: dict = {}
 _LOADER_USERS = ("infer.modules.vc.modules", "infer.modules.vc.hash", "infer.lib.rtrvc")
 _PIPELINE_MODULE, _RTRVC_MODULE = "infer.modules.vc.pipeline", "infer.lib.rtrvc"
 _FAISS_USERS = ("infer.modules.vc.pipeline", "infer.lib.rtrvc")
+_GUI_GATE_MODULES = ("infer.modules.gui", "infer.modules.gui.torchgate")
 
 
 class _FaissShim(types.ModuleType):
@@ -115,8 +119,29 @@ def _rebind_methods(rebound) -> None:
             rebound.append((cls, "infer", old))
 
 
-def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True) -> None:
-    """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent)."""
+def _rebind_gate(rebound) -> None:
+    """``TorchGate`` as ``infer.modules.gui`` and ``infer.modules.gui.torchgate`` export it -> ``TorchGateHIP`` (same constructor,
+    ``forward(x, xn)``), so the realtime GUI's ``TorchGate(sr=..., n_fft=4 * zc, prop_decrease=0.9)`` (gui.py:869-871) builds the
+    device gate.  A module that is not importable is left alone."""
+    from .gate import TorchGateHIP
+
+    for modname in _GUI_GATE_MODULES:
+        mod = sys.modules.get(modname)
+        if mod is None:
+            try:
+                mod = importlib.import_module(modname)
+            except Exception:  # noqa  (torchgate.py imports rvc.f0.stft, which needs librosa)
+                continue
+        old = getattr(mod, "TorchGate", None)
+        if old is not None and old is not TorchGateHIP:
+            setattr(mod, "TorchGate", TorchGateHIP)
+            rebound.append((mod, "TorchGate", old))
+
+
+def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
+            patch_gui: bool = False) -> None:
+    """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
+    also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -172,6 +197,8 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
                 mod.faiss = shim
     if patch_pipeline:
         _rebind_methods(rebound)
+    if patch_gui:
+        _rebind_gate(rebound)
 
 
 def uninstall() -> None:

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, glue
+from .gate import TorchGateHIP
 
 
 def f0_extractor_frame(block_frame_16k: int, method: str = "fcpe", window: int = 160) -> int:
@@ -235,16 +236,22 @@ class RealtimeStream:
     Per block: the input gate (host, when ``threhold > -60``), rolling ``input_wav`` / ``input_wav_res`` buffers and the 16 kHz
     resample, ``rvc.infer``, the ``tgt_sr -> samplerate`` resample, the envelope mix (``rms_mix_rate < 1``) and the SOLA stitch
     (sin^2 or phase-vocoder fade), all on the device: one host-to-device copy (the block), none back.  The keyword names are the
-    GUI's ``GUIConfig`` fields; ``samplerate=None`` is the model rate.  Not covered: noise reduction (TorchGate) and the "im"
-    monitor mode."""
+    GUI's ``GUIConfig`` fields; ``samplerate=None`` is the model rate.  ``I_noise_reduce`` / ``O_noise_reduce`` (the GUI's
+    noise-reduction boxes, gui.py:974-992, 1015-1022) gate the input and the converted block with ``TorchGateHIP``;
+    ``function="im"`` is the monitor mode (gui.py:1000-1013: no ``rvc.infer``, ``rvc`` may be None when ``samplerate`` is given).
+    All three are plain attributes that may change between blocks, as the GUI's hot update does."""
 
     def __init__(self, rvc, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05, extra_time: float = 2.5,
-                 threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe", device=None):
+                 threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe", device=None,
+                 I_noise_reduce: bool = False, O_noise_reduce: bool = False, function: str = "vc"):
         self.rvc = rvc
-        self.tgt_sr = int(rvc.tgt_sr)
+        if rvc is None and samplerate is None:
+            raise ValueError("RealtimeStream without an rvc object (the \"im\" mode) needs samplerate")
+        self.tgt_sr = int(rvc.tgt_sr) if rvc is not None else int(samplerate)
         self.samplerate = self.tgt_sr if samplerate is None else int(samplerate)
         self.block_time, self.crossfade_time, self.extra_time = block_time, crossfade_time, extra_time
         self.threhold, self.rms_mix_rate, self.use_pv, self.f0method = threhold, float(rms_mix_rate), bool(use_pv), f0method
+        self.I_noise_reduce, self.O_noise_reduce, self.function = I_noise_reduce, O_noise_reduce, function
         if device is None:
             device = getattr(rvc, "device", None) or "cuda:0"
         self.device = torch.device(device)
@@ -257,12 +264,17 @@ class RealtimeStream:
         self.input_wav_res = torch.zeros(self.input_wav_res_len, device=self.device, dtype=torch.float32)
         self.rms_buffer = np.zeros(4 * self.zc, dtype="float32")
         self.sola_buffer = torch.zeros(self.sola_buffer_frame, device=self.device, dtype=torch.float32)
+        # gui.py:825, 835-836: kept whatever the noise-reduction boxes say, updated only while they are ticked
+        self.input_wav_denoise = self.input_wav.clone()
+        self.nr_buffer = self.sola_buffer.clone()
+        self.output_buffer = self.input_wav.clone()
         # the GUI's fp32 expression (gui.py:841-855), on the CPU and uploaded once
         fade_in = torch.sin(0.5 * np.pi * torch.linspace(0.0, 1.0, steps=self.sola_buffer_frame, dtype=torch.float32)) ** 2
         self.fade_in_window = fade_in.to(self.device)
         self.fade_out_window = (1 - fade_in).to(self.device)
         self.resampler = SincResample(self.samplerate, 16000, self.device)
         self.resampler2 = SincResample(self.tgt_sr, self.samplerate, self.device) if self.tgt_sr != self.samplerate else None
+        self.tg = TorchGateHIP(sr=self.samplerate, n_fft=4 * self.zc, prop_decrease=0.9).to(self.device)   # gui.py:869-871
         self.last_offset = None  # device int32 [1]: the SOLA offset of the last block
 
     def process(self, indata) -> torch.Tensor:
@@ -278,16 +290,35 @@ class RealtimeStream:
         self.input_wav[:-blk] = self.input_wav[blk:].clone()
         self.input_wav[-m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         self.input_wav_res[:-blk16] = self.input_wav_res[blk16:].clone()
-        self.input_wav_res[-160 * (m // self.zc + 1):] = self.resampler(self.input_wav[-m - 2 * self.zc:])[160:]
-        infer_wav = self.rvc.infer(self.input_wav_res, blk16, self.skip_head, self.return_length, self.f0method)
-        if self.resampler2 is not None:
-            infer_wav = self.resampler2(infer_wav)
-        infer_wav = infer_wav.reshape(-1)
-        if infer_wav.dtype != torch.float32 or not infer_wav.is_contiguous():
-            infer_wav = infer_wav.float().contiguous()
-        if self.rms_mix_rate < 1:
+        Lb = self.sola_buffer_frame
+        if self.I_noise_reduce:                                                          # gui.py:974-992
+            self.input_wav_denoise[:-blk] = self.input_wav_denoise[blk:].clone()
+            input_wav = self.tg(self.input_wav[None, -Lb - blk:], self.input_wav[None]).squeeze(0)
+            input_wav[:Lb] *= self.fade_in_window
+            input_wav[:Lb] += self.nr_buffer * self.fade_out_window
+            self.input_wav_denoise[-blk:] = input_wav[:blk]
+            self.nr_buffer[:] = input_wav[blk:]
+            self.input_wav_res[-blk16 - 160:] = self.resampler(self.input_wav_denoise[-blk - 2 * self.zc:])[160:]
+        else:
+            self.input_wav_res[-160 * (m // self.zc + 1):] = self.resampler(self.input_wav[-m - 2 * self.zc:])[160:]
+        vc = self.function == "vc"
+        if vc:
+            infer_wav = self.rvc.infer(self.input_wav_res, blk16, self.skip_head, self.return_length, self.f0method)
+            if self.resampler2 is not None:
+                infer_wav = self.resampler2(infer_wav)
+            infer_wav = infer_wav.reshape(-1)
+            if infer_wav.dtype != torch.float32 or not infer_wav.is_contiguous():
+                infer_wav = infer_wav.float().contiguous()
+        else:                                                                            # gui.py:1000-1013, "im"
+            infer_wav = (self.input_wav_denoise if self.I_noise_reduce else self.input_wav)[self.extra_frame:].clone()
+        if self.O_noise_reduce and vc:                                                   # gui.py:1015-1022
+            self.output_buffer[:-blk] = self.output_buffer[blk:].clone()
+            self.output_buffer[-blk:] = infer_wav[-blk:]
+            infer_wav = self.tg(infer_wav[None], self.output_buffer[None]).squeeze(0)
+        if self.rms_mix_rate < 1 and vc:
             n = int(infer_wav.numel())
-            glue.envelope_mix(self.input_wav[self.extra_frame: self.extra_frame + n], infer_wav, self.zc, self.rms_mix_rate)
+            src = self.input_wav_denoise if self.I_noise_reduce else self.input_wav
+            glue.envelope_mix(src[self.extra_frame: self.extra_frame + n], infer_wav, self.zc, self.rms_mix_rate)
         out, self.last_offset = glue.sola(infer_wav, self.sola_buffer, self.fade_in_window, self.fade_out_window, blk, self.sola_search_frame,
                                           return_offset=True, use_pv=self.use_pv)
         return out
