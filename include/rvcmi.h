@@ -394,6 +394,23 @@ int rvcmi_glue_spectral_gate(const float* x_dev, int B, int64_t n, const float* 
 /* Bytes of scratch rvcmi_glue_spectral_gate needs (nn = 0: no noise signal); 0 when the arguments are out of range. */
 size_t rvcmi_glue_spectral_gate_scratch_bytes(int B, int64_t n, int64_t nn, int n_fft, int hop);
 
+/* Where Pipeline.pipeline cuts a long input (infer/modules/vc/pipeline.py:219-236): for every t in range(t_center, n, t_center),
+ *   cuts_dev[c] = t - t_query + first argmin of audio_sum[t - t_query : min(t + t_query, n)],
+ *   audio_sum[j] = (((0 + |p[j]|) + |p[j + 1]|) + ... + |p[j + window - 1]|),  p = np.pad(audio, window / 2, mode="reflect"),
+ * in IEEE fp64 with the adds in exactly that order, so the sums -- and the cuts -- are BIT-equal to numpy's `window` passes; only
+ * the positions a search window looks at are computed.  audio_dev [n] fp64 (the filtfilt output); the reflection is index
+ * arithmetic.  cuts_dev [>= len(range(t_center, n, t_center))] int64; sums_dev (or NULL) [cuts][2 t_query] fp64 receives the
+ * window sums (entries past the end of the signal are left untouched).  RVCMI_ERR_INVALID, and nothing launched, when the number
+ * of cuts exceeds max_cuts (or 65535), window is odd, below 2 or above 1024 (the LDS staging; the reference's is 160),
+ * n <= window, or t_query > t_center (numpy's negative slice start would wrap there; no reference configuration has it).
+ * Comparisons with NaN are false, so a NaN is never the minimum and a window of nothing but NaN yields its first position; the
+ * reference raises IndexError as soon as a window holds one NaN (an enqueue-only call cannot raise on data).
+ * Enqueue-only, deterministic (no float atomics).  scratch_dev: rvcmi_glue_cut_points_scratch_bytes(...) bytes.               */
+int rvcmi_glue_cut_points(const double* audio_dev, int64_t n, int window, int64_t t_center, int64_t t_query, int64_t* cuts_dev,
+                          int64_t max_cuts, double* sums_dev, void* scratch_dev, void* stream);
+/* Bytes of scratch rvcmi_glue_cut_points needs; 0 when the arguments are out of range (or there is no cut). */
+size_t rvcmi_glue_cut_points_scratch_bytes(int64_t n, int window, int64_t t_center, int64_t t_query);
+
 /* The formant-shift resample of the realtime path (rtrvc.py:248-259, torchaudio.transforms.Resample(orig_freq = upp_res,
  * new_freq = tgt_sr / 100)): out[j * new + p] = sum_{k < K} kernel[p][k] * xpad[j * orig + k], xpad = x with `width` zeros in
  * front and zeros behind; orig / new already divided by their gcd; kernel_dev [new][K] (K = 2 * width + orig) is torchaudio's

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "cut_kernels.hpp"
 #include "gate_kernels.hpp"
 #include "glue_kernels.hpp"
 
@@ -56,7 +57,46 @@ static bool gate_layout(int B, int64_t n, int64_t nn, int n_fft, int hop, GateLa
     return true;
 }
 
+// Geometry of rvcmi_glue_cut_points: false when the arguments are out of range.  cuts = len(range(t_center, n, t_center)).
+static bool cut_layout(int64_t n, int window, int64_t t_center, int64_t t_query, int64_t* cuts, int* tiles) {
+    if (window < 2 || (window & 1) || window > RVCMI_CUT_MAX_WINDOW || n <= window || t_center < 1 || t_query < 1 || t_query > t_center)
+        return false;
+    const int64_t nt = (2 * t_query + CUT_TILE - 1) / CUT_TILE;
+    *cuts = n > t_center ? (n - 1) / t_center : 0;
+    if (nt > 0x7fffffff || *cuts > 65535) return false;
+    *tiles = (int)nt;
+    return true;
+}
+
 extern "C" {
+
+size_t rvcmi_glue_cut_points_scratch_bytes(int64_t n, int window, int64_t t_center, int64_t t_query) {
+    int64_t cuts;
+    int tiles;
+    if (!cut_layout(n, window, t_center, t_query, &cuts, &tiles)) return 0;
+    return (size_t)cuts * tiles * sizeof(CutBest);
+}
+
+int rvcmi_glue_cut_points(const double* audio, int64_t n, int window, int64_t t_center, int64_t t_query, int64_t* cuts_out, int64_t max_cuts,
+                          double* sums, void* scratch, void* stream) {
+    return guarded([&] {
+        int64_t cuts;
+        int tiles;
+        if (!cut_layout(n, window, t_center, t_query, &cuts, &tiles))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "cut_points: window = %d must be even and in [2, %d], n = %lld > window, 1 <= t_query = %lld <= t_center = %lld, "
+                       "at most 65535 cuts", window, RVCMI_CUT_MAX_WINDOW, (long long)n, (long long)t_query, (long long)t_center);
+        if (cuts > max_cuts) RVCMI_FAIL(RVCMI_ERR_INVALID, "cut_points: %lld cuts, room for %lld", (long long)cuts, (long long)max_cuts);
+        if (!cuts) return;
+        if (!audio || !cuts_out || !scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "cut_points: null pointer");
+        hipStream_t st = (hipStream_t)stream;
+        CutBest* best = static_cast<CutBest*>(scratch);
+        hipLaunchKernelGGL(k_cut_sums, dim3((unsigned)tiles, (unsigned)cuts), dim3(CUT_THREADS), 0, st, audio, n, window, t_center, t_query, tiles,
+                           best, sums);
+        hipLaunchKernelGGL(k_cut_pick, dim3((unsigned)cuts), dim3(CUT_THREADS), 0, st, (const CutBest*)best, tiles, t_center, t_query, cuts_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 
 size_t rvcmi_glue_spectral_gate_scratch_bytes(int B, int64_t n, int64_t nn, int n_fft, int hop) {
     GateLayout g;

@@ -6,6 +6,7 @@ row 2), so that nothing between the PyTorch-ROCm feature extractors and ``net_g.
     f0_post(f0, f0_up_key)                                                    rvc/f0/gen.py:10-41
     change_rms(audio16k, 16000, audio_opt, tgt_sr, rms_mix_rate)              pipeline.py:26-46,351
     scale_int16_range(audio)                                                  pipeline.py:355-359
+    cut_points(audio64, window, t_center, t_query)                            pipeline.py:219-236
 
 and of the realtime GUI's block (gui.py:934-1090, assembled by ``realtime.RealtimeStream``):
 
@@ -136,6 +137,35 @@ def change_rms(data1: torch.Tensor, sr1: int, data2: torch.Tensor, sr2: int, rat
         _lib.check(_lib.lib().rvcmi_glue_change_rms(_ptr(data1), n1, int(sr1), _ptr(data2), n2, int(sr2), float(rate), _ptr(scratch),
                                                     _stream(dev)))
     return data2
+
+
+def cut_count(n: int, t_center: int) -> int:
+    """How many cuts an input of ``n`` samples gets: ``len(range(t_center, n, t_center))`` (pipeline.py:228)."""
+    return len(range(int(t_center), int(n), int(t_center)))
+
+
+def cut_points(audio: torch.Tensor, window: int, t_center: int, t_query: int, return_sums: bool = False):
+    """The quiet-point search of pipeline.py:219-236 on the device: ``audio`` [n] float64 (the ``filtfilt`` output) -> int64 tensor
+    ``[cut_count(n, t_center)]``, ``cut = t - t_query + first argmin of audio_sum[t - t_query : t + t_query]`` for every multiple
+    ``t`` of ``t_center`` below ``n``; the window sums are numpy's, bit for bit (include/rvcmi.h).  ``return_sums=True`` also
+    returns them as ``[cuts, 2 t_query]`` float64, NaN where a search window runs past the end of the signal.  A tensor that is
+    not float64 raises ``TypeError``: a cast would change the sums.  Enqueue-only; the caller reads the cuts back."""
+    if audio.dtype != torch.float64:
+        raise TypeError("audio must be float64 (got %s): the sums are defined on the float64 signal" % audio.dtype)
+    dev = _dev(audio, "audio")
+    if audio.dim() != 1 or not audio.is_contiguous():
+        raise ValueError("audio must be a contiguous 1-D tensor")
+    n, window, t_center, t_query = int(audio.numel()), int(window), int(t_center), int(t_query)
+    L = _lib.lib()
+    ncuts = cut_count(n, t_center) if t_center > 0 else 0
+    nbytes = int(L.rvcmi_glue_cut_points_scratch_bytes(n, window, t_center, t_query))
+    cuts = torch.empty(ncuts, device=dev, dtype=torch.int64)
+    sums = torch.full((ncuts, 2 * max(t_query, 0)), float("nan"), device=dev, dtype=torch.float64) if return_sums else None
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(L.rvcmi_glue_cut_points(_ptr(audio), n, window, t_center, t_query, _ptr(cuts), ncuts, _ptr(sums), _ptr(scratch),
+                                           _stream(dev)))
+    return (cuts, sums) if return_sums else cuts
 
 
 def scale_int16_range(audio: torch.Tensor) -> torch.Tensor:

@@ -40,7 +40,9 @@ def retrieve_blend(feats: torch.Tensor, index: IVFFlatHIP, index_rate: float, k:
 # search + blend + x2 + protect mix in one launch (rvcmi_ivf_search_blend_expand), ``net_g.infer`` on the HIP front + generator,
 # segments concatenated, ``change_rms`` and the int16-range scaling on the device, ONE copy to the host at the very end
 # (the API returns a numpy array).  Host work that remains is the reference's own input preparation on the 16 kHz waveform
-# (high-pass ``filtfilt``, the quiet-point search that chooses the cut positions) and estimators other than RMVPE.
+# (high-pass ``filtfilt``) and estimators other than RMVPE.  The quiet-point search that chooses the cut positions of a long input
+# runs on the device (``glue.cut_points``, bit-equal to the host loop): one upload of the filtered fp64 signal, which
+# ``change_rms`` then shares, and one small synchronising read-back of the cuts per long file -- segment shapes depend on them.
 
 def _ref_module(self):
     import sys
@@ -250,6 +252,38 @@ def _cut_points(self, audio, audio_pad_w):
     return opt_ts
 
 
+def _device_cuts(self, audio, dev):
+    """The cut positions of ``_cut_points`` from the device search, or None when the host loop has to run (no GPU, a signal that is
+    not float64, ``t_query > t_center`` -- numpy's negative slice start wraps there, the kernel refuses it --, a window the kernel
+    does not stage, ``RVCMI_DEVICE_CUTS=0``).  -> (list of ints, the filtered signal as a float64 device tensor).  One upload, one
+    synchronising read-back of ``len(opt_ts)`` integers."""
+    import os
+
+    import numpy as np
+
+    from . import glue
+
+    w = int(self.window)
+    if (dev.type != "cuda" or os.environ.get("RVCMI_DEVICE_CUTS", "1") == "0" or audio.dtype != np.float64 or audio.ndim != 1
+            or self.t_query > self.t_center or self.t_query < 1 or w % 2 or not 2 <= w <= 1024 or audio.shape[0] <= w):
+        return None
+    a64 = torch.from_numpy(np.ascontiguousarray(audio)).to(dev)
+    return glue.cut_points(a64, w, int(self.t_center), int(self.t_query)).tolist(), a64
+
+
+def _file_cuts(self, audio, dev):
+    """pipeline.py:222-236 for one filtered input: -> (opt_ts, its float64 device copy or None).  The search runs when the input,
+    padded by half a window at each end, is longer than ``t_max`` (the reference's condition): on the device where that is
+    possible, else by the host loop, which also answers ``[]`` for a short input."""
+    import numpy as np
+
+    if audio.shape[0] + 2 * (self.window // 2) > self.t_max:
+        got = _device_cuts(self, audio, dev)
+        if got is not None:
+            return got
+    return _cut_points(self, audio, np.pad(audio, (self.window // 2, self.window // 2), mode="reflect")), None
+
+
 RMVPE_THRED = 0.03  # rvc/f0/gen.py:113: Generator.calculate hard-codes compute_f0(..., filter_radius=0.03) for rmvpe
 
 
@@ -334,7 +368,8 @@ def _open_index(self, file_index, index_rate):
 def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect):
     """``Pipeline.pipeline`` from its input to the point where a segment would enter ``vc`` (pipeline.py:219-300): high-pass,
     cut points, reflection pad, f0 (RMVPE decoded on the device), then ``collect(audio_segment, pitch_slice, pitchf_slice)`` for
-    every segment in order.  -> the filtered 16 kHz input (``change_rms`` needs it)."""
+    every segment in order.  -> (the filtered 16 kHz input (``change_rms`` needs it), the number of cuts, its float64 device copy
+    when the cut search uploaded one, else None)."""
     import traceback
     from time import time
 
@@ -343,7 +378,7 @@ def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, f
     ref = _ref_module(self)
     dev = torch.device(self.device)
     audio = ref.signal.filtfilt(ref.bh, ref.ah, audio)
-    opt_ts = _cut_points(self, audio, np.pad(audio, (self.window // 2, self.window // 2), mode="reflect"))
+    opt_ts, a64 = _file_cuts(self, audio, dev)
     t1 = time()
     audio_pad = np.pad(audio, (self.t_pad, self.t_pad), mode="reflect")
     p_len = audio_pad.shape[0] // self.window
@@ -380,12 +415,13 @@ def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, f
         s = t
     lo = (t // w) if t is not None else 0
     collect(audio_pad[t:], pitch[:, lo:] if if_f0 else None, pitchf[:, lo:] if if_f0 else None)
-    return audio, len(opt_ts)
+    return audio, len(opt_ts), a64
 
 
-def _finish_file(self, segs, audio, tgt_sr, resample_sr, rms_mix_rate):
+def _finish_file(self, segs, audio, tgt_sr, resample_sr, rms_mix_rate, audio_dev=None):
     """pipeline.py:344-360 on the device: concatenate the trimmed segments, ``change_rms``, (``resample_sr``: host, like the
-    reference), int16-range scaling, ONE copy to the host."""
+    reference), int16-range scaling, ONE copy to the host.  ``audio_dev``: the float64 device copy of ``audio`` the cut search
+    made, if any; its ``.float()`` is the same single rounding as numpy's ``astype(float32)``, so it is not uploaded again."""
     import numpy as np
 
     from . import glue
@@ -393,7 +429,10 @@ def _finish_file(self, segs, audio, tgt_sr, resample_sr, rms_mix_rate):
     dev = torch.device(self.device)
     audio_opt = torch.cat([o[self.t_pad_tgt: o.shape[0] - self.t_pad_tgt].float() for o in segs]).contiguous()
     if rms_mix_rate != 1:
-        a16 = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32), device=dev)
+        if audio_dev is not None:
+            a16 = audio_dev.float()
+        else:
+            a16 = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32), device=dev)
         audio_opt = glue.change_rms(a16, 16000, audio_opt, int(tgt_sr), float(rms_mix_rate))
     if tgt_sr != resample_sr >= 16000:
         # librosa's soxr resampler has no device twin (and no offline oracle): this one option goes through the host like the
@@ -423,7 +462,7 @@ def pipeline_hip(self, model, net_g, sid, audio, times, f0_up_key, f0_method, fi
     def collect(a0, pt, pf):
         pending.append((a0, pt, pf))
 
-    audio, ncuts = _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect)
+    audio, ncuts, a64 = _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect)
     if can_batch and ncuts > 0:
         from time import time
 
@@ -433,7 +472,7 @@ def pipeline_hip(self, model, net_g, sid, audio, times, f0_up_key, f0_method, fi
         segs = infer_segments(net_g, sid, items, times)
     else:
         segs = [vc_device(self, model, net_g, sid, a0, pt, pf, times, index, index_rate, version, protect) for a0, pt, pf in pending]
-    return _finish_file(self, segs, audio, tgt_sr, resample_sr, rms_mix_rate)
+    return _finish_file(self, segs, audio, tgt_sr, resample_sr, rms_mix_rate, a64)
 
 
 def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, file_index, index_rate, if_f0, filter_radius, tgt_sr,
@@ -441,7 +480,8 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     """``Pipeline.pipeline`` for SEVERAL inputs in one go -- the body of ``VC.vc_multi``'s loop (infer/modules/vc/modules.py:201-266:
     ``load_audio`` + ``vc_single`` -> ``pipeline`` per file of a folder) with the files batched on the GPU:
 
-      1. per file, as ``pipeline`` does it: high-pass, cut points, f0 (RMVPE on the device), HuBERT per segment;
+      1. per file, as ``pipeline`` does it: high-pass, cut points (a long file's on the device, its own call), f0 (RMVPE on the device),
+         HuBERT per segment;
       2. ONE retrieval call for the HuBERT frames of every segment of every file (``blend_segments``: one coarse pass and one
          list-major scan per ``MAX_BATCH_QUERIES`` frames instead of one per segment);
       3. the segments of all files through ``net_g.infer`` as ragged batches (``infer_segments``, at most ``MAX_BATCH_FRAMES`` padded
@@ -486,12 +526,15 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
             owner.append(i)
             times[0] += time() - t0
 
-        filtered.append(_prepare_file(self, model, sid, a, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0f, collect)[0])
+        got = _prepare_file(self, model, sid, a, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0f, collect)
+        # (of the device copy only what change_rms reads is kept while the group's other files are prepared)
+        filtered.append((got[0], got[2].float() if got[2] is not None and rms_mix_rate != 1 else None))
     t0 = time()
     items = blend_segments(raw, index, index_rate, protect)
     times[0] += time() - t0
     outs = infer_segments(net_g, sid, items, times)
     res = []
     for i in range(len(audios)):
-        res.append(_finish_file(self, [o for o, w in zip(outs, owner) if w == i], filtered[i], tgt_sr, resample_sr, rms_mix_rate))
+        res.append(_finish_file(self, [o for o, w in zip(outs, owner) if w == i], filtered[i][0], tgt_sr, resample_sr, rms_mix_rate,
+                                filtered[i][1]))
     return res
