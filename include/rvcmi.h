@@ -411,6 +411,28 @@ int rvcmi_glue_cut_points(const double* audio_dev, int64_t n, int window, int64_
 /* Bytes of scratch rvcmi_glue_cut_points needs; 0 when the arguments are out of range (or there is no cut). */
 size_t rvcmi_glue_cut_points_scratch_bytes(int64_t n, int window, int64_t t_center, int64_t t_query);
 
+/* scipy.signal.filtfilt(b, a, x) with scipy's defaults (padtype="odd", padlen = 3 * (order + 1), method="pad") for a ragged batch:
+ * the input preparation of Pipeline.pipeline (infer/modules/vc/pipeline.py:23,221).  x_dev: one flat buffer of float (x_is_f64 = 0)
+ * or double samples, widened on the device; offsets_dev [B + 1] int64 on the device, item i = x[offsets[i] .. offsets[i + 1]);
+ * max_len (<= 2^28) >= the longest item and total >= offsets[B] are given by the host (they size the grid and the buffers; an item that
+ * contradicts them, or is not longer than padlen, is left untouched).  b, a, zi are HOST arrays of order + 1, order + 1 and order
+ * doubles, 1 <= order <= 8, a[0] == 1 (divide by a[0] first, as lfilter does), zi = lfilter_zi(b, a); they travel by value.
+ * Both passes are direct form II transposed in fp64 with every operation rounded on its own (no FMA), each starting from
+ * zi * first sample.  One thread produces 1024 consecutive outputs of a pass after a warm-up of `warmup` samples (a multiple of
+ * 1024) that starts from zi * in[start]; no filter state is passed between threads.  The caller derives warmup from the poles so
+ * that the start has decayed below 2^-64 (rvc_amd.glue.filt_warmup).  An item with n + 2 padlen <= warmup + 1024 is computed from
+ * scipy's own initial state throughout and is BIT-equal to scipy; longer items differ from scipy by the rounding noise of an
+ * independent fp64 evaluation of the recurrence.  Batch item i is computed exactly as a call with that item alone.
+ * out_dev [total] fp64, same layout as x.  out_pad_dev (or NULL): item i's np.pad(out_i, pad, mode="reflect") at
+ * offsets[i] + 2 pad i, n_i + 2 pad doubles (a copy, exact; written only for items with n_i > pad; pad < max_len).
+ * The odd extension and the reversal of the second pass are index arithmetic.  Enqueue-only, no allocation, deterministic.
+ * scratch_dev: rvcmi_glue_filtfilt_scratch_bytes(B, total, order) bytes (the forward pass's output).                          */
+int rvcmi_glue_filtfilt(const void* x_dev, int x_is_f64, const int64_t* offsets_dev, int B, int64_t max_len, int64_t total,
+                        const double* b, const double* a, const double* zi, int order, int warmup, double* out_dev, double* out_pad_dev,
+                        int64_t pad, void* scratch_dev, size_t scratch_bytes, void* stream);
+/* Bytes of scratch rvcmi_glue_filtfilt needs; 0 when the arguments are out of range. */
+size_t rvcmi_glue_filtfilt_scratch_bytes(int B, int64_t total, int order);
+
 /* The formant-shift resample of the realtime path (rtrvc.py:248-259, torchaudio.transforms.Resample(orig_freq = upp_res,
  * new_freq = tgt_sr / 100)): out[j * new + p] = sum_{k < K} kernel[p][k] * xpad[j * orig + k], xpad = x with `width` zeros in
  * front and zeros behind; orig / new already divided by their gcd; kernel_dev [new][K] (K = 2 * width + orig) is torchaudio's

@@ -10,7 +10,7 @@ from .front import FrontHIP, front_config_from_reference, infer_hip
 from .nsf import GeneratorHIP, NSFGeneratorHIP, config_from_reference
 from .pipeline import retrieve_blend
 from . import glue
-from .glue import cut_count, cut_points
+from .glue import cut_count, cut_points, filtfilt, highpass16k
 from .gru import GRUHIP, accelerate_rmvpe
 from .synthesizer import accelerate_synthesizer, get_synthesizer, load_synthesizer
 from . import dist
@@ -21,5 +21,5 @@ from .realtime import PitchCache, RealtimeStream, RealtimeVC, SincResample, f0_e
 __all__ = [
     "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "GeneratorHIP", "NSFGeneratorHIP",
     "config_from_reference", "FrontHIP", "front_config_from_reference", "infer_hip", "retrieve_blend", "accelerate_synthesizer", "get_synthesizer", "load_synthesizer", "dist", "glue", "install", "uninstall", "RealtimeVC", "PitchCache", "f0_extractor_frame", "SincResample", "sinc_resample_kernel", "GRUHIP", "accelerate_rmvpe",
-    "RealtimeStream", "stream_geometry", "TorchGateHIP", "cut_points", "cut_count",
+    "RealtimeStream", "stream_geometry", "TorchGateHIP", "cut_points", "cut_count", "filtfilt", "highpass16k",
 ]

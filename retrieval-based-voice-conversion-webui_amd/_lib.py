@@ -117,6 +117,9 @@ SYMBOLS = [
     ("rvcmi_glue_spectral_gate_scratch_bytes", C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     ("rvcmi_glue_cut_points", C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("rvcmi_glue_cut_points_scratch_bytes", C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
+    ("rvcmi_glue_filtfilt", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P,
+                                      C.c_size_t, _P]),
+    ("rvcmi_glue_filtfilt_scratch_bytes", C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     ("rvcmi_gru_create", C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(_P)]),
     ("rvcmi_gru_destroy", C.c_int, [_P]),
     ("rvcmi_gru_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -4,6 +4,7 @@
 
 #include "common.hpp"
 #include "cut_kernels.hpp"
+#include "filt_kernels.hpp"
 #include "gate_kernels.hpp"
 #include "glue_kernels.hpp"
 
@@ -56,6 +57,67 @@ static bool gate_layout(int B, int64_t n, int64_t nn, int n_fft, int hop, GateLa
     g->total = o;
     return true;
 }
+
+// rvcmi_glue_filtfilt: one launch per pass; the kernel is instantiated per filter order (zero-padded coefficients would add
+// +-0 terms to the chain, which is not scipy's arithmetic) and per input type.
+template <typename T>
+static void launch_filtfilt(int order, const T* x, const int64_t* offsets, int64_t total, int64_t max_len, const FiltCoef& c, int padlen,
+                            int warm, double* y1, double* out, double* out_pad, int64_t pad, dim3 grid, hipStream_t st) {
+#define RVCMI_FILT_CASE(O)                                                                                                                \
+    case O:                                                                                                                               \
+        hipLaunchKernelGGL((k_filt_pass<O, T, false>), grid, dim3(FILT_WAVE), 0, st, x, offsets, total, max_len, c, padlen, warm, y1,    \
+                           (double*)nullptr, (double*)nullptr, (int64_t)0);                                                               \
+        hipLaunchKernelGGL((k_filt_pass<O, T, true>), grid, dim3(FILT_WAVE), 0, st, x, offsets, total, max_len, c, padlen, warm, y1, out, \
+                           out_pad, pad);                                                                                                 \
+        break;
+    switch (order) {
+        RVCMI_FILT_CASE(1) RVCMI_FILT_CASE(2) RVCMI_FILT_CASE(3) RVCMI_FILT_CASE(4) RVCMI_FILT_CASE(5) RVCMI_FILT_CASE(6) RVCMI_FILT_CASE(7)
+        RVCMI_FILT_CASE(8)
+    }
+#undef RVCMI_FILT_CASE
+}
+
+extern "C" {
+
+size_t rvcmi_glue_filtfilt_scratch_bytes(int B, int64_t total, int order) {
+    if (B < 1 || B > 65535 || total < 1 || order < 1 || order > RVCMI_FILT_MAX_ORDER) return 0;
+    return (size_t)(total + 2 * 3 * (int64_t)(order + 1) * B) * sizeof(double);
+}
+
+int rvcmi_glue_filtfilt(const void* x, int x_is_f64, const int64_t* offsets, int B, int64_t max_len, int64_t total, const double* b,
+                        const double* a, const double* zi, int order, int warmup, double* out, double* out_pad, int64_t pad, void* scratch,
+                        size_t scratch_bytes, void* stream) {
+    return guarded([&] {
+        if (order < 1 || order > RVCMI_FILT_MAX_ORDER)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: filter order %d outside [1, %d]", order, RVCMI_FILT_MAX_ORDER);
+        if (!x || !offsets || !b || !a || !zi || !out || !scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: null pointer");
+        if (a[0] != 1.0) RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: a[0] = %g, the coefficients must be normalised to a[0] = 1", a[0]);
+        const int padlen = 3 * (order + 1);
+        if (B < 1 || B > 65535 || max_len <= padlen || max_len > RVCMI_FILT_MAX_LEN || total < max_len)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: B = %d in [1, 65535], longest item %lld in (padlen = %d, 2^28], total %lld >= longest item", B,
+                       (long long)max_len, padlen, (long long)total);
+        if (warmup < 0 || warmup % FILT_LANE || warmup > (1 << 20))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: warm-up of %d samples must be a multiple of %d in [0, 2^20]", warmup, FILT_LANE);
+        if (out_pad && (pad < 0 || pad >= max_len)) RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: reflection pad %lld outside [0, longest item)", (long long)pad);
+        const size_t need = rvcmi_glue_filtfilt_scratch_bytes(B, total, order);
+        if (scratch_bytes < need) RVCMI_FAIL(RVCMI_ERR_INVALID, "filtfilt: scratch of %zu bytes, %zu needed", scratch_bytes, need);
+        const int64_t lanes = (max_len + 2 * padlen + FILT_LANE - 1) / FILT_LANE;
+        const int64_t gx = (lanes + FILT_WAVE - 1) / FILT_WAVE;
+        FiltCoef c = {};
+        for (int k = 0; k <= order; ++k) c.b[k] = b[k], c.a[k] = a[k];
+        for (int k = 0; k < order; ++k) c.zi[k] = zi[k];
+        const dim3 grid((unsigned)gx, (unsigned)B);
+        hipStream_t st = (hipStream_t)stream;
+        double* y1 = static_cast<double*>(scratch);
+        if (x_is_f64)
+            launch_filtfilt(order, static_cast<const double*>(x), offsets, total, max_len, c, padlen, warmup, y1, out, out_pad, pad, grid, st);
+        else
+            launch_filtfilt(order, static_cast<const float*>(x), offsets, total, max_len, c, padlen, warmup, y1, out, out_pad, pad, grid, st);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+}  // extern "C"
 
 // Geometry of rvcmi_glue_cut_points: false when the arguments are out of range.  cuts = len(range(t_center, n, t_center)).
 static bool cut_layout(int64_t n, int window, int64_t t_center, int64_t t_query, int64_t* cuts, int* tiles) {

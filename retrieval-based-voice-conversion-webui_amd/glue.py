@@ -7,6 +7,7 @@ row 2), so that nothing between the PyTorch-ROCm feature extractors and ``net_g.
     change_rms(audio16k, 16000, audio_opt, tgt_sr, rms_mix_rate)              pipeline.py:26-46,351
     scale_int16_range(audio)                                                  pipeline.py:355-359
     cut_points(audio64, window, t_center, t_query)                            pipeline.py:219-236
+    filtfilt(x, b, a) / highpass16k(x)                                        pipeline.py:23,221 (scipy.signal.filtfilt)
 
 and of the realtime GUI's block (gui.py:934-1090, assembled by ``realtime.RealtimeStream``):
 
@@ -22,6 +23,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -166,6 +168,209 @@ def cut_points(audio: torch.Tensor, window: int, t_center: int, t_query: int, re
         _lib.check(L.rvcmi_glue_cut_points(_ptr(audio), n, window, t_center, t_query, _ptr(cuts), ncuts, _ptr(sums), _ptr(scratch),
                                            _stream(dev)))
     return (cuts, sums) if return_sums else cuts
+
+
+# ---- scipy.signal.filtfilt on the device (csrc/filt_kernels.hpp) ---------------------------------------------------------------------
+FILT_MAX_ORDER = 8
+FILT_LANE = 1024            # outputs per thread of a pass (csrc/filt_kernels.hpp FILT_LANE)
+FILT_WARMUP_CAP = 1 << 16   # samples; a filter whose poles ask for a longer warm-up is refused (see filt_warmup)
+# scipy.signal.butter(N=5, Wn=48, btype="high", fs=16000) (pipeline.py:23) as scipy 1.15 gives it; used by highpass16k only when
+# neither the reference module nor scipy is there to ask
+_HP16K = (tuple(float.fromhex(h) for h in ("0x1.f09eae82f17f2p-1", "-0x1.36632d11d6ef7p+2", "0x1.36632d11d6ef7p+3", "-0x1.36632d11d6ef7p+3",
+                                            "0x1.36632d11d6ef7p+2", "-0x1.f09eae82f17f2p-1")),
+          tuple(float.fromhex(h) for h in ("0x1.0000000000000p+0", "-0x1.3c189b160d9bbp+2", "0x1.38406b02c5ae9p+3", "-0x1.347726c291cb2p+3",
+                                            "0x1.30bc870194e75p+2", "-0x1.e1b3a34ba432ap-1")))
+_FILT_PLANS: dict = {}
+
+
+def _normalized_ba(b, a):
+    """``b``, ``a`` as ``lfilter`` / ``lfilter_zi`` see them: 1-D float64, leading zeros of ``a`` dropped, divided by ``a[0]``,
+    zero-padded to one length.  scipy's own ValueErrors for what it refuses."""
+    b = np.atleast_1d(np.asarray(b, dtype=np.float64))
+    a = np.atleast_1d(np.asarray(a, dtype=np.float64))
+    if b.ndim != 1:
+        raise ValueError("Numerator b must be 1-D.")
+    if a.ndim != 1:
+        raise ValueError("Denominator a must be 1-D.")
+    while len(a) > 1 and a[0] == 0.0:
+        a = a[1:]
+    if a.size < 1 or a[0] == 0.0:
+        raise ValueError("There must be at least one nonzero `a` coefficient.")
+    if a[0] != 1.0:
+        b = b / a[0]
+        a = a / a[0]
+    n = max(len(a), len(b))
+    if len(a) < n:
+        a = np.r_[a, np.zeros(n - len(a))]
+    elif len(b) < n:
+        b = np.r_[b, np.zeros(n - len(b))]
+    return b, a
+
+
+def lfilter_zi(b, a) -> np.ndarray:
+    """``scipy.signal.lfilter_zi(b, a)`` in numpy, the same arithmetic and therefore the same bits: the steady state of the step
+    response, ``(I - companion(a).T) zi = b[1:] - a[1:] b[0]``, solved by ``np.linalg.solve`` as scipy does (its explicit
+    running-sum formulas give the same numbers to a few ulp, not the same bits)."""
+    b, a = _normalized_ba(b, a)
+    n = len(a)
+    if n < 2:
+        return np.zeros(0)
+    comp = np.zeros((n - 1, n - 1))  # scipy.linalg.companion(a): first row -a[1:] / a[0], ones on the sub-diagonal
+    comp[0, :] = -a[1:] / (1.0 * a[0])
+    comp[np.arange(1, n - 1), np.arange(0, n - 2)] = 1.0
+    return np.linalg.solve(np.eye(n - 1) - comp.T, b[1:] - a[1:] * b[0])
+
+
+def filt_warmup(a) -> int:
+    """Samples a thread of the device filter runs before its first stored output, derived from the poles (never a constant).
+
+    The state of direct form II transposed obeys ``z[n + 1] = A z[n] + B x[n]`` with ``A = companion(a).T``, so two runs over the
+    same input whose states differ by ``e`` at sample ``s`` differ by ``A^W e = V diag(lambda^W) V^-1 e`` after ``W`` more samples:
+    at most ``cond(V) rho^W |e|`` in the 2-norm, ``rho`` the largest pole radius and ``V`` the eigenvectors of ``A``.  A thread
+    starts from the steady state of a constant input instead of the true state; ``W`` is the smallest multiple of ``FILT_LANE`` with
+
+        cond(V) * rho ** W < 2 ** -64,
+
+    i.e. what is left of that start is 2^-11 of ONE rounding error of a state of its own size, far below the rounding noise the
+    recurrence itself accumulates (which the poles amplify by about cond(V)).  For the pipeline's high-pass (rho = 0.99419, cond(V) =
+    9.2e8) the bound asks for 11 161 samples, W = 11 264.  ``RvcmiError`` when the filter is unstable (rho >= 1), has a defective
+    pole set, or W would exceed ``FILT_WARMUP_CAP`` = 65 536 samples (rho above about 0.9992): a thread would spend its time warming up."""
+    a = _normalized_ba([1.0], a)[1]
+    while len(a) > 1 and a[-1] == 0.0:  # trailing zeros are poles at the origin: they decay in one step each
+        a = a[:-1]
+    m = len(a) - 1
+    if m < 1:
+        return 0
+    comp = np.zeros((m, m))
+    comp[0, :] = -a[1:]
+    comp[np.arange(1, m), np.arange(0, m - 1)] = 1.0
+    lam, V = np.linalg.eig(comp.T)
+    rho = float(np.abs(lam).max())
+    cond = float(np.linalg.cond(V))
+    if not (rho < 1.0) or not np.isfinite(cond):
+        raise _lib.RvcmiError("filtfilt: the filter is not strictly stable (largest pole radius %.6g, cond(V) %.3g)" % (rho, cond), code=_lib.ERR_INVALID)
+    if rho == 0.0:
+        return FILT_LANE
+    need = (64.0 * np.log(2.0) + np.log(cond)) / -np.log(rho)
+    W = int(-(-need // FILT_LANE)) * FILT_LANE
+    if not W <= FILT_WARMUP_CAP:
+        raise _lib.RvcmiError("filtfilt: largest pole radius %.9g with cond(V) = %.3g needs a warm-up of %.0f samples per thread, above the "
+                              "cap of %d" % (rho, cond, need, FILT_WARMUP_CAP), code=_lib.ERR_INVALID)
+    return max(W, FILT_LANE)
+
+
+def _filt_plan(b, a):
+    """-> (b, a normalised [order + 1] float64, zi [order], order, padlen, warm-up); cached per coefficient set."""
+    b, a = _normalized_ba(b, a)
+    key = (b.tobytes(), a.tobytes())
+    hit = _FILT_PLANS.get(key)
+    if hit is None:
+        order = len(a) - 1
+        if not 1 <= order <= FILT_MAX_ORDER:
+            raise _lib.RvcmiError("filtfilt: filter order %d; the kernel serves 1 .. %d" % (order, FILT_MAX_ORDER), code=_lib.ERR_INVALID)
+        hit = (np.ascontiguousarray(b), np.ascontiguousarray(a), np.ascontiguousarray(lfilter_zi(b, a)), order, 3 * (order + 1), filt_warmup(a))
+        if len(_FILT_PLANS) > 64:
+            _FILT_PLANS.clear()
+        _FILT_PLANS[key] = hit
+    return hit
+
+
+def filtfilt_exact_len(b, a) -> int:
+    """The longest input ``filtfilt`` computes from scipy's own initial state in every thread, i.e. BIT-equal to
+    ``scipy.signal.filtfilt``: ``n + 2 padlen <= warm-up + FILT_LANE``."""
+    plan = _filt_plan(b, a)
+    return plan[5] + FILT_LANE - 2 * plan[4]
+
+
+def filtfilt_flat(flat: torch.Tensor, lengths, b, a, reflect_pad: int = 0):
+    """``filtfilt`` for a ragged batch that already lies in one flat device buffer: ``flat`` 1-D float32 or float64, item ``i`` =
+    the next ``lengths[i]`` samples.  -> list of float64 views (one per item) into one output buffer; with ``reflect_pad`` > 0 a
+    second list, ``np.pad(out_i, reflect_pad, mode="reflect")`` per item (every item must be longer than the pad).  One call:
+    two launches, whatever the number of items."""
+    if flat.dtype not in (torch.float32, torch.float64):
+        raise TypeError("x must be float32 or float64 (got %s)" % flat.dtype)
+    if flat.dim() != 1 or not flat.is_contiguous():
+        raise ValueError("x must be a contiguous 1-D tensor")
+    lengths = [int(n) for n in lengths]
+    bn, an, zi, order, padlen, warm = _filt_plan(b, a)
+    pad = int(reflect_pad)
+    if not lengths or sum(lengths) != int(flat.numel()):
+        raise ValueError("lengths %s do not add up to the %d samples of x" % (lengths[:8], int(flat.numel())))
+    for n in lengths:
+        if n <= padlen:  # scipy's message (signal/_signaltools.py _validate_pad)
+            raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
+        if pad < 0 or (pad and n <= pad):
+            raise ValueError("reflect_pad = %d needs every item longer than it (got %d samples)" % (pad, n))
+    dev = _dev(flat, "x")  # (after the argument checks: they are scipy's and need no GPU)
+    B, total, max_len = len(lengths), int(flat.numel()), max(lengths)
+    L = _lib.lib()
+    nbytes = int(L.rvcmi_glue_filtfilt_scratch_bytes(B, total, order))
+    if nbytes == 0:
+        raise _lib.RvcmiError("filtfilt: a batch of %d items / %d samples is out of range" % (B, total), code=_lib.ERR_INVALID)
+    starts = [0]
+    for n in lengths:
+        starts.append(starts[-1] + n)
+    offsets = torch.tensor(starts, dtype=torch.int64).to(dev)
+    out = torch.empty(total, device=dev, dtype=torch.float64)
+    out_pad = torch.empty(total + 2 * pad * B, device=dev, dtype=torch.float64) if pad else None
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(L.rvcmi_glue_filtfilt(_ptr(flat), 1 if flat.dtype == torch.float64 else 0, _ptr(offsets), B, max_len, total, dptr(bn), dptr(an),
+                                         dptr(zi), order, warm, _ptr(out), _ptr(out_pad), pad, _ptr(scratch), nbytes, _stream(dev)))
+    outs = [out[starts[i]: starts[i + 1]] for i in range(B)]
+    if not pad:
+        return outs
+    return outs, [out_pad[starts[i] + 2 * pad * i: starts[i + 1] + 2 * pad * (i + 1)] for i in range(B)]
+
+
+def filtfilt(x, b, a, reflect_pad: int = 0):
+    """``scipy.signal.filtfilt(b, a, x)`` with scipy's defaults (odd extension by ``padlen = 3 max(len(a), len(b))``, both passes
+    from ``lfilter_zi(b, a) * first sample``, direct form II transposed in fp64) on the device.  ``x``: a 1-D float32 or float64
+    device tensor, or a list of them (a ragged batch, one call; item ``i`` is computed exactly as a call with it alone) -> float64
+    tensor(s).  ``reflect_pad`` > 0 also returns ``np.pad(result, reflect_pad, mode="reflect")``: ``(y, y_padded)``.
+
+    An input of at most ``filtfilt_exact_len(b, a)`` samples equals scipy bit for bit.  A longer one is computed by independent
+    threads, each warmed up over ``filt_warmup(a)`` samples, and differs from scipy as two fp64 evaluations of an ill-conditioned
+    recurrence do: for the pipeline's high-pass both are about 3e-8 (signal peak 0.5) from the exact result.
+    ``ValueError`` for an input not longer than ``padlen`` (scipy's), ``RvcmiError`` for a filter order above 8 or poles so close to
+    the unit circle that the warm-up would exceed ``FILT_WARMUP_CAP``.  zi is computed here on the host; scipy is not needed."""
+    single = isinstance(x, torch.Tensor)
+    xs = [x] if single else list(x)
+    if not xs:
+        raise ValueError("no input")
+    for t in xs:
+        if t.dim() != 1:
+            raise ValueError("x must be 1-D (got shape %s)" % (tuple(t.shape),))
+        if t.dtype != xs[0].dtype or t.device != xs[0].device:
+            raise ValueError("the items of a batch must share dtype and device")
+    flat = xs[0].contiguous() if len(xs) == 1 else torch.cat(xs)
+    got = filtfilt_flat(flat, [int(t.numel()) for t in xs], b, a, reflect_pad)
+    if not reflect_pad:
+        return got[0] if single else got
+    return (got[0][0], got[1][0]) if single else got
+
+
+def highpass_coefficients(ref_module=None):
+    """``bh, ah`` of the pipeline's input high-pass (pipeline.py:23: ``signal.butter(N=5, Wn=48, btype="high", fs=16000)``): the
+    reference module's own when it is bound (``ref_module``, or ``infer.modules.vc.pipeline`` if imported), else computed by scipy,
+    else -- no scipy -- the stored fp64 values of that call."""
+    import sys
+
+    mod = ref_module if ref_module is not None else sys.modules.get("infer.modules.vc.pipeline")
+    if mod is not None and hasattr(mod, "bh") and hasattr(mod, "ah"):
+        return np.asarray(mod.bh, dtype=np.float64), np.asarray(mod.ah, dtype=np.float64)
+    try:
+        from scipy import signal
+    except ImportError:
+        return np.array(_HP16K[0]), np.array(_HP16K[1])
+    return signal.butter(N=5, Wn=48, btype="high", fs=16000)
+
+
+def highpass16k(x, reflect_pad: int = 0, ref_module=None):
+    """The input preparation of ``Pipeline.pipeline`` (pipeline.py:221): ``filtfilt(bh, ah, x)`` on the device (see ``filtfilt``)."""
+    bh, ah = highpass_coefficients(ref_module)
+    return filtfilt(x, bh, ah, reflect_pad)
 
 
 def scale_int16_range(audio: torch.Tensor) -> torch.Tensor:

@@ -139,9 +139,11 @@ def _rebind_gate(rebound) -> None:
 
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
-            patch_gui: bool = False) -> None:
+            patch_gui: bool = False, device_prep: bool = False) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
-    also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``."""
+    also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
+    ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
+    high-pass and the reflection pad on the device (``glue.filtfilt``; equal to scipy to fp64 rounding noise, not bit for bit)."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -199,6 +201,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
         _rebind_methods(rebound)
     if patch_gui:
         _rebind_gate(rebound)
+    from . import pipeline as _plm
+
+    _plm.DEVICE_PREP = bool(device_prep)  # last: an install() that raised above leaves the switch as it was
 
 
 def uninstall() -> None:
@@ -214,4 +219,7 @@ def uninstall() -> None:
             sys.modules.pop("faiss", None)
         else:
             sys.modules["faiss"] = _state["faiss_prev"]
+    from . import pipeline as _plm
+
+    _plm.DEVICE_PREP = False
     _state.clear()

@@ -43,6 +43,18 @@ def retrieve_blend(feats: torch.Tensor, index: IVFFlatHIP, index_rate: float, k:
 # (high-pass ``filtfilt``) and estimators other than RMVPE.  The quiet-point search that chooses the cut positions of a long input
 # runs on the device (``glue.cut_points``, bit-equal to the host loop): one upload of the filtered fp64 signal, which
 # ``change_rms`` then shares, and one small synchronising read-back of the cuts per long file -- segment shapes depend on them.
+#
+# Opt-in (``install(device_prep=True)`` or ``RVCMI_DEVICE_PREP=1``; default off): the input preparation itself on the device.
+# The raw input is uploaded ONCE in its own dtype, ``glue.filtfilt_flat`` filters it (all files of a ``convert_files`` group in one
+# call; a call with less than ``DEVICE_PREP_MIN_SAMPLES`` of audio, where the host filter is faster, stays on the host) and writes the
+# ``t_pad`` reflection pad in the same launch; the cut search, the HuBERT segments, RMVPE and ``change_rms``
+# read device slices of that one signal, and it visits the host (one D2H, the same signal, never a second host-filtered one) only
+# when an f0 estimator other than the device RMVPE path needs ``audio_pad`` as numpy.  It is off by default because it cannot be
+# bit-equal to scipy beyond ``glue.filtfilt_exact_len`` samples: the recurrence is ill-conditioned, and the device result is as far
+# from the exact one as scipy's own is, which after the fp32 / fp16 cast moves about half the samples by one ulp.
+# The casts themselves are the host's: ``.float()`` of an fp64 device tensor is the one IEEE rounding ``torch.as_tensor(numpy_f64)
+# .float()`` does, and ``.half()`` goes through fp32 on both (c10::Half is constructed from float), which
+# tests/test_gpu_prep.py::test_device_casts_round_as_the_host_casts checks on values that tell the two routes apart.
 
 def _ref_module(self):
     import sys
@@ -264,24 +276,85 @@ def _device_cuts(self, audio, dev):
     from . import glue
 
     w = int(self.window)
-    if (dev.type != "cuda" or os.environ.get("RVCMI_DEVICE_CUTS", "1") == "0" or audio.dtype != np.float64 or audio.ndim != 1
-            or self.t_query > self.t_center or self.t_query < 1 or w % 2 or not 2 <= w <= 1024 or audio.shape[0] <= w):
+    on_device = isinstance(audio, torch.Tensor)  # the device preparation's signal: searched where it lies, no upload
+    f64 = torch.float64 if on_device else np.float64
+    if (dev.type != "cuda" or os.environ.get("RVCMI_DEVICE_CUTS", "1") == "0" or audio.dtype != f64 or audio.ndim != 1
+            or self.t_query > self.t_center or self.t_query < 1 or w % 2 or not 2 <= w <= 1024 or audio.shape[0] <= w
+            or (on_device and audio.device.type != "cuda")):
         return None
-    a64 = torch.from_numpy(np.ascontiguousarray(audio)).to(dev)
+    a64 = audio.contiguous() if on_device else torch.from_numpy(np.ascontiguousarray(audio)).to(dev)
     return glue.cut_points(a64, w, int(self.t_center), int(self.t_query)).tolist(), a64
 
 
 def _file_cuts(self, audio, dev):
-    """pipeline.py:222-236 for one filtered input: -> (opt_ts, its float64 device copy or None).  The search runs when the input,
+    """pipeline.py:222-236 for one filtered input (numpy, or the float64 device tensor of the device preparation): -> (opt_ts, its
+    float64 device copy or None).  The search runs when the input,
     padded by half a window at each end, is longer than ``t_max`` (the reference's condition): on the device where that is
-    possible, else by the host loop, which also answers ``[]`` for a short input."""
+    possible, else by the host loop, which also answers ``[]`` for a short numpy input; a short device tensor is answered ``[]``
+    where it lies (no copy, no synchronisation)."""
     import numpy as np
 
+    on_device = isinstance(audio, torch.Tensor)
     if audio.shape[0] + 2 * (self.window // 2) > self.t_max:
         got = _device_cuts(self, audio, dev)
         if got is not None:
             return got
-    return _cut_points(self, audio, np.pad(audio, (self.window // 2, self.window // 2), mode="reflect")), None
+    elif on_device:
+        return [], audio  # not searched at all (the common case: a clip under t_max): nothing to compute, and nothing leaves the device
+    a64 = None
+    if on_device:  # a device-prepared LONG input the device search does not serve (RVCMI_DEVICE_CUTS=0, t_query > t_center): host loop on a copy
+        a64, audio = audio, audio.cpu().numpy()
+    return _cut_points(self, audio, np.pad(audio, (self.window // 2, self.window // 2), mode="reflect")), a64
+
+
+DEVICE_PREP = False  # install(device_prep=True) sets it; RVCMI_DEVICE_PREP=1 / =0 overrides it per call
+# The device filter is used for the shapes where it was measured faster than the host's (tools/prep_time.py, profiles/prep_time.json).
+# Its time hardly depends on the amount of audio -- every thread runs warm-up + 1024 samples of the recurrence, about 1.8 ms per call from
+# 10 s to 64 x 10 s -- while scipy's grows by 0.23-0.33 ms per second of audio: 70 s, 305 s and a group of 64 x 10 s are faster on the
+# device (10x, 27x, 18x with the uploads); for a single 10 s clip the device median is lower but the ranges of the two overlap, which
+# counts as a tie.  Below 24 s of audio in one call (a file alone, or all files of a convert_files group together), where the gap is
+# not yet a clear factor of two, the host prepares the input.
+DEVICE_PREP_MIN_SAMPLES = 24 * 16000
+
+
+def _device_prep_on() -> bool:
+    import os
+
+    env = os.environ.get("RVCMI_DEVICE_PREP")
+    return env == "1" if env in ("0", "1") else bool(DEVICE_PREP)
+
+
+def _device_prep(self, audios, dev):
+    """The input preparation of pipeline.py:221,241 for SEVERAL inputs on the device: one upload of the raw samples (float32 or
+    float64 as they come; anything else is widened to float64 on the host, as scipy would), ONE ``glue.filtfilt_flat`` call (per
+    sample type) that also writes the ``t_pad`` reflection pad.  -> per input (filtered float64 device tensor, its padded twin), or None for an input
+    the device path does not serve (CPU device, not 1-D, not longer than ``t_pad`` / the filter's padlen: np.pad reflects such a
+    signal several times over; or less than ``DEVICE_PREP_MIN_SAMPLES`` of audio in the whole call, where the host is faster): the
+    caller prepares that one on the host."""
+    import numpy as np
+
+    from . import glue
+
+    res = [None] * len(audios)
+    if dev.type != "cuda" or not _device_prep_on():
+        return res
+    ref = _ref_module(self)
+    padlen = 3 * max(len(ref.ah), len(ref.bh))
+    arrs = [np.asarray(a) for a in audios]
+    pick = [i for i, a in enumerate(arrs) if a.ndim == 1 and a.shape[0] > max(int(self.t_pad), padlen)]
+    if not pick or sum(arrs[i].shape[0] for i in pick) < DEVICE_PREP_MIN_SAMPLES:
+        return res
+    # one call per sample type (a folder is one type in practice): a float32 input's odd extension is rounded in float32, as scipy
+    # does it, so widening it to share a call with float64 files would not be "exactly as a call with that item alone"
+    for dt in (np.float32, np.float64):
+        grp = [i for i in pick if (arrs[i].dtype == np.float32) == (dt is np.float32)]
+        if not grp:
+            continue
+        flat = np.concatenate([arrs[i].astype(dt, copy=False) for i in grp]) if len(grp) > 1 else np.ascontiguousarray(arrs[grp[0]], dtype=dt)
+        outs, pads = glue.filtfilt_flat(torch.from_numpy(flat).to(dev), [arrs[i].shape[0] for i in grp], ref.bh, ref.ah, int(self.t_pad))
+        for j, i in enumerate(grp):
+            res[i] = (outs[j], pads[j])
+    return res
 
 
 RMVPE_THRED = 0.03  # rvc/f0/gen.py:113: Generator.calculate hard-codes compute_f0(..., filter_radius=0.03) for rmvpe
@@ -365,11 +438,12 @@ def _open_index(self, file_index, index_rate):
         return None, False
 
 
-def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect):
+def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect, prepped=None):
     """``Pipeline.pipeline`` from its input to the point where a segment would enter ``vc`` (pipeline.py:219-300): high-pass,
     cut points, reflection pad, f0 (RMVPE decoded on the device), then ``collect(audio_segment, pitch_slice, pitchf_slice)`` for
     every segment in order.  -> (the filtered 16 kHz input (``change_rms`` needs it), the number of cuts, its float64 device copy
-    when the cut search uploaded one, else None)."""
+    when the cut search uploaded one, else None).  ``prepped``: this input's ``_device_prep`` result when the caller prepared a whole
+    group in one call; with the device preparation the segments are device slices and the first return value is None."""
     import traceback
     from time import time
 
@@ -377,10 +451,18 @@ def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, f
 
     ref = _ref_module(self)
     dev = torch.device(self.device)
-    audio = ref.signal.filtfilt(ref.bh, ref.ah, audio)
-    opt_ts, a64 = _file_cuts(self, audio, dev)
-    t1 = time()
-    audio_pad = np.pad(audio, (self.t_pad, self.t_pad), mode="reflect")
+    if prepped is None:
+        prepped = _device_prep(self, [audio], dev)[0]
+    if prepped is not None:
+        audio_dev, audio_pad = prepped  # float64 device tensors: the filtered signal and np.pad(.., t_pad, "reflect") of it
+        opt_ts, a64 = _file_cuts(self, audio_dev, dev)
+        audio, a64 = None, audio_dev
+        t1 = time()
+    else:
+        audio = ref.signal.filtfilt(ref.bh, ref.ah, audio)
+        opt_ts, a64 = _file_cuts(self, audio, dev)
+        t1 = time()
+        audio_pad = np.pad(audio, (self.t_pad, self.t_pad), mode="reflect")
     p_len = audio_pad.shape[0] // self.window
     inp_f0 = None
     if hasattr(f0_file, "name"):
@@ -400,7 +482,9 @@ def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, f
             pitch, pitchf = got[0][:, :p_len].long(), got[1][:, :p_len].float()
         else:
             if if_f0 == 1:
-                pitch, pitchf = self.f0_gen.calculate(audio_pad, p_len, f0_up_key, f0_method, filter_radius, inp_f0)
+                # a host estimator: the device-prepared signal comes down once (the same signal the segments are cut from)
+                pad_np = audio_pad.cpu().numpy() if isinstance(audio_pad, torch.Tensor) else audio_pad
+                pitch, pitchf = self.f0_gen.calculate(pad_np, p_len, f0_up_key, f0_method, filter_radius, inp_f0)
             else:
                 pitch, pitchf = f0_method  # pipeline.py:268-269: a precomputed (coarse, Hz) pair
             pitch = torch.as_tensor(np.asarray(pitch)[:p_len], device=dev).unsqueeze(0).long()
@@ -480,8 +564,8 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     """``Pipeline.pipeline`` for SEVERAL inputs in one go -- the body of ``VC.vc_multi``'s loop (infer/modules/vc/modules.py:201-266:
     ``load_audio`` + ``vc_single`` -> ``pipeline`` per file of a folder) with the files batched on the GPU:
 
-      1. per file, as ``pipeline`` does it: high-pass, cut points (a long file's on the device, its own call), f0 (RMVPE on the device),
-         HuBERT per segment;
+      1. per file, as ``pipeline`` does it: high-pass (with ``RVCMI_DEVICE_PREP=1``: all files in one device call), cut points (a long
+         file's on the device, its own call), f0 (RMVPE on the device), HuBERT per segment;
       2. ONE retrieval call for the HuBERT frames of every segment of every file (``blend_segments``: one coarse pass and one
          list-major scan per ``MAX_BATCH_QUERIES`` frames instead of one per segment);
       3. the segments of all files through ``net_g.infer`` as ragged batches (``infer_segments``, at most ``MAX_BATCH_FRAMES`` padded
@@ -493,7 +577,10 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     files (``vc_multi`` passes the same sid / f0 method / index / rates for the whole folder); ``f0_files``: None or one entry per
     input.  -> list of numpy arrays in input order.  Every item is computed exactly as its own call would compute it (same noise
     draws in the same order, ragged batch items = separate calls; bit-equal with the shape-dependent kernel choices pinned --
-    generator ``RB_STREAM`` / ``NO_RB_SPLIT``, front ``FR_NJ`` / ``FR_FFN_SPLIT`` -- and equal to operand rounding otherwise), so the result does not depend on how the files are grouped.  A synthesizer that is not the HIP one, or an
+    generator ``RB_STREAM`` / ``NO_RB_SPLIT``, front ``FR_NJ`` / ``FR_FFN_SPLIT`` -- and equal to operand rounding otherwise), so the result does not depend on how the files are grouped.
+    One exception, with the device preparation switched on (``RVCMI_DEVICE_PREP=1``, off by default): ``DEVICE_PREP_MIN_SAMPLES`` is judged on the
+    audio of the whole call, so a 10 s file is high-passed on the device inside a group and on the host through ``pipeline`` alone; the two
+    filters agree to fp64 rounding noise only, which moves about half of the fp32 input samples by one ulp (bit-equal again with the threshold at 0).  A synthesizer that is not the HIP one, or an
     index only real faiss reads, or ``RVCMI_PIPELINE_BATCH=0``, takes the plain per-file loop over ``self.pipeline``."""
     audios = list(audios)
     f0_files = list(f0_files) if f0_files is not None else [None] * len(audios)
@@ -519,6 +606,7 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     dev = torch.device(self.device)
     sid = torch.tensor(sid, device=dev).unsqueeze(0).long()
     raw, owner, filtered = [], [], []
+    prepped = _device_prep(self, audios, dev)  # RVCMI_DEVICE_PREP: every file of the group filtered in ONE call (else all None)
     for i, (a, f0f) in enumerate(zip(audios, f0_files)):
         def collect(a0, pt, pf, i=i):
             t0 = time()
@@ -526,7 +614,7 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
             owner.append(i)
             times[0] += time() - t0
 
-        got = _prepare_file(self, model, sid, a, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0f, collect)
+        got = _prepare_file(self, model, sid, a, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0f, collect, prepped[i])
         # (of the device copy only what change_rms reads is kept while the group's other files are prepared)
         filtered.append((got[0], got[2].float() if got[2] is not None and rms_mix_rate != 1 else None))
     t0 = time()
