@@ -452,8 +452,36 @@ int rvcmi_gru_create(int input_size, int hidden_size, const float* w_ih, const f
                      int device, rvcmi_gru** out);
 int rvcmi_gru_destroy(rvcmi_gru* h);
 /* x16_dev [B][T][I] fp16; y_dev [B][T][2H] fp32 = nn.GRU's `output` with h_0 = 0; hn_dev [2][B][H] fp32 = its `h_n` (or NULL).
- * The projection workspace grows with the largest B * T seen (a hipMalloc on such a call: not for use inside a stream capture). */
+ * The projection workspace grows with the largest B * T seen (a hipMalloc on such a call: the FIRST call of a size must not be inside a
+ * stream capture); the smaller workspaces it replaces stay allocated until destroy, so a graph captured earlier keeps replaying. */
 int rvcmi_gru_forward(rvcmi_gru* h, int B, int T, const void* x16_dev, float* y_dev, float* hn_dev, void* stream);
+
+/* ---- beyond SURVEY.md section 8: the deep U-Net of the RMVPE f0 network and its head -----------------------------------------
+ * Stands in for `self.cnn(self.unet(mel))` of rvc/f0/e2e.py:46 (DeepUnet of rvc/f0/deepunet.py + Conv2d(16, 3, 3x3)): everything between
+ * the transposed mel input and the GRU's input.  `weights`: fp32 host tensors under their state-dict names ("unet.encoder.bn.weight",
+ * "unet.encoder.layers.0.conv.0.conv.0.weight", ..., "cnn.weight", "cnn.bias"; running statistics included, tensors with other prefixes
+ * are ignored).  The geometry (levels, units per level, intermediate layers, base channels) is read from the names and shapes.  Supported:
+ * one input channel, 128 mel bins, pooling (2, 2), channel counts that are multiples of 16; anything else, or a tensor under "unet." /
+ * "cnn." the recognised network does not use: RVCMI_ERR_INVALID (the caller keeps torch's modules).  Operands and stored activations fp16,
+ * accumulation and the BatchNorm / ReLU / residual epilogues fp32.  Results are bit-identical from run to run.                          */
+typedef struct rvcmi_unet rvcmi_unet;
+int rvcmi_unet_create(const rvcmi_tensor* weights, int n_weights, int device, rvcmi_unet** out);
+int rvcmi_unet_destroy(rvcmi_unet* h);
+int rvcmi_unet_head_channels(rvcmi_unet* h);
+/* Bytes of device workspace one forward of (B, T) needs; 0 for a shape the handle does not serve (T not a multiple of 2^levels,
+ * B * T > 2^22, a launch beyond the grid limits).                                                                                  */
+size_t rvcmi_unet_workspace_bytes(rvcmi_unet* h, int B, int T);
+/* Enqueue only.  mel_dev [B][T][128] fp32 (the [B, 1, T, 128] input of DeepUnet.forward); out_dev [B][T][head channels][128] fp32, i.e.
+ * the `.transpose(1, 2).flatten(-2)` of e2e.py:46 already applied; ws_dev: rvcmi_unet_workspace_bytes(h, B, T) bytes, 256-byte aligned.
+ * The handle allocates and frees nothing after create: safe inside a stream capture.                                                */
+int rvcmi_unet_forward(rvcmi_unet* h, int B, int T, const float* mel_dev, float* out_dev, void* ws_dev, void* stream);
+/* Test hook: ONE primitive on caller-supplied data (synchronous; allocates).  kind 0: 3x3 convolution, 1: 1x1, 2: transposed 3x3 stride 2,
+ * 3: 2x2 average pool, 4 / 5: the one-input-channel 3x3 / 1x1 behind the input scale and shift (x0_dev fp32 [B][H][W]), 6: 3x3 with the
+ * head's fp32 [B][H][Cout][W] output.  Activations fp16 [B][H][W][C]; w in torch's layout ([Cout][Cin][k][k]; kind 2: [Cin][Cout][3][3]);
+ * out = relu?(acc * scale + shift) + res.  ksplit 0: the forward's own choice, else the number of K slices.                           */
+int rvcmi_unet_debug_op(int kind, int B, int H, int W, int C0, int C1, int Cout, const float* w, const float* scale, const float* shift,
+                        int relu, float in_scale, float in_shift, const void* x0_dev, const void* x1_dev, const void* res_dev,
+                        void* out_dev, int ksplit, int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ from typing import List
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RVCMI_LIB") or os.path.join(_HERE, "librvcmi.so")  # RVCMI_LIB: dev A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip"]
+SOURCES = ["nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip"]
 
 RVCMI_MAX_UPS, RVCMI_MAX_RB, RVCMI_MAX_DIL = 8, 4, 4
 RVCMI_VERSION = 2  # include/rvcmi.h; the argument lists of SYMBOLS below are those of this ABI version
@@ -123,6 +123,12 @@ SYMBOLS = [
     ("rvcmi_gru_create", C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(_P)]),
     ("rvcmi_gru_destroy", C.c_int, [_P]),
     ("rvcmi_gru_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    ("rvcmi_unet_create", C.c_int, [C.POINTER(Tensor), C.c_int, C.c_int, C.POINTER(_P)]),
+    ("rvcmi_unet_destroy", C.c_int, [_P]),
+    ("rvcmi_unet_head_channels", C.c_int, [_P]),
+    ("rvcmi_unet_workspace_bytes", C.c_size_t, [_P, C.c_int, C.c_int]),
+    ("rvcmi_unet_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    ("rvcmi_unet_debug_op", C.c_int, [C.c_int] * 7 + [_P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
 ]
 
 

@@ -180,6 +180,7 @@ static __global__ void __launch_bounds__(GNT) k_gru_seq(const half2v* __restrict
 struct rvcmi_gru {
     int device = 0, input = 0;
     DevBuf wih, whh, bias, bhn, gx;
+    std::vector<DevBuf> retired;  // earlier, smaller projection workspaces: a captured graph may still point at one, so they live as long as the handle
     size_t gx_rows = 0;
 };
 
@@ -241,6 +242,7 @@ int rvcmi_gru_forward(rvcmi_gru* h, int B, int T, const void* x16, float* y, flo
         const size_t M = (size_t)B * T;
         if (M > h->gx_rows) {  // (grows with the longest call seen; f0 runs once per file, outside any capture)
             HIP_CHECK(hipStreamSynchronize(st));
+            if (h->gx.p) h->retired.push_back(std::move(h->gx));  // not freed: a graph captured at the smaller size replays into it
             h->gx.alloc(M * 2 * GR * sizeof(float));
             h->gx_rows = M;
         }

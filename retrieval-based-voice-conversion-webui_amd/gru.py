@@ -95,7 +95,8 @@ def accelerate_rmvpe(model: torch.nn.Module) -> int:
 
 def accelerate_f0_rmvpe(rmvpe) -> int:
     """What the rebound ``Pipeline.pipeline`` / ``RVC.infer`` do with the ``RMVPE`` object (rvc/f0/rmvpe.py) of their f0 generator, once:
-    ``accelerate_rmvpe(rmvpe.model)`` unless ``RVCMI_RMVPE_GRU=0``.  The count is remembered on the object (``_rvcmi_gru``)."""
+    ``accelerate_rmvpe(rmvpe.model)`` unless ``RVCMI_RMVPE_GRU=0``.  The count is remembered on the object (``_rvcmi_gru``).  With the opt-in
+    switch of ``unet.py`` on, also ``accelerate_rmvpe_unet(rmvpe.model)`` (count: ``_rvcmi_unet``)."""
     import os
 
     n = getattr(rmvpe, "_rvcmi_gru", None)
@@ -107,6 +108,17 @@ def accelerate_f0_rmvpe(rmvpe) -> int:
         try:
             rmvpe._rvcmi_gru = n
         except Exception:  # noqa  (an object without a __dict__: try again next time)
+            pass
+    # opt-in (RVCMI_RMVPE_UNET=1 / install(rmvpe_unet=True), default off): the U-Net and head in front of the GRU on csrc/unet.hip; its own
+    # count (_rvcmi_unet), so the switch can come on after the GRU swap was made
+    from . import unet as _unet
+
+    if _unet.unet_on() and getattr(rmvpe, "_rvcmi_unet", None) is None:
+        net = getattr(rmvpe, "model", None)
+        m = _unet.accelerate_rmvpe_unet(net) if isinstance(net, torch.nn.Module) else 0
+        try:
+            rmvpe._rvcmi_unet = m
+        except Exception:  # noqa
             pass
     return n
 

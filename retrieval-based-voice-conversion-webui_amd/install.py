@@ -139,11 +139,13 @@ def _rebind_gate(rebound) -> None:
 
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
-            patch_gui: bool = False, device_prep: bool = False) -> None:
+            patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
-    high-pass and the reflection pad on the device (``glue.filtfilt``; equal to scipy to fp64 rounding noise, not bit for bit)."""
+    high-pass and the reflection pad on the device (``glue.filtfilt``; equal to scipy to fp64 rounding noise, not bit for bit).
+    ``rmvpe_unet=True`` (opt-in, as ``RVCMI_RMVPE_UNET=1``): the f0 step also runs RMVPE's U-Net and head on ``csrc/unet.hip``
+    (``unet.accelerate_rmvpe_unet``), next to the GRU swap."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -203,7 +205,10 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
         _rebind_gate(rebound)
     from . import pipeline as _plm
 
+    from . import unet as _unet
+
     _plm.DEVICE_PREP = bool(device_prep)  # last: an install() that raised above leaves the switch as it was
+    _unet.RMVPE_UNET = bool(rmvpe_unet)
 
 
 def uninstall() -> None:
@@ -221,5 +226,8 @@ def uninstall() -> None:
             sys.modules["faiss"] = _state["faiss_prev"]
     from . import pipeline as _plm
 
+    from . import unet as _unet
+
     _plm.DEVICE_PREP = False
+    _unet.RMVPE_UNET = False
     _state.clear()
