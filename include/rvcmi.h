@@ -326,6 +326,13 @@ int rvcmi_glue_rmvpe_f0(const float* salience_dev, int n, int nbins, float thred
 /* post_process only (f0 in Hz from any other estimator, fp64 [n]).                                 */
 int rvcmi_glue_f0_post(const double* f0_dev, int n, int f0_up_key, int64_t* pitch_dev, float* pitchf_dev,
                        void* stream);
+/* The same two with a fractional key (the realtime GUI's formant slider moves f0_up_key - formant_shift in steps of 0.05): the factor is
+ * pow(2, f0_up_key / 12) in fp64, as the reference's post_process evaluates it for a python float.  The integer entry points above forward
+ * here; for an integral key the factor is the same double.  A key that is not finite: RVCMI_ERR_INVALID.                              */
+int rvcmi_glue_rmvpe_f0_key(const float* salience_dev, int n, int nbins, float thred, int p_len, double f0_up_key,
+                            double* scratch_dev, int64_t* pitch_dev, float* pitchf_dev, void* stream);
+int rvcmi_glue_f0_post_key(const double* f0_dev, int n, double f0_up_key, int64_t* pitch_dev, float* pitchf_dev,
+                           void* stream);
 
 /* change_rms (infer/modules/vc/pipeline.py:26-46, called at :351 when rms_mix_rate != 1): mixes the loudness envelope of the
  * input (data1 at sr1 = 16000) into the converted audio data2 (sr2 = tgt_sr), IN PLACE on data2:
@@ -482,6 +489,37 @@ int rvcmi_unet_forward(rvcmi_unet* h, int B, int T, const float* mel_dev, float*
 int rvcmi_unet_debug_op(int kind, int B, int H, int W, int C0, int C1, int Cout, const float* w, const float* scale, const float* shift,
                         int relu, float in_scale, float in_shift, const void* x0_dev, const void* x1_dev, const void* res_dev,
                         void* out_dev, int ksplit, int device, void* stream);
+
+/* ---- beyond SURVEY.md section 8: the log-mel front end and the head of the RMVPE f0 network ------------------------------------
+ * With these two, rvcmi_unet_*, rvcmi_gru_* and rvcmi_glue_rmvpe_f0_key a C caller goes from a 16 kHz waveform to (pitch, pitchf):
+ *   mel_forward [B][T_pad][128] -> unet_forward [B][T_pad][3][128] -> (fp16) gru_forward [B][T_pad][512] -> rmvpe_head [B * T_pad][360]
+ *   -> glue_rmvpe_f0_key on the first T rows.
+ *
+ * rvcmi_mel: MelSpectrogram.forward(audio, keyshift=0, speed=1, center=True) of rvc/f0/mel.py:58-71 over rvc/f0/stft.py:165-180:
+ *   reflect pad by n_fft / 2, periodic Hann window of win_length, magnitude of the one-sided transform, mel_basis @ magnitude,
+ *   (round_half: rounded to fp16, where the reference's `.half()` sits), clamp(min=clamp), log (round_half: rounded to fp16 again, as
+ *   torch's half log does); stored as fp32.  mel_basis_host [n_mels][n_fft / 2 + 1] fp32 is DATA: the reference's `mel_basis` buffer.
+ *   Any matrix is served exactly (per row the sum runs over [first non-zero, last non-zero + 1)).  Transform, magnitude and mel sum
+ *   are fp64.  Supported: n_fft == win_length == 1024, n_mels == 128, hop >= 1, clamp > 0; anything else RVCMI_ERR_INVALID (the
+ *   caller keeps torch).                                                                                                        */
+typedef struct rvcmi_mel rvcmi_mel;
+int rvcmi_mel_create(int n_fft, int hop, int win_length, int n_mels, const float* mel_basis_host, float clamp, int device,
+                     rvcmi_mel** out);
+int rvcmi_mel_destroy(rvcmi_mel* h);
+/* Frames of an n-sample input: n / hop + 1 (center=True); 0 when n <= n_fft / 2, which torch's reflection pad refuses. */
+int64_t rvcmi_mel_frames(rvcmi_mel* h, int64_t n);
+/* wav_dev [B][n] fp32 -> out_dev [B][T_pad][n_mels] fp32, T_pad >= T = rvcmi_mel_frames(h, n): the transposed [B, 1, T, 128] that
+ * rvcmi_unet_forward reads (the transpose of e2e.py:44 is gone); frames T .. T_pad - 1 are written as zeros, the
+ * F.pad(mel, (0, n_pad)) of rvc/f0/rmvpe.py:141-144.  Enqueue-only, allocates nothing (safe inside a stream capture), bit-identical
+ * from run to run.  n <= n_fft / 2, T_pad < T, B outside 1 .. 65535: RVCMI_ERR_INVALID, nothing launched.                       */
+int rvcmi_mel_forward(rvcmi_mel* h, int B, int64_t n, const float* wav_dev, int round_half, int T_pad, float* out_dev, void* stream);
+
+/* Linear(512, 360) + sigmoid of rvc/f0/e2e.py:33-35 (the Dropout between them is the identity in eval), one launch on the current
+ * device: salience[m][f] = sigmoid(sum_k y[m][k] * w[f][k] + b[f]).  y_dev [M][512] (the GRU's output), w_dev [360][512], b_dev [360],
+ * all fp32 on the device and 16-byte aligned; operands rounded to fp16 when half_operands, else fp32; fp32 MFMA accumulation over K in
+ * chunks of 32 whose sums, the bias and the sigmoid are carried in fp64 and rounded once to fp32.  salience_dev [M][360] fp32.     */
+int rvcmi_rmvpe_head(const float* y_dev, int M, const float* w_dev, const float* b_dev, int half_operands, float* salience_dev,
+                     void* stream);
 
 #ifdef __cplusplus
 }

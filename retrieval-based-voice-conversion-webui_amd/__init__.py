@@ -13,6 +13,7 @@ from . import glue
 from .glue import cut_count, cut_points, filtfilt, highpass16k
 from .gru import GRUHIP, accelerate_rmvpe
 from .unet import UNetHIP, accelerate_rmvpe_unet, restore_rmvpe_unet
+from .rmvpe import RMVPEHIP
 from .synthesizer import accelerate_synthesizer, get_synthesizer, load_synthesizer
 from . import dist
 from .install import install, uninstall
@@ -22,6 +23,6 @@ from .realtime import PitchCache, RealtimeStream, RealtimeVC, SincResample, f0_e
 __all__ = [
     "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "GeneratorHIP", "NSFGeneratorHIP",
     "config_from_reference", "FrontHIP", "front_config_from_reference", "infer_hip", "retrieve_blend", "accelerate_synthesizer", "get_synthesizer", "load_synthesizer", "dist", "glue", "install", "uninstall", "RealtimeVC", "PitchCache", "f0_extractor_frame", "SincResample", "sinc_resample_kernel", "GRUHIP", "accelerate_rmvpe",
-    "UNetHIP", "accelerate_rmvpe_unet", "restore_rmvpe_unet",
+    "UNetHIP", "accelerate_rmvpe_unet", "restore_rmvpe_unet", "RMVPEHIP",
     "RealtimeStream", "stream_geometry", "TorchGateHIP", "cut_points", "cut_count", "filtfilt", "highpass16k",
 ]

@@ -14,7 +14,7 @@ from typing import List
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RVCMI_LIB") or os.path.join(_HERE, "librvcmi.so")  # RVCMI_LIB: dev A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip"]
+SOURCES = ["nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip", "rmvpe.hip"]
 
 RVCMI_MAX_UPS, RVCMI_MAX_RB, RVCMI_MAX_DIL = 8, 4, 4
 RVCMI_VERSION = 2  # include/rvcmi.h; the argument lists of SYMBOLS below are those of this ABI version
@@ -105,6 +105,8 @@ SYMBOLS = [
     ("rvcmi_glue_expand_protect", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, C.c_float, C.c_int64, _P, _P]),
     ("rvcmi_glue_rmvpe_f0", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),
     ("rvcmi_glue_f0_post", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    ("rvcmi_glue_rmvpe_f0_key", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, _P, _P, _P, _P]),
+    ("rvcmi_glue_f0_post_key", C.c_int, [_P, C.c_int, C.c_double, _P, _P, _P]),
     ("rvcmi_glue_change_rms", C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
     ("rvcmi_glue_scale_int16_range", C.c_int, [_P, C.c_int64, _P, _P]),
     ("rvcmi_glue_resample_poly", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
@@ -129,6 +131,11 @@ SYMBOLS = [
     ("rvcmi_unet_workspace_bytes", C.c_size_t, [_P, C.c_int, C.c_int]),
     ("rvcmi_unet_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     ("rvcmi_unet_debug_op", C.c_int, [C.c_int] * 7 + [_P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    ("rvcmi_mel_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.POINTER(_P)]),
+    ("rvcmi_mel_destroy", C.c_int, [_P]),
+    ("rvcmi_mel_frames", C.c_int64, [_P, C.c_int64]),
+    ("rvcmi_mel_forward", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
+    ("rvcmi_rmvpe_head", C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P]),
 ]
 
 

@@ -231,7 +231,13 @@ int rvcmi_glue_expand_protect(const float* feats, int64_t nq, int d, int reps, c
 
 int rvcmi_glue_rmvpe_f0(const float* salience, int n, int nbins, float thred, int p_len, int f0_up_key, double* scratch,
                         int64_t* pitch, float* pitchf, void* stream) {
+    return rvcmi_glue_rmvpe_f0_key(salience, n, nbins, thred, p_len, (double)f0_up_key, scratch, pitch, pitchf, stream);
+}
+
+int rvcmi_glue_rmvpe_f0_key(const float* salience, int n, int nbins, float thred, int p_len, double f0_up_key, double* scratch,
+                            int64_t* pitch, float* pitchf, void* stream) {
     return guarded([&] {
+        if (!std::isfinite(f0_up_key)) RVCMI_FAIL(RVCMI_ERR_INVALID, "rmvpe_f0: the key is not finite");
         if (!salience || !scratch || !pitch || !pitchf || n < 1 || nbins < 1 || p_len < 1)
             RVCMI_FAIL(RVCMI_ERR_INVALID, "rmvpe_f0: bad argument");
         // work arrays: LDS when (n + p_len) doubles fit, else global (scratch in place + the pitch buffer) -- no length limit
@@ -242,7 +248,7 @@ int rvcmi_glue_rmvpe_f0(const float* salience, int n, int nbins, float thred, in
         hipLaunchKernelGGL(k_rmvpe_decode, dim3((n + 3) / 4), dim3(256), 0, st, salience, n, nbins, thred, scratch);
         ensure_dyn_lds(k_f0_post, 160 * 1024, g_attr_f0);
         // the host evaluates the scalars exactly as the reference does (python floats / math.log, rvc/f0/gen.py:18, 70-73)
-        const double key_mul = std::pow(2.0, (double)f0_up_key / 12.0);
+        const double key_mul = std::pow(2.0, f0_up_key / 12.0);  // (an integral key: the same double as (double)int / 12.0)
         const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
         hipLaunchKernelGGL(k_f0_post, dim3(1), dim3(256), smem, st, scratch, n, p_len, 1, 1, key_mul, mel_min, mel_max, pitch, pitchf,
                            in_lds ? nullptr : scratch, in_lds ? nullptr : reinterpret_cast<double*>(pitch));
@@ -251,13 +257,17 @@ int rvcmi_glue_rmvpe_f0(const float* salience, int n, int nbins, float thred, in
 }
 
 int rvcmi_glue_f0_post(const double* f0, int n, int f0_up_key, int64_t* pitch, float* pitchf, void* stream) {
+    return rvcmi_glue_f0_post_key(f0, n, (double)f0_up_key, pitch, pitchf, stream);
+}
+
+int rvcmi_glue_f0_post_key(const double* f0, int n, double f0_up_key, int64_t* pitch, float* pitchf, void* stream) {
     return guarded([&] {
-        if (!f0 || !pitch || !pitchf || n < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "f0_post: bad argument");
+        if (!f0 || !pitch || !pitchf || n < 1 || !std::isfinite(f0_up_key)) RVCMI_FAIL(RVCMI_ERR_INVALID, "f0_post: bad argument");
         size_t smem = (size_t)(2 * n) * sizeof(double);
         const bool in_lds = smem <= 160 * 1024;
         if (!in_lds) smem = 0;
         ensure_dyn_lds(k_f0_post, 160 * 1024, g_attr_f0);
-        const double key_mul = std::pow(2.0, (double)f0_up_key / 12.0);
+        const double key_mul = std::pow(2.0, f0_up_key / 12.0);
         const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
         hipLaunchKernelGGL(k_f0_post, dim3(1), dim3(256), smem, (hipStream_t)stream, f0, n, n, 0, 0, key_mul, mel_min, mel_max, pitch, pitchf,
                            (double*)nullptr, in_lds ? nullptr : reinterpret_cast<double*>(pitch));

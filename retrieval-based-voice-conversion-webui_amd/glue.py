@@ -97,9 +97,10 @@ def retrieve_blend_expand(feats: torch.Tensor, index, index_rate: float, pitchf:
     return out.unsqueeze(0).to(feats.dtype)
 
 
-def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key: int = 0, thred: float = 0.03) -> Tuple[torch.Tensor, torch.Tensor]:
+def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.03) -> Tuple[torch.Tensor, torch.Tensor]:
     """RMVPE salience [n, 360] -> (pitch int64 [1, p_len], pitchf float32 [1, p_len]) as ``Generator.calculate`` +
-    pipeline.py:270-277 produce them."""
+    pipeline.py:270-277 produce them.  ``f0_up_key``: an int or a float (the realtime GUI's key minus its formant shift); the factor is
+    ``pow(2, f0_up_key / 12)`` in fp64 either way, as in rvc/f0/gen.py:18."""
     dev = _dev(salience, "salience")
     if salience.dim() != 2:
         raise ValueError("salience must be [n, bins]")
@@ -109,20 +110,20 @@ def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key: int = 0, thred: floa
     pitch = torch.empty(int(p_len), device=dev, dtype=torch.int64)
     pitchf = torch.empty(int(p_len), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_rmvpe_f0(_ptr(s), n, nb, float(thred), int(p_len), int(f0_up_key), _ptr(scratch), _ptr(pitch),
-                                                  _ptr(pitchf), _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_rmvpe_f0_key(_ptr(s), n, nb, float(thred), int(p_len), float(f0_up_key), _ptr(scratch), _ptr(pitch),
+                                                      _ptr(pitchf), _stream(dev)))
     return pitch.unsqueeze(0), pitchf.unsqueeze(0)
 
 
-def f0_post(f0: torch.Tensor, f0_up_key: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """f0 in Hz [n] (any estimator) -> (pitch int64 [1, n], pitchf float32 [1, n]): rvc/f0/gen.py post_process."""
+def f0_post(f0: torch.Tensor, f0_up_key=0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """f0 in Hz [n] (any estimator) -> (pitch int64 [1, n], pitchf float32 [1, n]): rvc/f0/gen.py post_process (``f0_up_key``: int or float)."""
     dev = _dev(f0, "f0")
     x = f0.reshape(-1).to(torch.float64).contiguous()
     n = int(x.numel())
     pitch = torch.empty(n, device=dev, dtype=torch.int64)
     pitchf = torch.empty(n, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_f0_post(_ptr(x), n, int(f0_up_key), _ptr(pitch), _ptr(pitchf), _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_f0_post_key(_ptr(x), n, float(f0_up_key), _ptr(pitch), _ptr(pitchf), _stream(dev)))
     return pitch.unsqueeze(0), pitchf.unsqueeze(0)
 
 

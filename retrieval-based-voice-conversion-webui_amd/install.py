@@ -139,13 +139,14 @@ def _rebind_gate(rebound) -> None:
 
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
-            patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False) -> None:
+            patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
     high-pass and the reflection pad on the device (``glue.filtfilt``; equal to scipy to fp64 rounding noise, not bit for bit).
     ``rmvpe_unet=True`` (opt-in, as ``RVCMI_RMVPE_UNET=1``): the f0 step also runs RMVPE's U-Net and head on ``csrc/unet.hip``
-    (``unet.accelerate_rmvpe_unet``), next to the GRU swap."""
+    (``unet.accelerate_rmvpe_unet``), next to the GRU swap.  ``rmvpe_hip=True`` (opt-in, as ``RVCMI_RMVPE_HIP=1``): the f0 step runs the whole
+    estimator -- mel front end, U-Net, GRU, head, decode -- as ``rmvpe.RMVPEHIP``, and the realtime entry keeps a fractional key on the device."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -209,6 +210,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
 
     _plm.DEVICE_PREP = bool(device_prep)  # last: an install() that raised above leaves the switch as it was
     _unet.RMVPE_UNET = bool(rmvpe_unet)
+    from . import rmvpe as _rmvpe
+
+    _rmvpe.RMVPE_HIP = bool(rmvpe_hip)
 
 
 def uninstall() -> None:
@@ -230,4 +234,7 @@ def uninstall() -> None:
 
     _plm.DEVICE_PREP = False
     _unet.RMVPE_UNET = False
+    from . import rmvpe as _rmvpe
+
+    _rmvpe.RMVPE_HIP = False
     _state.clear()

@@ -380,6 +380,16 @@ def _rmvpe_on_device(self, audio_pad, p_len, f0_up_key):
     r = gen.rmvpe
     if not (hasattr(r, "mel_extractor") and hasattr(r, "_mel2hidden")) or "privateuseone" in str(getattr(r, "device", "")):
         return None
+    # opt-in (RVCMI_RMVPE_HIP=1 / install(rmvpe_hip=True), default off): the whole estimator on this project's kernels (rmvpe.py) -- mel front end
+    # and head included, no torch op but one cast between the waveform and (pitch, pitchf) -- and a key that may be fractional.  A model the
+    # kernels do not serve keeps the path below.
+    from . import rmvpe as _rm
+
+    on = _rm.rmvpe_on()
+    if on:
+        hip = _rm.for_generator(gen, r)
+        if hip is not None:
+            return hip.f0(torch.as_tensor(audio_pad).float().to(hip.device), p_len, f0_up_key, RMVPE_THRED)
     # (beyond SURVEY.md section 8) the network's bidirectional GRU -- 75-90 % of a conversion as MIOpen runs it, bench.py --e2e -- on the
     # persistent HIP kernel, once per RMVPE object; everything else of RMVPE stays on PyTorch-ROCm.  RVCMI_RMVPE_GRU=0 keeps torch's GRU.
     from .gru import accelerate_f0_rmvpe
@@ -389,7 +399,7 @@ def _rmvpe_on_device(self, audio_pad, p_len, f0_up_key):
     with torch.no_grad():
         mel = r.mel_extractor(wav.float().to(r.device).unsqueeze(0), center=True)
         hidden = r._mel2hidden(mel)
-    return glue.rmvpe_f0(hidden.squeeze(0).float(), p_len, int(f0_up_key), RMVPE_THRED)
+    return glue.rmvpe_f0(hidden.squeeze(0).float(), p_len, f0_up_key if on else int(f0_up_key), RMVPE_THRED)
 
 
 INDEX_CACHE_ENTRIES = 2  # index files kept resident (a WebUI session alternates between very few voices)

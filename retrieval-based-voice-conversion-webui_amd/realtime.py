@@ -341,7 +341,7 @@ def _rmvpe_f0_graphed(self, wav: torch.Tensor, p_len: int, key: int):
     if os.environ.get("RVCMI_RT_GRAPH", "1") == "0" or not (torch.is_tensor(wav) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 1):
         return _rmvpe_on_device(self, wav, p_len, key)
     cache = self.__dict__.setdefault("_rvcmi_f0_graphs", {})
-    k = (int(wav.shape[0]), int(p_len), int(key), str(wav.device))
+    k = (int(wav.shape[0]), int(p_len), int(key) if float(key).is_integer() else float(key), str(wav.device))  # (the key's factor is baked into the graph)
     e = cache.setdefault(k, {"calls": 0})
     if "graph" in e:
         e["in"].copy_(wav)
@@ -401,15 +401,17 @@ def rvc_infer_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, ret
         n = f0_extractor_frame(block_frame_16k, f0method, self.window)
         key = self.f0_up_key - self.formant_shift
         got = None
-        if f0method == "rmvpe" and float(key).is_integer() and getattr(self, "f0_gen", None) is not None:
+        from .rmvpe import rmvpe_on
+
+        if f0method == "rmvpe" and (float(key).is_integer() or rmvpe_on()) and getattr(self, "f0_gen", None) is not None:
             # RMVPE stays on the device from the waveform to (pitch, pitchf): the reference's Generator.calculate (rvc/f0/gen.py:58-59, 103-113) copies
             # the window to the host, the salience back, and decodes it in numpy with a python loop over frames; pipeline._rmvpe_on_device is the same
             # chain (mel, network, rvcmi_glue_rmvpe_f0 = _decode + _resize_f0 + _interpolate_f0 + post_process, golden-tested against the reference's)
             # without a host hop, and swaps the network's GRU for the HIP one (3.7 / 7.2 ms -> 0.06 / 0.10 ms for a 32- / 64-frame window,
-            # tools/gru_time.py), replayed from a hipGraph after the first blocks (_rmvpe_f0_graphed).  The integer key is the C ABI's; a fractional key (formant
-            # slider) takes the reference's own method below.
+            # tools/gru_time.py), replayed from a hipGraph after the first blocks (_rmvpe_f0_graphed).  A fractional key (formant slider) takes the
+            # reference's own method below unless the opt-in RMVPE switch (rmvpe.py) is on: then it stays on the device too.
             w_f0 = input_wav[-n:]
-            got = _rmvpe_f0_graphed(self, w_f0.contiguous() if torch.is_tensor(w_f0) else w_f0, int(w_f0.shape[0]) // self.window, int(key))
+            got = _rmvpe_f0_graphed(self, w_f0.contiguous() if torch.is_tensor(w_f0) else w_f0, int(w_f0.shape[0]) // self.window, int(key) if float(key).is_integer() else float(key))
         if got is not None:
             pitch, pitchf = got[0][0], got[1][0]
         else:

@@ -1,0 +1,228 @@
+"""The whole RMVPE f0 estimator (rvc/f0/rmvpe.py) on this project's kernels -- like ``gru.py`` and ``unet.py`` BEYOND the scope table
+(SURVEY.md section 8), and the piece that closes the chain: the log-mel front end and the ``Linear`` + sigmoid head of ``csrc/rmvpe.hip``
+around ``UNetHIP`` and ``GRUHIP``, decoded by ``glue.rmvpe_f0``.
+
+    hip = rvc_amd.RMVPEHIP.from_reference(rmvpe)     # an rvc.f0.rmvpe.RMVPE-like object; None when it is not one the kernels serve
+    pitch, pitchf = hip.f0(wav16k, p_len, f0_up_key) # what Generator.calculate(..., "rmvpe") + post_process return, on the device
+
+Between the input cast ``wav.float()`` and the result torch allocates buffers and makes the one fp32 -> fp16 cast in front of the GRU;
+everything else is enqueue-only HIP, so the chain captures into a hipGraph once its first call of a size has happened eagerly.
+
+Opt-in (``RVCMI_RMVPE_HIP=1`` or ``rvc_amd.install(rmvpe_hip=True)``; default off): with the switch on, ``pipeline._rmvpe_on_device`` runs
+this object instead of the reference's ``mel_extractor`` + ``_mel2hidden``, and the realtime entry keeps a fractional key (formant slider)
+on the device.  The reference object is read, never changed.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from . import glue
+from . import unet as _unet
+from .gru import GRUHIP
+from .gru import supports as _gru_supports
+
+N_MELS, N_FFT, N_CLASS = 128, 1024, 360
+CACHE_ROWS = 512   # workspaces of calls with B * T_pad <= this stay with the object (the realtime windows: a captured graph points at them, so
+                   # they are never dropped); longer inputs take theirs from torch's caching allocator per call
+RMVPE_HIP = False  # install(rmvpe_hip=True) sets it; RVCMI_RMVPE_HIP=1 / =0 overrides it per call
+
+
+def rmvpe_on() -> bool:
+    env = os.environ.get("RVCMI_RMVPE_HIP")
+    return env == "1" if env in ("0", "1") else bool(RMVPE_HIP)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _network_parts(model):
+    """-> (UNetHIP or state dict, GRUHIP or nn.GRU, nn.Linear, device) of an ``E2E``-like network (rvc/f0/e2e.py: U-Net, 3-channel head, one
+    bidirectional GRU, Linear(512, 360), sigmoid), recognised by its state-dict keys and module types; None for anything else."""
+    if not isinstance(model, torch.nn.Module) or isinstance(model, torch.jit.ScriptModule):
+        return None
+    named = list(model.named_modules())
+    grus = [(n, m) for n, m in named if isinstance(m, (torch.nn.GRU, GRUHIP))]
+    lins = [(n, m) for n, m in named if isinstance(m, torch.nn.Linear)]
+    if len(grus) != 1 or len(lins) != 1:
+        return None
+    (gname, gru), (lname, lin) = grus[0], lins[0]
+    if isinstance(gru, torch.nn.GRU) and not _gru_supports(gru):
+        return None
+    if gru.input_size != 3 * N_MELS or (lin.in_features, lin.out_features) != (2 * gru.hidden_size, N_CLASS) or lin.bias is None:
+        return None
+    sd = model.state_dict()
+    rest = {k for k in sd if not (k.startswith("unet.") or k.startswith("cnn."))}
+    want = {lname + ".weight", lname + ".bias"}
+    if isinstance(gru, torch.nn.GRU):
+        want |= {"%s.%s" % (gname, p) for p, _ in gru.named_parameters()}
+    if rest != want:
+        return None
+    un = getattr(model, "unet", None)
+    if isinstance(un, _unet.UNetHIP):  # already swapped by accelerate_rmvpe_unet: the same handle serves
+        net = un
+        geo = un.geometry
+    else:
+        geo = _unet.geometry({k: tuple(v.shape) for k, v in sd.items()})
+        if geo is None or not isinstance(un, torch.nn.Module) or not _unet._pooling_ok(un):
+            return None
+        net = sd
+    if geo is None or geo["head"] != 3:
+        return None
+    devs = {v.device for v in sd.values()} | ({gru._device} if isinstance(gru, GRUHIP) else set()) | ({un._device} if isinstance(un, _unet.UNetHIP) else set())
+    if len(devs) != 1 or next(iter(devs)).type != "cuda":
+        return None
+    dev = next(iter(devs))
+    return net, gru, lin, torch.device("cuda", _lib.device_index(dev))
+
+
+class RMVPEHIP:
+    """waveform at 16 kHz -> log-mel -> U-Net -> GRU -> salience -> (pitch, pitchf), every stage a HIP kernel of this project."""
+
+    def __init__(self, n_fft: int, hop_length: int, win_length: int, clamp: float, mel_basis: torch.Tensor, is_half: bool, net, gru, linear, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.RvcmiError("RMVPEHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
+        dev = torch.device("cuda", _lib.device_index(dev))
+        basis = mel_basis.detach().float().cpu().contiguous()
+        if basis.dim() != 2 or basis.shape[1] != int(n_fft) // 2 + 1:
+            raise _lib.RvcmiError("RMVPEHIP: mel_basis %s does not belong to n_fft %d" % (tuple(basis.shape), n_fft), code=_lib.ERR_INVALID)
+        h = C.c_void_p()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rvcmi_mel_create(int(n_fft), int(hop_length), int(win_length), int(basis.shape[0]), _ptr(basis), float(clamp),
+                                                   dev.index, C.byref(h)))
+        self._h = h
+        self.device, self.is_half, self.hop_length, self.n_fft = dev, bool(is_half), int(hop_length), int(n_fft)
+        self.unet = net if isinstance(net, _unet.UNetHIP) else _unet.UNetHIP(net, dev)
+        self.gru = gru if isinstance(gru, GRUHIP) else GRUHIP(gru, dev)
+        self._w = linear.weight.detach().to(dev, torch.float32).contiguous().clone()  # uploaded once
+        self._b = linear.bias.detach().to(dev, torch.float32).contiguous().clone()
+        self._ws = {}
+
+    @classmethod
+    def from_reference(cls, rmvpe) -> Optional["RMVPEHIP"]:
+        """``rmvpe``: an ``rvc.f0.rmvpe.RMVPE``-like object (``mel_extractor`` with ``n_fft, hop_length, win_length, clamp, mel_basis, is_half``
+        and the ``E2E`` network as ``model``).  None -- and nothing touched -- for what the kernels do not serve: another mel or network
+        geometry, a CPU model, the onnx session of a ``privateuseone`` device, a TorchScript model."""
+        if "privateuseone" in str(getattr(rmvpe, "device", "")):
+            return None
+        me = getattr(rmvpe, "mel_extractor", None)
+        try:
+            n_fft, hop, win, clamp = int(me.n_fft), int(me.hop_length), int(me.win_length), float(me.clamp)
+            basis, is_half = me.mel_basis, bool(me.is_half)
+        except (AttributeError, TypeError, ValueError):
+            return None
+        if not torch.is_tensor(basis) or tuple(basis.shape) != (N_MELS, N_FFT // 2 + 1) or (n_fft, win) != (N_FFT, N_FFT) or hop < 1:
+            return None
+        parts = _network_parts(getattr(rmvpe, "model", None))
+        if parts is None:
+            return None
+        net, gru, lin, dev = parts
+        try:
+            return cls(n_fft, hop, win, clamp, basis, is_half, net, gru, lin, dev)
+        except _lib.RvcmiError as e:
+            if e.code == _lib.ERR_INVALID:  # a configuration the kernels do not serve: the caller keeps torch
+                return None
+            raise
+
+    def __del__(self):
+        h = self.__dict__.pop("_h", None)
+        if h:
+            try:
+                _lib.lib().rvcmi_mel_destroy(h)
+            except Exception:  # noqa  (interpreter shutdown)
+                pass
+
+    def frames(self, n: int) -> int:
+        return int(_lib.lib().rvcmi_mel_frames(self._h, int(n)))
+
+    def _wav(self, wav) -> torch.Tensor:
+        if not torch.is_tensor(wav) or wav.device.type != "cuda":
+            raise _lib.RvcmiError("RMVPEHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(wav, "device", type(wav)))
+        if wav.device != self.device:
+            raise _lib.RvcmiError("RMVPEHIP: the input is on %s, the weights on %s" % (wav.device, self.device))
+        x = wav.detach().float()
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        if x.dim() != 2:
+            raise _lib.RvcmiError("RMVPEHIP: expected a waveform [n] or [B, n], got %s" % (tuple(wav.shape),), code=_lib.ERR_INVALID)
+        return x.contiguous()
+
+    def _buffers(self, B: int, T_pad: int) -> dict:
+        ws = self._ws.get((B, T_pad))
+        if ws is None:
+            nbytes = self.unet.workspace_bytes(B, T_pad)
+            if not nbytes:
+                msg = _lib.lib().rvcmi_last_error()
+                raise _lib.RvcmiError("RMVPEHIP: B = %d, %d frames not served (%s)" % (B, T_pad, msg.decode(errors="replace") if msg else "?"), code=_lib.ERR_INVALID)
+            dev, f32 = self.device, torch.float32
+            ws = dict(mel=torch.empty(B, T_pad, N_MELS, device=dev, dtype=f32), feat=torch.empty(B, T_pad, 3 * N_MELS, device=dev, dtype=f32),
+                      unet=torch.empty(nbytes, device=dev, dtype=torch.uint8), x16=torch.empty(B, T_pad, 3 * N_MELS, device=dev, dtype=torch.float16),
+                      y=torch.empty(B, T_pad, 2 * self.gru.hidden_size, device=dev, dtype=f32), sal=torch.empty(B, T_pad, N_CLASS, device=dev, dtype=f32))
+            if B * T_pad <= CACHE_ROWS:
+                self._ws[(B, T_pad)] = ws
+        return ws
+
+    def _mel(self, x: torch.Tensor, ws=None) -> Tuple[torch.Tensor, int]:
+        B, n = int(x.shape[0]), int(x.shape[1])
+        T = self.frames(n)
+        if T < 1:
+            raise _lib.RvcmiError("RMVPEHIP: a %d-sample input is not longer than the reflection pad %d" % (n, self.n_fft // 2), code=_lib.ERR_INVALID)
+        T_pad = 32 * ((T - 1) // 32 + 1)
+        ws = ws if ws is not None else self._buffers(B, T_pad)
+        _lib.check(_lib.lib().rvcmi_mel_forward(self._h, B, n, _ptr(x), 1 if self.is_half else 0, T_pad, _ptr(ws["mel"]), self._stream()))
+        return ws, T
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _salience(self, x: torch.Tensor) -> Tuple[torch.Tensor, int]:
+        """-> ([B, T_pad, 360] fp32, T).  Up to ``CACHE_ROWS`` rows the tensor belongs to the object: the next call of the same shape overwrites it."""
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            ws, T = self._mel(x)
+            B, T_pad = int(ws["mel"].shape[0]), int(ws["mel"].shape[1])
+            st = self._stream()
+            _lib.check(L.rvcmi_unet_forward(self.unet._h, B, T_pad, _ptr(ws["mel"]), _ptr(ws["feat"]), _ptr(ws["unet"]), st))
+            ws["x16"].copy_(ws["feat"])  # the fp32 -> fp16 cast GRUHIP.forward makes
+            _lib.check(L.rvcmi_gru_forward(self.gru._h, B, T_pad, _ptr(ws["x16"]), _ptr(ws["y"]), None, st))
+            _lib.check(L.rvcmi_rmvpe_head(_ptr(ws["y"]), B * T_pad, _ptr(self._w), _ptr(self._b), 1 if self.is_half else 0, _ptr(ws["sal"]), st))
+        return ws["sal"], T
+
+    def mel(self, wav: torch.Tensor) -> torch.Tensor:
+        """[n] or [B, n] -> log-mel [B, T_pad, 128] fp32, T_pad = T rounded up to 32, frames T .. T_pad - 1 zero: the U-Net's input."""
+        x = self._wav(wav)
+        with torch.cuda.device(self.device):
+            return self._mel(x)[0]["mel"].clone()
+
+    def salience(self, wav: torch.Tensor) -> torch.Tensor:
+        """[n] or [1, n] -> salience [T, 360] fp32 (``RMVPE._mel2hidden`` of the mel spectrogram, squeezed); [B, n] -> [B, T, 360]."""
+        x = self._wav(wav)
+        sal, T = self._salience(x)
+        return sal[0, :T].clone() if x.shape[0] == 1 else sal[:, :T].clone()
+
+    def f0(self, wav: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.03) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (pitch int64 [1, p_len], pitchf float32 [1, p_len]) as ``glue.rmvpe_f0`` returns them; ``f0_up_key`` may be fractional."""
+        x = self._wav(wav)
+        if x.shape[0] != 1:
+            raise _lib.RvcmiError("RMVPEHIP.f0: one waveform at a time (the decode is per sequence)", code=_lib.ERR_INVALID)
+        sal, T = self._salience(x)
+        return glue.rmvpe_f0(sal[0, :T], p_len, f0_up_key, thred)
+
+
+def for_generator(gen, rmvpe) -> Optional[RMVPEHIP]:
+    """The ``RMVPEHIP`` of ``rmvpe``, built once and remembered on the f0 generator that owns it (not on the reference object); None when the
+    kernels do not serve it."""
+    got = getattr(gen, "_rvcmi_rmvpe_hip", None)
+    if got is None or got[0] is not rmvpe:
+        got = (rmvpe, RMVPEHIP.from_reference(rmvpe))
+        try:
+            gen._rvcmi_rmvpe_hip = got
+        except Exception:  # noqa  (an object without a __dict__: built again next time)
+            pass
+    return got[1]

@@ -1,5 +1,6 @@
 """The deep U-Net of the RMVPE f0 network and its head on the HIP kernels of ``csrc/unet.hip`` -- like ``gru.py`` BEYOND the scope table
-(SURVEY.md section 8).  Together with ``GRUHIP`` it leaves only the mel front end and the final ``Linear`` + sigmoid of RMVPE on PyTorch-ROCm.
+(SURVEY.md section 8).  Together with ``GRUHIP`` it leaves only the mel front end and the final ``Linear`` + sigmoid of RMVPE on PyTorch-ROCm;
+``rmvpe.py`` (``RMVPEHIP``, its own opt-in switch) puts those two on ``csrc/rmvpe.hip`` as well.
 
 ``UNetHIP`` stands in for ``E2E.unet`` (rvc/f0/deepunet.py ``DeepUnet``) AND ``E2E.cnn`` (rvc/f0/e2e.py:29) at once: its forward returns the
 head's result, so ``accelerate_rmvpe_unet(model)`` replaces ``model.unet`` by it and ``model.cnn`` by an identity, and the unmodified
