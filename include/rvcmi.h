@@ -462,6 +462,14 @@ int rvcmi_gru_destroy(rvcmi_gru* h);
  * The projection workspace grows with the largest B * T seen (a hipMalloc on such a call: the FIRST call of a size must not be inside a
  * stream capture); the smaller workspaces it replaces stay allocated until destroy, so a graph captured earlier keeps replaying. */
 int rvcmi_gru_forward(rvcmi_gru* h, int B, int T, const void* x16_dev, float* y_dev, float* hn_dev, void* stream);
+/* The same for a RAGGED batch: nseq sequences packed along the row axis, sequence i in rows [offsets[i], offsets[i + 1]) of x16_dev [R][I]
+ * and y_dev [R][2H], R = offsets[nseq]; hn_dev [2][nseq][H] or NULL.  offsets_host and offsets_dev hold the same nseq + 1 ints (the host
+ * copy is checked, the device copy is what the kernel reads; the caller keeps both alive until the work has run).  Every sequence is
+ * computed exactly as rvcmi_gru_forward(h, 1, its length, its rows) computes it, bit for bit: each direction starts from h_0 = 0 at the
+ * sequence's own first / last row.  offsets[0] != 0, offsets that do not ascend strictly, nseq outside 1 .. 65535, R > 2^30:
+ * RVCMI_ERR_INVALID, nothing launched.  The projection workspace grows with R as it does with B * T above.                        */
+int rvcmi_gru_forward_ragged(rvcmi_gru* h, int nseq, const int* offsets_host, const int* offsets_dev, const void* x16_dev, float* y_dev,
+                             float* hn_dev, void* stream);
 
 /* ---- beyond SURVEY.md section 8: the deep U-Net of the RMVPE f0 network and its head -----------------------------------------
  * Stands in for `self.cnn(self.unet(mel))` of rvc/f0/e2e.py:46 (DeepUnet of rvc/f0/deepunet.py + Conv2d(16, 3, 3x3)): everything between
@@ -482,6 +490,17 @@ size_t rvcmi_unet_workspace_bytes(rvcmi_unet* h, int B, int T);
  * the `.transpose(1, 2).flatten(-2)` of e2e.py:46 already applied; ws_dev: rvcmi_unet_workspace_bytes(h, B, T) bytes, 256-byte aligned.
  * The handle allocates and frees nothing after create: safe inside a stream capture.                                                */
 int rvcmi_unet_forward(rvcmi_unet* h, int B, int T, const float* mel_dev, float* out_dev, void* ws_dev, void* stream);
+/* The same for a RAGGED batch: nseq sequences packed along the frame axis, sequence i in rows [offsets[i], offsets[i + 1]) of
+ * mel_dev [R][128] and out_dev [R][head channels][128], R = offsets[nseq]; no row is spent on padding to the longest.  Every sequence sees
+ * the zero border of its own convolutions at its first and last row -- the rows of its neighbours are never read -- so it comes out as
+ * its own rvcmi_unet_forward(h, 1, its length, ...) gives it, up to the summation order of the layers that split their K loop (the split
+ * is chosen from the launch size, R here).  offsets_host / offsets_dev: the same nseq + 1 ints on the host (checked) and on the device
+ * (read by the kernels; both alive until the work has run).  nseq < 1, offsets[0] != 0, a length that is not a positive multiple of
+ * 2^levels (so also offsets that do not ascend), R > 2^22, a launch beyond the grid limits: RVCMI_ERR_INVALID / 0 bytes, nothing launched.
+ * Enqueue only, nothing allocated; ws_dev: rvcmi_unet_workspace_bytes_ragged bytes.                                                  */
+size_t rvcmi_unet_workspace_bytes_ragged(rvcmi_unet* h, int nseq, const int* offsets_host);
+int rvcmi_unet_forward_ragged(rvcmi_unet* h, int nseq, const int* offsets_host, const int* offsets_dev, const float* mel_dev,
+                              float* out_dev, void* ws_dev, void* stream);
 /* Test hook: ONE primitive on caller-supplied data (synchronous; allocates).  kind 0: 3x3 convolution, 1: 1x1, 2: transposed 3x3 stride 2,
  * 3: 2x2 average pool, 4 / 5: the one-input-channel 3x3 / 1x1 behind the input scale and shift (x0_dev fp32 [B][H][W]), 6: 3x3 with the
  * head's fp32 [B][H][Cout][W] output.  Activations fp16 [B][H][W][C]; w in torch's layout ([Cout][Cin][k][k]; kind 2: [Cin][Cout][3][3]);

@@ -125,11 +125,14 @@ SYMBOLS = [
     ("rvcmi_gru_create", C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(_P)]),
     ("rvcmi_gru_destroy", C.c_int, [_P]),
     ("rvcmi_gru_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    ("rvcmi_gru_forward_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("rvcmi_unet_create", C.c_int, [C.POINTER(Tensor), C.c_int, C.c_int, C.POINTER(_P)]),
     ("rvcmi_unet_destroy", C.c_int, [_P]),
     ("rvcmi_unet_head_channels", C.c_int, [_P]),
     ("rvcmi_unet_workspace_bytes", C.c_size_t, [_P, C.c_int, C.c_int]),
     ("rvcmi_unet_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    ("rvcmi_unet_workspace_bytes_ragged", C.c_size_t, [_P, C.c_int, _P]),
+    ("rvcmi_unet_forward_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("rvcmi_unet_debug_op", C.c_int, [C.c_int] * 7 + [_P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     ("rvcmi_mel_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.POINTER(_P)]),
     ("rvcmi_mel_destroy", C.c_int, [_P]),

@@ -77,9 +77,12 @@ __device__ __forceinline__ float lane_xor4(float v) {
 }
 
 // grid (2 directions, B sequences).  whh: fp16 pairs packed [dir][thread][8 rows][16 pairs]; gx [dir][B * T][GR]; bhn [dir][GH];
-// y [B][T][2 * GH] fp32; hn [2][B][GH] fp32 (final states, may be null)
+// y [B][T][2 * GH] fp32; hn [2][B][GH] fp32 (final states, may be null).  Ragged (seq_off != null): sequence b is rows [seq_off[b],
+// seq_off[b + 1]) of the M packed rows of gx [dir][M][GR] and y [M][2 * GH]; the block takes its own first row and length where the dense
+// form takes b * T and T, so the backward direction starts at the sequence's own last row.  (Block-uniform scalars: no register more.)
 static __global__ void __launch_bounds__(GNT) k_gru_seq(const half2v* __restrict__ whh, const float* __restrict__ gx, const float* __restrict__ bhn,
-                                                        float* __restrict__ y, float* __restrict__ hn, int B, int T) {
+                                                        float* __restrict__ y, float* __restrict__ hn, int B, int T, const int* __restrict__ seq_off,
+                                                        int M) {
     __shared__ __attribute__((aligned(16))) _Float16 hbuf[2][GH];
     __shared__ float gh[GR];
     const int dir = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, ks = tid & 7;
@@ -93,7 +96,12 @@ static __global__ void __launch_bounds__(GNT) k_gru_seq(const half2v* __restrict
     }
     if (tid < GH) hbuf[0][tid] = (_Float16)0.f;
     const bool gate = tid < GH;  // threads 0..255 also own hidden unit `tid`
-    const float* gxb = gx + ((size_t)dir * B + b) * (size_t)T * GR;
+    int row0 = b * T;
+    if (seq_off) {
+        row0 = seq_off[b];
+        T = seq_off[b + 1] - row0;
+    }
+    const float* gxb = gx + ((size_t)dir * M + row0) * GR;
     const float bn = gate ? bhn[dir * GH + tid] : 0.f;
     float hprev = 0.f;
     float g[GPD][3];
@@ -163,7 +171,7 @@ static __global__ void __launch_bounds__(GNT) k_gru_seq(const half2v* __restrict
                 hprev = (1.f - z) * n + z * hprev;
                 hbuf[cur ^ 1][tid] = (_Float16)hprev;
                 const int t = tstep(s);
-                y[((size_t)b * T + t) * (2 * GH) + dir * GH + tid] = hprev;
+                y[((size_t)row0 + t) * (2 * GH) + dir * GH + tid] = hprev;
                 const float* p = gxb + (size_t)tstep(min(s + GPD, T - 1)) * GR + tid;  // the request for step s + GPD (clamped)
                 g[u][0] = p[0];
                 g[u][1] = p[GH];
@@ -233,23 +241,48 @@ int rvcmi_gru_destroy(rvcmi_gru* h) {
     return guarded([&] { delete h; });
 }
 
+}  // extern "C"
+
+namespace {
+
+// x16 [M][I] fp16 -> y [M][2 * GH]: the projection of all M rows, then one recurrence block per (direction, sequence).  seq_off: device
+// offsets of a ragged batch (M = all packed rows), or null for B sequences of T rows.
+void gru_run(rvcmi_gru* h, int B, int T, size_t M, const int* seq_off, const void* x16, float* y, float* hn, void* stream) {
+    DeviceGuard dg(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (M > h->gx_rows) {  // (grows with the largest row count seen -- B * T, or all packed rows of a ragged batch; such a call must be outside any capture)
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (h->gx.p) h->retired.push_back(std::move(h->gx));  // not freed: a graph captured at the smaller size replays into it
+        h->gx.alloc(M * 2 * GR * sizeof(float));
+        h->gx_rows = M;
+    }
+    hipLaunchKernelGGL(k_gru_xproj, dim3((unsigned)((M + 31) / 32), 2 * GR / 128), dim3(256), 0, st, (const _Float16*)x16, h->wih.as<_Float16>(),
+                       h->bias.as<float>(), h->gx.as<float>(), (int)M, h->input);
+    hipLaunchKernelGGL(k_gru_seq, dim3(2, B), dim3(GNT), 0, st, h->whh.as<half2v>(), h->gx.as<float>(), h->bhn.as<float>(), y, hn, B, T, seq_off, (int)M);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
 int rvcmi_gru_forward(rvcmi_gru* h, int B, int T, const void* x16, float* y, float* hn, void* stream) {
     return guarded([&] {
         if (!h || !x16 || !y) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward: null argument");
         if (B < 1 || T < 1 || (long long)B * T > (1ll << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward: B = %d, T = %d", B, T);
-        DeviceGuard dg(h->device);
-        hipStream_t st = (hipStream_t)stream;
-        const size_t M = (size_t)B * T;
-        if (M > h->gx_rows) {  // (grows with the longest call seen; f0 runs once per file, outside any capture)
-            HIP_CHECK(hipStreamSynchronize(st));
-            if (h->gx.p) h->retired.push_back(std::move(h->gx));  // not freed: a graph captured at the smaller size replays into it
-            h->gx.alloc(M * 2 * GR * sizeof(float));
-            h->gx_rows = M;
-        }
-        hipLaunchKernelGGL(k_gru_xproj, dim3((unsigned)((M + 31) / 32), 2 * GR / 128), dim3(256), 0, st, (const _Float16*)x16, h->wih.as<_Float16>(),
-                           h->bias.as<float>(), h->gx.as<float>(), (int)M, h->input);
-        hipLaunchKernelGGL(k_gru_seq, dim3(2, B), dim3(GNT), 0, st, h->whh.as<half2v>(), h->gx.as<float>(), h->bhn.as<float>(), y, hn, B, T);
-        HIP_CHECK(hipGetLastError());
+        gru_run(h, B, T, (size_t)B * T, nullptr, x16, y, hn, stream);
+    });
+}
+
+int rvcmi_gru_forward_ragged(rvcmi_gru* h, int nseq, const int* offsets_host, const int* offsets_dev, const void* x16, float* y, float* hn,
+                             void* stream) {
+    return guarded([&] {
+        if (!h || !offsets_host || !offsets_dev || !x16 || !y) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward_ragged: null argument");
+        if (nseq < 1 || nseq > 65535 || offsets_host[0] != 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward_ragged: %d sequences, first offset %d", nseq, offsets_host[0]);
+        for (int i = 0; i < nseq; ++i)
+            if (offsets_host[i + 1] <= offsets_host[i] || offsets_host[i + 1] > (1 << 30))
+                RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward_ragged: the offsets do not ascend at sequence %d (or pass 2^30 rows)", i);
+        gru_run(h, nseq, 0, (size_t)offsets_host[nseq], offsets_dev, x16, y, hn, stream);
     });
 }
 

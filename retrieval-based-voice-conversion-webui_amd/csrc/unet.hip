@@ -90,7 +90,16 @@ struct Ctx {
     int force_ksplit = 0;
     float* part = nullptr;
     size_t max_part = 0;
+    const int* seq_off = nullptr;  // ragged: device offsets of the packed sequences (unet_kernels.hpp), R = rows at level 0
+    int nseq = 0, R = 0;
 };
+
+// level of an image of H rows in a ragged forward of c.R rows
+int level_of(const Ctx& c, int H) {
+    int l = 0;
+    while ((c.R >> l) > H) ++l;
+    return l;
+}
 
 void check_grid(unsigned long long gx, unsigned long long gy, unsigned long long gz) {
     if (gx == 0 || gy == 0 || gz == 0 || gx > 2147483647ull || gy > 65535ull || gz > 65535ull)
@@ -126,6 +135,7 @@ void conv(Ctx& c, const Conv& L, const _Float16* x0, int C0, const _Float16* x1,
     a.out = out;
     a.part = c.part;
     a.B = B, a.H = H, a.W = W, a.C0 = C0, a.C1 = C1, a.Cout = L.Cout, a.mode = L.mode, a.relu = relu, a.ksplit = ksplit, a.out_kind = out_kind;
+    a.seq_off = c.seq_off, a.nseq = c.nseq, a.seq_shift = c.seq_off ? level_of(c, H) : 0;
     const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)(phases * ksplit));
     if (cfg == 0) hipLaunchKernelGGL((k_unet_conv<1, 1>), grid, dim3(256), 0, c.st, a);
     else if (cfg == 1) hipLaunchKernelGGL((k_unet_conv<2, 1>), grid, dim3(256), 0, c.st, a);
@@ -142,7 +152,7 @@ void first(Ctx& c, const Conv& L, int ntaps, const float* x, float in_scale, flo
     check_grid(gx, 1, 1);
     if (c.dry) return;
     hipLaunchKernelGGL(k_unet_first, dim3((unsigned)gx), dim3(256), 0, c.st, x, in_scale, in_shift, (const _Float16*)(c.wbase + L.w), ntaps,
-                       (const float*)(c.wbase + L.scale), (const float*)(c.wbase + L.shift), relu, out, B, H, W, L.Cout);
+                       (const float*)(c.wbase + L.scale), (const float*)(c.wbase + L.shift), relu, out, B, H, W, L.Cout, c.seq_off, c.nseq);
 }
 
 void pool(Ctx& c, const _Float16* x, _Float16* out, int B, int H, int W, int C) {
@@ -229,12 +239,27 @@ bool shape_ok(const rvcmi_unet* h, int B, int T) {
     return h && B >= 1 && T >= (1 << h->levels) && T % (1 << h->levels) == 0 && (long long)B * T <= (1ll << 22);
 }
 
-// Enqueues (or, dry, sizes and checks) one forward.  -> workspace bytes.
-size_t run(const rvcmi_unet* h, int B, int T, const float* mel, float* out, char* ws, hipStream_t st, bool dry) {
+// A ragged batch: nseq >= 1 sequences, off[0] == 0, every length off[i + 1] - off[i] a positive multiple of 2^levels, R = off[nseq] <= 2^22
+void check_ragged(const rvcmi_unet* h, int nseq, const int* off, const char* who) {
+    if (!h || !off || nseq < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: %d sequences", who, nseq);
+    const int step = 1 << h->levels;
+    if (off[0] != 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: the first offset is %d, not 0", who, off[0]);
+    for (int i = 0; i < nseq; ++i) {
+        const long long len = (long long)off[i + 1] - off[i];
+        if (len < step || len % step)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: sequence %d has %lld rows (offsets must ascend by multiples of %d)", who, i, len, step);
+        if (off[i + 1] > (1 << 22)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: more than 2^22 rows", who);
+    }
+}
+
+// Enqueues (or, dry, sizes and checks) one forward.  -> workspace bytes.  seq_off_dev / nseq: a ragged forward (B = 1, T = all packed rows).
+size_t run(const rvcmi_unet* h, int B, int T, const float* mel, float* out, char* ws, hipStream_t st, bool dry, const int* seq_off_dev = nullptr,
+           int nseq = 0) {
     Ctx c;
     c.wbase = h->arena.as<char>();
     c.st = st;
     c.dry = dry;
+    c.seq_off = seq_off_dev, c.nseq = nseq, c.R = T;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         const size_t o = off;
@@ -404,6 +429,27 @@ int rvcmi_unet_forward(rvcmi_unet* h, int B, int T, const float* mel_dev, float*
         run(h, B, T, nullptr, nullptr, nullptr, nullptr, true);  // every grid checked before the first launch
         DeviceGuard dg(h->device);
         run(h, B, T, mel_dev, out_dev, (char*)ws_dev, (hipStream_t)stream, false);
+    });
+}
+
+size_t rvcmi_unet_workspace_bytes_ragged(rvcmi_unet* h, int nseq, const int* offsets_host) {
+    size_t n = 0;
+    const int rc = guarded([&] {
+        check_ragged(h, nseq, offsets_host, "unet_workspace_bytes_ragged");
+        n = run(h, 1, offsets_host[nseq], nullptr, nullptr, nullptr, nullptr, true);  // (sizes and grids depend on the row count only)
+    });
+    return rc == RVCMI_OK ? n : 0;
+}
+
+int rvcmi_unet_forward_ragged(rvcmi_unet* h, int nseq, const int* offsets_host, const int* offsets_dev, const float* mel_dev, float* out_dev,
+                              void* ws_dev, void* stream) {
+    return guarded([&] {
+        if (!h || !offsets_host || !offsets_dev || !mel_dev || !out_dev || !ws_dev) RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_forward_ragged: null argument");
+        check_ragged(h, nseq, offsets_host, "unet_forward_ragged");
+        const int R = offsets_host[nseq];
+        run(h, 1, R, nullptr, nullptr, nullptr, nullptr, true);  // every grid checked before the first launch
+        DeviceGuard dg(h->device);
+        run(h, 1, R, mel_dev, out_dev, (char*)ws_dev, (hipStream_t)stream, false, offsets_dev, nseq);
     });
 }
 

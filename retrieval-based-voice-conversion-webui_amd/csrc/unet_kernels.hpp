@@ -13,6 +13,12 @@
 //   k_unet_first   the layers with one input channel (K = 9 or 1, no MFMA): the input BatchNorm is applied while the input is staged, so the
 //                  zero padding stays zero.
 //   k_unet_pool    AvgPool2d(2, 2).
+//
+// Ragged batches (rvcmi_unet_forward_ragged): B sequences packed along the frame axis, sequence i in rows [off[i], off[i + 1]) of ONE image of
+// R = off[B] rows, every length a multiple of 2^levels -- so at level l the boundaries are off[i] >> l, and the pool and the transposed
+// convolution, which pair rows 2 y and 2 y + 1, never straddle one.  The only thing that differs from a dense batch is where the frame axis
+// ends for a 3x3 tap: a pixel looks up the sequence that owns its row ONCE (seq_rows, a binary search of the offsets) and carries that
+// sequence's first row and row count where the dense form carries b * H and H.  K loop, operand loads and epilogues are the same code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,7 +42,23 @@ struct ConvArgs {
     void* out;             // OUT_NHWC16: fp16 [B][Ho][Wo][Cout];  OUT_HEAD32: fp32 [B][H][Cout][W]
     float* part;           // ksplit > 1: [ksplit][output pixels][Cout] fp32
     int B, H, W, C0, C1, Cout, mode, relu, ksplit, out_kind;
+    const int* seq_off;    // ragged: [nseq + 1] ascending level-0 row offsets (B = 1, H = seq_off[nseq] >> seq_shift); null: a dense batch
+    int nseq, seq_shift;   // seq_shift: the level of this layer's INPUT rows
 };
+
+// The sequence that owns row `r` of a packed image at level `shift`: -> its first row, `rows` = its row count.  off[0] == 0 and
+// r < off[nseq] >> shift, so the search ends inside the array.
+__device__ __forceinline__ int seq_rows(const int* __restrict__ off, int nseq, int shift, int r, int& rows) {
+    int lo = 0, hi = nseq;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((off[mid] >> shift) <= r) lo = mid;
+        else hi = mid;
+    }
+    const int first = off[lo] >> shift;
+    rows = (off[lo + 1] >> shift) - first;
+    return first;
+}
 
 // taps of a phase of the transposed convolution (kernel 3, stride 2, padding 1, output_padding 1): out[2y + p] takes in[y] * w[1] for p = 0 and
 // in[y + 1] * w[0] + in[y] * w[2] for p = 1
@@ -67,7 +89,9 @@ __global__ void __launch_bounds__(256) k_unet_conv(const ConvArgs a) {
     const int niter = ntaps * nch;
     const int it0 = (int)((long long)ks * niter / a.ksplit), it1 = (int)((long long)(ks + 1) * niter / a.ksplit);
 
-    int py[2], px[2], pb[2];
+    // a pixel: column px, row py of an image of ph rows whose first row is row pr of the whole tensor (dense: image = batch item, ph = H;
+    // ragged: image = the sequence that owns the row)
+    int py[2], px[2], pr[2], ph[2];
     bool pv[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -76,8 +100,14 @@ __global__ void __launch_bounds__(256) k_unet_conv(const ConvArgs a) {
         const int mm = pv[i] ? m : 0;
         px[i] = mm % a.W;
         const int r = mm / a.W;
-        py[i] = r % a.H;
-        pb[i] = r / a.H;
+        if (a.seq_off) {
+            pr[i] = seq_rows(a.seq_off, a.nseq, a.seq_shift, r, ph[i]);
+            py[i] = r - pr[i];
+        } else {
+            py[i] = r % a.H;
+            pr[i] = r - py[i];
+            ph[i] = a.H;
+        }
     }
     const _Float16* wrow[CT];
     bool wv[CT];
@@ -116,8 +146,8 @@ __global__ void __launch_bounds__(256) k_unet_conv(const ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int yy = py[i] + dy, xx = px[i] + dx;
-            const bool ok = pv[i] && cv && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-            xf[i] = ok ? *(const half8*)(src + ((size_t)(pb[i] * a.H + yy) * a.W + xx) * cs + cc) : zero;
+            const bool ok = pv[i] && cv && yy >= 0 && yy < ph[i] && xx >= 0 && xx < a.W;
+            xf[i] = ok ? *(const half8*)(src + ((size_t)(pr[i] + yy) * a.W + xx) * cs + cc) : zero;
         }
 #pragma unroll
         for (int j = 0; j < CT; ++j) wf[j] = (wv[j] && cv) ? *(const half8*)(wrow[j] + (size_t)tap * Cin + c) : zero;
@@ -129,13 +159,13 @@ __global__ void __launch_bounds__(256) k_unet_conv(const ConvArgs a) {
 
     // lane: pixel l16 of the subtile, output channels 4 g .. 4 g + 3 of the channel subtile
     const bool up = a.mode == MODE_UP;
-    const int Ho = up ? 2 * a.H : a.H, Wo = up ? 2 * a.W : a.W;
+    const int Ho = up ? 2 * a.H : a.H, Wo = up ? 2 * a.W : a.W;  // (Ho: of the whole tensor, for the partials' slice stride)
     const size_t Mo = (size_t)a.B * Ho * Wo;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         if (!pv[i]) continue;
         const int oy = up ? 2 * py[i] + ph_y : py[i], ox = up ? 2 * px[i] + ph_x : px[i];
-        const size_t opix = ((size_t)pb[i] * Ho + oy) * Wo + ox;
+        const size_t opix = ((size_t)(up ? 2 * pr[i] : pr[i]) + oy) * Wo + ox;
 #pragma unroll
         for (int j = 0; j < CT; ++j) {
             const int co = co0 + j * 16 + g * 4;
@@ -156,7 +186,7 @@ __global__ void __launch_bounds__(256) k_unet_conv(const ConvArgs a) {
                 float* out = (float*)a.out;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (co + r < a.Cout) out[(((size_t)pb[i] * a.H + py[i]) * a.Cout + co + r) * a.W + px[i]] = o[r];
+                    if (co + r < a.Cout) out[((size_t)(pr[i] + py[i]) * a.Cout + co + r) * a.W + px[i]] = o[r];
             } else {
                 if (a.res) {
                     const half4 rr = *(const half4*)(a.res + opix * a.Cout + co);
@@ -203,25 +233,33 @@ __global__ void __launch_bounds__(256) k_unet_reduce(const float* __restrict__ p
 }
 
 // One input channel: x fp32 [B][H][W]; staged value = fp16(x * in_scale + in_shift) inside the image, 0 outside.  w [Cout][ntaps] fp16
-// (ntaps 9: 3x3 with padding 1, 1: the 1x1 shortcut).  A thread: one pixel, 8 output channels.
+// (ntaps 9: 3x3 with padding 1, 1: the 1x1 shortcut).  A thread: one pixel, 8 output channels.  seq_off: as in ConvArgs, at level 0.
 __global__ void __launch_bounds__(256) k_unet_first(const float* __restrict__ x, float in_scale, float in_shift, const _Float16* __restrict__ w,
                                                            int ntaps, const float* __restrict__ scale, const float* __restrict__ shift, int relu,
-                                                           _Float16* __restrict__ out, int B, int H, int W, int Cout) {
+                                                           _Float16* __restrict__ out, int B, int H, int W, int Cout,
+                                                           const int* __restrict__ seq_off, int nseq) {
     const int groups = Cout >> 3;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t M = (size_t)B * H * W;
     if (i >= M * groups) return;
     const int cg = (int)(i % groups);
     const size_t m = i / groups;
-    const int xx = (int)(m % W), yy = (int)((m / W) % H);
-    const size_t b = m / ((size_t)W * H);
+    const int xx = (int)(m % W);
+    const size_t row = m / W;
+    int yy = (int)(row % H), rows = H;
+    size_t first = row - yy;  // first row of the image this pixel belongs to
+    if (seq_off && ntaps == 9) {
+        const int f = seq_rows(seq_off, nseq, 0, (int)row, rows);
+        first = f;
+        yy = (int)row - f;
+    }
     float in[9];
     if (ntaps == 9) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-            const bool ok = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
-            in[t] = ok ? (float)(_Float16)fmaf(x[(b * H + y2) * W + x2], in_scale, in_shift) : 0.f;
+            const bool ok = y2 >= 0 && y2 < rows && x2 >= 0 && x2 < W;
+            in[t] = ok ? (float)(_Float16)fmaf(x[(first + y2) * W + x2], in_scale, in_shift) : 0.f;
         }
     } else {
         in[0] = (float)(_Float16)fmaf(x[m], in_scale, in_shift);

@@ -360,15 +360,9 @@ def _device_prep(self, audios, dev):
 RMVPE_THRED = 0.03  # rvc/f0/gen.py:113: Generator.calculate hard-codes compute_f0(..., filter_radius=0.03) for rmvpe
 
 
-def _rmvpe_on_device(self, audio_pad, p_len, f0_up_key):
-    """RMVPE salience on PyTorch-ROCm (the reference's own mel extractor + network), decoded by ``rvcmi_glue_rmvpe_f0``
-    (rvc/f0/rmvpe.py:119-164, f0.py:31-78, gen.py:10-41) without visiting the host.  None when this f0_gen has no torch RMVPE.
-
-    The caller's ``filter_radius`` is NOT the voicing threshold: it is harvest's median radius (the UI slider 0..7, web.py:794)
-    that ``vc_single`` forwards to every estimator; ``Generator.calculate`` ignores it for rmvpe and passes the constant 0.03
-    (rvc/f0/gen.py:113), and so does this function."""
-    from . import glue
-
+def _torch_rmvpe(self):
+    """This f0_gen's torch RMVPE object (loaded on first use, as ``Generator`` does), or None when there is none the device path can read:
+    no checkpoint, an onnx-only build, the onnx session of a ``privateuseone`` device."""
     gen = self.f0_gen
     if not hasattr(gen, "rmvpe"):
         try:
@@ -379,6 +373,22 @@ def _rmvpe_on_device(self, audio_pad, p_len, f0_up_key):
             return None
     r = gen.rmvpe
     if not (hasattr(r, "mel_extractor") and hasattr(r, "_mel2hidden")) or "privateuseone" in str(getattr(r, "device", "")):
+        return None
+    return r
+
+
+def _rmvpe_on_device(self, audio_pad, p_len, f0_up_key):
+    """RMVPE salience on PyTorch-ROCm (the reference's own mel extractor + network), decoded by ``rvcmi_glue_rmvpe_f0``
+    (rvc/f0/rmvpe.py:119-164, f0.py:31-78, gen.py:10-41) without visiting the host.  None when this f0_gen has no torch RMVPE.
+
+    The caller's ``filter_radius`` is NOT the voicing threshold: it is harvest's median radius (the UI slider 0..7, web.py:794)
+    that ``vc_single`` forwards to every estimator; ``Generator.calculate`` ignores it for rmvpe and passes the constant 0.03
+    (rvc/f0/gen.py:113), and so does this function."""
+    from . import glue
+
+    gen = self.f0_gen
+    r = _torch_rmvpe(self)
+    if r is None:
         return None
     # opt-in (RVCMI_RMVPE_HIP=1 / install(rmvpe_hip=True), default off): the whole estimator on this project's kernels (rmvpe.py) -- mel front end
     # and head included, no torch op but one cast between the waveform and (pitch, pitchf) -- and a key that may be fractional.  A model the
@@ -400,6 +410,19 @@ def _rmvpe_on_device(self, audio_pad, p_len, f0_up_key):
         mel = r.mel_extractor(wav.float().to(r.device).unsqueeze(0), center=True)
         hidden = r._mel2hidden(mel)
     return glue.rmvpe_f0(hidden.squeeze(0).float(), p_len, f0_up_key if on else int(f0_up_key), RMVPE_THRED)
+
+
+def _rmvpe_batch_f0(self, pads, p_lens, f0_up_key):
+    """The f0 of SEVERAL padded inputs in ONE ``RMVPEHIP.f0_batch`` call (a ragged batch: every file comes out as its own ``hip.f0`` call
+    gives it, to operand rounding).  None -- nothing computed -- when this f0_gen's RMVPE is not one the kernels serve: the caller keeps the
+    per-file calls.  (Whether a group takes this path at all is ``convert_files``' decision.)"""
+    from . import rmvpe as _rm
+
+    r = _torch_rmvpe(self)
+    hip = _rm.for_generator(self.f0_gen, r) if r is not None else None
+    if hip is None:
+        return None
+    return hip.f0_batch([torch.as_tensor(a).float().to(hip.device) for a in pads], list(p_lens), f0_up_key, RMVPE_THRED)
 
 
 INDEX_CACHE_ENTRIES = 2  # index files kept resident (a WebUI session alternates between very few voices)
@@ -448,12 +471,24 @@ def _open_index(self, file_index, index_rate):
         return None, False
 
 
-def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect, prepped=None):
+def _host_prep(self, audio):
+    """pipeline.py:221,241 on the host: -> (the high-passed signal, its ``t_pad`` reflection pad)."""
+    import numpy as np
+
+    ref = _ref_module(self)
+    audio = ref.signal.filtfilt(ref.bh, ref.ah, audio)
+    return audio, np.pad(audio, (self.t_pad, self.t_pad), mode="reflect")
+
+
+def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0_file, collect, prepped=None,
+                  host_prepped=None, f0_pair=None):
     """``Pipeline.pipeline`` from its input to the point where a segment would enter ``vc`` (pipeline.py:219-300): high-pass,
     cut points, reflection pad, f0 (RMVPE decoded on the device), then ``collect(audio_segment, pitch_slice, pitchf_slice)`` for
     every segment in order.  -> (the filtered 16 kHz input (``change_rms`` needs it), the number of cuts, its float64 device copy
     when the cut search uploaded one, else None).  ``prepped``: this input's ``_device_prep`` result when the caller prepared a whole
-    group in one call; with the device preparation the segments are device slices and the first return value is None."""
+    group in one call; with the device preparation the segments are device slices and the first return value is None.  ``host_prepped``:
+    this input's ``_host_prep`` result and ``f0_pair``: its precomputed (pitch, pitchf) when the caller estimated a whole group's f0 in one
+    call (``convert_files``); the RMVPE step is then skipped."""
     import traceback
     from time import time
 
@@ -467,6 +502,10 @@ def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, f
         audio_dev, audio_pad = prepped  # float64 device tensors: the filtered signal and np.pad(.., t_pad, "reflect") of it
         opt_ts, a64 = _file_cuts(self, audio_dev, dev)
         audio, a64 = None, audio_dev
+        t1 = time()
+    elif host_prepped is not None:
+        audio, audio_pad = host_prepped
+        opt_ts, a64 = _file_cuts(self, audio, dev)
         t1 = time()
     else:
         audio = ref.signal.filtfilt(ref.bh, ref.ah, audio)
@@ -485,8 +524,8 @@ def _prepare_file(self, model, sid, audio, times, f0_up_key, f0_method, if_f0, f
             traceback.print_exc()
     pitch = pitchf = None
     if if_f0:
-        got = None
-        if if_f0 == 1 and f0_method == "rmvpe" and inp_f0 is None:
+        got = f0_pair
+        if got is None and if_f0 == 1 and f0_method == "rmvpe" and inp_f0 is None:
             got = _rmvpe_on_device(self, audio_pad, p_len, f0_up_key)
         if got is not None:
             pitch, pitchf = got[0][:, :p_len].long(), got[1][:, :p_len].float()
@@ -575,7 +614,10 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     ``load_audio`` + ``vc_single`` -> ``pipeline`` per file of a folder) with the files batched on the GPU:
 
       1. per file, as ``pipeline`` does it: high-pass (with ``RVCMI_DEVICE_PREP=1``: all files in one device call), cut points (a long
-         file's on the device, its own call), f0 (RMVPE on the device), HuBERT per segment;
+         file's on the device, its own call), f0 (RMVPE on the device), HuBERT per segment.  With the HIP estimator switched on
+         (``RVCMI_RMVPE_HIP=1``, off by default), its group switch on (``RVCMI_RMVPE_BATCH=1``; ``rmvpe.RMVPE_BATCH``, off until measured)
+         and at least ``rmvpe.RMVPE_BATCH_MIN_FILES`` files without an ``f0_file``, the f0 of those files is ONE ``RMVPEHIP.f0_batch``
+         call on the ragged batch of their padded signals, made before the per-file loop;
       2. ONE retrieval call for the HuBERT frames of every segment of every file (``blend_segments``: one coarse pass and one
          list-major scan per ``MAX_BATCH_QUERIES`` frames instead of one per segment);
       3. the segments of all files through ``net_g.infer`` as ragged batches (``infer_segments``, at most ``MAX_BATCH_FRAMES`` padded
@@ -590,7 +632,10 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     generator ``RB_STREAM`` / ``NO_RB_SPLIT``, front ``FR_NJ`` / ``FR_FFN_SPLIT`` -- and equal to operand rounding otherwise), so the result does not depend on how the files are grouped.
     One exception, with the device preparation switched on (``RVCMI_DEVICE_PREP=1``, off by default): ``DEVICE_PREP_MIN_SAMPLES`` is judged on the
     audio of the whole call, so a 10 s file is high-passed on the device inside a group and on the host through ``pipeline`` alone; the two
-    filters agree to fp64 rounding noise only, which moves about half of the fp32 input samples by one ulp (bit-equal again with the threshold at 0).  A synthesizer that is not the HIP one, or an
+    filters agree to fp64 rounding noise only, which moves about half of the fp32 input samples by one ulp (bit-equal again with the threshold at 0).
+    A second one, with the HIP estimator switched on: a file's f0 inside a group equals that of its lone call to operand rounding, not bit for
+    bit -- no sequence reads another's frames, but the U-Net layers that split their K loop choose the split from the launch size, which is
+    the group's (bit-equal with the group switch off).  A synthesizer that is not the HIP one, or an
     index only real faiss reads, or ``RVCMI_PIPELINE_BATCH=0``, takes the plain per-file loop over ``self.pipeline``."""
     audios = list(audios)
     f0_files = list(f0_files) if f0_files is not None else [None] * len(audios)
@@ -617,6 +662,23 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     sid = torch.tensor(sid, device=dev).unsqueeze(0).long()
     raw, owner, filtered = [], [], []
     prepped = _device_prep(self, audios, dev)  # RVCMI_DEVICE_PREP: every file of the group filtered in ONE call (else all None)
+    # RVCMI_RMVPE_HIP + RVCMI_RMVPE_BATCH (opt-in): the f0 of every file without an f0_file in ONE ragged RMVPEHIP.f0_batch call instead of one call per file.  It
+    # needs each file's padded signal first, so the host preparation of those files moves in front of the loop (same calls, same order).
+    host_prepped, f0_pairs = [None] * len(audios), [None] * len(audios)
+    if if_f0 == 1 and f0_method == "rmvpe":
+        from . import rmvpe as _rm
+
+        todo = [i for i, f in enumerate(f0_files) if not hasattr(f, "name")]
+        if _rm.rmvpe_batch_on() and len(todo) >= _rm.RMVPE_BATCH_MIN_FILES:
+            for i in todo:
+                if prepped[i] is None:
+                    host_prepped[i] = _host_prep(self, audios[i])
+            pads = [prepped[i][1] if prepped[i] is not None else host_prepped[i][1] for i in todo]
+            t1 = time()
+            pairs = _rmvpe_batch_f0(self, pads, [p.shape[0] // self.window for p in pads], f0_up_key)
+            times[1] += time() - t1
+            for i, pair in zip(todo, pairs or ()):
+                f0_pairs[i] = pair
     for i, (a, f0f) in enumerate(zip(audios, f0_files)):
         def collect(a0, pt, pf, i=i):
             t0 = time()
@@ -624,7 +686,8 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
             owner.append(i)
             times[0] += time() - t0
 
-        got = _prepare_file(self, model, sid, a, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0f, collect, prepped[i])
+        got = _prepare_file(self, model, sid, a, times, f0_up_key, f0_method, if_f0, filter_radius, version, f0f, collect, prepped[i],
+                            host_prepped[i], f0_pairs[i])
         # (of the device copy only what change_rms reads is kept while the group's other files are prepared)
         filtered.append((got[0], got[2].float() if got[2] is not None and rms_mix_rate != 1 else None))
     t0 = time()

@@ -4,6 +4,7 @@ around ``UNetHIP`` and ``GRUHIP``, decoded by ``glue.rmvpe_f0``.
 
     hip = rvc_amd.RMVPEHIP.from_reference(rmvpe)     # an rvc.f0.rmvpe.RMVPE-like object; None when it is not one the kernels serve
     pitch, pitchf = hip.f0(wav16k, p_len, f0_up_key) # what Generator.calculate(..., "rmvpe") + post_process return, on the device
+    pairs = hip.f0_batch(wavs, p_lens, f0_up_key)    # the same for waveforms of ANY lengths in one pass (a ragged batch): one (pitch, pitchf) each
 
 Between the input cast ``wav.float()`` and the result torch allocates buffers and makes the one fp32 -> fp16 cast in front of the GRU;
 everything else is enqueue-only HIP, so the chain captures into a hipGraph once its first call of a size has happened eagerly.
@@ -16,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -37,8 +38,35 @@ def rmvpe_on() -> bool:
     return env == "1" if env in ("0", "1") else bool(RMVPE_HIP)
 
 
+RMVPE_BATCH = False        # the group path of pipeline.convert_files (ONE f0_batch call per group); RVCMI_RMVPE_BATCH=1 / =0 overrides it per call.
+                           # Off until tools/rmvpe_batch_time.py has been run: profiles/rmvpe_batch_time.json decides the default and the threshold
+RMVPE_BATCH_MIN_FILES = 2  # ... and with it on, a group takes that path from this many files to estimate
+
+
+def rmvpe_batch_on() -> bool:
+    env = os.environ.get("RVCMI_RMVPE_BATCH")
+    return rmvpe_on() and (env == "1" if env in ("0", "1") else bool(RMVPE_BATCH))
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def ragged_layout(frames: Sequence[int]) -> Tuple[List[int], int]:
+    """Frame counts ``T_i`` of a ragged batch -> (row offsets, R): every sequence padded to ``Tp_i = 32 * ceil(T_i / 32)`` as the reference pads a
+    single one (rvc/f0/rmvpe.py:141-144) and PACKED along the frame axis -- sequence i owns rows ``[offsets[i], offsets[i] + Tp_i)``,
+    ``R = offsets[-1] = sum(Tp_i)``; no row is spent on padding to the longest."""
+    frames = [int(t) for t in frames]
+    if not frames:
+        raise _lib.RvcmiError("RMVPEHIP: an empty batch", code=_lib.ERR_INVALID)
+    off = [0]
+    for t in frames:
+        if t < 1:
+            raise _lib.RvcmiError("RMVPEHIP: a sequence of %d frames" % t, code=_lib.ERR_INVALID)
+        off.append(off[-1] + 32 * ((t - 1) // 32 + 1))
+    if off[-1] > 1 << 22:
+        raise _lib.RvcmiError("RMVPEHIP: %d packed frames in one batch (at most 2^22)" % off[-1], code=_lib.ERR_INVALID)
+    return off, off[-1]
 
 
 def _network_parts(model):
@@ -205,6 +233,73 @@ class RMVPEHIP:
         x = self._wav(wav)
         sal, T = self._salience(x)
         return sal[0, :T].clone() if x.shape[0] == 1 else sal[:, :T].clone()
+
+    def _wavs(self, wavs) -> List[torch.Tensor]:
+        """The members of a ragged batch, each checked as ``_wav`` checks a lone input and BEFORE anything is enqueued."""
+        if isinstance(wavs, torch.Tensor) or not isinstance(wavs, (list, tuple)):
+            raise _lib.RvcmiError("RMVPEHIP: a batch is a list of 1-D waveforms (got %s)" % type(wavs).__name__, code=_lib.ERR_INVALID)
+        if len(wavs) == 0:
+            raise _lib.RvcmiError("RMVPEHIP: an empty batch", code=_lib.ERR_INVALID)
+        xs = []
+        for w in wavs:
+            if torch.is_tensor(w) and w.dim() != 1:
+                raise _lib.RvcmiError("RMVPEHIP: a batch member must be a 1-D waveform, got %s" % (tuple(w.shape),), code=_lib.ERR_INVALID)
+            x = self._wav(w)
+            if x.shape[1] <= self.n_fft // 2:
+                raise _lib.RvcmiError("RMVPEHIP: a %d-sample input is not longer than the reflection pad %d" % (x.shape[1], self.n_fft // 2), code=_lib.ERR_INVALID)
+            xs.append(x)
+        return xs
+
+    def _salience_ragged(self, xs: List[torch.Tensor], mark=None) -> Tuple[torch.Tensor, List[int], List[int]]:
+        """-> (packed salience [R, 360] fp32, row offsets, frame counts).  Mel per sequence into its own rows (its own reflection pad, its own
+        zero pad frames), then ONE ragged U-Net, ONE ragged GRU and ONE head launch over the R packed rows.  ``mark(stage)``: called after each
+        stage has been enqueued (tools/rmvpe_batch_time.py puts a synchronising clock there)."""
+        mark = mark or (lambda stage: None)
+        L = _lib.lib()
+        frames = [self.frames(int(x.shape[1])) for x in xs]
+        off, R = ragged_layout(frames)
+        nseq = len(xs)
+        off_host = (C.c_int * (nseq + 1))(*off)
+        with torch.cuda.device(self.device):
+            nbytes = L.rvcmi_unet_workspace_bytes_ragged(self.unet._h, nseq, off_host)
+            if not nbytes:
+                msg = L.rvcmi_last_error()
+                raise _lib.RvcmiError("RMVPEHIP: a batch of %d sequences, %d frames not served (%s)" % (nseq, R, msg.decode(errors="replace") if msg else "?"),
+                                      code=_lib.ERR_INVALID)
+            dev, f32 = self.device, torch.float32
+            off_dev = torch.tensor(off, dtype=torch.int32, device=dev)
+            mel = torch.empty(R, N_MELS, device=dev, dtype=f32)
+            feat = torch.empty(R, 3 * N_MELS, device=dev, dtype=f32)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            y = torch.empty(R, 2 * self.gru.hidden_size, device=dev, dtype=f32)
+            sal = torch.empty(R, N_CLASS, device=dev, dtype=f32)
+            st, half = self._stream(), 1 if self.is_half else 0
+            for i, x in enumerate(xs):
+                _lib.check(L.rvcmi_mel_forward(self._h, 1, int(x.shape[1]), _ptr(x), half, off[i + 1] - off[i],
+                                               C.c_void_p(mel.data_ptr() + 4 * N_MELS * off[i]), st))
+            mark("mel")
+            _lib.check(L.rvcmi_unet_forward_ragged(self.unet._h, nseq, off_host, _ptr(off_dev), _ptr(mel), _ptr(feat), _ptr(ws), st))
+            mark("unet")
+            x16 = feat.half()  # the fp32 -> fp16 cast GRUHIP.forward makes
+            _lib.check(L.rvcmi_gru_forward_ragged(self.gru._h, nseq, off_host, _ptr(off_dev), _ptr(x16), _ptr(y), None, st))
+            mark("gru")
+            _lib.check(L.rvcmi_rmvpe_head(_ptr(y), R, _ptr(self._w), _ptr(self._b), half, _ptr(sal), st))
+            mark("head")
+        return sal, off, frames
+
+    def salience_batch(self, wavs) -> List[torch.Tensor]:
+        """A list of 1-D waveforms of ANY lengths -> their saliences ``[T_i, 360]`` fp32 from ONE pass over the packed batch; each is what
+        ``salience`` of that waveform alone returns, to the summation order of the U-Net layers that split their K loop by launch size."""
+        sal, off, frames = self._salience_ragged(self._wavs(wavs))
+        return [sal[o: o + t].clone() for o, t in zip(off, frames)]
+
+    def f0_batch(self, wavs, p_lens, f0_up_key=0, thred: float = 0.03) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """-> per waveform (pitch int64 [1, p_len_i], pitchf float32 [1, p_len_i]): ``glue.rmvpe_f0`` of its rows of ``salience_batch``."""
+        xs = self._wavs(wavs)
+        if not isinstance(p_lens, (list, tuple)) or len(p_lens) != len(xs) or any(int(p) < 1 for p in p_lens):
+            raise _lib.RvcmiError("RMVPEHIP.f0_batch: one positive p_len per waveform", code=_lib.ERR_INVALID)
+        sal, off, frames = self._salience_ragged(xs)
+        return [glue.rmvpe_f0(sal[o: o + t], int(p), f0_up_key, thred) for o, t, p in zip(off, frames, p_lens)]
 
     def f0(self, wav: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.03) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (pitch int64 [1, p_len], pitchf float32 [1, p_len]) as ``glue.rmvpe_f0`` returns them; ``f0_up_key`` may be fractional."""
