@@ -230,7 +230,7 @@ int rvcmi_ivf_create_from_file(const char* path, int device, rvcmi_ivf** out);
  *   k-means for the nlist centroids (niter Lloyd iterations from nlist seeded training vectors; every assignment
  *   is the exact fp64 nearest centroid, computed by the search path's own coarse kernels; empty lists are re-seeded
  *   by splitting the largest one), then every vector goes to the list of its nearest centroid, ids = row numbers
- *   in add order.  x_host [n,d] fp32 HOST (what np.load gives).  nprobe = 1 (web.py:552).  objective_out
+ *   in add order (rvcmi_ivf_train's centroids followed by the device-side placement of rvcmi_ivf_add).  x_host [n,d] fp32 HOST (what np.load gives).  nprobe = 1 (web.py:552).  objective_out
  *   (optional, niter+1 doubles) receives the sum of squared distances at every assignment step.
  *   faiss' own k-means (its RNG, sub-sampling and split heuristics) is not reproduced: retrieval semantics do not
  *   depend on how the centroids were found, and the reference pins nothing here.                      */
@@ -243,6 +243,24 @@ int rvcmi_ivf_build(int d, int64_t n, const float* x_host, int64_t nlist, int ni
  * [k,d] fp32 HOST, objective_out optional (niter doubles).                                                              */
 int rvcmi_kmeans(int d, int64_t n, const float* x_host, int64_t k, int niter, uint64_t seed, int device, double* objective_out,
                  float* centroids_out_host);
+/* index.train(big_npy) alone  (web.py:553-554; tools/cmd/train-index-v2.py:56-57): the k-means of rvcmi_kmeans, returned as a
+ * trained, EMPTY index (ntotal 0, nprobe 1) -- what the reference writes as trained_IVF*.index (web.py:556-559) before it adds.
+ * x_host [n,d] fp32 HOST, n >= nlist; objective_out optional (niter doubles, as rvcmi_kmeans).                              */
+int rvcmi_ivf_train(int d, int64_t n, const float* x_host, int64_t nlist, int niter, uint64_t seed, int device,
+                    double* objective_out, rvcmi_ivf** out);
+/* index.add(x)  (web.py:561-563: `for i in range(0, N, 8192): index.add(big_npy[i : i + 8192])`): appends n rows [n,d] fp32 with
+ * ids ntotal .. ntotal + n - 1 (faiss' sequential add; add_with_ids is not offered).  x is a DEVICE pointer on the index's device
+ * when x_on_device != 0, else a host pointer (copied up once).  Every row goes to the list of its exact nearest centroid -- the
+ * assignment of rvcmi_ivf_search's coarse step and of rvcmi_ivf_build, ties to the lowest list -- behind the list's old rows, new
+ * rows in ascending id order: the result is a function of (old index, x) alone, and adding in batches equals adding at once.
+ * Assignment, counting, the new list offsets, the move of the old rows and the placement of the new ones all run on the device.
+ * The index moves to a NEW blob of the size for ntotal + n rows: the pointer rvcmi_ivf_blob reports CHANGES; the old blob is freed
+ * if the handle owned it, a blob adopted by rvcmi_ivf_create_from_blob without ownership is left untouched (the handle owns the
+ * new one).  Peak device memory: old blob + new blob + x (+ the assignment scratch).  The search workspace reserved so far is
+ * rebuilt for the new rows before the call returns.  A build-time call: it allocates and synchronises `stream` -- never call it
+ * under stream capture, nor concurrently with a search on the same handle.
+ * n == 0 is a no-op; an untrained / foreign handle, a null x with n > 0, a negative n or one that overflows: RVCMI_ERR_INVALID. */
+int rvcmi_ivf_add(rvcmi_ivf* h, int64_t n, const float* x, int x_on_device, void* stream);
 /* faiss.write_index(index, path)  (web.py:571) -- so indices round-trip with stock RVC.       */
 int rvcmi_ivf_write_file(const rvcmi_ivf* h, const char* path);
 

@@ -5,7 +5,7 @@ reference's own Python call surface.  See DESIGN.md / INTEGRATION.md.
 """
 from . import _lib
 from ._lib import RvcmiError, build
-from .ivf import IVFFlatHIP, kmeans, read_index, reduce_features, train_index, write_index
+from .ivf import IVFFlatHIP, extract_index_ivf, index_factory, kmeans, read_index, reduce_features, train_index, write_index
 from .front import FrontHIP, front_config_from_reference, infer_hip
 from .nsf import GeneratorHIP, NSFGeneratorHIP, config_from_reference
 from .pipeline import retrieve_blend
@@ -21,7 +21,7 @@ from .gate import TorchGateHIP
 from .realtime import PitchCache, RealtimeStream, RealtimeVC, SincResample, f0_extractor_frame, sinc_resample_kernel, stream_geometry
 
 __all__ = [
-    "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "GeneratorHIP", "NSFGeneratorHIP",
+    "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "index_factory", "extract_index_ivf", "GeneratorHIP", "NSFGeneratorHIP",
     "config_from_reference", "FrontHIP", "front_config_from_reference", "infer_hip", "retrieve_blend", "accelerate_synthesizer", "get_synthesizer", "load_synthesizer", "dist", "glue", "install", "uninstall", "RealtimeVC", "PitchCache", "f0_extractor_frame", "SincResample", "sinc_resample_kernel", "GRUHIP", "accelerate_rmvpe",
     "UNetHIP", "accelerate_rmvpe_unet", "restore_rmvpe_unet", "RMVPEHIP",
     "RealtimeStream", "stream_geometry", "TorchGateHIP", "cut_points", "cut_count", "filtfilt", "highpass16k",

@@ -827,6 +827,7 @@ __global__ void __launch_bounds__(256) k_blend(float* __restrict__ feats, const 
 
 }  // namespace rvcmi
 #include "ivf_lm_kernels.hpp"
+#include "ivf_add_kernels.hpp"
 namespace rvcmi {
 
 // ---- index build (web.py:544-563: index.train = k-means for the nlist centroids, index.add = nearest-centroid lists) ----
@@ -916,6 +917,25 @@ static void validate(int d, int64_t n, int64_t nlist, int nprobe) {
     if (nprobe < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "nprobe must be >= 1");
 }
 
+// the section offsets and the size of a blob of h.ntotal rows (h.d, h.nlist set): a function of the three sizes alone
+static void blob_layout(BlobHeader& h) {
+    const uint64_t n1 = (uint64_t)std::max<int64_t>(h.ntotal, 1), nlist = (uint64_t)h.nlist, d = (uint64_t)h.d;
+    uint64_t off = sizeof(BlobHeader);
+    h.off_centroids = off;
+    off = align_up(off + nlist * d * 4, 256);
+    h.off_list_offsets = off;
+    off = align_up(off + (nlist + 1) * 8, 256);
+    h.off_ids = off;
+    off = align_up(off + n1 * 8, 256);
+    h.off_vecs = off;
+    off = align_up(off + n1 * d * 4, 256);
+    h.off_centroids_t = off;
+    off = align_up(off + nlist * d * 4, 256);
+    h.off_cnorm = off;
+    off = align_up(off + nlist * 4, 256);
+    h.total_bytes = off;
+}
+
 static std::vector<char> build_blob(int d, int64_t n, int64_t nlist, int nprobe, const float* centroids,
                                     const int64_t* list_offsets, const int64_t* ids, const float* vecs) {
     validate(d, n, nlist, nprobe);
@@ -934,21 +954,8 @@ static std::vector<char> build_blob(int d, int64_t n, int64_t nlist, int nprobe,
     for (int64_t i = 0; i < n; ++i)
         if (ids[i] == n - 1) h.pos_last = i;
     if (h.pos_last < 0) h.pos_last = n > 0 ? n - 1 : 0;
-    uint64_t off = sizeof(BlobHeader);
-    h.off_centroids = off;
-    off = align_up(off + (uint64_t)nlist * d * 4, 256);
-    h.off_list_offsets = off;
-    off = align_up(off + (uint64_t)(nlist + 1) * 8, 256);
-    h.off_ids = off;
-    off = align_up(off + (uint64_t)std::max<int64_t>(n, 1) * 8, 256);
-    h.off_vecs = off;
-    off = align_up(off + (uint64_t)std::max<int64_t>(n, 1) * d * 4, 256);
-    h.off_centroids_t = off;
-    off = align_up(off + (uint64_t)nlist * d * 4, 256);
-    h.off_cnorm = off;
-    off = align_up(off + (uint64_t)nlist * 4, 256);
-    h.total_bytes = off;
-    std::vector<char> blob(off, 0);
+    blob_layout(h);
+    std::vector<char> blob(h.total_bytes, 0);
     memcpy(blob.data(), &h, sizeof(h));
     memcpy(blob.data() + h.off_centroids, centroids, (size_t)nlist * d * 4);
     memcpy(blob.data() + h.off_list_offsets, list_offsets, (size_t)(nlist + 1) * 8);
@@ -1405,6 +1412,94 @@ static bool search(rvcmi_ivf* h, int64_t nq, const float* q, int k, float* D, in
     return fused;
 }
 
+// Exact (fp64-verified) nearest centroid of n device rows: the search path's own prefilter + verification kernels (ties -> lowest
+// list id), in chunks of `chunk` rows -- the size `S` (chunk x nlist fp32 scores) was allocated for.  Shared by the k-means
+// iterations of the build and by rvcmi_ivf_add: there is one assignment rule.
+static int64_t coarse_chunk(int64_t n, int64_t nlist) {
+    return std::max<int64_t>(64, std::min<int64_t>(n, ((int64_t)512 << 20) / (4 * nlist)));
+}
+static void coarse_assign_exact(const float* x, int64_t n, const float* cent, const float* cn, double cmax, int64_t nlist, int d, float* S,
+                                int64_t chunk, int64_t* assign, hipStream_t st) {
+    for (int64_t qs = 0; qs < n; qs += chunk) {
+        const int64_t nqc = std::min<int64_t>(chunk, n - qs);
+        const float* q = x + qs * d;
+        if (((nlist + 127) / 128) * ((nqc + 63) / 64) >= 512) {
+            dim3 grid((unsigned)((nlist + 127) / 128), (unsigned)((nqc + 63) / 64));
+            hipLaunchKernelGGL((k_coarse_gemm<2, 4>), grid, dim3(256), 0, st, q, cent, cn, nqc, nlist, d, S);
+        } else {
+            dim3 grid((unsigned)((nlist + 31) / 32), (unsigned)((nqc + 31) / 32));
+            hipLaunchKernelGGL((k_coarse_gemm<1, 1>), grid, dim3(64), 0, st, q, cent, cn, nqc, nlist, d, S);
+        }
+        hipLaunchKernelGGL(k_coarse_pick, dim3((unsigned)((nqc + 3) / 4)), dim3(256), 0, st, q, cent, S, nqc, nlist, d, cmax, assign + qs);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// index.add of n device rows (ivf_add_kernels.hpp).  assign_dev: their nearest centroids when the caller has them already (the
+// build's last assignment pass), else nullptr.  Allocates, synchronises `st`, replaces h->blob.
+static void ivf_add_device(rvcmi_ivf* h, int64_t n, const float* x_dev, const int64_t* assign_dev, hipStream_t st) {
+    const BlobHeader ob = h->hdr;
+    const int d = ob.d;
+    const int64_t nlist = ob.nlist, nt0 = ob.ntotal, nt1 = nt0 + n;
+    BlobHeader nh = ob;
+    nh.ntotal = nt1;
+    blob_layout(nh);
+    DevBuf As, Sc, Cnt, Cur, NB;
+    if (!assign_dev) {
+        As.alloc((size_t)n * 8);
+        const int64_t chunk = coarse_chunk(n, nlist);
+        Sc.alloc((size_t)chunk * nlist * 4);
+        coarse_assign_exact(x_dev, n, h->centroids(), h->cnorm(), ob.cmax, nlist, d, Sc.as<float>(), chunk, As.as<int64_t>(), st);
+        assign_dev = As.as<int64_t>();
+    }
+    Cnt.alloc((size_t)(nlist + 1) * 8);
+    Cur.alloc((size_t)(nlist + 1) * 8);
+    NB.alloc((size_t)nh.total_bytes);
+    char* nb = NB.as<char>();
+    // (the whole blob, padding included, is a function of the old index and x: blob() hands these bytes out)
+    HIP_CHECK(hipMemsetAsync(nb, 0, (size_t)nh.total_bytes, st));
+    HIP_CHECK(hipMemsetAsync(Cnt.p, 0, (size_t)(nlist + 1) * 8, st));
+    HIP_CHECK(hipMemcpyAsync(nb + nh.off_centroids, h->blob + ob.off_centroids, (size_t)nlist * d * 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(nb + nh.off_centroids_t, h->blob + ob.off_centroids_t, (size_t)nlist * d * 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(nb + nh.off_cnorm, h->blob + ob.off_cnorm, (size_t)nlist * 4, hipMemcpyDeviceToDevice, st));
+    int64_t* new_off = (int64_t*)(nb + nh.off_list_offsets);
+    int64_t* new_ids = (int64_t*)(nb + nh.off_ids);
+    const unsigned nblk = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(k_add_count, dim3(nblk), dim3(256), 0, st, assign_dev, n, nlist, Cnt.as<unsigned long long>());
+    hipLaunchKernelGGL(k_add_offsets, dim3(1), dim3(1024), 0, st, Cnt.as<unsigned long long>(), nlist, h->list_off(), assign_dev, n, new_off,
+                       Cur.as<unsigned long long>());
+    hipLaunchKernelGGL(k_add_claim, dim3(nblk), dim3(256), 0, st, assign_dev, n, nlist, nt0, Cur.as<unsigned long long>(), new_ids);
+    hipLaunchKernelGGL(k_add_sort, dim3((unsigned)nlist), dim3(1024), 0, st, h->list_off(), new_off, new_ids);
+    hipLaunchKernelGGL(k_add_fill, dim3((unsigned)((nt1 + 3) / 4)), dim3(256), 0, st, h->list_off(), new_off, nlist, h->ids(), h->vecs(), x_dev, nt0,
+                       nt1, d, new_ids, (float*)(nb + nh.off_vecs));
+    HIP_CHECK(hipGetLastError());
+    unsigned long long pos_last = 0;
+    HIP_CHECK(hipMemcpyAsync(&pos_last, Cur.as<unsigned long long>() + nlist, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    nh.pos_last = (int64_t)pos_last;
+    HIP_CHECK(hipMemcpy(nb, &nh, sizeof(BlobHeader), hipMemcpyHostToDevice));
+    // the new blob is live: an adopted old blob stays with its owner, an owned one is freed
+    if (h->owns_blob && h->blob) (void)hipFree(h->blob);
+    h->blob = nb;
+    NB.p = nullptr;
+    NB.bytes = 0;
+    h->owns_blob = true;
+    h->hdr = nh;
+    // everything derived from the stored rows is stale (row norms, the largest norm -- the error bound of the list-major prefilter --,
+    // the longest list and the item capacity sized from it): dropped here and rebuilt for the capacity the handle had reserved
+    const int64_t want = h->cap_nq;
+    h->lm_ready = false;
+    h->lm_vmax = 0.0;
+    h->lm_maxlen = h->lm_cap_items = h->lm_cap_nq = h->lm_buf_nq = 0;
+    h->cap_nq = 0;
+    if (want > 0) reserve(h, want);
+}
+
+static rvcmi_ivf* empty_index(int d, int64_t nlist, int nprobe, const float* centroids, int device) {
+    const std::vector<int64_t> off((size_t)nlist + 1, 0);
+    return from_host_blob(build_blob(d, 0, nlist, nprobe, centroids, off.data(), nullptr, nullptr), device);
+}
+
 }  // namespace rvcmi
 
 extern "C" {
@@ -1442,7 +1537,7 @@ static int ivf_build_impl(int d, int64_t n, const float* x_host, int64_t nlist, 
         Ord.alloc((size_t)n * 8);
         Off.alloc((size_t)(nlist + 1) * 8);
         Dist.alloc((size_t)n * 8);
-        const int64_t chunk = std::max<int64_t>(64, std::min<int64_t>(n, ((int64_t)512 << 20) / (4 * nlist)));
+        const int64_t chunk = coarse_chunk(n, nlist);
         Sc.alloc((size_t)chunk * nlist * 4);
         // init: nlist distinct training vectors (seeded partial Fisher-Yates), like faiss' random subset initialisation
         std::vector<float> cent((size_t)nlist * d);
@@ -1472,32 +1567,21 @@ static int ivf_build_impl(int d, int64_t n, const float* x_host, int64_t nlist, 
             HIP_CHECK(hipMemcpyAsync(Cd.p, cent.data(), cent.size() * 4, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(Cn.p, cn.data(), cn.size() * 4, hipMemcpyHostToDevice, st));
             // exact (fp64-verified) nearest centroid of every training vector: the search path's own coarse kernels
-            for (int64_t qs = 0; qs < n; qs += chunk) {
-                const int64_t nqc = std::min<int64_t>(chunk, n - qs);
-                const float* q = X.as<float>() + qs * d;
-                if (((nlist + 127) / 128) * ((nqc + 63) / 64) >= 512) {
-                    dim3 grid((unsigned)((nlist + 127) / 128), (unsigned)((nqc + 63) / 64));
-                    hipLaunchKernelGGL((k_coarse_gemm<2, 4>), grid, dim3(256), 0, st, q, Cd.as<float>(), Cn.as<float>(), nqc, nlist, d, Sc.as<float>());
-                } else {
-                    dim3 grid((unsigned)((nlist + 31) / 32), (unsigned)((nqc + 31) / 32));
-                    hipLaunchKernelGGL((k_coarse_gemm<1, 1>), grid, dim3(64), 0, st, q, Cd.as<float>(), Cn.as<float>(), nqc, nlist, d, Sc.as<float>());
-                }
-                hipLaunchKernelGGL(k_coarse_pick, dim3((unsigned)((nqc + 3) / 4)), dim3(256), 0, st, q, Cd.as<float>(), Sc.as<float>(), nqc,
-                                   nlist, d, std::sqrt(cmax2), As.as<int64_t>() + qs);
-            }
-            HIP_CHECK(hipGetLastError());
+            coarse_assign_exact(X.as<float>(), n, Cd.as<float>(), Cn.as<float>(), std::sqrt(cmax2), nlist, d, Sc.as<float>(), chunk, As.as<int64_t>(), st);
             if (objective_out) {
                 hipLaunchKernelGGL(k_assigned_dist, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, X.as<float>(), Cd.as<float>(),
                                    As.as<int64_t>(), n, d, Dist.as<double>());
                 HIP_CHECK(hipMemcpyAsync(dist.data(), Dist.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
             }
-            HIP_CHECK(hipMemcpyAsync(assign.data(), As.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            // (the assignment after the last update stays on the device: the add below places the rows from it)
+            if (it < niter) HIP_CHECK(hipMemcpyAsync(assign.data(), As.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             if (objective_out) {
                 double o = 0.0;
                 for (int64_t i = 0; i < n; ++i) o += dist[i];
                 objective_out[it] = o;
             }
+            if (it == niter) break;
             // lists: stable counting sort by centroid => ids ascending inside a list (what sequential index.add produces)
             std::fill(off.begin(), off.end(), 0);
             for (int64_t i = 0; i < n; ++i) off[assign[i] + 1]++;
@@ -1508,7 +1592,6 @@ static int ivf_build_impl(int d, int64_t n, const float* x_host, int64_t nlist, 
             }
             HIP_CHECK(hipMemcpyAsync(Ord.p, order.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(Off.p, off.data(), (size_t)(nlist + 1) * 8, hipMemcpyHostToDevice, st));
-            if (it == niter) break;
             hipLaunchKernelGGL(k_list_mean, dim3((unsigned)nlist), dim3(256), 0, st, X.as<float>(), Ord.as<int64_t>(), Off.as<int64_t>(), d,
                                Cd.as<float>());
             HIP_CHECK(hipMemcpyAsync(cent.data(), Cd.p, cent.size() * 4, hipMemcpyDeviceToHost, st));
@@ -1620,15 +1703,14 @@ static int ivf_build_impl(int d, int64_t n, const float* x_host, int64_t nlist, 
             memcpy(centroids_out, cent.data(), cent.size() * 4);
             return;
         }
-        // index.add: list-major copy of the vectors, then the packed blob (same layout the reader produces)
-        DevBuf V;
-        V.alloc((size_t)std::max<int64_t>(n, 1) * d * 4);
-        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n), dim3(256), 0, st, X.as<float>(), Ord.as<int64_t>(), n, d, V.as<float>());
-        HIP_CHECK(hipGetLastError());
-        std::vector<float> vecs((size_t)n * d);
-        HIP_CHECK(hipMemcpy(vecs.data(), V.p, vecs.size() * 4, hipMemcpyDeviceToHost));
-        auto blob = build_blob(d, n, nlist, 1, cent.data(), off.data(), order.data(), vecs.data());
-        *out = from_host_blob(blob, device);
+        // index.add: the trained, empty index takes every row by the device-side add (the last assignment pass above is its input)
+        Sc.free();
+        Ord.free();
+        Off.free();
+        Dist.free();
+        std::unique_ptr<rvcmi_ivf> h(empty_index(d, nlist, 1, cent.data(), device));
+        ivf_add_device(h.get(), n, X.as<float>(), As.as<int64_t>(), st);
+        *out = h.release();
     });
 }
 int rvcmi_ivf_build(int d, int64_t n, const float* x_host, int64_t nlist, int niter, uint64_t seed, int device,
@@ -1640,6 +1722,37 @@ int rvcmi_kmeans(int d, int64_t n, const float* x_host, int64_t k, int niter, ui
                  float* centroids_out_host) {
     if (!centroids_out_host) return rvcmi::guarded([&] { RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument"); });
     return ivf_build_impl(d, n, x_host, k, niter, seed, device, objective_out, centroids_out_host, nullptr);
+}
+int rvcmi_ivf_train(int d, int64_t n, const float* x_host, int64_t nlist, int niter, uint64_t seed, int device, double* objective_out,
+                    rvcmi_ivf** out) {
+    return guarded([&] {
+        if (!out) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
+        validate(d, n, nlist, 1);
+        std::vector<float> cent((size_t)nlist * d);
+        const int rc = ivf_build_impl(d, n, x_host, nlist, niter, seed, device, objective_out, cent.data(), nullptr);
+        if (rc != RVCMI_OK) throw Error{rc};  // (the message is already set)
+        *out = empty_index(d, nlist, 1, cent.data(), device);
+    });
+}
+int rvcmi_ivf_add(rvcmi_ivf* h, int64_t n, const float* x, int x_on_device, void* stream) {
+    return guarded([&] {
+        if (!h || h->hdr.magic != kMagic || !h->blob) RVCMI_FAIL(RVCMI_ERR_INVALID, "add: not a trained rvcmi IVF index");
+        if (n < 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "add: n=%lld is negative", (long long)n);
+        if (n == 0) return;
+        if (!x) RVCMI_FAIL(RVCMI_ERR_INVALID, "add: null x with n=%lld", (long long)n);
+        const int64_t lim = (int64_t)(((uint64_t)1 << 62) / ((uint64_t)h->hdr.d * 4));  // the vectors section stays below 2^62 bytes
+        if (n > lim || h->hdr.ntotal > lim - n)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "add: ntotal %lld + n %lld overflows the index", (long long)h->hdr.ntotal, (long long)n);
+        DeviceGuard dg(h->device);
+        hipStream_t st = (hipStream_t)stream;
+        DevBuf X;
+        if (!x_on_device) {
+            X.alloc((size_t)n * h->hdr.d * 4);
+            HIP_CHECK(hipMemcpyAsync(X.p, x, (size_t)n * h->hdr.d * 4, hipMemcpyHostToDevice, st));
+            x = X.as<float>();
+        }
+        ivf_add_device(h, n, x, nullptr, st);
+    });
 }
 int rvcmi_ivf_create(int d, int64_t n, int64_t nlist, int nprobe, const float* centroids, const int64_t* list_offsets,
                      const int64_t* ids, const float* vecs, int device, rvcmi_ivf** out) {

@@ -10,7 +10,8 @@ rebinds the two names the reference resolves its hot path through:
 * the name ``faiss`` as seen by ``infer.modules.vc.pipeline`` (pipeline.py:11,214-215,126) and ``infer.lib.rtrvc``
   (rtrvc.py:7,56-57,130-131,172): ``faiss.read_index`` returns an ``IVFFlatHIP`` (``.ntotal``, ``.reconstruct_n``, ``.search``);
   every other attribute is forwarded to the real ``faiss`` module when one is installed (index training in web.py keeps
-  working), and raises a clear error when it is not.
+  working), and raises a clear error when it is not.  With ``index_build=True`` (opt-in) ``faiss.index_factory(d, "IVF<n>,Flat")`` and
+  ``faiss.extract_index_ivf`` are served too: web.py's index recipe (train, write, batched add, write) runs on the HIP index.
 
 * ``Pipeline.vc`` / ``Pipeline.pipeline`` (infer/modules/vc/pipeline.py:76,186) and ``RVC.infer`` (infer/lib/rtrvc.py:134): replaced
   ON THE REFERENCE'S OWN CLASSES by the device-resident versions (``rvc_amd.pipeline.vc_hip`` / ``pipeline_hip``,
@@ -26,6 +27,7 @@ Nothing of the reference is edited; ``uninstall()`` restores the original bindin
 from __future__ import annotations
 
 import importlib
+import os
 import sys
 import types
 from typing import Optional
@@ -46,16 +48,21 @@ _GUI_GATE_MODULES = ("infer.modules.gui", "infer.modules.gui.torchgate")
 class _FaissShim(types.ModuleType):
     """``faiss`` as the inference path sees it; ``read_index`` is served by the HIP index."""
 
-    def __init__(self, real: Optional[types.ModuleType], device):
+    def __init__(self, real: Optional[types.ModuleType], device, index_build: bool = False):
         super().__init__("faiss")
         self.__dict__["_rvcmi_real"] = real
         self.__dict__["_rvcmi_device"] = device
+        self.__dict__["_rvcmi_index_build"] = bool(index_build)
         self.__dict__["__doc__"] = "rvc_amd faiss shim (read_index -> IVFFlatHIP); other names forwarded to the real faiss"
 
-    def read_index(self, path, *a, **k):
+    def _rvcmi_dev(self):
         dev = self._rvcmi_device
         if dev is None:  # the process's current GPU (the reference passes config.device to the loader, not to faiss)
             dev = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        return dev
+
+    def read_index(self, path, *a, **k):
+        dev = self._rvcmi_dev()
         try:
             return _ivf.read_index(path, device=dev)
         except _lib.RvcmiError as e:
@@ -71,7 +78,28 @@ class _FaissShim(types.ModuleType):
             return _ivf.write_index(index, path)
         return self.__getattr__("write_index")(index, path)
 
+    # index_build (opt-in): the index recipe of web.py:547-571 on the HIP index.  Reached through __getattr__, so that with the
+    # switch off the two names behave exactly as before (forwarded to the real faiss, AttributeError without one).
+    def _rvcmi_index_factory(self, d, description, *a, **k):
+        try:
+            return _ivf.index_factory(d, description, device=self._rvcmi_dev())
+        except ValueError:
+            real = self.__dict__.get("_rvcmi_real")
+            if real is None:
+                raise
+            return real.index_factory(d, description, *a, **k)  # a description the HIP index does not serve
+
+    def _rvcmi_extract_index_ivf(self, index):
+        if isinstance(index, _ivf.IVFFlatHIP):
+            return index
+        real = self.__dict__.get("_rvcmi_real")
+        if real is None:
+            return _ivf.extract_index_ivf(index)  # raises: not one of ours, and there is no faiss to ask
+        return real.extract_index_ivf(index)
+
     def __getattr__(self, name):
+        if name in ("index_factory", "extract_index_ivf") and self.__dict__.get("_rvcmi_index_build"):
+            return getattr(self, "_rvcmi_" + name)
         real = self.__dict__.get("_rvcmi_real")
         if real is None:
             raise AttributeError("faiss.%s: faiss is not installed and rvc_amd only replaces read_index / write_index / "
@@ -139,14 +167,18 @@ def _rebind_gate(rebound) -> None:
 
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
-            patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False) -> None:
+            patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False,
+            index_build: Optional[bool] = None) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
     high-pass and the reflection pad on the device (``glue.filtfilt``; equal to scipy to fp64 rounding noise, not bit for bit).
     ``rmvpe_unet=True`` (opt-in, as ``RVCMI_RMVPE_UNET=1``): the f0 step also runs RMVPE's U-Net and head on ``csrc/unet.hip``
     (``unet.accelerate_rmvpe_unet``), next to the GRU swap.  ``rmvpe_hip=True`` (opt-in, as ``RVCMI_RMVPE_HIP=1``): the f0 step runs the whole
-    estimator -- mel front end, U-Net, GRU, head, decode -- as ``rmvpe.RMVPEHIP``, and the realtime entry keeps a fractional key on the device."""
+    estimator -- mel front end, U-Net, GRU, head, decode -- as ``rmvpe.RMVPEHIP``, and the realtime entry keeps a fractional key on the device.
+    ``index_build=True`` (opt-in, as ``RVCMI_INDEX_BUILD=1``; default off): the faiss shim also serves ``index_factory(d, "IVF<n>,Flat")`` and
+    ``extract_index_ivf`` for the HIP index, so the unmodified index recipe (web.py:547-571: factory, nprobe, train, write, batched add,
+    write) runs without faiss; any other description goes to the real faiss when there is one."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -192,7 +224,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
                 real = real._rvcmi_real
         except ImportError:
             real = None
-        shim = _FaissShim(real, device)
+        if index_build is None:
+            index_build = os.environ.get("RVCMI_INDEX_BUILD", "0") == "1"
+        shim = _FaissShim(real, device, index_build=index_build)
         _state["faiss_prev"] = sys.modules.get("faiss")
         sys.modules["faiss"] = shim  # modules imported from now on bind the shim with their `import faiss`
         for m in _FAISS_USERS:  # ... and the ones already imported are rebound

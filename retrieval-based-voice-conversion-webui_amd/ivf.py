@@ -7,6 +7,8 @@ Mirrors exactly the surface the reference touches:
     score, ix = index.search(npy, k=8)             -> index.search(npy, k=8)      pipeline.py:126
     faiss.extract_index_ivf(index).nprobe = 1      -> index.nprobe = 1            web.py:551-552
     faiss.write_index(index, path)                 -> write_index(index, path)    web.py:571
+    index = faiss.index_factory(d, "IVF%s,Flat")   -> index_factory(d, "IVF<n>,Flat") web.py:547
+    index.train(big_npy); index.add(big_npy[i:j])  -> index.train(x); index.add(x)    web.py:553,561-563
 
 plus the device-resident fast path ``search_blend`` that fuses pipeline.py:126-138 and removes the
 two D2H + two H2D hops around retrieval.  numpy in -> numpy out (drop-in); torch.cuda in -> torch.cuda out.
@@ -14,6 +16,7 @@ two D2H + two H2D hops around retrieval.  numpy in -> numpy out (drop-in); torch
 from __future__ import annotations
 
 import ctypes as C
+import re
 from typing import List, Tuple, Union
 
 import numpy as np
@@ -72,6 +75,49 @@ class IVFFlatHIP:
         return (idx, obj) if return_objective else idx
 
     @classmethod
+    def trained(cls, big_npy: np.ndarray, nlist: int = None, niter: int = 10, seed: int = 1234, device="cuda:0",
+                return_objective: bool = False):
+        """``index.train(big_npy)`` alone (web.py:553): the k-means of :meth:`train`, returned as a trained, EMPTY index (what the
+        reference writes as ``trained_IVF*.index``); rows come in with :meth:`add`.  Same ``nlist`` default as :meth:`train`;
+        ``trained(x, ...)`` followed by ``add(x)`` is :meth:`train`, bit for bit.  The objective has ``niter`` entries (``kmeans``)."""
+        dev = _cuda(device)
+        x = np.ascontiguousarray(big_npy, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("big_npy must be [N, d]")
+        n, d = x.shape
+        if nlist is None:
+            nlist = max(1, min(int(16 * np.sqrt(n)), n // 39))
+        obj = np.zeros(int(niter), dtype=np.float64)
+        h = C.c_void_p(None)
+        _lib.check(_lib.lib().rvcmi_ivf_train(d, n, x.ctypes.data_as(C.c_void_p), int(nlist), int(niter), int(seed), _idx(dev),
+                                              obj.ctypes.data_as(C.c_void_p) if return_objective else C.c_void_p(None), C.byref(h)))
+        idx = IVFFlatHIP(h, dev)
+        return (idx, obj) if return_objective else idx
+
+    def add(self, x: ArrayLike) -> None:
+        """``index.add(x)`` (web.py:561-563): appends the rows ``x`` [n, d] with ids ``ntotal .. ntotal + n - 1``, each to the list of
+        its exact nearest centroid, on the device (``rvcmi_ivf_add``).  A numpy array of any float dtype is converted to fp32 and
+        copied up once; a CUDA tensor must be contiguous fp32 on the index's device and is read in place.  Adding in batches gives
+        the same index as adding at once.  The index moves to a new blob (``blob()`` copies; an adopted ``from_blob`` tensor is left
+        as it was).  Not for use under stream capture."""
+        h = self._h
+        d = self.d
+        if isinstance(x, torch.Tensor):
+            if x.device.type != "cuda" or _idx(x.device) != _idx(self.device):
+                raise ValueError("add: a tensor must live on the index's device %s (got %s); pass host rows as a numpy array" % (self.device, x.device))
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError("add: a CUDA tensor must be contiguous float32 (it is read in place)")
+            ptr, on_device, keep = x.data_ptr(), 1, x
+        else:
+            keep = np.ascontiguousarray(x, dtype=np.float32)
+            ptr, on_device = keep.ctypes.data, 0
+        if keep.ndim != 2 or keep.shape[1] != d:
+            raise ValueError("add: rows must be [n, %d], got %s" % (d, tuple(keep.shape)))  # faiss: assert d == self.d
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().rvcmi_ivf_add(h, int(keep.shape[0]), C.c_void_p(ptr), on_device, C.c_void_p(st)))
+
+    @classmethod
     def from_blob(cls, blob: torch.Tensor) -> "IVFFlatHIP":
         """Adopt a device blob (uint8 CUDA tensor), e.g. one received by an RCCL broadcast."""
         if blob.dtype != torch.uint8 or blob.device.type != "cuda" or not blob.is_contiguous():
@@ -100,6 +146,10 @@ class IVFFlatHIP:
             pass
 
     # -- faiss attribute surface -------------------------------------------------------------------
+    @property
+    def is_trained(self) -> bool:
+        return True  # every handle holds centroids (the untrained state exists only in index_factory's object)
+
     @property
     def ntotal(self) -> int:
         return int(_lib.lib().rvcmi_ivf_ntotal(self._h))
@@ -138,6 +188,7 @@ class IVFFlatHIP:
 
     def search(self, x: ArrayLike, k: int = 8) -> Tuple[ArrayLike, ArrayLike]:
         """``index.search(x, k)`` -> (D squared-L2 ascending, I int64, -1/FLT_MAX padded)."""
+        self._h  # (an untrained index_factory object raises here, before anything is copied)
         is_np = isinstance(x, np.ndarray)
         if is_np:
             if x.dtype != np.float32:
@@ -194,6 +245,100 @@ def read_index(path: str, device="cuda:0") -> IVFFlatHIP:
 def write_index(index: IVFFlatHIP, path: str) -> None:
     """``faiss.write_index(index, path)``."""
     _lib.check(_lib.lib().rvcmi_ivf_write_file(index._h, str(path).encode()))
+
+
+_SERVED = 'only "IVF<nlist>,Flat" (faiss IndexIVFFlat, METRIC_L2: every index the reference builds, web.py:547) is served'
+
+
+def parse_description(description: str) -> int:
+    """``nlist`` of an ``"IVF<nlist>,Flat"`` factory string; anything else (``"IVF%s,PQ128x4fs,RFlat"`` ...) is a ValueError."""
+    m = re.fullmatch(r"IVF([0-9]+),Flat", description) if isinstance(description, str) else None
+    if m is None or int(m.group(1)) < 1:
+        raise ValueError("index_factory(%r): %s" % (description, _SERVED))
+    return int(m.group(1))
+
+
+class FactoryIVFFlatHIP(IVFFlatHIP):
+    """What ``faiss.index_factory(d, "IVF<nlist>,Flat")`` returns: untrained until ``train(x)`` (an instance method here, faiss'
+    meaning, unlike the classmethod it shadows), afterwards an ordinary :class:`IVFFlatHIP`.  Untrained, ``is_trained`` is False,
+    ``ntotal`` 0, ``d`` / ``nlist`` / ``nprobe`` readable and ``nprobe`` settable (web.py:551-552; carried into the trained index);
+    everything that needs centroids raises ``RvcmiError`` ("not trained"), as faiss asserts."""
+
+    def __init__(self, d: int, nlist: int, device="cuda:0", niter: int = 10, seed: int = 1234):
+        self._handle = None
+        self._d, self._nlist, self._nprobe = int(d), int(nlist), 1
+        self.niter, self.seed = int(niter), int(seed)
+        super().__init__(None, _cuda(device))
+
+    @property
+    def _h(self):
+        if self._handle is None:
+            raise _lib.RvcmiError("the index is not trained: call index.train(x) first (faiss: 'is_trained' assertion)")
+        return self._handle
+
+    @_h.setter
+    def _h(self, v):
+        self._handle = v
+
+    @property
+    def is_trained(self) -> bool:
+        return self._handle is not None
+
+    @property
+    def ntotal(self) -> int:
+        return IVFFlatHIP.ntotal.fget(self) if self.is_trained else 0
+
+    @property
+    def d(self) -> int:
+        return self._d
+
+    @property
+    def nlist(self) -> int:
+        return self._nlist
+
+    @property
+    def nprobe(self) -> int:
+        return IVFFlatHIP.nprobe.fget(self) if self.is_trained else self._nprobe
+
+    @nprobe.setter
+    def nprobe(self, v: int) -> None:
+        if int(v) < 1:
+            raise _lib.RvcmiError("bad nprobe", code=_lib.ERR_INVALID)
+        if self.is_trained:
+            IVFFlatHIP.nprobe.fset(self, v)
+        self._nprobe = int(v)
+
+    def train(self, x: np.ndarray) -> None:  # noqa  (faiss' instance method; IVFFlatHIP.train is the one-shot classmethod)
+        """``index.train(x)``: k-means for the ``nlist`` centroids (``rvcmi_ivf_train``); needs at least ``nlist`` rows.  A second call
+        is a no-op, as in faiss."""
+        if self.is_trained:
+            return
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self._d:
+            raise ValueError("train: rows must be [n, %d], got %s" % (self._d, tuple(x.shape)))
+        if x.shape[0] < self._nlist:
+            raise _lib.RvcmiError("train: need at least nlist=%d training vectors, got %d" % (self._nlist, x.shape[0]), code=_lib.ERR_INVALID)
+        h = C.c_void_p(None)
+        _lib.check(_lib.lib().rvcmi_ivf_train(self._d, x.shape[0], x.ctypes.data_as(C.c_void_p), self._nlist, self.niter, self.seed,
+                                              _idx(self.device), C.c_void_p(None), C.byref(h)))
+        self._handle = h
+        if self._nprobe != 1:
+            IVFFlatHIP.nprobe.fset(self, self._nprobe)
+
+
+def index_factory(d: int, description: str, device="cuda:0") -> FactoryIVFFlatHIP:
+    """``faiss.index_factory(d, "IVF%s,Flat" % n_ivf)`` (web.py:547, tools/cmd/train-index{,-v2}.py): an untrained IVF-Flat / L2 index."""
+    nlist = parse_description(description)
+    if int(d) < 4 or int(d) % 4:
+        raise ValueError("index_factory: dimension %s must be a positive multiple of 4" % (d,))
+    return FactoryIVFFlatHIP(int(d), nlist, device=device)
+
+
+def extract_index_ivf(index: IVFFlatHIP) -> IVFFlatHIP:
+    """``faiss.extract_index_ivf(index)``: the index itself (the reference only sets ``.nprobe`` on it, web.py:551-552)."""
+    if not isinstance(index, IVFFlatHIP):
+        raise TypeError("extract_index_ivf: not an rvc_amd index: %r" % (type(index),))
+    return index
 
 
 def _cuda(device) -> torch.device:
