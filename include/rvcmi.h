@@ -478,7 +478,8 @@ int rvcmi_gru_create(int input_size, int hidden_size, const float* w_ih, const f
 int rvcmi_gru_destroy(rvcmi_gru* h);
 /* x16_dev [B][T][I] fp16; y_dev [B][T][2H] fp32 = nn.GRU's `output` with h_0 = 0; hn_dev [2][B][H] fp32 = its `h_n` (or NULL).
  * The projection workspace grows with the largest B * T seen (a hipMalloc on such a call: the FIRST call of a size must not be inside a
- * stream capture); the smaller workspaces it replaces stay allocated until destroy, so a graph captured earlier keeps replaying. */
+ * stream capture); the smaller workspaces it replaces stay allocated until destroy, so a graph captured earlier keeps replaying.
+ * B outside 1 .. 65535, T < 1, B * T > 2^30: RVCMI_ERR_INVALID, nothing launched, the workspace untouched.                          */
 int rvcmi_gru_forward(rvcmi_gru* h, int B, int T, const void* x16_dev, float* y_dev, float* hn_dev, void* stream);
 /* The same for a RAGGED batch: nseq sequences packed along the row axis, sequence i in rows [offsets[i], offsets[i + 1]) of x16_dev [R][I]
  * and y_dev [R][2H], R = offsets[nseq]; hn_dev [2][nseq][H] or NULL.  offsets_host and offsets_dev hold the same nseq + 1 ints (the host

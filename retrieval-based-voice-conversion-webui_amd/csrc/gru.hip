@@ -270,6 +270,7 @@ int rvcmi_gru_forward(rvcmi_gru* h, int B, int T, const void* x16, float* y, flo
     return guarded([&] {
         if (!h || !x16 || !y) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward: null argument");
         if (B < 1 || T < 1 || (long long)B * T > (1ll << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward: B = %d, T = %d", B, T);
+        if (B > 65535) RVCMI_FAIL(RVCMI_ERR_INVALID, "gru_forward: B = %d sequences (at most 65535: one block per (direction, sequence), grid y)", B);
         gru_run(h, B, T, (size_t)B * T, nullptr, x16, y, hn, stream);
     });
 }
