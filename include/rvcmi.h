@@ -559,6 +559,34 @@ int rvcmi_mel_forward(rvcmi_mel* h, int B, int64_t n, const float* wav_dev, int 
 int rvcmi_rmvpe_head(const float* y_dev, int M, const float* w_dev, const float* b_dev, int half_operands, float* salience_dev,
                      void* stream);
 
+/* ---- beyond SURVEY.md section 8: HuBERT's convolutional feature extractor -------------------------------------------------------
+ * Stands in for the `feature_extractor` of a HuBERT-base content encoder (fairseq ConvFeatureExtractionModel with extractor_mode
+ * "default"; transformers HubertFeatureEncoder with feat_extract_norm "group"): seven bias-free Conv1d layers, 1 -> 512 k 10 stride 5 with
+ * GroupNorm(512 groups, eps 1e-5, affine), 512 -> 512 k 3 stride 2 four times, 512 -> 512 k 2 stride 2 twice, exact (erf) GELU after each.
+ * `weights`: fp32 host tensors under fairseq's names, "conv_layers.<i>.0.weight" ([512][1][10], [512][512][3], [512][512][2]) and
+ * "conv_layers.0.2.weight" / ".bias" ([512]).  A missing tensor: RVCMI_ERR_MISSING; another shape, or any further tensor (a conv bias, an
+ * eighth layer): RVCMI_ERR_INVALID (the caller keeps torch's module).  Operands and inter-layer streams fp16, accumulation and epilogues
+ * fp32, the GroupNorm statistics fp64 from the centred covariance of the input.  Results are bit-identical from run to run.          */
+typedef struct rvcmi_hubert_fe rvcmi_hubert_fe;
+int rvcmi_hubert_fe_create(const rvcmi_tensor* weights, int n_weights, int device, rvcmi_hubert_fe** out);
+int rvcmi_hubert_fe_destroy(rvcmi_hubert_fe* h);
+/* Output frames of an N-sample input: (N - 400) / 320 + 1; 0 when N < 400 or N > 2^30. */
+int64_t rvcmi_hubert_fe_frames(int64_t N);
+/* Bytes of device workspace one forward of (B, N) needs; 0 for a shape that is not served (B outside 1 .. 65535, N outside 400 .. 2^30). */
+size_t rvcmi_hubert_fe_workspace_bytes(rvcmi_hubert_fe* h, int B, int64_t N);
+/* Enqueue only.  x_dev [B][N] fp16 (x_is_half) or fp32; out16_dev [B][frames][512] fp16, channels-last (the caller views it as
+ * [B, 512, frames]).  ws_dev: rvcmi_hubert_fe_workspace_bytes(h, B, N) bytes, 256-byte aligned -- the handle then allocates nothing (safe
+ * inside a stream capture); or NULL: the handle's own workspace, which grows with the largest shape seen (a hipMalloc on such a call: the
+ * FIRST call of a size must not be inside a stream capture) while the smaller ones it replaces stay allocated until destroy, so a graph
+ * captured earlier keeps replaying.  A shape that is not served: RVCMI_ERR_INVALID, nothing launched, the workspace untouched.
+ * (For the tests: the workspace begins with layer 0's output, fp16 [B][L0][512], L0 = (N - 10) / 5 + 1; layers 2 and 4 reuse that buffer
+ * from its start, so with B == 1 the rows from layer 2's count on still hold layer 0 after the forward.)                              */
+int rvcmi_hubert_fe_forward(rvcmi_hubert_fe* h, int B, int64_t N, const void* x_dev, int x_is_half, void* out16_dev, void* ws_dev,
+                            void* stream);
+/* Test hook: ONE of layers 1 - 6 WITHOUT the activation on caller-supplied data (synchronous; allocates).  taps 3 or 2; w in torch's layout
+ * [512][512][taps] on the host; x16_dev fp16 [B][L_in][512]; out32_dev fp32 [B][(L_in - taps) / 2 + 1][512].                          */
+int rvcmi_hubert_fe_debug_conv(int taps, int B, int L_in, const float* w, const void* x16_dev, float* out32_dev, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ from typing import List
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RVCMI_LIB") or os.path.join(_HERE, "librvcmi.so")  # RVCMI_LIB: dev A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip", "rmvpe.hip"]
+SOURCES = ["nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip", "rmvpe.hip", "hubert_fe.hip"]
 
 RVCMI_MAX_UPS, RVCMI_MAX_RB, RVCMI_MAX_DIL = 8, 4, 4
 RVCMI_VERSION = 2  # include/rvcmi.h; the argument lists of SYMBOLS below are those of this ABI version
@@ -141,6 +141,12 @@ SYMBOLS = [
     ("rvcmi_mel_frames", C.c_int64, [_P, C.c_int64]),
     ("rvcmi_mel_forward", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     ("rvcmi_rmvpe_head", C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    ("rvcmi_hubert_fe_create", C.c_int, [C.POINTER(Tensor), C.c_int, C.c_int, C.POINTER(_P)]),
+    ("rvcmi_hubert_fe_destroy", C.c_int, [_P]),
+    ("rvcmi_hubert_fe_frames", C.c_int64, [C.c_int64]),
+    ("rvcmi_hubert_fe_workspace_bytes", C.c_size_t, [_P, C.c_int, C.c_int64]),
+    ("rvcmi_hubert_fe_forward", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, _P, _P, _P]),
+    ("rvcmi_hubert_fe_debug_conv", C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
 ]
 
 

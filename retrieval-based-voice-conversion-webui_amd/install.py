@@ -168,7 +168,7 @@ def _rebind_gate(rebound) -> None:
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
             patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False,
-            index_build: Optional[bool] = None) -> None:
+            index_build: Optional[bool] = None, hubert_fe: bool = False) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
@@ -178,7 +178,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     estimator -- mel front end, U-Net, GRU, head, decode -- as ``rmvpe.RMVPEHIP``, and the realtime entry keeps a fractional key on the device.
     ``index_build=True`` (opt-in, as ``RVCMI_INDEX_BUILD=1``; default off): the faiss shim also serves ``index_factory(d, "IVF<n>,Flat")`` and
     ``extract_index_ivf`` for the HIP index, so the unmodified index recipe (web.py:547-571: factory, nprobe, train, write, batched add,
-    write) runs without faiss; any other description goes to the real faiss when there is one."""
+    write) runs without faiss; any other description goes to the real faiss when there is one.  ``hubert_fe=True`` (opt-in, as
+    ``RVCMI_HUBERT_FE=1``; default off): the conversion paths swap HuBERT's convolutional feature extractor for ``hubert.HubertFrontHIP``
+    (``hubert.accelerate_hubert``), once per model object."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -247,6 +249,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     from . import rmvpe as _rmvpe
 
     _rmvpe.RMVPE_HIP = bool(rmvpe_hip)
+    from . import hubert as _hubert
+
+    _hubert.HUBERT_FE = bool(hubert_fe)
 
 
 def uninstall() -> None:
@@ -271,4 +276,7 @@ def uninstall() -> None:
     from . import rmvpe as _rmvpe
 
     _rmvpe.RMVPE_HIP = False
+    from . import hubert as _hubert
+
+    _hubert.HUBERT_FE = False
     _state.clear()

@@ -77,6 +77,9 @@ def hubert_device(self, model, audio0, pitch, pitchf, version):
     assert feats.dim() == 1, feats.dim()
     feats = feats.view(1, -1)
     padding_mask = torch.zeros(feats.shape, dtype=torch.bool, device=dev)
+    from .hubert import accelerate_hubert_once
+
+    accelerate_hubert_once(model)  # (beyond SURVEY 8; opt-in, a no-op with the switch off) the extractor's seven convolutions on HIP
     with torch.no_grad():
         logits = model.extract_features(source=feats.to(dev), padding_mask=padding_mask, output_layer=9 if version == "v1" else 12)
         feats = model.final_proj(logits[0]) if version == "v1" else logits[0]
