@@ -98,6 +98,8 @@ def test_sine_source_and_stage_taps_fp32(gpu):
 
 
 def test_mfma_stage_taps_fp16(gpu):
+    # the coarse second opinion (2e-3 relative, end to end against the UNROUNDED oracle): the sharp per-layer check, with an RMS and a max-abs bar derived
+    # from the rounded oracle's own fp32 floor, is tests/test_gpu_nsf_layers.py
     import rvc_amd
 
     cfg = nsf_oracle.CONFIGS["v2_48k"]
