@@ -583,6 +583,17 @@ size_t rvcmi_hubert_fe_workspace_bytes(rvcmi_hubert_fe* h, int B, int64_t N);
  * from its start, so with B == 1 the rows from layer 2's count on still hold layer 0 after the forward.)                              */
 int rvcmi_hubert_fe_forward(rvcmi_hubert_fe* h, int B, int64_t N, const void* x_dev, int x_is_half, void* out16_dev, void* ws_dev,
                             void* stream);
+/* A RAGGED batch: x_dev [B][N_max], item i = its first lens[i] samples; what lies behind them is never read for a valid output and may be
+ * anything (NaN included).  out16_dev [B][frames(N_max)][512] fp16: rows t < frames(lens[i]) of item i are BIT-equal to
+ * rvcmi_hubert_fe_forward(h, 1, lens[i], ...) on that item alone (its statistics chunks and their merge order depend on its own length only,
+ * a GEMM output row on no other row of its tile); the rows behind them are exactly zero.  lens_host / lens_dev: the same B ints on the host
+ * (checked) and on the device (read by the kernels, also on every replay of a capture).  Workspace and capture rules as for the dense entry;
+ * the bytes are those of the dense (B, N_max).  B outside 1 .. 65535, a lens[i] outside 400 .. N_max, N_max > 2^30, no item as long as N_max,
+ * or a null lens pointer: RVCMI_ERR_INVALID, nothing launched.  Tiles wholly behind an item's end return at once, so the time follows the
+ * sum of the lengths rather than B * N_max.                                                                                              */
+size_t rvcmi_hubert_fe_workspace_bytes_ragged(rvcmi_hubert_fe* h, int B, int64_t N_max);
+int rvcmi_hubert_fe_forward_ragged(rvcmi_hubert_fe* h, int B, int64_t N_max, const int* lens_host, const int* lens_dev, const void* x_dev,
+                                   int x_is_half, void* out16_dev, void* ws_dev, void* stream);
 /* Test hook: ONE of layers 1 - 6 WITHOUT the activation on caller-supplied data (synchronous; allocates).  taps 3 or 2; w in torch's layout
  * [512][512][taps] on the host; x16_dev fp16 [B][L_in][512]; out32_dev fp32 [B][(L_in - taps) / 2 + 1][512].                          */
 int rvcmi_hubert_fe_debug_conv(int taps, int B, int L_in, const float* w, const void* x16_dev, float* out32_dev, int device, void* stream);

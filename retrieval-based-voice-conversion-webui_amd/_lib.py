@@ -146,6 +146,8 @@ SYMBOLS = [
     ("rvcmi_hubert_fe_frames", C.c_int64, [C.c_int64]),
     ("rvcmi_hubert_fe_workspace_bytes", C.c_size_t, [_P, C.c_int, C.c_int64]),
     ("rvcmi_hubert_fe_forward", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, _P, _P, _P]),
+    ("rvcmi_hubert_fe_workspace_bytes_ragged", C.c_size_t, [_P, C.c_int, C.c_int64]),
+    ("rvcmi_hubert_fe_forward_ragged", C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("rvcmi_hubert_fe_debug_conv", C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
 ]
 

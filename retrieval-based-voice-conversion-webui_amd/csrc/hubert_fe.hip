@@ -6,6 +6,8 @@
 // [B][N] samples -> [B][L6][512] fp16, L6 = (N - 400) / 320 + 1.  Like csrc/unet.hip it is BEYOND the scope table of SURVEY.md section 8.
 // Kernels: hubert_fe_kernels.hpp.  Weights are packed once at create ([Cout][tap][Cin] fp16: K = tap x channel is contiguous in both GEMM
 // operands).  A forward is five launches for layer 0's statistics and pass plus one per later layer, all enqueued on the caller's stream.
+// rvcmi_hubert_fe_forward_ragged runs the same launches on a [B][N_max] batch whose items have lengths of their own (the kernels' RAGGED
+// instantiations): buffers and grids are those of N_max, every item's rows are those of its lone call.
 #include <memory>
 #include <string>
 
@@ -14,6 +16,8 @@
 
 using namespace rvcmi;
 using namespace rvcmi::hubert;
+
+struct rvcmi_hubert_fe;
 
 namespace {
 
@@ -74,12 +78,22 @@ std::vector<_Float16> pack_conv(const float* w, int taps) {
     return o;
 }
 
-void gemm(const _Float16* x, const _Float16* w, void* out, int B, int Lin, int taps, bool out32, hipStream_t st) {
+// lens == NULL: dense.  Else layer ``layer`` of the ragged batch (Lin: the longest item's rows, the stride); ``zero_tail``: the last layer.
+void gemm(const _Float16* x, const _Float16* w, void* out, int B, int Lin, int taps, bool out32, hipStream_t st, const int* lens = nullptr, int layer = 0,
+          bool zero_tail = false) {
     const int Lout = (Lin - taps) / 2 + 1;
     const dim3 grid((unsigned)((Lout + GM - 1) / GM), HC / GN, (unsigned)B);
-    if (out32) hipLaunchKernelGGL(k_hfe_gemm<true>, grid, dim3(256), 0, st, x, w, out, Lin, Lout, taps * HC);
-    else hipLaunchKernelGGL(k_hfe_gemm<false>, grid, dim3(256), 0, st, x, w, out, Lin, Lout, taps * HC);
+    if (lens) hipLaunchKernelGGL((k_hfe_gemm<false, true>), grid, dim3(256), 0, st, x, w, out, Lin, Lout, taps * HC, lens, layer, zero_tail ? 1 : 0);
+    else if (out32) hipLaunchKernelGGL((k_hfe_gemm<true, false>), grid, dim3(256), 0, st, x, w, out, Lin, Lout, taps * HC, (const int*)nullptr, 0, 0);
+    else hipLaunchKernelGGL((k_hfe_gemm<false, false>), grid, dim3(256), 0, st, x, w, out, Lin, Lout, taps * HC, (const int*)nullptr, 0, 0);
 }
+
+// the handle's own workspace (ws_dev == NULL), grown to ``bytes``: such a call must be outside any capture
+char* own_workspace(rvcmi_hubert_fe* h, size_t bytes, hipStream_t st);
+
+// the launches of one forward; lens == NULL: dense (N is every item's length), else ragged (N = N_max, the strides)
+template <bool RAGGED>
+void enqueue(rvcmi_hubert_fe* h, const Plan& p, int B, size_t N, const int* lens, const void* x_dev, int x_is_half, void* out16_dev, char* ws, hipStream_t st);
 
 }  // namespace
 
@@ -89,6 +103,43 @@ struct rvcmi_hubert_fe {
     DevBuf ws;                           // the handle's own workspace (forward with ws_dev == NULL)
     std::vector<DevBuf> retired;         // earlier, smaller workspaces: a captured graph may still point at one, so they live as long as the handle
 };
+
+namespace {
+
+char* own_workspace(rvcmi_hubert_fe* h, size_t bytes, hipStream_t st) {
+    if (bytes > h->ws.bytes) {  // (grows with the largest shape seen; such a call must be outside any capture)
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (h->ws.p) h->retired.push_back(std::move(h->ws));  // not freed: a graph captured at the smaller size replays into it
+        h->ws.alloc(bytes);
+    }
+    return h->ws.as<char>();
+}
+
+template <bool RAGGED>
+void enqueue(rvcmi_hubert_fe* h, const Plan& p, int B, size_t N, const int* lens, const void* x_dev, int x_is_half, void* out16_dev, char* ws, hipStream_t st) {
+    _Float16 *A = (_Float16*)(ws + p.off_a), *Bb = (_Float16*)(ws + p.off_b);
+    double* part = (double*)(ws + p.off_part);
+    float *meanf = (float*)(ws + p.off_meanf), *scale = (float*)(ws + p.off_scale), *shift = (float*)(ws + p.off_shift);
+    const int L0 = p.L[0];
+    const dim3 gs((unsigned)p.nchunk, (unsigned)B), g0((unsigned)((L0 + F0_BLK - 1) / F0_BLK), (unsigned)B);
+    if (x_is_half) hipLaunchKernelGGL((k_hfe_stats<_Float16, RAGGED>), gs, dim3(256), 0, st, (const _Float16*)x_dev, N, L0, part, lens);
+    else hipLaunchKernelGGL((k_hfe_stats<float, RAGGED>), gs, dim3(256), 0, st, (const float*)x_dev, N, L0, part, lens);
+    hipLaunchKernelGGL(k_hfe_stats_final<RAGGED>, dim3((unsigned)B), dim3(HC), 0, st, part, p.nchunk, L0, h->w0.as<float>(), h->gamma.as<float>(),
+                       h->beta.as<float>(), GN_EPS, meanf, scale, shift, lens);
+    if (x_is_half)
+        hipLaunchKernelGGL((k_hfe_conv0<_Float16, RAGGED>), g0, dim3(256), 0, st, (const _Float16*)x_dev, N, L0, h->w0.as<float>(), meanf, scale, shift, A,
+                           lens);
+    else
+        hipLaunchKernelGGL((k_hfe_conv0<float, RAGGED>), g0, dim3(256), 0, st, (const float*)x_dev, N, L0, h->w0.as<float>(), meanf, scale, shift, A, lens);
+    _Float16* cur = A;
+    for (int l = 1; l < NLAYERS; ++l) {
+        _Float16* dst = l == NLAYERS - 1 ? (_Float16*)out16_dev : (cur == A ? Bb : A);
+        gemm(cur, h->w[l].as<_Float16>(), dst, B, p.L[l - 1], TAPS[l], false, st, RAGGED ? lens : nullptr, l, l == NLAYERS - 1);
+        cur = dst;
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -160,33 +211,39 @@ int rvcmi_hubert_fe_forward(rvcmi_hubert_fe* h, int B, int64_t N, const void* x_
         const Plan p = plan_of(B, (int)N);
         DeviceGuard dg(h->device);
         hipStream_t st = (hipStream_t)stream;
-        char* ws = (char*)ws_dev;
-        if (!ws) {
-            if (p.bytes > h->ws.bytes) {  // (grows with the largest shape seen; such a call must be outside any capture)
-                HIP_CHECK(hipStreamSynchronize(st));
-                if (h->ws.p) h->retired.push_back(std::move(h->ws));  // not freed: a graph captured at the smaller size replays into it
-                h->ws.alloc(p.bytes);
-            }
-            ws = h->ws.as<char>();
+        char* ws = ws_dev ? (char*)ws_dev : own_workspace(h, p.bytes, st);
+        enqueue<false>(h, p, B, (size_t)N, nullptr, x_dev, x_is_half, out16_dev, ws, st);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+size_t rvcmi_hubert_fe_workspace_bytes_ragged(rvcmi_hubert_fe* h, int B, int64_t N_max) {
+    size_t n = 0;
+    const int rc = guarded([&] {
+        if (!h) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_workspace_bytes_ragged: null handle");
+        check_shape(B, N_max, "hubert_fe_workspace_bytes_ragged");
+        n = plan_of(B, (int)N_max).bytes;
+    });
+    return rc == RVCMI_OK ? n : 0;
+}
+
+int rvcmi_hubert_fe_forward_ragged(rvcmi_hubert_fe* h, int B, int64_t N_max, const int* lens_host, const int* lens_dev, const void* x_dev, int x_is_half,
+                                   void* out16_dev, void* ws_dev, void* stream) {
+    return guarded([&] {
+        if (!h || !x_dev || !out16_dev || !lens_host || !lens_dev) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_forward_ragged: null argument");
+        check_shape(B, N_max, "hubert_fe_forward_ragged");
+        bool full = false;
+        for (int i = 0; i < B; ++i) {
+            if (lens_host[i] < 400 || lens_host[i] > N_max)
+                RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_forward_ragged: item %d has %d samples (400 .. N_max = %lld)", i, lens_host[i], (long long)N_max);
+            full = full || lens_host[i] == N_max;
         }
-        _Float16 *A = (_Float16*)(ws + p.off_a), *Bb = (_Float16*)(ws + p.off_b);
-        double* part = (double*)(ws + p.off_part);
-        float *meanf = (float*)(ws + p.off_meanf), *scale = (float*)(ws + p.off_scale), *shift = (float*)(ws + p.off_shift);
-        const int L0 = p.L[0];
-        const dim3 gs((unsigned)p.nchunk, (unsigned)B), g0((unsigned)((L0 + F0_BLK - 1) / F0_BLK), (unsigned)B);
-        if (x_is_half) hipLaunchKernelGGL(k_hfe_stats<_Float16>, gs, dim3(256), 0, st, (const _Float16*)x_dev, (size_t)N, L0, part);
-        else hipLaunchKernelGGL(k_hfe_stats<float>, gs, dim3(256), 0, st, (const float*)x_dev, (size_t)N, L0, part);
-        hipLaunchKernelGGL(k_hfe_stats_final, dim3((unsigned)B), dim3(HC), 0, st, part, p.nchunk, L0, h->w0.as<float>(), h->gamma.as<float>(),
-                           h->beta.as<float>(), GN_EPS, meanf, scale, shift);
-        if (x_is_half)
-            hipLaunchKernelGGL(k_hfe_conv0<_Float16>, g0, dim3(256), 0, st, (const _Float16*)x_dev, (size_t)N, L0, h->w0.as<float>(), meanf, scale, shift, A);
-        else hipLaunchKernelGGL(k_hfe_conv0<float>, g0, dim3(256), 0, st, (const float*)x_dev, (size_t)N, L0, h->w0.as<float>(), meanf, scale, shift, A);
-        _Float16* cur = A;
-        for (int l = 1; l < NLAYERS; ++l) {
-            _Float16* dst = l == NLAYERS - 1 ? (_Float16*)out16_dev : (cur == A ? Bb : A);
-            gemm(cur, h->w[l].as<_Float16>(), dst, B, p.L[l - 1], TAPS[l], false, st);
-            cur = dst;
-        }
+        if (!full) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_forward_ragged: no item is N_max = %lld samples long", (long long)N_max);
+        const Plan p = plan_of(B, (int)N_max);
+        DeviceGuard dg(h->device);
+        hipStream_t st = (hipStream_t)stream;
+        char* ws = ws_dev ? (char*)ws_dev : own_workspace(h, p.bytes, st);
+        enqueue<true>(h, p, B, (size_t)N_max, lens_dev, x_dev, x_is_half, out16_dev, ws, st);
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -16,6 +16,12 @@
 //                      The weight fragment is the MFMA's A operand, so a lane ends with 4 consecutive output channels of one frame.
 //
 // No atomics anywhere and every reduction in a fixed order: results are bit-identical from run to run.
+//
+// RAGGED = true (rvcmi_hubert_fe_forward_ragged): item b is the first lens[b] samples of its row of a [B][N_max] batch, and every buffer keeps
+// the strides of N_max.  Each kernel takes the item's OWN row count from lens[b] where the dense one takes the launch's: the statistics chunks
+// and their merge, layer 0 and every GEMM row then see exactly what a lone call of that item sees (a chunk's content and the merge order depend
+// on the item's L0 alone, a GEMM output row on no other row of its tile, the K order is fixed), so the valid rows are bit-equal to that call.
+// Nothing behind an item's end is read; the last layer writes zeros there.  RAGGED = false compiles to the dense kernels unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +42,13 @@ constexpr int GM = 128, GN = 128, GK = 64, GPAD = 8;  // k_hfe_gemm: frames, cha
 
 __host__ __device__ inline int tri(int j, int k) { return j * K0 - j * (j - 1) / 2 + (k - j); }  // j <= k
 
+// rows after layer l (0 .. 6) of an n-sample input (n >= 400): 10 taps stride 5, then 3, 3, 3, 3, 2, 2 taps stride 2
+__host__ __device__ inline int rows_after(int n, int l) {
+    int L = (n - K0) / S0 + 1;
+    for (int i = 1; i <= l; ++i) L = (L - (i <= 4 ? 3 : 2)) / 2 + 1;
+    return L;
+}
+
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
 // sum over the block's 256 threads, in a fixed order: lanes by shuffle, then the four waves in wave order.  sh: [4] doubles.
@@ -48,11 +61,14 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
-// part [B][nchunk][ST_VALS]: the chunk's ten means, then its 55 co-moments about them.  grid (nchunk, B).
-template <typename T>
-__global__ void __launch_bounds__(256) k_hfe_stats(const T* __restrict__ x, size_t N, int L0, double* __restrict__ part) {
+// part [B][nchunk][ST_VALS]: the chunk's ten means, then its 55 co-moments about them.  grid (nchunk, B).  RAGGED: L0 is the item's own, and a
+// chunk wholly behind its end is skipped (it has no frames to average; k_hfe_stats_final does not read it).
+template <typename T, bool RAGGED>
+__global__ void __launch_bounds__(256) k_hfe_stats(const T* __restrict__ x, size_t N, int L0, double* __restrict__ part, const int* __restrict__ lens) {
     __shared__ double sh[4];
+    if (RAGGED) L0 = rows_after(lens[blockIdx.y], 0);
     const int f0 = blockIdx.x * ST_FRAMES, f1 = min(L0, f0 + ST_FRAMES);
+    if (RAGGED && f0 >= L0) return;
     const T* xb = x + (size_t)blockIdx.y * N;
     double s[K0];
 #pragma unroll
@@ -92,12 +108,19 @@ __global__ void __launch_bounds__(256) k_hfe_stats(const T* __restrict__ x, size
 
 // w0 [512][10] (the fp16-rounded weights as floats), gamma / beta [512].  -> meanf [B][10] (the input means as the floats k_hfe_conv0 subtracts),
 // scale / shift [B][512]: layer 0's output before the GELU is scale * sum_k w_k (x_k - meanf_k) + shift.  grid (B), 512 threads.
+// RAGGED: nchunk is the stride of ``part`` (the longest item's chunks); the item merges its own ceil(L0 / ST_FRAMES) and divides by its own L0.
+template <bool RAGGED>
 __global__ void __launch_bounds__(512) k_hfe_stats_final(const double* __restrict__ part, int nchunk, int L0, const float* __restrict__ w0,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, double eps,
-                                                         float* __restrict__ meanf, float* __restrict__ scale, float* __restrict__ shift) {
+                                                         float* __restrict__ meanf, float* __restrict__ scale, float* __restrict__ shift,
+                                                         const int* __restrict__ lens) {
     __shared__ double mean[K0], cov[K0 * K0];
     const int b = blockIdx.x, tid = threadIdx.x;
     const double* pb = part + (size_t)b * nchunk * ST_VALS;
+    if (RAGGED) {
+        L0 = rows_after(lens[b], 0);
+        nchunk = (L0 + ST_FRAMES - 1) / ST_FRAMES;
+    }
     auto rows = [&](int i) { return (double)(min(L0, (i + 1) * ST_FRAMES) - i * ST_FRAMES); };
     if (tid < K0) {
         double s = 0.0;
@@ -135,11 +158,15 @@ __global__ void __launch_bounds__(512) k_hfe_stats_final(const double* __restric
     shift[(size_t)b * HC + tid] = (float)((double)beta[tid] - (mu - mu_f) * sc);  // (what rounding the means to float left behind)
 }
 
-// out [B][L0][512] fp16.  grid (ceil(L0 / F0_BLK), B); thread: 8 channels (tid & 63) of 8 frames.
-template <typename T>
+// out [B][L0][512] fp16.  grid (ceil(L0 / F0_BLK), B); thread: 8 channels (tid & 63) of 8 frames.  RAGGED: L0 stays the row stride of ``out``,
+// the item stops at its own count.
+template <typename T, bool RAGGED>
 __global__ void __launch_bounds__(256) k_hfe_conv0(const T* __restrict__ x, size_t N, int L0, const float* __restrict__ w0, const float* __restrict__ meanf,
-                                                   const float* __restrict__ scale, const float* __restrict__ shift, _Float16* __restrict__ out) {
+                                                   const float* __restrict__ scale, const float* __restrict__ shift, _Float16* __restrict__ out,
+                                                   const int* __restrict__ lens) {
     const int oct = threadIdx.x & 63, fl = threadIdx.x >> 6, b = blockIdx.y;
+    const int Lb = RAGGED ? rows_after(lens[b], 0) : L0;
+    if (RAGGED && (int)blockIdx.x * F0_BLK >= Lb) return;
     const T* xb = x + (size_t)b * N;
     float w[8][K0], sc[8], sh[8], m[K0];
 #pragma unroll
@@ -154,7 +181,7 @@ __global__ void __launch_bounds__(256) k_hfe_conv0(const T* __restrict__ x, size
     for (int k = 0; k < K0; ++k) m[k] = meanf[b * K0 + k];
     for (int i = 0; i < F0_BLK / 4; ++i) {
         const int f = blockIdx.x * F0_BLK + fl * (F0_BLK / 4) + i;
-        if (f >= L0) break;
+        if (f >= Lb) break;
         const T* p = xb + (size_t)f * S0;
         float d[K0];
 #pragma unroll
@@ -173,14 +200,26 @@ __global__ void __launch_bounds__(256) k_hfe_conv0(const T* __restrict__ x, size
 
 // x [B][Lin][512] fp16, w [512][K] fp16 (K = taps * 512, tap-major), Lout = (Lin - taps) / 2 + 1.  OUT32 = false: out fp16 [B][Lout][512] =
 // GELU(conv); OUT32 = true (the test hook): out fp32, no activation.  grid (ceil(Lout / GM), 512 / GN, B), 256 threads.
-template <bool OUT32>
+// RAGGED (``layer`` 1 .. 6 of items of lens[b] samples): Lin / Lout are the row strides of x / out and the grid's extent; the item's own output
+// rows Lb follow from lens[b].  A tile wholly behind Lb returns before the K loop, so the cost follows the items' own lengths.  ``zero_tail``
+// (the last layer): rows Lb .. Lout of the item are written as zeros, by that early return and by the partial tile's epilogue.
+template <bool OUT32, bool RAGGED>
 __global__ void __launch_bounds__(256) k_hfe_gemm(const _Float16* __restrict__ x, const _Float16* __restrict__ w, void* __restrict__ out, int Lin, int Lout,
-                                                  int K) {
+                                                  int K, const int* __restrict__ lens, int layer, int zero_tail) {
     __shared__ _Float16 sW[GN][GK + GPAD], sX[GM][GK + GPAD];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, g = lane >> 4;
     const int wn = wave & 1, wm = wave >> 1;
     const int t0 = blockIdx.x * GM, n0 = blockIdx.y * GN, b = blockIdx.z;
     const _Float16* xb = x + (size_t)b * Lin * HC;
+    const int Lb = RAGGED ? rows_after(lens[b], layer) : Lout;  // the item's own output rows (<= Lout)
+    if (RAGGED && t0 >= Lb) {
+        if (zero_tail) {  // 128 rows x 128 channels of fp16 zeros: 16 lanes per row
+            const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int r = tid >> 4; r < GM && t0 + r < Lout; r += 16)
+                *(half8*)((_Float16*)out + ((size_t)b * Lout + t0 + r) * HC + n0 + (tid & 15) * 8) = z;
+        }
+        return;
+    }
     // a thread moves chunks (row, kc) = ((tid >> 3) + 32 i, tid & 7) of both tiles: 8 halves each
     const int lr = tid >> 3, kc = (tid & 7) * 8;
     const _Float16* wp[4];
@@ -190,7 +229,7 @@ __global__ void __launch_bounds__(256) k_hfe_gemm(const _Float16* __restrict__ x
     for (int i = 0; i < 4; ++i) {
         const int r = lr + 32 * i, t = t0 + r;
         wp[i] = w + (size_t)(n0 + r) * K + kc;
-        xv[i] = t < Lout;
+        xv[i] = t < Lb;
         xp[i] = xb + (size_t)(xv[i] ? t : 0) * (2 * HC) + kc;  // (stride 2: two input rows per frame)
     }
     const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -234,7 +273,14 @@ __global__ void __launch_bounds__(256) k_hfe_gemm(const _Float16* __restrict__ x
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int t = t0 + wm * 64 + i * 16 + l16;
-        if (t >= Lout) continue;
+        if (t >= Lb) {
+            if (RAGGED && zero_tail && t < Lout) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    *(half4*)((_Float16*)out + ((size_t)b * Lout + t) * HC + n0 + wn * 64 + j * 16 + g * 4) = half4{0, 0, 0, 0};
+            }
+            continue;
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const size_t o = ((size_t)b * Lout + t) * HC + n0 + wn * 64 + j * 16 + g * 4;

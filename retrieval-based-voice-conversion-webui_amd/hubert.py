@@ -11,13 +11,19 @@ the same attribute, ``[B, N]`` samples -> ``[B, 512, L]``, ``L = (N - 400) // 32
 Opt-in (``RVCMI_HUBERT_FE=1`` or ``rvc_amd.install(hubert_fe=True)``; default off): parity rests on seeded weights, not on a real
 ``hubert_base.pt``.  Operands and stored activations are fp16 (like the reference's own ``.half()`` HuBERT), accumulation
 and the GELU epilogues fp32, the GroupNorm statistics fp64.
+
+Several inputs in ONE pass (opt-in on top of the above: ``RVCMI_HUBERT_BATCH=1`` or ``rvc_amd.install(hubert_batch=True)``):
+``HubertFrontHIP.forward_ragged`` runs a zero-padded ``[B, N_max]`` batch whose items keep their own lengths -- layer 0's GroupNorm averages
+over the item's own frames, not over the padding -- and ``extract_features_batch`` hands such a batch to a fairseq-shaped model together
+with a sample mask (``sample_mask``) from which fairseq's ``forward_padding_mask`` derives exactly the frames behind each item's end.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import re
-from typing import Dict, Optional
+import contextlib
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -32,6 +38,16 @@ HUBERT_FE = False  # install(hubert_fe=True) sets it; RVCMI_HUBERT_FE=1 / =0 ove
 # extractor's range of times below torch's, not overlapping it, at every length it measured; the shortest of those is 1 s, and below it nothing
 # is measured, so shorter inputs stay where they were.
 MIN_SAMPLES = 16000
+HUBERT_BATCH = False  # install(hubert_batch=True) sets it; RVCMI_HUBERT_BATCH=1 / =0 overrides it per call.  Effective only with the switch above.
+# tools/hubert_batch_time.py (profiles/hubert_batch_time.json) found the batched call's range of times below the per-item loop's, not overlapping it, at
+# 2, 8 and 64 items of 12 s and on a mixed group of 3 - 12 s, for the extractor alone and for a fairseq-shaped HuBERT-base.  The switch stays off all the
+# same: that model is a stand-in with random weights, and the effect on a whole conversion is unmeasured.
+HUBERT_BATCH_MIN_ITEMS = 2    # with the switch on, a planned group of at least this many segments takes the batched call (2 x 12 s: 6.93 -> 5.06 ms)
+# A group's padded samples B * N_max may exceed the sum of its lengths by this fraction.  Measured on the mixed group planned at 0 / 0.1 / 0.25 / 0.5 / 1.0:
+# 37.5 / 22.8 / 13.9 / 11.4 / 10.8 ms against the loop's 40 - 42 -- fewer, larger groups won at every step.  At 1.0 the one group's actual waste was 0.57,
+# so a waste above that is unmeasured, and the bound stays at the largest setting that keeps every group inside what was.
+HUBERT_BATCH_MAX_WASTE = 0.5
+HUBERT_BATCH_MAX_SAMPLES = 64 * 12 * 16000  # B * N_max of one group (the extractor's workspace takes ~310 bytes per sample): the largest shape the timing tool runs
 
 
 def hubert_on() -> bool:
@@ -39,9 +55,71 @@ def hubert_on() -> bool:
     return env == "1" if env in ("0", "1") else bool(HUBERT_FE)
 
 
+def hubert_batch_on() -> bool:
+    env = os.environ.get("RVCMI_HUBERT_BATCH")
+    return hubert_on() and (env == "1" if env in ("0", "1") else bool(HUBERT_BATCH))
+
+
 def frames(n: int) -> int:
     """Output frames of an ``n``-sample input (0: too short)."""
     return (int(n) - 400) // 320 + 1 if n >= 400 else 0
+
+
+def _lens_list(lens) -> List[int]:
+    if torch.is_tensor(lens):
+        lens = lens.tolist()
+    return [int(n) for n in lens]
+
+
+def frame_mask(lens, N_max: int) -> torch.Tensor:
+    """bool ``[B, frames(N_max)]`` (on the host), True where ``t >= frames(lens[i])``: the frames item ``i``'s own call never computes."""
+    lens = _lens_list(lens)
+    t = torch.arange(frames(N_max)).unsqueeze(0)
+    return t >= torch.tensor([frames(n) for n in lens], dtype=torch.long).unsqueeze(1)
+
+
+def sample_mask(lens, N_max: int) -> torch.Tensor:
+    """bool ``[B, N_max]`` (on the host) from which fairseq's ``forward_padding_mask`` -- drop the ``N_max % L_max`` tail,
+    ``view(B, L_max, -1).all(-1)`` -- derives exactly ``frame_mask(lens, N_max)``: samples ``[t c, (t + 1) c)``, ``c = N_max // L_max``, are set
+    for every padded frame ``t`` and nothing else.  (The plain mask, True from sample ``lens[i]`` on, leaves one frame too many unmasked
+    whenever ``lens[i]`` is not a multiple of ``c``: that rule is only approximate.)"""
+    fm = frame_mask(lens, N_max)
+    B, L = fm.shape
+    if L < 1:
+        raise _lib.RvcmiError("sample_mask: N_max = %d is shorter than one frame (400 samples)" % N_max, code=_lib.ERR_INVALID)
+    c = int(N_max) // L
+    out = torch.zeros(B, int(N_max), dtype=torch.bool)
+    out[:, :L * c] = fm.unsqueeze(2).expand(B, L, c).reshape(B, L * c)
+    return out
+
+
+def plan_groups(lens, max_waste: Optional[float] = None, max_samples: Optional[int] = None) -> List[List[int]]:
+    """Host only.  Which inputs share a padded batch: the indices sorted by length (ties by index), consecutive runs packed while
+    ``B * N_max <= (1 + max_waste) * sum(lens)`` holds for the run (and ``B * N_max <= max_samples``).  -> lists of indices, every input in
+    exactly one; inputs under ``MIN_SAMPLES`` (below it nothing is measured) come back alone.  The same input gives the same plan."""
+    lens = _lens_list(lens)
+    w = HUBERT_BATCH_MAX_WASTE if max_waste is None else float(max_waste)
+    cap = HUBERT_BATCH_MAX_SAMPLES if max_samples is None else int(max_samples)
+    if w < 0:
+        raise ValueError("max_waste must be >= 0")
+    order = sorted(range(len(lens)), key=lambda i: (lens[i], i))
+    groups, cur, total = [], [], 0
+    for i in order:
+        n = lens[i]
+        if n < MIN_SAMPLES:
+            groups.append([i])
+            continue
+        # (ascending: n is the run's N_max once i has joined it)
+        if cur and (len(cur) + 1) * n <= (1.0 + w) * (total + n) and (len(cur) + 1) * n <= cap:
+            cur.append(i)
+            total += n
+        else:
+            if cur:
+                groups.append(cur)
+            cur, total = [i], n
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 _HF_CONV = re.compile(r"conv_layers\.(\d+)\.conv\.(weight|bias)$")
@@ -167,9 +245,84 @@ class HubertFrontHIP(torch.nn.Module):
     def workspace_bytes(self, B: int, N: int) -> int:
         return int(_lib.lib().rvcmi_hubert_fe_workspace_bytes(self._h, int(B), int(N)))
 
+    def workspace_bytes_ragged(self, B: int, N_max: int) -> int:
+        return int(_lib.lib().rvcmi_hubert_fe_workspace_bytes_ragged(self._h, int(B), int(N_max)))
+
+    _LENS_KEPT = 64
+
+    def _lens_dev(self, lens: tuple) -> torch.Tensor:
+        """The lengths on the device.  The last ``_LENS_KEPT`` tuples are kept (a group converted again uploads nothing); one used inside a stream
+        capture is kept for the handle's life, since the graph's kernels read it on every replay."""
+        kept = self.__dict__.setdefault("_lens_kept", {})
+        held = self.__dict__.setdefault("_lens_held", {})
+        t = held.get(lens)
+        if t is None:
+            t = kept.pop(lens, None)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if t is None:
+            if capturing:
+                raise _lib.RvcmiError("HubertFrontHIP.forward_ragged: these lengths are not on the device yet, and an upload cannot be captured; "
+                                      "call once with them before the capture (as for the handle's own workspace)")
+            t = torch.tensor(lens, dtype=torch.int32).to(self._device)
+        if capturing:
+            held[lens] = t
+        elif lens not in held:
+            kept[lens] = t  # (re-inserted: most recently used last)
+            while len(kept) > self._LENS_KEPT:
+                kept.pop(next(iter(kept)))
+        return t
+
+    def forward_ragged(self, x: torch.Tensor, lens, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``x`` ``[B, N_max]``: item ``i`` is its first ``lens[i]`` samples (host ints; at least 400 each, the longest ``N_max``); whatever
+        lies behind them is not read.  -> the same transposed view as ``forward``, ``[B, 512, frames(N_max)]``: item ``i``'s first
+        ``frames(lens[i])`` frames are bit-equal to ``forward`` of that item alone, the frames behind them exactly zero.  ``workspace``: as in
+        ``forward`` (``workspace_bytes_ragged(B, N_max)`` bytes).  Inside a stream capture the lengths must have been used once before."""
+        if not torch.is_tensor(x) or x.device.type != "cuda":
+            raise _lib.RvcmiError("HubertFrontHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(x, "device", type(x)))
+        if x.device != self._device:
+            raise _lib.RvcmiError("HubertFrontHIP: the input is on %s, the weights on %s" % (x.device, self._device))
+        if x.dim() != 2 or x.dtype not in (torch.float16, torch.float32):
+            raise _lib.RvcmiError("HubertFrontHIP: expected an fp16 or fp32 [B, N_max], got %s %s" % (x.dtype, tuple(x.shape)), code=_lib.ERR_INVALID)
+        lens = tuple(_lens_list(lens))
+        B, N = int(x.shape[0]), int(x.shape[1])
+        if len(lens) != B or B < 1 or min(lens) < 400 or max(lens) != N:
+            raise _lib.RvcmiError("HubertFrontHIP.forward_ragged: lens %s do not fit an input of shape %s (one length per item, each >= 400, the "
+                                  "longest equal to N_max)" % (list(lens[:8]), tuple(x.shape)), code=_lib.ERR_INVALID)
+        x = x.detach().contiguous()
+        out = torch.empty(B, frames(N), CHANNELS, device=x.device, dtype=torch.float16)
+        ws = 0
+        if workspace is not None:
+            need = self.workspace_bytes_ragged(B, N)
+            if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() < need or need == 0:
+                raise _lib.RvcmiError("HubertFrontHIP: the workspace must be %d uint8 on %s" % (need, x.device), code=_lib.ERR_INVALID)
+            ws = workspace.data_ptr()
+        host = (C.c_int * B)(*lens)
+        dev = self._lens_dev(lens)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().rvcmi_hubert_fe_forward_ragged(self._h, B, N, host, C.c_void_p(dev.data_ptr()), C.c_void_p(x.data_ptr()),
+                                                                 1 if x.dtype == torch.float16 else 0, C.c_void_p(out.data_ptr()), C.c_void_p(ws),
+                                                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        return out.to(x.dtype).transpose(1, 2)
+
+    @contextlib.contextmanager
+    def ragged(self, lens):
+        """Inside the block the plain ``forward(x)`` -- what a model calls on its ``feature_extractor`` -- is ``forward_ragged(x, lens)``: how
+        the lengths reach an extractor the model calls itself.  An ``x`` that does not fit ``lens`` raises.  Cleared on exit, exceptions too."""
+        lens = tuple(_lens_list(lens))
+        if self.__dict__.get("_ragged") is not None:
+            raise _lib.RvcmiError("HubertFrontHIP.ragged: already inside a ragged block")
+        object.__setattr__(self, "_ragged", lens)
+        try:
+            yield self
+        finally:
+            object.__setattr__(self, "_ragged", None)
+
     def forward(self, x: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``workspace``: a uint8 tensor of ``workspace_bytes(B, N)`` bytes to run in (nothing is allocated by the handle then); default: the
         handle's own, which grows on the first call of a larger shape -- such a call must not be inside a stream capture."""
+        lens = self.__dict__.get("_ragged")
+        if lens is not None:
+            return self.forward_ragged(x, lens, workspace)
         if not torch.is_tensor(x) or x.device.type != "cuda":
             raise _lib.RvcmiError("HubertFrontHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(x, "device", type(x)))
         if x.device != self._device:
@@ -205,6 +358,46 @@ def debug_conv(x16: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         _lib.check(_lib.lib().rvcmi_hubert_fe_debug_conv(taps, B, L_in, C.c_void_p(wh.data_ptr()), C.c_void_p(x16.data_ptr()), C.c_void_p(out.data_ptr()),
                                                          _lib.device_index(x16.device), C.c_void_p(torch.cuda.current_stream(x16.device).cuda_stream)))
     return out
+
+
+def batch_capable(model) -> bool:
+    """Whether ``extract_features_batch`` may run ``model``, by structure (like ``supported``): its ``feature_extractor`` is a swapped
+    ``HubertFrontHIP``, it is on the GPU and in eval mode, and it has fairseq's ``forward_padding_mask`` -- the method through which a
+    sample mask becomes the frame mask the encoder honours.  A model without it (one that ignores ``padding_mask``) would attend to the padding."""
+    fe = getattr(model, "feature_extractor", None)
+    if not isinstance(model, torch.nn.Module) or not isinstance(fe, HubertFrontHIP) or fe.__dict__.get("_original") is None:
+        return False
+    if model.training or not callable(getattr(model, "forward_padding_mask", None)) or not callable(getattr(model, "extract_features", None)):
+        return False
+    devs = {p.device for p in model.parameters()}
+    return len(devs) == 1 and next(iter(devs)) == fe._device
+
+
+def extract_features_batch(model, wavs: Sequence[torch.Tensor], output_layer) -> List[torch.Tensor]:
+    """``model.extract_features`` for SEVERAL waveforms (1-D, one dtype, fp16 or fp32; each at least 400 samples) in one call: zero-padded to the
+    longest, the extractor told the lengths (``HubertFrontHIP.ragged``), the model handed ``sample_mask`` -- so a padded frame is zeroed in front
+    of ``pos_conv`` and masked as an attention key, and no item sees another's or its own padding.  -> one ``[1, L_i, d]`` tensor per input,
+    ``L_i = frames(len(wavs[i]))``.  The extractor's rows are bit-equal to the lone calls'; the transformer's GEMMs see another M, so the result
+    equals the lone call's to operand rounding."""
+    if not batch_capable(model):
+        raise _lib.RvcmiError("extract_features_batch: the model is not batch_capable (swapped HubertFrontHIP extractor, GPU, eval mode, "
+                              "forward_padding_mask)", code=_lib.ERR_INVALID)
+    fe = model.feature_extractor
+    wavs = [torch.as_tensor(w) for w in wavs]
+    if not wavs or any(w.dim() != 1 for w in wavs) or len({w.dtype for w in wavs}) != 1:
+        raise _lib.RvcmiError("extract_features_batch: expected 1-D waveforms of one dtype", code=_lib.ERR_INVALID)
+    lens = [int(w.shape[0]) for w in wavs]
+    N = max(lens)
+    x = torch.zeros(len(wavs), N, dtype=wavs[0].dtype, device=fe._device)
+    for i, w in enumerate(wavs):
+        x[i, :lens[i]] = w.to(fe._device)
+    mask = sample_mask(lens, N).to(fe._device)
+    with torch.no_grad(), fe.ragged(lens):
+        logits = model.extract_features(source=x, padding_mask=mask, output_layer=output_layer)
+    y = logits[0]
+    if y.dim() != 3 or int(y.shape[0]) != len(wavs) or int(y.shape[1]) != frames(N):
+        raise _lib.RvcmiError("extract_features_batch: the model returned %s for %d items of %d frames" % (tuple(y.shape), len(wavs), frames(N)))
+    return [y[i:i + 1, :frames(n)].contiguous() for i, n in enumerate(lens)]
 
 
 def _holders(model):

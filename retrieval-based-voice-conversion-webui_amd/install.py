@@ -168,7 +168,7 @@ def _rebind_gate(rebound) -> None:
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
             patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False,
-            index_build: Optional[bool] = None, hubert_fe: bool = False) -> None:
+            index_build: Optional[bool] = None, hubert_fe: bool = False, hubert_batch: bool = False) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
@@ -180,7 +180,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     ``extract_index_ivf`` for the HIP index, so the unmodified index recipe (web.py:547-571: factory, nprobe, train, write, batched add,
     write) runs without faiss; any other description goes to the real faiss when there is one.  ``hubert_fe=True`` (opt-in, as
     ``RVCMI_HUBERT_FE=1``; default off): the conversion paths swap HuBERT's convolutional feature extractor for ``hubert.HubertFrontHIP``
-    (``hubert.accelerate_hubert``), once per model object."""
+    (``hubert.accelerate_hubert``), once per model object.  ``hubert_batch=True`` (opt-in, as ``RVCMI_HUBERT_BATCH=1``; default off;
+    effective only together with ``hubert_fe``): ``convert_files`` and a long input's segments run HuBERT once per planned group of segments
+    (``hubert.extract_features_batch``) instead of once per segment, for a model that honours ``padding_mask`` (``hubert.batch_capable``)."""
     if _state.get("installed"):
         return
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
@@ -252,6 +254,7 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     from . import hubert as _hubert
 
     _hubert.HUBERT_FE = bool(hubert_fe)
+    _hubert.HUBERT_BATCH = bool(hubert_batch)
 
 
 def uninstall() -> None:
@@ -279,4 +282,5 @@ def uninstall() -> None:
     from . import hubert as _hubert
 
     _hubert.HUBERT_FE = False
+    _hubert.HUBERT_BATCH = False
     _state.clear()

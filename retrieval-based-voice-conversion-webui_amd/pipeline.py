@@ -66,29 +66,72 @@ def _is_hip_index(index) -> bool:
     return isinstance(index, IVFFlatHIP)
 
 
-def hubert_device(self, model, audio0, pitch, pitchf, version):
-    """The HuBERT half of ``Pipeline.vc`` (pipeline.py:90-112, 146-151): -> (feats [1, nq, d] on the GPU, BEFORE retrieval,
-    pitch [1, p_len] or None, pitchf or None, p_len)."""
-    dev = torch.device(self.device)
+def _hubert_wave(self, audio0):
+    """The waveform as HuBERT takes it (pipeline.py:93-99): 1-D, fp16 / fp32 by ``is_half``, two channels averaged."""
     feats = torch.as_tensor(audio0)
     feats = feats.half() if self.is_half else feats.float()
     if feats.dim() == 2:  # double channels (pipeline.py:98-99)
         feats = feats.mean(-1)
     assert feats.dim() == 1, feats.dim()
-    feats = feats.view(1, -1)
-    padding_mask = torch.zeros(feats.shape, dtype=torch.bool, device=dev)
-    from .hubert import accelerate_hubert_once
+    return feats
 
-    accelerate_hubert_once(model)  # (beyond SURVEY 8; opt-in, a no-op with the switch off) the extractor's seven convolutions on HIP
-    with torch.no_grad():
-        logits = model.extract_features(source=feats.to(dev), padding_mask=padding_mask, output_layer=9 if version == "v1" else 12)
-        feats = model.final_proj(logits[0]) if version == "v1" else logits[0]
+
+def hubert_device(self, model, audio0, pitch, pitchf, version, feats=None):
+    """The HuBERT half of ``Pipeline.vc`` (pipeline.py:90-112, 146-151): -> (feats [1, nq, d] on the GPU, BEFORE retrieval,
+    pitch [1, p_len] or None, pitchf or None, p_len).  ``feats``: the model's output for this segment when it has been computed already
+    (``hubert_device_many``); only the tail -- ``final_proj``, ``p_len``, the pitch cut -- runs then."""
+    if feats is None:
+        dev = torch.device(self.device)
+        feats = _hubert_wave(self, audio0).view(1, -1)
+        padding_mask = torch.zeros(feats.shape, dtype=torch.bool, device=dev)
+        from .hubert import accelerate_hubert_once
+
+        accelerate_hubert_once(model)  # (beyond SURVEY 8; opt-in, a no-op with the switch off) the extractor's seven convolutions on HIP
+        with torch.no_grad():
+            logits = model.extract_features(source=feats.to(dev), padding_mask=padding_mask, output_layer=9 if version == "v1" else 12)
+            feats = model.final_proj(logits[0]) if version == "v1" else logits[0]
+    elif version == "v1":
+        with torch.no_grad():
+            feats = model.final_proj(feats)
     use_f0 = pitch is not None and pitchf is not None
     nq = int(feats.shape[1])
     p_len = min(int(audio0.shape[0]) // self.window, 2 * nq)  # pipeline.py:146-151
     if use_f0:
         pitch, pitchf = pitch[:, :p_len], pitchf[:, :p_len]
     return feats, (pitch if use_f0 else None), (pitchf if use_f0 else None), p_len
+
+
+def hubert_batched(model) -> bool:
+    """Whether the segments of a call go through ``hubert_device_many``'s grouped path: both switches on (``RVCMI_HUBERT_FE`` and
+    ``RVCMI_HUBERT_BATCH``, off by default) and a model that honours ``padding_mask`` (``hubert.batch_capable``).  Swaps the extractor first."""
+    from . import hubert as hb
+
+    if not hb.hubert_batch_on():
+        return False
+    hb.accelerate_hubert_once(model)
+    return hb.batch_capable(model)
+
+
+def hubert_device_many(self, model, pending, version):
+    """``hubert_device`` for every ``(audio0, pitch, pitchf)`` of ``pending``, in that order, with HuBERT run ONCE per planned group of
+    segments of similar length (``hubert.plan_groups`` / ``hubert.extract_features_batch``: a ragged batch) instead of once
+    per segment.  A group of fewer than ``hubert.HUBERT_BATCH_MIN_ITEMS`` segments, and everything when ``hubert_batched(model)`` is false,
+    takes the per-segment call."""
+    from . import hubert as hb
+
+    out = [None] * len(pending)
+    if not pending or not hubert_batched(model):
+        return [hubert_device(self, model, a0, pt, pf, version) for a0, pt, pf in pending]
+    waves = [_hubert_wave(self, a0) for a0, _, _ in pending]
+    layer = 9 if version == "v1" else 12
+    for group in hb.plan_groups([int(w.shape[0]) for w in waves], hb.HUBERT_BATCH_MAX_WASTE):
+        if len(group) < hb.HUBERT_BATCH_MIN_ITEMS:
+            for i in group:
+                out[i] = hubert_device(self, model, *pending[i], version)
+            continue
+        for i, f in zip(group, hb.extract_features_batch(model, [waves[i] for i in group], layer)):
+            out[i] = hubert_device(self, model, *pending[i], version, feats=f)
+    return out
 
 
 def features_device(self, model, audio0, pitch, pitchf, times, index, index_rate, version, protect):
@@ -603,7 +646,8 @@ def pipeline_hip(self, model, net_g, sid, audio, times, f0_up_key, f0_method, fi
         from time import time
 
         t0 = time()
-        items = blend_segments([hubert_device(self, model, a0, pt, pf, version) for a0, pt, pf in pending], index, index_rate, protect)
+        # (RVCMI_HUBERT_FE + RVCMI_HUBERT_BATCH, opt-in: HuBERT once per group of segments; otherwise the per-segment calls, in this order)
+        items = blend_segments(hubert_device_many(self, model, pending, version), index, index_rate, protect)
         times[0] += time() - t0
         segs = infer_segments(net_g, sid, items, times)
     else:
@@ -638,7 +682,11 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
     filters agree to fp64 rounding noise only, which moves about half of the fp32 input samples by one ulp (bit-equal again with the threshold at 0).
     A second one, with the HIP estimator switched on: a file's f0 inside a group equals that of its lone call to operand rounding, not bit for
     bit -- no sequence reads another's frames, but the U-Net layers that split their K loop choose the split from the launch size, which is
-    the group's (bit-equal with the group switch off).  A synthesizer that is not the HIP one, or an
+    the group's (bit-equal with the group switch off).  A third one, with the HIP feature extractor and its group switch on
+    (``RVCMI_HUBERT_FE=1`` and ``RVCMI_HUBERT_BATCH=1``, both off by default) and a model that honours ``padding_mask``
+    (``hubert.batch_capable``): the HuBERT features of a segment inside a group equal those of its lone call to operand rounding, not bit for
+    bit -- the extractor's rows are bit-equal and no segment attends to another or to padding, but the transformer's GEMMs on torch see
+    another M (bit-equal with the group switch off).  A synthesizer that is not the HIP one, or an
     index only real faiss reads, or ``RVCMI_PIPELINE_BATCH=0``, takes the plain per-file loop over ``self.pipeline``."""
     audios = list(audios)
     f0_files = list(f0_files) if f0_files is not None else [None] * len(audios)
@@ -682,10 +730,16 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
             times[1] += time() - t1
             for i, pair in zip(todo, pairs or ()):
                 f0_pairs[i] = pair
+    # RVCMI_HUBERT_FE + RVCMI_HUBERT_BATCH (opt-in): the segments are only gathered in the loop and HuBERT runs once per planned group of them behind it
+    batch_hubert = hubert_batched(model)
+    pending = []
     for i, (a, f0f) in enumerate(zip(audios, f0_files)):
         def collect(a0, pt, pf, i=i):
             t0 = time()
-            raw.append(hubert_device(self, model, a0, pt, pf, version))
+            if batch_hubert:
+                pending.append((a0, pt, pf))
+            else:
+                raw.append(hubert_device(self, model, a0, pt, pf, version))
             owner.append(i)
             times[0] += time() - t0
 
@@ -694,6 +748,8 @@ def convert_files(self, model, net_g, sid, audios, times, f0_up_key, f0_method, 
         # (of the device copy only what change_rms reads is kept while the group's other files are prepared)
         filtered.append((got[0], got[2].float() if got[2] is not None and rms_mix_rate != 1 else None))
     t0 = time()
+    if batch_hubert:
+        raw = hubert_device_many(self, model, pending, version)  # same tuples, same order as the per-segment calls
     items = blend_segments(raw, index, index_rate, protect)
     times[0] += time() - t0
     outs = infer_segments(net_g, sid, items, times)

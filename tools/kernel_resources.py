@@ -5,9 +5,9 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "retrieval-based-voice-conversion-webui_amd", "csrc")
 KEEP = ("k_lm_", "k_add_", "k_rb_pair", "k_rb_full", "k_rb_stream", "k_frame_rms", "k_change_rms", "k_ups", "k_conv_mfma", "k_post", "k_scan", "k_coarse", "k_blend", "k_fr_", "k_sola", "k_f0_post",
-        "k_rmvpe", "k_phase_scan", "k_sine", "k_unet", "k_gru")
+        "k_rmvpe", "k_phase_scan", "k_sine", "k_unet", "k_gru", "k_hfe")
 with tempfile.TemporaryDirectory() as tmp:
-    for src in ("nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "rmvpe.hip", "unet.hip", "gru.hip"):
+    for src in ("nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "rmvpe.hip", "unet.hip", "gru.hip", "hubert_fe.hip"):
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-O3", "-std=c++17", "-c", os.path.join(CSRC, src), "-o",
                         os.path.join(tmp, src + ".o"), "-save-temps=obj"], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         asm = [f for f in os.listdir(tmp) if f.startswith(src.split(".")[0] + "-hip-amdgcn") and f.endswith(".s")]
