@@ -814,10 +814,14 @@ __device__ __forceinline__ void conv_prefetch(typename Op<OpT>::frag (&A)[NB][KG
 //   * the ds_reads of the NEXT k-step and the global weight loads of group g+NB-1 are spread one per MFMA and the
 //     order is pinned with sched_group_barrier (MFMA, DS_READ, MFMA, DS_READ, ..., MFMA, VMEM, ...).
 // Measured in tools/ubench/kloop.hip (C=64, k=7): 58.5 -> see DESIGN.md cycles per MFMA.
-template <typename OpT, int CIN, int MI, int NJ, int KGROUP, int NB>
+// REAL (only where a k-group holds several taps, C_in < 16 * KGROUP): the packed tap count is rounded up to a whole k-group, so the
+// last group ends in taps of zero weights.  `nks` = k-steps that carry real taps (taps * CC); the wave leaves the last group at the
+// first tap boundary at or behind it (wave-uniform), skipping the MFMAs, the B reads and the ring requests of the dead slots.
+// nks >= ntaps_p * CC runs the padded loop.
+template <typename OpT, int CIN, int MI, int NJ, int KGROUP, int NB, bool REAL = false>
 __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>::frag (&A)[NB][KGROUP][MI],
                                          const char* lds_lane, const OpT* wlane, long ct_stride, int ntaps_p, int roff,
-                                         int dstep, int dbg = 0) {
+                                         int dstep, int dbg = 0, int nks = 0) {
     using frag = typename Op<OpT>::frag;
     using TL = Tile<CIN>;
     constexpr int CC = TL::CC;
@@ -830,6 +834,7 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
     const int NG = ntaps_p * CC / KGROUP;
     const int dS = dstep * STRIDE;
     (void)dbg;
+    (void)nks;
 
     // byte offset of k-step k of a group relative to the group base
     auto koff = [&](int k) { return (CC >= KGROUP) ? k * 32 : (k / CC) * dS + (k % CC) * 32; };
@@ -872,6 +877,8 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
                 // 24 MFMAs = the 37 instead of 32 cycles per MFMA measured in round 2).
 #pragma unroll
                 for (int k = 0; k < KGROUP; ++k) {
+                    if constexpr (REAL && TPG > 1)
+                        if (k > 0 && k % CC == 0 && g * KGROUP + k >= nks) goto done;  // only zero taps are left
                     const char* nbp = (k + 1 < KGROUP) ? gb + koff(k + 1) : gbn + koff(0);
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi)
@@ -924,6 +931,7 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
             }
         }
     }
+done:;
 }
 
 // ---- the lean K loop (round 3) ---------------------------------------------------------------------------------------
@@ -1943,6 +1951,7 @@ struct RbFullArgs {
     int yh;  // 1: dst streams are fp16 (pack4_h), same element layout
     int xh;  // 1: src (X0, the start of the fp32 residual stream) is fp16 (option X0_F16)
     unsigned long long* ts;  // dbg & 32: per-wave s_memtime stamps [block][wave][16]
+    int pad_tap;  // 1: C <= 32 also multiplies the zero taps that round k up to a whole k-group (option RBF_PAD_TAP)
 };
 
 constexpr int RBF_G = 32;   // zero guard rows around X (>= max dilated half-width + one padded tap)
@@ -2149,6 +2158,9 @@ static __global__ void __launch_bounds__(64 * NWV, OCC) k_rb_full(RbFullArgs a) 
     const char* xl = X + (size_t)(slab + (lane & 31)) * STRIDE + (lane >> 5) * 16;
     const char* hl = H + (size_t)(slab + (lane & 31)) * STRIDE + (lane >> 5) * 16;
     const int p2 = (J.k - 1) / 2;
+    // C <= 32: a k-group is 2 (C = 32) or 4 (C = 16) taps and k = 11 / 7 / 3 is packed as 12 / 8 / 4; the K loops stop behind the real taps
+    constexpr bool REAL = TL::CC < KG;
+    const int nks = (REAL && !a.pad_tap ? J.k : J.k_p) * TL::CC;
 
     for (int m = 0; m < J.nd; ++m) {
         const int p1 = J.dil[m] * (J.k - 1) / 2;
@@ -2167,7 +2179,7 @@ static __global__ void __launch_bounds__(64 * NWV, OCC) k_rb_full(RbFullArgs a) 
                         for (int e = 0; e < 4; ++e) hacc[mi][jt][4 * g + e] = bv[e];
                 }
         }
-        conv_run<OpT, C, MI, NJ, KG, NB>(hacc, A, xl, (const OpT*)J.w1[m] + lane * 8, J.ct1, J.k_p, RBF_G - p1, J.dil[m], a.dbg);
+        conv_run<OpT, C, MI, NJ, KG, NB, REAL>(hacc, A, xl, (const OpT*)J.w1[m] + lane * 8, J.ct1, J.k_p, RBF_G - p1, J.dil[m], a.dbg, nks);
         conv_prefetch<OpT, C, MI, KG, NB>(A, (const OpT*)J.w2[m] + lane * 8, J.ct2, J.k_p);  // in flight across the publish + barrier
         if (m == 0) stamp();  // 4: conv1 done
         if (interior) publish_operand<OpT, C, MI, NJ, STRIDE, false>(hw, hacc, rowmask);
@@ -2189,7 +2201,7 @@ static __global__ void __launch_bounds__(64 * NWV, OCC) k_rb_full(RbFullArgs a) 
                         for (int e = 0; e < 4; ++e) xacc[mi][jt][4 * g + e] += bv[e];
                 }
         }
-        conv_run<OpT, C, MI, NJ, KG, NB>(xacc, A, hl, (const OpT*)J.w2[m] + lane * 8, J.ct2, J.k_p, RBF_G2 - p2, 1, a.dbg);
+        conv_run<OpT, C, MI, NJ, KG, NB, REAL>(xacc, A, hl, (const OpT*)J.w2[m] + lane * 8, J.ct2, J.k_p, RBF_G2 - p2, 1, a.dbg, nks);
         if (m + 1 < J.nd) conv_prefetch<OpT, C, MI, KG, NB>(A, (const OpT*)J.w1[m + 1] + lane * 8, J.ct1, J.k_p);
         if (m == 0) stamp();  // 7: conv2 done
         if (m + 1 < J.nd) {  // publish lrelu(x') for the next pair
