@@ -157,7 +157,7 @@ def search_blend(index: dict, feats: np.ndarray, index_rate: float, k: int = 8) 
 
 # ----------------------------------------------------------------------------------------------
 # faiss on-disk format (IndexIVFFlat, METRIC_L2) -- independent python reader/writer used to
-# cross-check the C++ reader in the product (csrc/ivf_io.cpp).
+# cross-check the C++ reader in the product (csrc/ivf_format.hpp).
 # ----------------------------------------------------------------------------------------------
 
 def _index_header(d: int, ntotal: int, metric: int = 1) -> bytes:

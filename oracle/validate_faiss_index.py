@@ -13,7 +13,7 @@ queries, this tool reports exactly where the restatement and faiss disagree:
     #   q = (big[np.random.default_rng(0).integers(0, ix.ntotal, 599)] + 0.05).astype("float32")
     #   D, I = ix.search(q, 8); np.savez("qdi.npz", q=q, D=D, I=I, big_head=big[:64])
 
-Checks: (1) layout -- every fourcc / header field / vector length against what csrc/ivf.hip and oracle/ivf_oracle.py expect,
+Checks: (1) layout -- every fourcc / header field / vector length against what csrc/ivf_format.hpp and oracle/ivf_oracle.py expect,
 without stopping at the first surprise; (2) ``reconstruct_n`` rows vs ``big_head`` when present; (3) search -- the CPU oracle
 (fp64 distances, ties -> lowest id) and, on a GPU box, the HIP index read by the product's own C++ reader, against faiss'
 (D, I): identical top-1, identical top-k sequence, same top-k SET (order flips inside exact/near ties are benign: faiss

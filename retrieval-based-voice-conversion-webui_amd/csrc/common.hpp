@@ -1,8 +1,9 @@
-// Shared host-side plumbing for librvcmi.so: error reporting across the C ABI, HIP call checking,
+// Shared host-side plumbing for librvcmi.so: error reporting across the C ABI (error.hpp), HIP call checking,
 // device buffers and the HIP-event kernel profiler used by bench.py's roofline leg.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -14,20 +15,9 @@
 #include <vector>
 
 #include "../../include/rvcmi.h"
+#include "error.hpp"
 
 namespace rvcmi {
-
-void set_error(const char* fmt, ...);
-
-struct Error {
-    int code;
-};
-
-#define RVCMI_FAIL(code_, ...)            \
-    do {                                  \
-        ::rvcmi::set_error(__VA_ARGS__);  \
-        throw ::rvcmi::Error{(code_)};    \
-    } while (0)
 
 #define HIP_CHECK(expr)                                                                          \
     do {                                                                                         \
@@ -36,23 +26,6 @@ struct Error {
             RVCMI_FAIL(RVCMI_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),     \
                        __FILE__, __LINE__);                                                      \
     } while (0)
-
-// Every extern "C" body runs inside this so that nothing throws across the ABI.
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return RVCMI_OK;
-    } catch (const Error& e) {
-        return e.code;
-    } catch (const std::exception& e) {
-        set_error("exception: %s", e.what());
-        return RVCMI_ERR_INVALID;
-    } catch (...) {
-        set_error("unknown exception");
-        return RVCMI_ERR_INVALID;
-    }
-}
 
 // Makes `device` current for the scope and restores the caller's device afterwards (the thread's current device is torch's too).
 struct DeviceGuard {
@@ -68,6 +41,21 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// CUs of the current device (cached per device).
+inline int num_cus() {
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    int v = cached[dev & 63].load();
+    if (!v) {
+        hipDeviceProp_t p;
+        HIP_CHECK(hipGetDeviceProperties(&p, dev));
+        v = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+        cached[dev & 63].store(v);
+    }
+    return v;
+}
 
 struct DevBuf {
     void* p = nullptr;

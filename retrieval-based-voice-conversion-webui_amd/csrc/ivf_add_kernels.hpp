@@ -1,6 +1,6 @@
 // index.add on the device (web.py:561-563: `index.add(big_npy[i : i + batch_size_add])`): the rows of a batch are appended to the
 // inverted lists of their nearest centroids, ids ntotal .. ntotal + n - 1, without a host hop.  Included by ivf.hip (after the coarse
-// kernels, whose exact assignment is the input here).
+// kernels of ivf_kernels.hpp, whose exact assignment is the input here).
 //
 // The new blob has the layout of build_blob for ntotal + n rows.  With cnt[l] = new rows of list l and shift = exclusive scan of cnt:
 //   new_off[l]            = old_off[l] + shift[l]

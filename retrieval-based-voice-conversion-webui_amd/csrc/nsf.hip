@@ -16,16 +16,6 @@
 
 namespace rvcmi {
 
-thread_local std::string g_last_error;
-void set_error(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
-
 struct Geom {
     int MI, NJ, WCO, TT;
 };
@@ -1428,9 +1418,6 @@ static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float
 
 // ---- C ABI -------------------------------------------------------------------------------------
 extern "C" {
-
-const char* rvcmi_last_error(void) { return g_last_error.c_str(); }
-int rvcmi_version(void) { return RVCMI_VERSION; }
 
 int rvcmi_nsf_create(const rvcmi_nsf_config* cfg, const rvcmi_tensor* weights, int n_weights, int device, int max_B,
                      int max_T, rvcmi_nsf** out) {

@@ -16,8 +16,6 @@
 //  k_rb_stream in round 3; removed in round 5, `git log -- csrc/rb_stream2_kernels.hpp` has them.)
 
 namespace rvcmi {
-int num_cus();
-
 namespace {
 
 #ifndef RS_KL_DEFAULT
@@ -83,20 +81,6 @@ void launch_t(int C, int nd, int NJ, const RbStreamArgs& a, int nblocks, int B, 
 }
 
 }  // namespace
-
-int num_cus() {
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    int v = cached[dev & 63].load();
-    if (!v) {
-        hipDeviceProp_t p;
-        HIP_CHECK(hipGetDeviceProperties(&p, dev));
-        v = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-        cached[dev & 63].store(v);
-    }
-    return v;
-}
 
 void rb_stream_prepare() {
     RbStreamArgs a;

@@ -530,6 +530,14 @@ def test_reader_and_object_reject_what_they_do_not_support_with_a_clear_message(
     open(p, "wb").write(bad)
     with pytest.raises(rvc_amd.RvcmiError, match="quantizer"):
         rvc_amd.read_index(p, device=gpu)
+    # list sizes that sum to ntotal modulo 2^64 (tests/test_cpu_ivf_format.py has the other crafted files): refused on the host
+    import ivf_cases
+
+    p = str(tmp_path / "wrapped.index")
+    open(p, "wb").write(ivf_cases.crafted(**ivf_cases.WRAPPED_SIZES))
+    with pytest.raises(rvc_amd.RvcmiError) as ei:
+        rvc_amd.read_index(p, device=gpu)
+    assert ei.value.code == rvc_amd._lib.ERR_IO
     h = rvc_amd.read_index(good, device=gpu)
     with pytest.raises(rvc_amd.RvcmiError, match="at most 8"):
         h.search(np.zeros((2, 64), np.float32), 9)
@@ -573,7 +581,7 @@ def test_reduce_features_quality_against_the_reference_minibatch_kmeans_call(gpu
     What it found (round 5): on WELL-SEPARATED blobs -- the adversarial case for a random initialisation: some blobs start without a
     centre, others with two, and plain Lloyd iterations never repair that -- ``rvc_amd.reduce_features`` ended 1.43x ABOVE the reference call
     (4.15e6 vs 2.90e6; the optimum is 1.92e6): sklearn re-seeds low-count centres every batch, ours re-seeded only EMPTY ones.  The build now
-    relocates centres (ivf.hip ``ivf_build_impl``: the centre that is cheapest to delete moves to the farthest point of the cluster with
+    relocates centres (ivf_kmeans.hpp ``kmeans_relocate``: the centre that is cheapest to delete moves to the farthest point of the cluster with
     the largest distortion whenever the exact gain exceeds the deletion cost -- the objective cannot go up): **0.66x** the reference call's
     objective, i.e. the optimum.  On rows without such structure (second case: one broad Gaussian, the regime of real HuBERT features) no
     move passes the gain test and the result is the plain iterations': 0.98x."""

@@ -1,4 +1,4 @@
-"""dev: numpy prototype of the centre relocation of ivf_build_impl (csrc/ivf.hip, round 5) next to the reference call of web.py:522-536
+"""dev: numpy prototype of the centre relocation of the index build (csrc/ivf_kmeans.hpp kmeans_relocate, round 5) next to the reference call of web.py:522-536
 (sklearn MiniBatchKMeans, init="random"): objective ratio with / without relocation on separated blobs and on a broad Gaussian, and that the
 objective never increases.  python tools/proto_kmeans_relocation.py"""
 import numpy as np, time
@@ -29,7 +29,7 @@ def lloyd(x,k,niter,reloc,seed=0,R_frac=0.05):
             order_rm=np.argsort(cost)
             order_sp=np.argsort(-S)
             # used: moved centre / split cluster / receiver of a move of this iteration; moved: centres no longer at their old place -- a later
-            # candidate whose nearest centre was moved has a stale cost and is skipped (same rule as csrc/ivf.hip)
+            # candidate whose nearest centre was moved has a stale cost and is skipped (same rule as csrc/ivf_kmeans.hpp)
             used=set(); moved=set(); nrel=0; R=max(1,int(k*R_frac)); si=0
             small=lambda o: n[o]<2
             for j in order_rm[:4*R]:
