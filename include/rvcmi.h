@@ -66,7 +66,11 @@ int rvcmi_version(void);
 typedef enum {
     RVCMI_OPERAND_F32 = 0,   /* exact-fp32 VALU convolutions (bring-up / highest fidelity) */
     RVCMI_OPERAND_BF16 = 1,  /* bf16 MFMA operands, fp32 accumulate + fp32 residual stream */
-    RVCMI_OPERAND_F16 = 2    /* fp16 MFMA operands, fp32 accumulate + fp32 residual stream */
+    RVCMI_OPERAND_F16 = 2,   /* fp16 MFMA operands, fp32 accumulate + fp32 residual stream */
+    RVCMI_OPERAND_F16X2 = 3  /* FRONT ONLY (rvcmi_front_config; rvcmi_nsf_create rejects it): every MFMA operand a (hi, lo) pair of fp16
+                              * values, three fp16 MFMAs per k-step, fp32 accumulate -- fp32-grade enc_p / flow on the fp16 matrix cores.
+                              * One launch form per layer: rvcmi_front_set_option returns RVCMI_ERR_INVALID for a key / value that
+                              * selects a fused or split form (FR_NO_FFN_FUSION 0, FR_FFN_SPLIT != 0, FR_WN_SPLIT != 1, FR_STAMPS != 0). */
 } rvcmi_operand;
 
 /* Mirrors the positional `cpt["config"]` list consumed by rvc/synthesizer.py:10-22
@@ -184,7 +188,7 @@ typedef struct {
     int flow_n_layers;        /* 3  (synthesizers.py:111-113)                                   */
     int flow_kernel_size;     /* 5                                                              */
     int flow_dilation_rate;   /* 1                                                              */
-    int operand;              /* RVCMI_OPERAND_F16 / _BF16 (MFMA operands; everything else fp32) */
+    int operand;              /* RVCMI_OPERAND_F16 / _BF16 / _F16X2 (MFMA operands; everything else fp32) */
 } rvcmi_front_config;
 
 typedef struct rvcmi_front rvcmi_front;

@@ -18,7 +18,7 @@ SOURCES = ["error.cpp", "nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glu
 
 RVCMI_MAX_UPS, RVCMI_MAX_RB, RVCMI_MAX_DIL = 8, 4, 4
 RVCMI_VERSION = 2  # include/rvcmi.h; the argument lists of SYMBOLS below are those of this ABI version
-OPERANDS = {"fp32": 0, "f32": 0, "bf16": 1, "fp16": 2, "f16": 2}
+OPERANDS = {"fp32": 0, "f32": 0, "bf16": 1, "fp16": 2, "f16": 2, "fp16x2": 3}  # fp16x2: the front only (RVCMI_OPERAND_F16X2)
 
 
 class NsfConfig(C.Structure):

@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "nsf_kernels.hpp"
+#include "split_f16.hpp"
 
 namespace rvcmi {
 
@@ -84,7 +85,10 @@ static void build_conv(ConvLayer& L, int cin, int cout, int nphase, const int* n
     const int KSP = L.ntaps_p * CC;
     const int ctiles = (cout + 31) / 32;
     L.ct_stride = (long)KSP * 512;
-    std::vector<uint16_t> pk((size_t)nphase * ctiles * L.ct_stride, 0);
+    // RVCMI_OPERAND_F16X2 (front only): a hi plane in exactly the fp16 layout, then the lo plane (split_f16.hpp) in the same layout
+    const bool pair = operand == RVCMI_OPERAND_F16X2;
+    const size_t plane = (size_t)nphase * ctiles * L.ct_stride;
+    std::vector<uint16_t> pk(plane * (pair ? 2 : 1), 0);
     for (int p = 0; p < nphase; ++p) {
         L.pack_off[p] = (long)p * ctiles * L.ct_stride;
         for (int ct = 0; ct < ctiles; ++ct)
@@ -97,7 +101,13 @@ static void build_conv(ConvLayer& L, int cin, int cout, int nphase, const int* n
                         for (int e = 0; e < 8; ++e) {
                             const int ci = cc * 16 + 8 * (lane >> 5) + e;
                             const float v = W(co, ci, p, tap);
-                            dst[lane * 8 + e] = operand == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
+                            if (pair) {
+                                const SplitF16 sp = split_f16(v);
+                                dst[lane * 8 + e] = sp.hi;
+                                dst[plane + lane * 8 + e] = sp.lo;
+                            } else {
+                                dst[lane * 8 + e] = operand == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
+                            }
                         }
                     }
                 }

@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "conv_pack.hpp"
 #include "front_kernels.hpp"
+#include "front_split_kernels.hpp"
 
 using namespace rvcmi;
 
@@ -87,6 +88,9 @@ static int pick_nj(const rvcmi_front* h, int B, int T) {
     return (long)B * ((T + 63) / 64) >= 192 ? 2 : 1;
 }
 
+template <typename OpT>
+constexpr bool PAIR = std::is_same<OpT, F16x2>::value;  // the fp16x2 mode: one launch form per layer, every operand two planes
+
 template <typename OpT, int CIN, int MI, int NW, int EPI, int NJ>
 void launch_conv_nj(rvcmi_front* h, const char* name, FrConvArgs a, const ConvLayer& L, int B, hipStream_t st) {
     a.w = L.w_pack.p;
@@ -96,7 +100,10 @@ void launch_conv_nj(rvcmi_front* h, const char* name, FrConvArgs a, const ConvLa
     a.cout = L.cout;
     constexpr int TT = NJ * 32;
     const int rows = TT + a.ntaps - 1 + 2;
-    const size_t smem = std::max<size_t>((size_t)rows * Tile<CIN>::STRIDE, 2 * NW * NJ * 32 * sizeof(float));
+    // (F16x2: two planes of a chunk of the input channels, no look-ahead rows; front_split_kernels.hpp)
+    const size_t tile = PAIR<OpT> ? 2 * (size_t)(TT + a.ntaps - 1) * FsTile<CIN>::STRIDE : (size_t)rows * Tile<CIN>::STRIDE;
+    const size_t smem = std::max<size_t>(tile, 2 * NW * NJ * 32 * sizeof(float));
+    if (smem > 160 * 1024) RVCMI_FAIL(RVCMI_ERR_INVALID, "front: %s with %d taps needs %zu bytes of LDS", name, a.ntaps, smem);
     const int ctiles = (L.cout + 31) / 32;
     const int gy = (ctiles + NW * MI - 1) / (NW * MI);
     auto kern = k_fr_conv<OpT, CIN, MI, NJ, NW, EPI>;
@@ -190,13 +197,36 @@ void launch_wn_split(rvcmi_front* h, const FrWnArgs& w, const ConvLayer& Lin, co
         }
     }
 }
+// The fp16x2 mode's only form of a WN layer: launch_wn_split's two launches (channel pairs over 3 blocks) at either tile height.
+template <bool LAST>
+void launch_wn_pair(rvcmi_front* h, const FrWnArgs& w, const ConvLayer& Lin, const ConvLayer& Lrs, int B, hipStream_t st) {
+    constexpr int H = 192;
+    {
+        FrConvArgs a = {};
+        a.in = w.x; a.in_op = 0; a.in_bstride = w.bstride; a.T = w.T; a.t_off = w.t_off; a.len = w.len;
+        a.pad = (Lin.ntaps[0] - 1) / 2; a.H = H;
+        a.out_op = h->A.p; a.out_op_bstride = (long)w.T * H;
+        a.gc = w.gc; a.gc_bstride = w.gc_bstride;
+        launch_conv<F16x2, H, 2, 2, FR_GATE>(h, "flow_wn_gate", a, Lin, B, st);
+    }
+    FrConvArgs a = {};
+    a.in = h->A.p; a.in_op = 1; a.in_bstride = (long)w.T * H; a.T = w.T; a.t_off = w.t_off; a.len = w.len; a.H = H;
+    a.res = w.x; a.out = LAST ? w.skip : w.x_out; a.out_bstride = w.bstride; a.out_C = H; a.skip = w.skip; a.first = w.first;
+    if constexpr (LAST) launch_conv<F16x2, H, 1, 2, FR_WN_RS_LAST>(h, "flow_wn_rs", a, Lrs, B, st);
+    else launch_conv<F16x2, H, 2, 2, FR_WN_RS>(h, "flow_wn_rs", a, Lrs, B, st);
+}
 template <typename OpT, bool LAST>
-void launch_wn(rvcmi_front* h, const FrWnArgs& a, const ConvLayer& Lin, const ConvLayer& Lrs, int B, hipStream_t st) {
+void launch_wn_op(rvcmi_front* h, const FrWnArgs& a, const ConvLayer& Lin, const ConvLayer& Lrs, int B, hipStream_t st) {
     const int nj = pick_nj(h, B, a.T);
     const long tiles = (long)((a.T + 32 * nj - 1) / (32 * nj)) * B;
     if (nj == 1 && h->opt.geti("FR_WN_SPLIT", tiles <= 96 ? 1 : 0) != 0) return launch_wn_split<OpT, LAST>(h, a, Lin, Lrs, B, st);
     if (nj == 1) launch_wn_nj<OpT, LAST, 1>(h, a, Lin, Lrs, B, st);
     else launch_wn_nj<OpT, LAST, 2>(h, a, Lin, Lrs, B, st);
+}
+template <typename OpT, bool LAST>
+void launch_wn(rvcmi_front* h, const FrWnArgs& a, const ConvLayer& Lin, const ConvLayer& Lrs, int B, hipStream_t st) {
+    if constexpr (PAIR<OpT>) return launch_wn_pair<LAST>(h, a, Lin, Lrs, B, st);
+    else return launch_wn_op<OpT, LAST>(h, a, Lin, Lrs, B, st);
 }
 
 template <typename OpT, int NJ1>
@@ -302,12 +332,18 @@ void front_forward_t(rvcmi_front* h, int B, int T, const float* phone, const lon
             a.T = T; a.Tp = Tp; a.H = H; a.ws = c.window_size;
             const double flops = 4.0 * (double)T * T * H * B;
             static unsigned long long* stamps = nullptr;  // dev only
-            const bool want_stamps = h->opt.on("FR_STAMPS");
+            const bool want_stamps = !PAIR<OpT> && h->opt.on("FR_STAMPS");
             if (want_stamps && !stamps) HIP_CHECK(hipMalloc((void**)&stamps, 256 * 8));
             a.stamps = want_stamps ? stamps : nullptr;
             h->prof.launch("enc_attn", flops, 0.0, st, [&] {
-                if (c.window_size <= 10) hipLaunchKernelGGL((k_fr_attn<OpT, 96, 21>), dim3((T + 31) / 32, c.n_heads, B), dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((k_fr_attn<OpT, 96, 31>), dim3((T + 31) / 32, c.n_heads, B), dim3(256), 0, st, a);
+                const dim3 grid((T + 31) / 32, c.n_heads, B);
+                if constexpr (PAIR<OpT>) {
+                    if (c.window_size <= 10) hipLaunchKernelGGL((k_fs_attn<96, 21>), grid, dim3(256), 0, st, a);
+                    else hipLaunchKernelGGL((k_fs_attn<96, 31>), grid, dim3(256), 0, st, a);
+                } else {
+                    if (c.window_size <= 10) hipLaunchKernelGGL((k_fr_attn<OpT, 96, 21>), grid, dim3(256), 0, st, a);
+                    else hipLaunchKernelGGL((k_fr_attn<OpT, 96, 31>), grid, dim3(256), 0, st, a);
+                }
             });
             HIP_CHECK(hipGetLastError());
             if (a.stamps) {
@@ -328,21 +364,26 @@ void front_forward_t(rvcmi_front* h, int B, int T, const float* phone, const lon
             if (i == 0) tap_copy(tr, "attn0", X, B, T, H, st);
             if (tr && tr->done) return;
         }
-        if (c.kernel_size <= 5 && !h->opt.on("FR_NO_FFN_FUSION")) {
-            // FFN + residual + LayerNorm in one launch; reads X (with a halo) and writes the other stream buffer
-            FrFfnArgs a = {};
-            a.x = X; a.xo = X2; a.bstride = (long)T * H; a.T = T; a.len = lengths;
-            a.gamma = L.g2.as<float>(); a.beta = L.b2.as<float>();
-            // few time tiles (a single clip): split the hidden channels over 4x the blocks; option FR_FFN_SPLIT = 0 / 1 pins the choice
-            const int nj = pick_nj(h, B, T);
-            const long tiles = (long)((T + 32 * nj - 3) / (32 * nj - 2)) * B;
-            const bool split = c.kernel_size == 3 && c.filter_channels == 768 && (size_t)B * T <= FFN_SPLIT_ROWS &&
-                               h->opt.geti("FR_FFN_SPLIT", tiles <= 96 ? 1 : 0) != 0;
-            if (split && nj == 1) launch_ffn_split_nj<OpT, 1>(h, a, L.f1, L.f2s, L.f2, B, st);
-            else if (split) launch_ffn_split_nj<OpT, 2>(h, a, L.f1, L.f2s, L.f2, B, st);
-            else launch_ffn<OpT>(h, a, L.f1, L.f2, B, st);
-            std::swap(X, X2);
-        } else {
+        // (operand pairs: one launch form per layer, the fused FFN kernels are not instantiated)
+        const bool fused = !PAIR<OpT> && c.kernel_size <= 5 && !h->opt.on("FR_NO_FFN_FUSION");
+        if constexpr (!PAIR<OpT>) {
+            if (fused) {
+                // FFN + residual + LayerNorm in one launch; reads X (with a halo) and writes the other stream buffer
+                FrFfnArgs a = {};
+                a.x = X; a.xo = X2; a.bstride = (long)T * H; a.T = T; a.len = lengths;
+                a.gamma = L.g2.as<float>(); a.beta = L.b2.as<float>();
+                // few time tiles (a single clip): split the hidden channels over 4x the blocks; option FR_FFN_SPLIT = 0 / 1 pins the choice
+                const int nj = pick_nj(h, B, T);
+                const long tiles = (long)((T + 32 * nj - 3) / (32 * nj - 2)) * B;
+                const bool split = c.kernel_size == 3 && c.filter_channels == 768 && (size_t)B * T <= FFN_SPLIT_ROWS &&
+                                   h->opt.geti("FR_FFN_SPLIT", tiles <= 96 ? 1 : 0) != 0;
+                if (split && nj == 1) launch_ffn_split_nj<OpT, 1>(h, a, L.f1, L.f2s, L.f2, B, st);
+                else if (split) launch_ffn_split_nj<OpT, 2>(h, a, L.f1, L.f2s, L.f2, B, st);
+                else launch_ffn<OpT>(h, a, L.f1, L.f2, B, st);
+                std::swap(X, X2);
+            }
+        }
+        if (!fused) {
             {
                 FrConvArgs a = {};
                 a.in = X; a.in_bstride = (long)T * H; a.T = T; a.len = lengths; a.premask = 1; a.pad = (c.kernel_size - 1) / 2;
@@ -370,7 +411,7 @@ void front_forward_t(rvcmi_front* h, int B, int T, const float* phone, const lon
         FrConvArgs a = {};
         a.in = X + (size_t)fh * H; a.in_bstride = (long)T * H; a.T = T2; a.t_off = fh; a.len = lengths; a.premask = 1;
         a.out = ZP; a.out_bstride = (long)T2 * H; a.out_C = H; a.noise = noise; a.H = H;
-        launch_conv<OpT, H, 2, 6, FR_PROJ_ZP>(h, "enc_proj_zp", a, h->proj, B, st);
+        launch_conv<OpT, H, 2, PAIR<OpT> ? 3 : 6, FR_PROJ_ZP>(h, "enc_proj_zp", a, h->proj, B, st);  // (pairs: 3 waves = 512 registers)
         tap_copy(tr, "z_p", ZP, B, T2, H, st);
         if (tr && tr->done) return;
     }
@@ -437,7 +478,10 @@ void front_forward(rvcmi_front* h, int B, int T, const float* phone, const int64
     const long long* pl = (const long long*)pitch;
     const long long* ll = (const long long*)lengths;
     const bool bf = h->cfg.operand == RVCMI_OPERAND_BF16;
-    if (h->cfg.in_channels == 768) {
+    if (h->cfg.operand == RVCMI_OPERAND_F16X2) {
+        if (h->cfg.in_channels == 768) front_forward_t<F16x2, 768>(h, B, T, phone, pl, ll, g, noise, fh, z_out, st, tr);
+        else front_forward_t<F16x2, 256>(h, B, T, phone, pl, ll, g, noise, fh, z_out, st, tr);
+    } else if (h->cfg.in_channels == 768) {
         if (bf) front_forward_t<__bf16, 768>(h, B, T, phone, pl, ll, g, noise, fh, z_out, st, tr);
         else front_forward_t<_Float16, 768>(h, B, T, phone, pl, ll, g, noise, fh, z_out, st, tr);
     } else {
@@ -454,8 +498,9 @@ void upload_vec(DevBuf& d, const float* p, size_t n) {
 rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* weights, int n_weights, int device, int max_B, int max_T) {
     if (!cfg || !weights) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
     const rvcmi_front_config& c = *cfg;
-    if (c.operand != RVCMI_OPERAND_BF16 && c.operand != RVCMI_OPERAND_F16)
-        RVCMI_FAIL(RVCMI_ERR_INVALID, "front: operand must be fp16 or bf16 (MFMA path only)");
+    if (c.operand != RVCMI_OPERAND_BF16 && c.operand != RVCMI_OPERAND_F16 && c.operand != RVCMI_OPERAND_F16X2)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "front: operand must be fp16, bf16 or fp16x2 (MFMA path only)");
+    const bool pair = c.operand == RVCMI_OPERAND_F16X2;
     if (c.hidden_channels != 192 || c.inter_channels != 192 || c.filter_channels != 768 || c.n_heads != 2)
         RVCMI_FAIL(RVCMI_ERR_INVALID, "front: unsupported geometry (hidden %d inter %d filter %d heads %d); every shipped RVC config is 192/192/768/2",
                    c.hidden_channels, c.inter_channels, c.filter_channels, c.n_heads);
@@ -469,7 +514,9 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
     WeightMap wm;
     for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
     std::unique_ptr<rvcmi_front> h(new rvcmi_front);
-    h->opt.load_env({"FR_NJ", "FR_NO_FFN_FUSION", "FR_FFN_SPLIT", "FR_WN_SPLIT", "FR_STAMPS"});
+    // (fp16x2 has one launch form per layer: only the tile height is an option there, see rvcmi_front_set_option)
+    if (pair) h->opt.load_env({"FR_NJ"});
+    else h->opt.load_env({"FR_NJ", "FR_NO_FFN_FUSION", "FR_FFN_SPLIT", "FR_WN_SPLIT", "FR_STAMPS"});
     h->cfg = c;
     h->device = device;
     h->max_B = max_B;
@@ -505,14 +552,21 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
                    wdata(wm, a + "conv_o.bias", {H}), op);
         // relative embeddings (attentions.py:45-54): keys as A fragments of one 32-row tile, values fp32
         const float* Ek = wdata(wm, a + "emb_rel_k", {1, nb, dk});
-        std::vector<uint16_t> pk((size_t)(dk / 16) * 512, 0);
+        const size_t rk_plane = (size_t)(dk / 16) * 512;
+        std::vector<uint16_t> pk(rk_plane * (pair ? 2 : 1), 0);  // fp16x2: hi plane, lo plane
         for (int s = 0; s < dk / 16; ++s)
             for (int lane = 0; lane < 64; ++lane) {
                 const int r = lane & 31;
                 if (r >= nb) continue;
                 for (int e = 0; e < 8; ++e) {
                     const float v = Ek[(size_t)r * dk + 16 * s + 8 * (lane >> 5) + e];
-                    pk[(size_t)s * 512 + lane * 8 + e] = op == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
+                    if (pair) {
+                        const SplitF16 sp = split_f16(v);
+                        pk[(size_t)s * 512 + lane * 8 + e] = sp.hi;
+                        pk[rk_plane + (size_t)s * 512 + lane * 8 + e] = sp.lo;
+                    } else {
+                        pk[(size_t)s * 512 + lane * 8 + e] = op == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
+                    }
                 }
             }
         L.relk.alloc(pk.size() * 2);
@@ -532,7 +586,7 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
                    wdata(wm, f + "conv_1.bias", {FC}), op);
         build_conv(L.f2, FC, H, 1, &ks, &zero, 1, [&](int co, int ci, int, int tap) { return W2[((size_t)co * FC + ci) * ks + tap]; },
                    wdata(wm, f + "conv_2.bias", {H}), op);
-        if (FC % FFN_SPLIT == 0) {
+        if (FC % FFN_SPLIT == 0 && !pair) {
             const int FSl = FC / FFN_SPLIT;
             for (int sp = 0; sp < FFN_SPLIT; ++sp)  // conv_2 restricted to the input channels [sp * FSl, (sp + 1) * FSl): a conv of its own
                 build_conv(L.f2s[sp], FSl, H, 1, &ks, &zero, 1,
@@ -603,17 +657,18 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
     };
     A(h->X, BT * H * 4);
     A(h->X2, BT * H * 4);
-    A(h->QK, BT * H * 2);
-    A(h->KF, (size_t)max_B * H * h->Tp * 2);
-    A(h->VT, (size_t)max_B * H * h->Tp * 2);
-    A(h->A, BT * H * 2);
-    A(h->F, BT * FC * 2);
+    const size_t ob = pair ? 4 : 2;  // bytes per operand element: fp16x2 keeps a hi and a lo plane of every operand buffer
+    A(h->QK, BT * H * ob);
+    A(h->KF, (size_t)max_B * H * h->Tp * ob);
+    A(h->VT, (size_t)max_B * H * h->Tp * ob);
+    A(h->A, BT * H * ob);
+    A(h->F, BT * FC * ob);
     A(h->ZP, BT * IC * 4);
     A(h->Ha, BT * H * 4);
     A(h->Hb, BT * H * 4);
     A(h->SK, BT * H * 4);
     A(h->GC, (size_t)max_B * gcn * c.flow_n_flows * 4 + 16);
-    A(h->FP, (size_t)FFN_SPLIT * std::min(BT, FFN_SPLIT_ROWS) * H * 4);
+    if (!pair) A(h->FP, (size_t)FFN_SPLIT * std::min(BT, FFN_SPLIT_ROWS) * H * 4);
     HIP_CHECK(hipMemset(h->VT.p, 0, h->VT.bytes));  // key padding columns must stay finite
     HIP_CHECK(hipMemset(h->KF.p, 0, h->KF.bytes));
     h->ws_bytes = ws;
@@ -659,6 +714,20 @@ int rvcmi_front_debug_forward(rvcmi_front* h, int B, int T, const float* phone, 
 int rvcmi_front_set_option(rvcmi_front* h, const char* key, double value) {
     return guarded([&] {
         if (!h || !key) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
+        if (h->cfg.operand == RVCMI_OPERAND_F16X2) {
+            // one launch form per layer: a key of the other modes is honoured only with the value that names that form (or NaN = default)
+            const struct { const char* key; double only; const char* form; } forms[] = {
+                {"FR_NO_FFN_FUSION", 1.0, "the FFN runs as two conv launches"},
+                {"FR_FFN_SPLIT", 0.0, "the FFN's hidden channels are not split"},
+                {"FR_WN_SPLIT", 1.0, "a WN layer is the gate launch + the res_skip launch"},
+                {"FR_STAMPS", 0.0, "its kernels carry no time stamps"}};
+            for (const auto& f : forms)
+                if (!strcmp(key, f.key)) {
+                    if (value == value && value != f.only)
+                        RVCMI_FAIL(RVCMI_ERR_INVALID, "option %s = %g selects a form the fp16x2 operand mode does not have (%s)", key, value, f.form);
+                    return;
+                }
+        }
         if (!h->opt.set(key, value)) RVCMI_FAIL(RVCMI_ERR_INVALID, "unknown option '%s' for this handle", key);
     });
 }

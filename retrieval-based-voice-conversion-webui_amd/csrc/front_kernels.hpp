@@ -14,6 +14,8 @@
 // elementwise step (bias, gates, masks, residual, LayerNorm, the coupling update) fused into the producing kernel.
 // The channel Flip between coupling layers is folded into the packed weights (no data movement).
 #pragma once
+#include <type_traits>
+
 #include "nsf_kernels.hpp"
 
 namespace rvcmi {
@@ -161,6 +163,37 @@ __device__ __forceinline__ void fr_stage_dyn(char* smem, const void* in, int in_
     }
 }
 
+// Operand tag of the "fp16x2" mode: every MFMA operand is a (hi, lo') pair of fp16 values (csrc/split_f16.hpp has the arithmetic), kept
+// PLANAR -- a hi plane and a lo plane, each with exactly the fp16 layout of the buffer.  The kernels are in front_split_kernels.hpp.
+struct F16x2 {};
+constexpr float FS_SCALE = 2048.f, FS_INV = 1.f / 2048.f;  // 2^11: the scale lo' is stored with; 2^-11: what folds the cross terms in
+
+// fp16x2 stores of 4 operand elements: hi at base[off + e * step], lo' at base[plane + off + e * step]  (step 1: one vector store each)
+__device__ __forceinline__ void fs_put4(void* base, size_t off, size_t plane, f32x4 v) {
+    using h4 = __attribute__((ext_vector_type(4))) _Float16;
+    h4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        hi[e] = to_op<_Float16>(v[e]);
+        lo[e] = to_op<_Float16>((v[e] - (float)hi[e]) * FS_SCALE);
+    }
+    *(h4*)((_Float16*)base + off) = hi;
+    *(h4*)((_Float16*)base + plane + off) = lo;
+}
+__device__ __forceinline__ void fs_put4_strided(void* base, size_t off, size_t plane, int step, f32x4 v) {
+    _Float16* p = (_Float16*)base + off;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const _Float16 hi = to_op<_Float16>(v[e]);
+        p[e * step] = hi;
+        p[plane + e * step] = to_op<_Float16>((v[e] - (float)hi) * FS_SCALE);
+    }
+}
+
+// (front_split_kernels.hpp) the sums of k_fr_conv's tile on operand pairs: acc = A_hi.B_hi + 2^-11 (A_hi.B_lo' + A_lo'.B_hi)
+template <int CIN, int MI, int NJ, int NW>
+__device__ __forceinline__ void fs_conv_sums(const FrConvArgs& a, f32x16 (&acc)[MI][NJ], char* smem, int b, int q0, int ct0, int lenrow);
+
 // Generic fused conv layer.  Block = NW waves, wave w owns MI consecutive packed 32-channel tiles, all waves share the
 // NJ*32-row time tile.  Grid: x = time tile, y = block of NW*MI tiles, z = utterance.
 template <typename OpT, int CIN, int MI, int NJ, int NW, int EPI>
@@ -173,31 +206,37 @@ static __global__ void __launch_bounds__(64 * NW) k_fr_conv(FrConvArgs a) {
     const int b = blockIdx.z;
     const int q0 = blockIdx.x * TT;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int rows = TT + a.ntaps - 1 + 2;  // + slack for the K loop's one-step-ahead reads
+    [[maybe_unused]] const int rows = TT + a.ntaps - 1 + 2;  // + slack for the K loop's one-step-ahead reads
     const int lenrow = (a.premask && a.len) ? (int)min((long long)a.T, a.len[b] - a.t_off) : a.T;
-    // these launches are small (tens of blocks at B = 1), so a wave's speed is set by how many weight bytes it keeps in
-    // flight: a 4-deep ring (12 k-steps ahead), requested BEFORE the activation tile is staged
     const int ct0 = ((int)blockIdx.y * NW + wave) * MI;
-    const OpT* wlane = (const OpT*)a.w + (size_t)ct0 * a.ct_stride + lane * 8;
-    typename Op<OpT>::frag Aw[FR_NB][KGROUP][MI];
-    conv_prefetch<OpT, CIN, MI, KGROUP, FR_NB>(Aw, wlane, a.ct_stride, a.ntaps);
-    fr_stage<OpT, CIN, NT>(smem, a.in, a.in_op, (long)b * a.in_bstride, a.T, q0 - a.pad, rows, lenrow);
-    __syncthreads();
-
     f32x16 acc[MI][NJ];
+    if constexpr (std::is_same<OpT, F16x2>::value) {
+        fs_conv_sums<CIN, MI, NJ, NW>(a, acc, smem, b, q0, ct0, lenrow);  // staging and K loop on operand pairs
+    } else {
+        // these launches are small (tens of blocks at B = 1), so a wave's speed is set by how many weight bytes it keeps in
+        // flight: a 4-deep ring (12 k-steps ahead), requested BEFORE the activation tile is staged
+        const OpT* wlane = (const OpT*)a.w + (size_t)ct0 * a.ct_stride + lane * 8;
+        typename Op<OpT>::frag Aw[FR_NB][KGROUP][MI];
+        conv_prefetch<OpT, CIN, MI, KGROUP, FR_NB>(Aw, wlane, a.ct_stride, a.ntaps);
+        fr_stage<OpT, CIN, NT>(smem, a.in, a.in_op, (long)b * a.in_bstride, a.T, q0 - a.pad, rows, lenrow);
+        __syncthreads();
+
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
+        for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int jt = 0; jt < NJ; ++jt)
+            for (int jt = 0; jt < NJ; ++jt)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][jt][e] = 0.f;
-    const char* lds_lane = smem + (size_t)(lane & 31) * STRIDE + (lane >> 5) * 16;
-    conv_run<OpT, CIN, MI, NJ, KGROUP, FR_NB>(acc, Aw, lds_lane, wlane, a.ct_stride, a.ntaps, 0, 1);
+                for (int e = 0; e < 16; ++e) acc[mi][jt][e] = 0.f;
+        const char* lds_lane = smem + (size_t)(lane & 31) * STRIDE + (lane >> 5) * 16;
+        conv_run<OpT, CIN, MI, NJ, KGROUP, FR_NB>(acc, Aw, lds_lane, wlane, a.ct_stride, a.ntaps, 0, 1);
+    }
 
     // ---- epilogue.  Every load is issued up front with clamped indices (hipcc turns a conditional load into an
     // exec-masked branch with its own wait; measured here: 15k cycles for a 24-load epilogue) ----
     const int hl = lane >> 5;
     const long long lenb = a.len ? a.len[b] : (long long)a.T + a.t_off;
+    constexpr bool PAIR = std::is_same<OpT, F16x2>::value;  // operand outputs go out as a hi and a lo plane (fs_put4)
+    [[maybe_unused]] const size_t op_plane = (size_t)gridDim.z * a.out_op_bstride;  // pairs: elements from out_op's hi plane to its lo plane
     int tt[NJ], tcl[NJ];
     float mk[NJ];
 #pragma unroll
@@ -301,7 +340,7 @@ static __global__ void __launch_bounds__(64 * NW) k_fr_conv(FrConvArgs a) {
         }
     } else if constexpr (EPI == FR_GATE) {
         static_assert(MI == 2, "paired (tanh, sigmoid) tiles");
-        using o4 = __attribute__((ext_vector_type(4))) OpT;
+        using o4 = __attribute__((ext_vector_type(4))) std::conditional_t<PAIR, _Float16, OpT>;
         const int pc = (ct0 / 2) * 32 + 4 * hl;
         f32x4 bt[4], bs[4];
 #pragma unroll
@@ -318,11 +357,19 @@ static __global__ void __launch_bounds__(64 * NW) k_fr_conv(FrConvArgs a) {
             if (tt[jt] >= a.T) continue;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
+                if constexpr (PAIR) {
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        o[e] = fast_tanh(acc[0][jt][4 * g + e] + bt[g][e]) * fast_sigmoid(acc[1][jt][4 * g + e] + bs[g][e]);
+                    fs_put4(a.out_op, (size_t)b * a.out_op_bstride + (size_t)tt[jt] * a.H + pc + 8 * g, op_plane, o);
+                } else {
                 o4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     o[e] = to_op<OpT>(fast_tanh(acc[0][jt][4 * g + e] + bt[g][e]) * fast_sigmoid(acc[1][jt][4 * g + e] + bs[g][e]));
                 *(o4*)((OpT*)a.out_op + (size_t)b * a.out_op_bstride + (size_t)tt[jt] * a.H + pc + 8 * g) = o;
+                }
             }
         }
     } else if constexpr (EPI == FR_WN_RS || EPI == FR_WN_RS_LAST) {
@@ -405,36 +452,60 @@ static __global__ void __launch_bounds__(64 * NW) k_fr_conv(FrConvArgs a) {
                     } else if constexpr (EPI == FR_QKV) {
                         // q -> [T][H] (pre-scaled); k and v -> per (head, 32-key tile) blocks in MFMA FRAGMENT order, so
                         // that the attention kernel's operand loads are contiguous 1 KiB per instruction
-                        using o4 = __attribute__((ext_vector_type(4))) OpT;
+                        using o4 = __attribute__((ext_vector_type(4))) std::conditional_t<PAIR, _Float16, OpT>;
                         constexpr int DKc = 96, KSc = DKc / 16, DTc = DKc / 32;
                         const int nh = a.H / DKc, ntl = a.Tp / 32, tile = t >> 5, kk = t & 31;
+                        [[maybe_unused]] const size_t kv_plane = (size_t)gridDim.z * a.H * a.Tp;  // pairs: hi -> lo plane of the k / v tiles
                         if (co < a.H) {
+                            if constexpr (PAIR) {
+                                fs_put4(a.out_op, (size_t)b * a.out_op_bstride + (size_t)t * a.H + co, op_plane, v / a.qdiv);
+                            } else {
                             o4 o;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) o[e] = to_op<OpT>(v[e] / a.qdiv);
                             *(o4*)((OpT*)a.out_op + (size_t)b * a.out_op_bstride + (size_t)t * a.H + co) = o;
+                            }
                         } else if (co < 2 * a.H) {
                             const int c = co - a.H, head = c / DKc, cc = c - head * DKc;
+                            if constexpr (PAIR) {
+                                const size_t off = ((((size_t)b * nh + head) * ntl + tile) * KSc + cc / 16) * 512 +
+                                                   ((((cc & 15) >> 3) * 32 + kk) * 8) + (cc & 7);
+                                fs_put4(a.kf, off, kv_plane, v);
+                            } else {
                             o4 o;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) o[e] = to_op<OpT>(v[e]);
                             const size_t off = ((((size_t)b * nh + head) * ntl + tile) * KSc + cc / 16) * 512 +
                                                ((((cc & 15) >> 3) * 32 + kk) * 8) + (cc & 7);
                             *(o4*)((OpT*)a.kf + off) = o;
+                            }
                         } else {
                             const int c = co - 2 * a.H, head = c / DKc, d = c - head * DKc;
                             const int s2 = kk >> 4, r = kk & 15, hv = (r >> 2) & 1, ev = (r & 3) + 4 * (r >> 3);
+                            if constexpr (PAIR) {
+                                const size_t off = (((((size_t)b * nh + head) * ntl + tile) * DTc + d / 32) * 2 + s2) * 512 +
+                                                   (size_t)(hv * 32 + (d & 31)) * 8 + ev;
+                                fs_put4_strided(a.vt, off, kv_plane, 8, v);
+                            } else {
                             OpT* vp = (OpT*)a.vt + (((((size_t)b * nh + head) * ntl + tile) * DTc + d / 32) * 2 + s2) * 512 +
                                       (size_t)(hv * 32 + (d & 31)) * 8 + ev;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) vp[e * 8] = to_op<OpT>(v[e]);
+                            }
                         }
                     } else if constexpr (EPI == FR_RELU_OP) {
+                        if constexpr (PAIR) {
+                            f32x4 o;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[e] = fmaxf(v[e], 0.f) * mk[jt];
+                            fs_put4(a.out_op, (size_t)b * a.out_op_bstride + (size_t)t * a.cout + co, op_plane, o);
+                        } else {
                         using o4 = __attribute__((ext_vector_type(4))) OpT;
                         o4 o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = to_op<OpT>(fmaxf(v[e], 0.f) * mk[jt]);
                         *(o4*)((OpT*)a.out_op + (size_t)b * a.out_op_bstride + (size_t)t * a.cout + co) = o;
+                        }
                     } else if constexpr (EPI == FR_F32_MASK) {
                         *(f32x4*)(a.out + (size_t)b * a.out_bstride + (size_t)t * a.out_C + co) = v * mk[jt];
                     } else if constexpr (EPI == FR_COUPLE) {

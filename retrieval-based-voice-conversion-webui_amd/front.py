@@ -6,6 +6,9 @@ C ABI (``rvcmi_front_*`` in include/rvcmi.h).  SURVEY.md section 8f row 1.
     front = FrontHIP.from_reference(net_g)            # after net_g.remove_weight_norm()
     z = front(phone, pitch, phone_lengths, g, flow_head=0)      # == flow(z_p, x_mask, g, reverse=True) * x_mask
 
+``operand``: ``"fp16"`` (default) / ``"bf16"`` MFMA operands, or ``"fp16x2"`` -- every MFMA operand a (hi, lo) pair of fp16 values, three
+MFMAs per k-step: fp32-grade z on the same matrix cores (csrc/front_split_kernels.hpp).  There is no ``"fp32"`` front.
+
 The one RNG draw of this stage (``torch.randn_like(m_p)``, synthesizers.py:182/188) is made here with the same
 shape on the same device unless ``noise=`` is given.  No CPU fallback: a non-GPU device raises.
 """
@@ -45,7 +48,7 @@ class FrontHIP(torch.nn.Module):
         super().__init__()
         self.cfg = {k: cfg[k] for k in _CFG_KEYS}
         if operand not in _lib.OPERANDS or _lib.OPERANDS[operand] == 0:
-            raise ValueError("front operand must be 'fp16' or 'bf16'")
+            raise ValueError("front operand must be 'fp16', 'bf16' or 'fp16x2'")
         self.operand = operand
         if operand == "bf16":
             from .nsf import _warn_bf16
@@ -163,7 +166,8 @@ class FrontHIP(torch.nn.Module):
     def set_option(self, key: str, value=None) -> None:
         """Dev / test option of this handle (``rvcmi_front_set_option``: ``FR_NJ``, ``FR_NO_FFN_FUSION``, ``FR_FFN_SPLIT``, ``FR_WN_SPLIT`` 0 / 1 / 2 = a WN
         layer as one launch / gate + res_skip launches, channel pairs over 3x the blocks (bit-identical to 0) / the gate's taps over the waves
-        (default for small grids)); ``None`` = default."""
+        (default for small grids)); ``None`` = default.  An ``operand="fp16x2"`` handle has one launch form per layer: a value that selects
+        another one raises ``RvcmiError`` (``code == ERR_INVALID``)."""
         _lib.set_option(_lib.lib().rvcmi_front_set_option, self._handle, key, value)  # raises on a key this handle does not honour
         if not hasattr(self, "_options"):
             self._options = {}

@@ -168,7 +168,8 @@ def _rebind_gate(rebound) -> None:
 
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
             patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False,
-            index_build: Optional[bool] = None, hubert_fe: bool = False, hubert_batch: bool = False) -> None:
+            index_build: Optional[bool] = None, hubert_fe: bool = False, hubert_batch: bool = False,
+            front_operand: Optional[str] = None) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
@@ -182,9 +183,13 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     ``RVCMI_HUBERT_FE=1``; default off): the conversion paths swap HuBERT's convolutional feature extractor for ``hubert.HubertFrontHIP``
     (``hubert.accelerate_hubert``), once per model object.  ``hubert_batch=True`` (opt-in, as ``RVCMI_HUBERT_BATCH=1``; default off;
     effective only together with ``hubert_fe``): ``convert_files`` and a long input's segments run HuBERT once per planned group of segments
-    (``hubert.extract_features_batch``) instead of once per segment, for a model that honours ``padding_mask`` (``hubert.batch_capable``)."""
+    (``hubert.extract_features_batch``) instead of once per segment, for a model that honours ``padding_mask`` (``hubert.batch_capable``).
+    ``front_operand="fp16x2"`` (opt-in, as ``RVCMI_FRONT_OPERAND=fp16x2``; default off): the loaders install the HIP front in that operand
+    mode whatever the generator's ``operand`` (``synthesizer.accelerate_synthesizer``): with ``operand="fp32"`` the whole ``infer`` runs
+    on HIP at fp32-grade fidelity instead of leaving ``enc_p`` / ``flow`` on torch."""
     if _state.get("installed"):
         return
+    _syn.front_operand_choice(front_operand)  # a bad name raises here, before anything is rebound
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
 
     ref_get, ref_load = rs.get_synthesizer, rs.load_synthesizer
@@ -255,6 +260,7 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
 
     _hubert.HUBERT_FE = bool(hubert_fe)
     _hubert.HUBERT_BATCH = bool(hubert_batch)
+    _syn.FRONT_OPERAND = front_operand
 
 
 def uninstall() -> None:
@@ -283,4 +289,5 @@ def uninstall() -> None:
 
     _hubert.HUBERT_FE = False
     _hubert.HUBERT_BATCH = False
+    _syn.FRONT_OPERAND = None
     _state.clear()

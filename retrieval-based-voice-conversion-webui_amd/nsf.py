@@ -58,10 +58,16 @@ def _cfg_struct(cfg: dict, operand: str) -> _lib.NsfConfig:
         c.n_dilations[j] = len(ds)
         for m, d in enumerate(ds):
             c.resblock_dilation_sizes[j][m] = int(d)
-    if operand not in _lib.OPERANDS:
-        raise ValueError("operand must be one of %s" % sorted(_lib.OPERANDS))
-    c.operand = _lib.OPERANDS[operand]
+    c.operand = _operand_code(operand)
     return c
+
+
+def _operand_code(operand: str) -> int:
+    if operand == "fp16x2":
+        raise ValueError("operand 'fp16x2' is front-only (FrontHIP / front_operand=); the generator's fp32-grade mode is operand='fp32'")
+    if operand not in _lib.OPERANDS:
+        raise ValueError("operand must be one of %s" % sorted(k for k in _lib.OPERANDS if k != "fp16x2"))
+    return _lib.OPERANDS[operand]
 
 
 class _HipGenerator(torch.nn.Module):
@@ -70,6 +76,7 @@ class _HipGenerator(torch.nn.Module):
     def __init__(self, cfg: dict, weights: Dict[str, torch.Tensor], device="cuda:0", operand: str = "fp16",
                  max_B: int = 1, max_T: int = 256):
         super().__init__()
+        _operand_code(operand)  # a bad name (or the front-only 'fp16x2') raises ValueError before anything else
         self.cfg = dict(cfg)
         self.operand = operand
         self.device = torch.device(device)
