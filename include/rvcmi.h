@@ -213,7 +213,7 @@ int rvcmi_front_forward(rvcmi_front* h, int B, int T, const float* phone_dev, co
 size_t rvcmi_front_workspace_bytes(const rvcmi_front* h);
 
 /* Test hook: stop after an internal stage and copy it to the host, channels-last [B][T'][192].
- * what: "emb", "attn0", "layer0".."layer5" (encoder stream), "z_p", "flow3".."flow0" (flow stream after a coupling). */
+ * what: "emb", "attn0".."attn5" (after an encoder layer's attention half: LayerNorm 1), "layer0".."layer5" (encoder stream), "z_p", "flow3".."flow0" (flow stream after a coupling). */
 int rvcmi_front_debug_forward(rvcmi_front* h, int B, int T, const float* phone_dev, const int64_t* pitch_dev,
                               const int64_t* lengths_dev, const float* g_dev, const float* noise_dev, int flow_head,
                               const char* what, float* out_host, size_t capacity_floats, int64_t shape_out[3],

@@ -361,8 +361,12 @@ void front_forward_t(rvcmi_front* h, int B, int T, const float* phone, const lon
             a.out = X; a.out_bstride = (long)T * H; a.out_C = H; a.res = X;
             a.gamma = L.g1.as<float>(); a.beta = L.b1.as<float>();
             launch_conv<OpT, H, 1, 6, FR_RES_LN>(h, "enc_o_ln", a, L.o, B, st);
-            if (i == 0) tap_copy(tr, "attn0", X, B, T, H, st);
-            if (tr && tr->done) return;
+            if (tr) {
+                char nm[32];
+                snprintf(nm, sizeof(nm), "attn%d", i);
+                tap_copy(tr, nm, X, B, T, H, st);
+                if (tr->done) return;
+            }
         }
         // (operand pairs: one launch form per layer, the fused FFN kernels are not instantiated)
         const bool fused = !PAIR<OpT> && c.kernel_size <= 5 && !h->opt.on("FR_NO_FFN_FUSION");
@@ -460,7 +464,8 @@ void front_forward_t(rvcmi_front* h, int B, int T, const float* phone, const lon
     }
     if (z_out) {
         h->prof.launch("front_out", 0.0, (double)B * T2 * H * 8, st, [&] {
-            hipLaunchKernelGGL(k_fr_out, dim3((T2 + 31) / 32, (H + 31) / 32, B), dim3(256), 0, st, ZP, z_out, T2, H, fh, lengths);
+            hipLaunchKernelGGL(k_fr_out, dim3((T2 + 31) / 32, (H + 31) / 32, B), dim3(256), 0, st, ZP, z_out, T2, H, fh, lengths,
+                               c.flow_n_flows % 2);
         });
         HIP_CHECK(hipGetLastError());
     }

@@ -1292,8 +1292,9 @@ static __global__ void __launch_bounds__(256) k_fr_ffn_ln(const float* __restric
 }
 
 // z * x_mask, channels-last [B][T][C] -> the generator's channel-first [B][C][T]   (synthesizers.py:192)
+// rev: the stream holds z with its channel axis reversed (an odd number of folded Flips in all, i.e. an odd flow_n_flows)
 static __global__ void __launch_bounds__(256) k_fr_out(const float* __restrict__ x, float* __restrict__ out, int T, int C, int t_off,
-                                                const long long* __restrict__ len) {
+                                                const long long* __restrict__ len, int rev) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
@@ -1301,7 +1302,7 @@ static __global__ void __launch_bounds__(256) k_fr_out(const float* __restrict__
         const int t = t0 + r, c = c0 + tx;
         float v = 0.f;
         if (t < T && c < C) {
-            v = x[((size_t)b * T + t) * C + c];
+            v = x[((size_t)b * T + t) * C + (rev ? C - 1 - c : c)];
             if (len && (long long)(t + t_off) >= len[b]) v = 0.f;
         }
         tile[r][tx] = v;
