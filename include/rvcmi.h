@@ -602,6 +602,32 @@ int rvcmi_hubert_fe_forward_ragged(rvcmi_hubert_fe* h, int B, int64_t N_max, con
  * [512][512][taps] on the host; x16_dev fp16 [B][L_in][512]; out32_dev fp32 [B][(L_in - taps) / 2 + 1][512].                          */
 int rvcmi_hubert_fe_debug_conv(int taps, int B, int L_in, const float* w, const void* x16_dev, float* out32_dev, int device, void* stream);
 
+/* ---- beyond SURVEY.md section 8: HuBERT's transformer encoder layers -------------------------------------------------------------
+ * The repeated block of a post-norm HuBERT (fairseq TransformerSentenceEncoderLayer with layer_norm_first = False; transformers
+ * HubertEncoderLayer): x = LN(x + Attn(x)); x = LN(x + FFN(x)), exact (erf) GELU, q scaled by head_dim^-0.5 after its bias.  Served: head
+ * dim 64 (heads * 64 == d), d a multiple of 64 up to 1024, ffn a multiple of 64 up to 4096, 1 .. 64 layers, 0 < ln_eps < 1; anything else
+ * RVCMI_ERR_INVALID (the caller keeps torch's modules).  `weights`: fp32 host tensors under fairseq's names, for every layer i
+ * "layers.<i>.self_attn.{q,k,v,out}_proj.{weight,bias}", "layers.<i>.self_attn_layer_norm.*", "layers.<i>.fc1.*", "layers.<i>.fc2.*",
+ * "layers.<i>.final_layer_norm.*" (Linear weights [out][in]).  A missing tensor: RVCMI_ERR_MISSING; another shape or any further tensor:
+ * RVCMI_ERR_INVALID.  MFMA operands fp16 (weights, the layer's input, q / k / v, the probabilities, the attention output, the stream in
+ * front of FFN-1, the GELU output), accumulation, softmax, residual adds and LayerNorm statistics fp32.  Five launches per layer; results
+ * are bit-identical from run to run, and an item's rows do not depend on the other items of the batch.                                  */
+typedef struct rvcmi_hubert_enc rvcmi_hubert_enc;
+int rvcmi_hubert_enc_create(const rvcmi_tensor* weights, int n_weights, int n_layers, int d, int heads, int ffn, float ln_eps, int device,
+                            rvcmi_hubert_enc** out);
+int rvcmi_hubert_enc_destroy(rvcmi_hubert_enc* h);
+/* Bytes of device workspace a forward of (B, T) needs; 0 for a shape that is not served (B outside 1 .. 65535, T < 1, B * T > 2^22). */
+size_t rvcmi_hubert_enc_workspace_bytes(rvcmi_hubert_enc* h, int B, int T);
+/* Enqueue only: layers first_layer .. first_layer + n - 1.  x_dev / out_dev [B][T][d], rows contiguous, fp16 (is_half) or fp32, 16-byte
+ * aligned; every layer's output is rounded once to that dtype, so n layers in one call are BIT-equal to n calls of one layer.
+ * key_mask_dev: uint8 [B][T] on the device, 1 = a padded key (its score is -inf), or NULL; padded QUERY rows are computed like any other.
+ * ws_dev: the caller's, rvcmi_hubert_enc_workspace_bytes(h, B, T) bytes, 256-byte aligned; the handle allocates nothing here (safe inside a
+ * stream capture).  A null pointer, a layer range outside the handle's, a shape that is not served: RVCMI_ERR_INVALID, nothing launched.
+ * (For the tests: the workspace holds, each 256-byte aligned and in this order, q / k / v fp16 [3][B][heads][T][64], the attention output fp16
+ * [B T][d], the stream behind the first LayerNorm fp32 [B T][d] and again fp16, then the GELU output fp16 [B T][ffn] of the LAST layer run.) */
+int rvcmi_hubert_enc_forward(rvcmi_hubert_enc* h, int first_layer, int n, int B, int T, const void* x_dev, int is_half,
+                             const uint8_t* key_mask_dev, void* out_dev, void* ws_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ from .glue import cut_count, cut_points, filtfilt, highpass16k
 from .gru import GRUHIP, accelerate_rmvpe
 from .unet import UNetHIP, accelerate_rmvpe_unet, restore_rmvpe_unet
 from .rmvpe import RMVPEHIP
-from .hubert import (HubertFrontHIP, accelerate_hubert, batch_capable, extract_features_batch, frame_mask, hubert_batch_on, hubert_on, plan_groups,
+from .hubert import (HubertEncoderHIP, HubertFrontHIP, HubertLayerHIP, accelerate_hubert, accelerate_hubert_layers, hubert_enc_on,
+                     restore_hubert_layers, supported_layer, batch_capable, extract_features_batch, frame_mask, hubert_batch_on, hubert_on, plan_groups,
                      restore_hubert, sample_mask)
 from .synthesizer import accelerate_synthesizer, get_synthesizer, load_synthesizer
 from . import dist
@@ -26,6 +27,6 @@ __all__ = [
     "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "index_factory", "extract_index_ivf", "GeneratorHIP", "NSFGeneratorHIP",
     "config_from_reference", "FrontHIP", "front_config_from_reference", "infer_hip", "retrieve_blend", "accelerate_synthesizer", "get_synthesizer", "load_synthesizer", "dist", "glue", "install", "uninstall", "RealtimeVC", "PitchCache", "f0_extractor_frame", "SincResample", "sinc_resample_kernel", "GRUHIP", "accelerate_rmvpe",
     "UNetHIP", "accelerate_rmvpe_unet", "restore_rmvpe_unet", "RMVPEHIP", "HubertFrontHIP", "accelerate_hubert", "restore_hubert", "hubert_on", "hubert_batch_on", "batch_capable", "extract_features_batch",
-    "frame_mask", "sample_mask", "plan_groups",
+    "frame_mask", "sample_mask", "plan_groups", "HubertEncoderHIP", "HubertLayerHIP", "accelerate_hubert_layers", "restore_hubert_layers", "supported_layer", "hubert_enc_on",
     "RealtimeStream", "stream_geometry", "TorchGateHIP", "cut_points", "cut_count", "filtfilt", "highpass16k",
 ]

@@ -14,7 +14,7 @@ from typing import List
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RVCMI_LIB") or os.path.join(_HERE, "librvcmi.so")  # RVCMI_LIB: dev A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["error.cpp", "nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip", "rmvpe.hip", "hubert_fe.hip"]
+SOURCES = ["error.cpp", "nsf.hip", "rb_stream.hip", "ivf.hip", "front.hip", "glue.hip", "gru.hip", "unet.hip", "rmvpe.hip", "hubert_fe.hip", "hubert_enc.hip"]
 
 RVCMI_MAX_UPS, RVCMI_MAX_RB, RVCMI_MAX_DIL = 8, 4, 4
 RVCMI_VERSION = 2  # include/rvcmi.h; the argument lists of SYMBOLS below are those of this ABI version
@@ -149,6 +149,10 @@ SYMBOLS = [
     ("rvcmi_hubert_fe_workspace_bytes_ragged", C.c_size_t, [_P, C.c_int, C.c_int64]),
     ("rvcmi_hubert_fe_forward_ragged", C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("rvcmi_hubert_fe_debug_conv", C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
+    ("rvcmi_hubert_enc_create", C.c_int, [C.POINTER(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(_P)]),
+    ("rvcmi_hubert_enc_destroy", C.c_int, [_P]),
+    ("rvcmi_hubert_enc_workspace_bytes", C.c_size_t, [_P, C.c_int, C.c_int]),
+    ("rvcmi_hubert_enc_forward", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
 ]
 
 

@@ -16,6 +16,12 @@ Several inputs in ONE pass (opt-in on top of the above: ``RVCMI_HUBERT_BATCH=1``
 ``HubertFrontHIP.forward_ragged`` runs a zero-padded ``[B, N_max]`` batch whose items keep their own lengths -- layer 0's GroupNorm averages
 over the item's own frames, not over the padding -- and ``extract_features_batch`` hands such a batch to a fairseq-shaped model together
 with a sample mask (``sample_mask``) from which fairseq's ``forward_padding_mask`` derives exactly the frames behind each item's end.
+
+The transformer's LAYERS on ``csrc/hubert_enc.hip`` (a switch of its own, ``RVCMI_HUBERT_ENC=1`` or ``rvc_amd.install(hubert_enc=True)``; default off;
+DESIGN.md 7.9): ``accelerate_hubert_layers(model)`` swaps every post-norm layer of ``model.encoder.layers`` for a ``HubertLayerHIP`` on one
+``HubertEncoderHIP`` -- all layers or none -- and ``restore_hubert_layers`` puts torch's back.  ``pos_conv``, the feature projection, the encoder's own
+LayerNorm, ``final_proj`` and the loop over the layers stay on torch.  Measured slower than torch's layers at every shape today
+(profiles/hubert_enc_time.json): the switch is for whoever wants the kernels' rounding, not for speed.
 """
 from __future__ import annotations
 
@@ -462,5 +468,303 @@ def accelerate_hubert_once(model) -> int:
         try:
             object.__setattr__(model, "_rvcmi_hubert_fe", n)
         except Exception:  # noqa  (an object without a __dict__: the swap is looked for again next time, and found done)
+            pass
+    return n
+
+
+# ---- the transformer's layers on csrc/hubert_enc.hip (opt-in: RVCMI_HUBERT_ENC=1 or rvc_amd.install(hubert_enc=True); default off) ----
+# Only the repeated block x = LN(x + Attn(x)); x = LN(x + FFN(x)) is served.  LayerNorm + post_extract_proj, pos_conv, the encoder's own LayerNorm,
+# final_proj and the loop over the layers stay on torch: the integration point is the single layer module, so output_layer = 9 / 12 and the ragged
+# batched path (a padding mask) need no plumbing of their own.
+HUBERT_ENC = False  # install(hubert_enc=True) sets it; RVCMI_HUBERT_ENC=1 / =0 overrides it per call.  Independent of HUBERT_FE.
+HEAD_DIM = 64
+_LAYER_TENSORS = tuple("%s.%s" % (m, p) for m in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "self_attn_layer_norm",
+                                                  "fc1", "fc2", "final_layer_norm") for p in ("weight", "bias"))
+
+
+def hubert_enc_on() -> bool:
+    env = os.environ.get("RVCMI_HUBERT_ENC")
+    return env == "1" if env in ("0", "1") else bool(HUBERT_ENC)
+
+
+def _layer_parts(m):
+    """-> (convention, {canonical name: module}, activation, attention module) of a layer under either convention's attribute names, else None."""
+    sub = lambda o, *names: [getattr(o, n, None) for n in names]
+    att = getattr(m, "self_attn", None)
+    if att is not None:
+        conv, ln1, fc1, fc2, ln2, act = "fairseq", *sub(m, "self_attn_layer_norm", "fc1", "fc2", "final_layer_norm", "activation_fn")
+    else:
+        att, ff = getattr(m, "attention", None), getattr(m, "feed_forward", None)
+        conv, ln1, ln2 = "transformers", *sub(m, "layer_norm", "final_layer_norm")
+        fc1, fc2, act = sub(ff, "intermediate_dense", "output_dense", "intermediate_act_fn")
+    q, k, v, o = sub(att, "q_proj", "k_proj", "v_proj", "out_proj")
+    parts = {"self_attn.q_proj": q, "self_attn.k_proj": k, "self_attn.v_proj": v, "self_attn.out_proj": o, "self_attn_layer_norm": ln1, "fc1": fc1,
+             "fc2": fc2, "final_layer_norm": ln2}
+    if any(p is None for p in parts.values()) or act is None:
+        return None
+    return conv, parts, act, att
+
+
+def _layer_cfg(m) -> Optional[dict]:
+    """The geometry of a layer the kernels serve (``supported_layer``), else None."""
+    nn = torch.nn
+    if not isinstance(m, nn.Module) or isinstance(m, HubertLayerHIP) or m.training:  # (eval mode: every dropout is the identity)
+        return None
+    got = _layer_parts(m)
+    if got is None:
+        return None
+    conv, parts, act, att = got
+    lin = [parts[n] for n in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "fc1", "fc2")]
+    lns = [parts["self_attn_layer_norm"], parts["final_layer_norm"]]
+    if not all(isinstance(l, nn.Linear) and l.bias is not None for l in lin) or not all(isinstance(l, nn.LayerNorm) for l in lns):
+        return None
+    d, ffn, heads = lin[0].in_features, lin[4].out_features, getattr(att, "num_heads", None)
+    if any((l.in_features, l.out_features) != (d, d) for l in lin[:4]) or (lin[4].in_features, lin[5].in_features, lin[5].out_features) != (d, ffn, d):
+        return None
+    if any(tuple(l.normalized_shape) != (d,) or l.weight is None or l.bias is None for l in lns) or lns[0].eps != lns[1].eps:
+        return None
+    if not isinstance(heads, int) or heads * HEAD_DIM != d or d % 64 or d > 1024 or ffn % 64 or ffn > 4096 or not _exact_gelu(act):
+        return None
+    ps = list(m.parameters())
+    if len(ps) != len(_LAYER_TENSORS) or len({p.device for p in ps}) != 1 or ps[0].device.type != "cuda" or len({p.dtype for p in ps}) != 1:
+        return None  # (a further parameter -- a relative-position table, say -- is a layer the kernels do not compute)
+    if conv == "fairseq":
+        if getattr(m, "layer_norm_first", None) is not False:
+            return None
+    else:
+        # transformers' pre-norm layer has the same attribute names: compare the module with the post-norm formula on its own submodules
+        try:
+            with torch.no_grad():
+                x = torch.linspace(-1.0, 1.0, 3 * d, device=ps[0].device, dtype=torch.float32).view(1, 3, d).to(ps[0].dtype).sin()
+                h = parts["self_attn_layer_norm"](x + att(x, attention_mask=None, output_attentions=False)[0])
+                want = parts["final_layer_norm"](h + m.feed_forward(h))
+                ok = bool((m(x)[0].float() - want.float()).abs().max() <= 1e-3 * (1.0 + want.float().abs().max()))
+        except Exception:  # noqa  (not a layer of this shape)
+            return None
+        if not ok:
+            return None
+    return dict(convention=conv, d=int(d), heads=int(heads), ffn=int(ffn), eps=float(lns[0].eps), device=ps[0].device)
+
+
+def supported_layer(m) -> bool:
+    """Whether ``m`` has the STRUCTURE of the layer the kernels serve (never its class name): either convention's attribute names
+    (``self_attn.{q,k,v,out}_proj``, ``self_attn_layer_norm``, ``fc1``, ``fc2``, ``final_layer_norm``; or ``attention.*``, ``layer_norm``,
+    ``feed_forward.intermediate_dense / output_dense``, ``final_layer_norm``), post-norm, the exact GELU, eval mode (no dropout effect), biases
+    everywhere, head dim 64, ``d <= 1024`` and ``ffn <= 4096`` in multiples of 64, and no further parameter, all on one GPU."""
+    return _layer_cfg(m) is not None
+
+
+def layer_state_dict(m) -> Dict[str, torch.Tensor]:
+    """The sixteen tensors of a layer under fairseq's names (``_LAYER_TENSORS``), whichever convention ``m`` follows."""
+    got = _layer_parts(m)
+    if got is None:
+        raise _lib.RvcmiError("layer_state_dict: not a transformer layer of either convention", code=_lib.ERR_INVALID)
+    return {"%s.%s" % (n, p): getattr(mod, p) for n, mod in got[1].items() for p in ("weight", "bias")}
+
+
+class HubertEncoderHIP:
+    """Some or all layers of a post-norm HuBERT transformer on the HIP kernels.  ``forward(x[B, T, d])`` -> the same shape and dtype (fp16 or
+    fp32), every layer's output rounded once to that dtype, so ``forward(first=0, n=2)`` is bit-equal to two calls of one layer."""
+
+    def __init__(self, state_dicts, cfg, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.RvcmiError("HubertEncoderHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
+        dev = torch.device("cuda", _lib.device_index(dev))
+        keep = []
+        for i, sd in enumerate(state_dicts):
+            for k, v in sd.items():
+                if torch.is_tensor(v) and v.is_floating_point() and 1 <= v.dim() <= 4:
+                    keep.append(("layers.%d.%s" % (i, k), v.detach().float().cpu().contiguous()))
+        if not keep:
+            raise _lib.RvcmiError("HubertEncoderHIP: no layer weights", code=_lib.ERR_INVALID)
+        arr = (_lib.Tensor * len(keep))()
+        for i, (k, v) in enumerate(keep):
+            arr[i].name = k.encode()
+            arr[i].data = v.data_ptr()
+            arr[i].ndim = v.dim()
+            for j, s in enumerate(v.shape):
+                arr[i].shape[j] = int(s)
+        h = C.c_void_p()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rvcmi_hubert_enc_create(arr, len(keep), len(state_dicts), int(cfg["d"]), int(cfg["heads"]), int(cfg["ffn"]),
+                                                          float(cfg.get("eps", 1e-5)), dev.index, C.byref(h)))
+        self._h = h
+        self._device = dev
+        self.n_layers, self.d = len(state_dicts), int(cfg["d"])
+        self._ws = None
+        self._retired = []  # earlier, smaller workspaces: a captured graph may still point at one
+
+    @classmethod
+    def from_state_dicts(cls, state_dicts, cfg, device) -> "HubertEncoderHIP":
+        """``state_dicts``: one dict per layer under fairseq's names (``layer_state_dict``); ``cfg``: ``d``, ``heads``, ``ffn``, ``eps``."""
+        return cls(list(state_dicts), cfg, device)
+
+    @classmethod
+    def from_layers(cls, modules, device=None) -> "HubertEncoderHIP":
+        """From torch layer modules on a GPU, fairseq's or transformers' (each recognised by ``supported_layer``, all of one geometry)."""
+        cfgs = [_layer_cfg(m) for m in modules]
+        if not cfgs or any(c is None for c in cfgs):
+            raise _lib.RvcmiError("HubertEncoderHIP: not the layers the kernels serve (post-norm, exact GELU, head dim 64, eval mode, on a GPU)",
+                                  code=_lib.ERR_INVALID)
+        key = lambda c: (c["d"], c["heads"], c["ffn"], c["eps"], c["device"])
+        if len({key(c) for c in cfgs}) != 1:
+            raise _lib.RvcmiError("HubertEncoderHIP: the layers differ in geometry or device", code=_lib.ERR_INVALID)
+        return cls([layer_state_dict(m) for m in modules], cfgs[0], cfgs[0]["device"] if device is None else device)
+
+    def __del__(self):
+        h = self.__dict__.pop("_h", None)
+        if h:
+            try:
+                _lib.lib().rvcmi_hubert_enc_destroy(h)
+            except Exception:  # noqa  (interpreter shutdown)
+                pass
+
+    def workspace_bytes(self, B: int, T: int) -> int:
+        return int(_lib.lib().rvcmi_hubert_enc_workspace_bytes(self._h, int(B), int(T)))
+
+    def _own_workspace(self, need: int) -> torch.Tensor:
+        if self._ws is None or self._ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.RvcmiError("HubertEncoderHIP: the first call of a larger shape allocates its workspace and must not be inside a stream "
+                                      "capture; call once before the capture or pass workspace=")
+            if self._ws is not None:
+                self._retired.append(self._ws)
+            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
+        return self._ws
+
+    def forward(self, x: torch.Tensor, key_mask: Optional[torch.Tensor] = None, first: int = 0, n: Optional[int] = None,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Layers ``first .. first + n - 1`` (default: all from ``first``).  ``key_mask``: bool / uint8 ``[B, T]`` on the GPU, nonzero = a padded
+        key no query attends to (padded QUERY rows are computed like any other, as torch does).  ``workspace``: a uint8 tensor of
+        ``workspace_bytes(B, T)`` bytes; default: the object's own, which grows on the first call of a larger shape (not inside a capture)."""
+        if not torch.is_tensor(x) or x.device.type != "cuda":
+            raise _lib.RvcmiError("HubertEncoderHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(x, "device", type(x)))
+        if x.device != self._device:
+            raise _lib.RvcmiError("HubertEncoderHIP: the input is on %s, the weights on %s" % (x.device, self._device))
+        if x.dim() != 3 or x.dtype not in (torch.float16, torch.float32) or int(x.shape[2]) != self.d:
+            raise _lib.RvcmiError("HubertEncoderHIP: expected an fp16 or fp32 [B, T, %d], got %s %s" % (self.d, x.dtype, tuple(x.shape)), code=_lib.ERR_INVALID)
+        B, T = int(x.shape[0]), int(x.shape[1])
+        n = self.n_layers - int(first) if n is None else int(n)
+        x = x.detach().contiguous()
+        km = 0
+        if key_mask is not None:
+            if key_mask.device != x.device or tuple(key_mask.shape) != (B, T):
+                raise _lib.RvcmiError("HubertEncoderHIP: the key mask must be [B, T] = %s on %s" % ((B, T), x.device), code=_lib.ERR_INVALID)
+            key_mask = (key_mask if key_mask.dtype in (torch.uint8, torch.bool) else key_mask != 0).contiguous()
+            key_mask = key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
+            km = key_mask.data_ptr()
+        need = self.workspace_bytes(B, T)
+        if workspace is not None:
+            if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() < need or need == 0:
+                raise _lib.RvcmiError("HubertEncoderHIP: the workspace must be %d uint8 on %s" % (need, x.device), code=_lib.ERR_INVALID)
+        else:
+            workspace = self._own_workspace(need)
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().rvcmi_hubert_enc_forward(self._h, int(first), n, B, T, C.c_void_p(x.data_ptr()), 1 if x.dtype == torch.float16 else 0,
+                                                           C.c_void_p(km), C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                                           C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        return out
+
+    __call__ = forward
+
+
+class HubertLayerHIP(torch.nn.Module):
+    """The drop-in for ONE layer: layer ``index`` of ``encoder``, answering in the convention of the module it replaced (``_original``, kept
+    unregistered).  fairseq: ``layer(x[T, B, C], self_attn_mask=None, self_attn_padding_mask=None, need_weights=False, att_args=None) ->
+    (x, (None, None))``.  transformers: ``layer(hidden_states[B, T, C], attention_mask=None, output_attentions=False) -> (hidden_states,)``.
+    What the kernels do not compute -- an attention mask over (query, key) pairs, attention weights -- goes to the original module."""
+
+    def __init__(self, encoder: HubertEncoderHIP, index: int, convention: str):
+        super().__init__()
+        if convention not in ("fairseq", "transformers"):
+            raise ValueError("convention: 'fairseq' or 'transformers'")
+        object.__setattr__(self, "encoder", encoder)
+        self.index = int(index)
+        self.convention = convention
+
+    def forward(self, *args, **kw):
+        return self._fairseq(*args, **kw) if self.convention == "fairseq" else self._transformers(*args, **kw)
+
+    def _fairseq(self, x, self_attn_mask=None, self_attn_padding_mask=None, need_weights=False, att_args=None):
+        if self_attn_mask is not None or need_weights:
+            return self.__dict__["_original"](x, self_attn_mask=self_attn_mask, self_attn_padding_mask=self_attn_padding_mask, need_weights=need_weights,
+                                              att_args=att_args)
+        y = self.encoder.forward(x.transpose(0, 1), self_attn_padding_mask, first=self.index, n=1)
+        return y.transpose(0, 1), (None, None)
+
+    def _transformers(self, hidden_states, attention_mask=None, output_attentions=False, **kw):
+        if output_attentions or kw:
+            return self.__dict__["_original"](hidden_states, attention_mask=attention_mask, output_attentions=output_attentions, **kw)
+        km = None
+        if attention_mask is not None:  # [B, 1, 1 or T, T]: additive (negative = masked) or boolean (True = attend); a device op, no sync
+            row = attention_mask[:, 0, 0, :]
+            km = ~row if row.dtype == torch.bool else row < 0
+        return (self.encoder.forward(hidden_states, km, first=self.index, n=1),)
+
+
+def _layer_lists(model):
+    """The ``ModuleList``s of transformer layers: ``model.encoder.layers``, else the same one attribute down (as ``_holders`` looks)."""
+    def of(m):
+        layers = getattr(getattr(m, "encoder", None), "layers", None)
+        return layers if isinstance(layers, torch.nn.ModuleList) and len(layers) else None
+    if of(model) is not None:
+        return [of(model)]
+    subs = list(model.children()) if isinstance(model, torch.nn.Module) else []
+    subs += [v for v in getattr(model, "__dict__", {}).values() if isinstance(v, torch.nn.Module)]
+    out = []
+    for m in subs:
+        if of(m) is not None and not any(of(m) is o for o in out):
+            out.append(of(m))
+    return out
+
+
+def accelerate_hubert_layers(model) -> int:
+    """Replace every layer of ``model.encoder.layers`` (or of the module one attribute down) by a ``HubertLayerHIP`` on ONE ``HubertEncoderHIP``
+    with the same weights, in place.  ALL OR NONE: if any layer is not ``supported_layer`` (or they differ in geometry), nothing is modified
+    and 0 is returned.  -> the number of layers swapped.  The originals stay on the HIP modules (unregistered) for ``restore_hubert_layers``."""
+    n = 0
+    for layers in _layer_lists(model):
+        mods = list(layers)
+        try:
+            enc = HubertEncoderHIP.from_layers(mods)
+        except _lib.RvcmiError as e:
+            if e.code == _lib.ERR_INVALID:  # layers the kernels do not serve: torch's modules stay
+                continue
+            raise
+        for i, m in enumerate(mods):
+            hip = HubertLayerHIP(enc, i, _layer_parts(m)[0])
+            hip.eval()
+            object.__setattr__(hip, "_original", m)  # (not registered: its weights must not appear twice in state_dict())
+            layers[i] = hip
+            n += 1
+    return n
+
+
+def restore_hubert_layers(model) -> int:
+    """Undo ``accelerate_hubert_layers``.  -> the number of torch modules put back."""
+    n = 0
+    for layers in _layer_lists(model):
+        for i, m in enumerate(list(layers)):
+            orig = m.__dict__.get("_original") if isinstance(m, HubertLayerHIP) else None
+            if orig is not None:
+                layers[i] = orig
+                n += 1
+    getattr(model, "__dict__", {}).pop("_rvcmi_hubert_enc", None)
+    return n
+
+
+def accelerate_hubert_layers_once(model) -> int:
+    """What the conversion paths call next to ``accelerate_hubert_once``: with the switch on, ``accelerate_hubert_layers(model)`` once per
+    model object (the count is remembered on it as ``_rvcmi_hubert_enc``); with it off, nothing."""
+    if not hubert_enc_on():
+        return 0
+    n = getattr(model, "_rvcmi_hubert_enc", None)
+    if n is None:
+        n = accelerate_hubert_layers(model)
+        try:
+            object.__setattr__(model, "_rvcmi_hubert_enc", n)
+        except Exception:  # noqa  (an object without a __dict__)
             pass
     return n

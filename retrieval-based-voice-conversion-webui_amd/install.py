@@ -169,7 +169,7 @@ def _rebind_gate(rebound) -> None:
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
             patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False,
             index_build: Optional[bool] = None, hubert_fe: bool = False, hubert_batch: bool = False,
-            front_operand: Optional[str] = None) -> None:
+            front_operand: Optional[str] = None, hubert_enc: bool = False) -> None:
     """Route the reference's loader, index reader and conversion methods through the HIP path (idempotent).  ``patch_gui=True``
     also rebinds the realtime GUI's ``TorchGate`` (``infer.modules.gui`` and ``infer.modules.gui.torchgate``) to ``TorchGateHIP``.
     ``device_prep=True`` (opt-in, as ``RVCMI_DEVICE_PREP=1``): the rebound ``Pipeline.pipeline`` / ``convert_files`` run the input
@@ -186,7 +186,9 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     (``hubert.extract_features_batch``) instead of once per segment, for a model that honours ``padding_mask`` (``hubert.batch_capable``).
     ``front_operand="fp16x2"`` (opt-in, as ``RVCMI_FRONT_OPERAND=fp16x2``; default off): the loaders install the HIP front in that operand
     mode whatever the generator's ``operand`` (``synthesizer.accelerate_synthesizer``): with ``operand="fp32"`` the whole ``infer`` runs
-    on HIP at fp32-grade fidelity instead of leaving ``enc_p`` / ``flow`` on torch."""
+    on HIP at fp32-grade fidelity instead of leaving ``enc_p`` / ``flow`` on torch.  ``hubert_enc=True`` (opt-in, as ``RVCMI_HUBERT_ENC=1``;
+    default off; independent of ``hubert_fe``): the conversion paths swap the layers of HuBERT's transformer for ``hubert.HubertLayerHIP``
+    (``hubert.accelerate_hubert_layers``: all layers or none), once per model object."""
     if _state.get("installed"):
         return
     _syn.front_operand_choice(front_operand)  # a bad name raises here, before anything is rebound
@@ -260,6 +262,7 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
 
     _hubert.HUBERT_FE = bool(hubert_fe)
     _hubert.HUBERT_BATCH = bool(hubert_batch)
+    _hubert.HUBERT_ENC = bool(hubert_enc)
     _syn.FRONT_OPERAND = front_operand
 
 
@@ -289,5 +292,6 @@ def uninstall() -> None:
 
     _hubert.HUBERT_FE = False
     _hubert.HUBERT_BATCH = False
+    _hubert.HUBERT_ENC = False
     _syn.FRONT_OPERAND = None
     _state.clear()

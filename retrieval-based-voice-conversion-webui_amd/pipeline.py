@@ -84,9 +84,10 @@ def hubert_device(self, model, audio0, pitch, pitchf, version, feats=None):
         dev = torch.device(self.device)
         feats = _hubert_wave(self, audio0).view(1, -1)
         padding_mask = torch.zeros(feats.shape, dtype=torch.bool, device=dev)
-        from .hubert import accelerate_hubert_once
+        from .hubert import accelerate_hubert_layers_once, accelerate_hubert_once
 
         accelerate_hubert_once(model)  # (beyond SURVEY 8; opt-in, a no-op with the switch off) the extractor's seven convolutions on HIP
+        accelerate_hubert_layers_once(model)  # (RVCMI_HUBERT_ENC, opt-in, likewise) the transformer's layers on HIP
         with torch.no_grad():
             logits = model.extract_features(source=feats.to(dev), padding_mask=padding_mask, output_layer=9 if version == "v1" else 12)
             feats = model.final_proj(logits[0]) if version == "v1" else logits[0]
@@ -109,6 +110,7 @@ def hubert_batched(model) -> bool:
     if not hb.hubert_batch_on():
         return False
     hb.accelerate_hubert_once(model)
+    hb.accelerate_hubert_layers_once(model)  # (RVCMI_HUBERT_ENC, opt-in: the swapped layers take the padding mask as their key mask)
     return hb.batch_capable(model)
 
 

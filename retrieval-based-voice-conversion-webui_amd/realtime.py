@@ -394,9 +394,10 @@ def rvc_infer_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, ret
             feats = feats.mean(-1)
         feats = feats.view(1, -1)
         mask = torch.zeros(feats.shape, dtype=torch.bool, device=feats.device)
-        from .hubert import accelerate_hubert_once
+        from .hubert import accelerate_hubert_layers_once, accelerate_hubert_once
 
         accelerate_hubert_once(self.hubert)  # (opt-in, a no-op with the switch off)
+        accelerate_hubert_layers_once(self.hubert)  # (RVCMI_HUBERT_ENC, opt-in, likewise)
         logits = self.hubert.extract_features(source=feats, padding_mask=mask, output_layer=9 if self.version == "v1" else 12)
         feats = self.hubert.final_proj(logits[0]) if self.version == "v1" else logits[0]
     pitch = pitchf = None
