@@ -271,6 +271,129 @@ def device_index(dev) -> int:
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+# ---- what every wrapper of a handle shares ----------------------------------------------------------------------
+
+def cuda_device(device, who: str):
+    """``device`` as ``torch.device("cuda", i)`` with the index filled in; anything that is not a GPU raises."""
+    import torch
+
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RvcmiError("%s needs a GPU device (got %s); there is no CPU fallback" % (who, device))
+    return torch.device("cuda", device_index(dev))
+
+
+def ptr(t) -> C.c_void_p:
+    """The data pointer of a tensor; ``None`` is the null pointer."""
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def stream_ptr(dev) -> C.c_void_p:
+    """torch's current stream on ``dev``: every launch of the library goes on the caller's stream."""
+    import torch
+
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def require_on(t, device, who: str) -> None:
+    """``t`` must be a tensor on the GPU ``device`` (normalised, as ``cuda_device`` returns it).  The library launches on the handle's
+    device with ``t``'s pointer and ``t``'s stream, so a mismatch must not get through."""
+    import torch
+
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise RvcmiError("%s input must live on the GPU (got %s); there is no CPU fallback" % (who, getattr(t, "device", type(t))))
+    if t.device != device:
+        raise RvcmiError("%s: the input is on %s, the weights on %s" % (who, t.device, device))
+
+
+def on_gpu(t, what: str):
+    """The argument ``what`` of a stateless entry point (the glue): on any GPU -> its device, which is where the call launches."""
+    if t.device.type != "cuda":
+        raise RvcmiError("%s must live on the GPU (got %s); the glue has no CPU fallback" % (what, t.device))
+    return t.device
+
+
+def workspace_ptr(workspace, need: int, device, who: str) -> C.c_void_p:
+    """A caller's workspace as a pointer: it must hold ``need`` (> 0) uint8 on ``device``."""
+    import torch
+
+    if workspace.device != device or workspace.dtype != torch.uint8 or workspace.numel() < need or need == 0:
+        raise RvcmiError("%s: the workspace must be %d uint8 on %s" % (who, need, device), code=ERR_INVALID)
+    return ptr(workspace)
+
+
+def pack_tensors(named):
+    """(name, fp32 contiguous CPU tensor) pairs -> the ``rvcmi_tensor`` array a create call reads.  The array keeps the encoded names and
+    the tensors alive (``.keep``), so it is valid for as long as the caller holds it."""
+    import torch
+
+    keep = [(k.encode(), t) for k, t in named]
+    arr = (Tensor * len(keep))()
+    for a, (kb, t) in zip(arr, keep):
+        if t.device.type != "cpu" or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() > 4:
+            raise ValueError("pack_tensors: '%s' must be a contiguous fp32 CPU tensor of at most 4 dimensions" % kb.decode())
+        a.name, a.data, a.ndim = kb, t.data_ptr(), t.dim()
+        a.shape[:t.dim()] = list(t.shape)
+    arr.keep = keep
+    return arr
+
+
+class Handle:
+    """Owns one ``rvcmi_*`` handle and the NAME of its destroy function (looked up at close: at interpreter shutdown the library may be
+    gone, and then there is nothing left to free).  Truthy while open; passes to ctypes as the pointer."""
+
+    def __init__(self, destroy: str, pointer: C.c_void_p):
+        self._destroy, self._as_parameter_ = destroy, pointer
+
+    def __bool__(self) -> bool:
+        return bool(self._as_parameter_)
+
+    def close(self) -> None:
+        p, self._as_parameter_ = self._as_parameter_, C.c_void_p(None)
+        if p:
+            getattr(lib(), self._destroy)(p)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa  (interpreter shutdown)
+            pass
+
+
+class Switch:
+    """An opt-in of the integration layer.  Its value IS the module global ``name`` of ``ns`` (what ``install()`` and the tests set), so the
+    global keeps its name and meaning; the environment variable ``env`` = ``"1"`` / ``"0"`` overrides it per call, any other value is
+    ignored.  ``base``: a switch this one is effective only together with."""
+
+    def __init__(self, env: str, ns: dict, name: str, base: "Switch" = None):
+        self.env, self._ns, self.name, self.base = env, ns, name, base
+
+    @property
+    def value(self):
+        return self._ns[self.name]
+
+    @value.setter
+    def value(self, v) -> None:
+        self._ns[self.name] = v
+
+    def on(self) -> bool:
+        env = os.environ.get(self.env)
+        return (self.base is None or self.base.on()) and (env == "1" if env in ("0", "1") else bool(self.value))
+
+
+def once(obj, attr: str, fn):
+    """``fn()`` once per object: the result is remembered on ``obj`` as ``attr`` and returned from then on.  An object that cannot hold
+    it (no ``__dict__``) has ``fn`` run again next time."""
+    got = getattr(obj, attr, None)
+    if got is None:
+        got = fn()
+        try:
+            object.__setattr__(obj, attr, got)
+        except Exception:  # noqa
+            pass
+    return got
+
+
 def set_option(fn, handle, key: str, value) -> None:
     """Dev / test option of one handle (include/rvcmi.h rvcmi_*_set_option); ``value=None`` restores the default."""
     check(fn(handle, key.encode(), float("nan") if value is None else float(value)))

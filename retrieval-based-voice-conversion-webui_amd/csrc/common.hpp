@@ -16,6 +16,7 @@
 
 #include "../../include/rvcmi.h"
 #include "error.hpp"
+#include "weights.hpp"
 
 namespace rvcmi {
 
@@ -94,6 +95,45 @@ struct DevBuf {
         return *this;
     }
 };
+
+// alloc + copy from the host (weights at create, test hooks): synchronous, so `src` may be a temporary
+inline void upload(DevBuf& d, const void* src, size_t bytes) {
+    d.alloc(bytes);
+    if (bytes) HIP_CHECK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+}
+template <typename T>
+void upload(DevBuf& d, const std::vector<T>& v) {
+    upload(d, v.data(), v.size() * sizeof(T));
+}
+
+// A handle's own workspace, grown to the largest size asked for.  A graph captured at a smaller size replays into the buffer of that
+// time, so an outgrown buffer is retired, not freed: it lives as long as the handle.  A call that grows must be outside any capture (it
+// synchronises `st` and allocates).  If the allocation throws, the previous buffer stays current and nothing is retired.
+struct GrowBuf {
+    DevBuf cur;
+    std::vector<DevBuf> retired;
+    char* ensure(size_t bytes, hipStream_t st) {
+        if (bytes > cur.bytes) {
+            HIP_CHECK(hipStreamSynchronize(st));
+            DevBuf next;
+            next.alloc(bytes);
+            if (cur.p) retired.push_back(std::move(cur));
+            cur = std::move(next);
+        }
+        return cur.as<char>();
+    }
+};
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is per device: set it once per (kernel, device).  `done`: one static per kernel
+// instantiation, one bit per device (a process-global flag would leave the second GPU of a multi-GPU process without it).
+inline void ensure_dyn_lds(const void* kernel, int bytes, std::atomic<unsigned long long>& done) {
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return;
+    HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_release);
+}
 
 // Dev / test options of a handle: a small key -> number table, filled ONCE at handle creation from the environment
 // (RVCMI_<KEY>) and changed afterwards only through rvcmi_{nsf,front,ivf}_set_option.  The forward / search paths read the

@@ -1,9 +1,8 @@
 // Host-side weight preparation shared by the generator (nsf.hip) and the encoder/flow front (front.hip):
-// fp32 -> operand conversion, MFMA fragment-order packing of convolution weights, named-tensor lookup.
+// fp32 -> operand conversion, MFMA fragment-order packing of convolution weights.
 #pragma once
 #include <functional>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "common.hpp"
@@ -59,8 +58,7 @@ static void build_conv(ConvLayer& L, int cin, int cout, int nphase, const int* n
     }
     L.flops_per_pos = 2.0 * cin * cout * jsum;
     if (bias) {
-        L.bias.alloc(sizeof(float) * cout);
-        HIP_CHECK(hipMemcpy(L.bias.p, bias, sizeof(float) * cout, hipMemcpyHostToDevice));
+        upload(L.bias, bias, sizeof(float) * cout);
     }
     if (operand == RVCMI_OPERAND_F32) {
         std::vector<float> w((size_t)jsum * cin * cout);
@@ -72,8 +70,7 @@ static void build_conv(ConvLayer& L, int cin, int cout, int nphase, const int* n
                     for (int co = 0; co < cout; ++co) w[off + ((size_t)j * cin + ci) * cout + co] = W(co, ci, p, j);
             off += (long)ntaps[p] * cin * cout;
         }
-        L.w_f32.alloc(w.size() * sizeof(float));
-        HIP_CHECK(hipMemcpy(L.w_f32.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        upload(L.w_f32, w);
         L.ntaps_p = jmax;
         return;
     }
@@ -112,31 +109,7 @@ static void build_conv(ConvLayer& L, int cin, int cout, int nphase, const int* n
                     }
                 }
     }
-    L.w_pack.alloc(pk.size() * 2);
-    HIP_CHECK(hipMemcpy(L.w_pack.p, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-}
-
-struct WeightMap {
-    std::unordered_map<std::string, const rvcmi_tensor*> m;
-    const rvcmi_tensor& get(const std::string& name, std::initializer_list<int64_t> shape) const {
-        auto it = m.find(name);
-        if (it == m.end()) RVCMI_FAIL(RVCMI_ERR_MISSING, "missing weight tensor '%s'", name.c_str());
-        const rvcmi_tensor& t = *it->second;
-        if ((size_t)t.ndim != shape.size()) RVCMI_FAIL(RVCMI_ERR_INVALID, "weight '%s': ndim %d", name.c_str(), t.ndim);
-        int i = 0;
-        for (int64_t s : shape) {
-            if (t.shape[i] != s)
-                RVCMI_FAIL(RVCMI_ERR_INVALID, "weight '%s': dim %d is %lld, expected %lld", name.c_str(), i,
-                           (long long)t.shape[i], (long long)s);
-            ++i;
-        }
-        return t;
-    }
-};
-
-static void upload(DevBuf& d, const std::vector<float>& v) {
-    d.alloc(v.size() * sizeof(float));
-    HIP_CHECK(hipMemcpy(d.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+    upload(L.w_pack, pk);
 }
 
 }  // namespace rvcmi

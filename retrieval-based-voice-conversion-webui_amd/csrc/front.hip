@@ -64,20 +64,6 @@ struct TapReq {
     bool done = false;
 };
 
-const float* wdata(const WeightMap& wm, const std::string& name, std::initializer_list<int64_t> shape) {
-    return (const float*)wm.get(name, shape).data;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set it once per (kernel instantiation, device).
-static void ensure_dyn_lds(const void* kern, std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return;
-    HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done.fetch_or(bit, std::memory_order_release);
-}
-
 // Time-tile height: 64 rows (NJ = 2) when that still gives every CU a block, else 32 rows -- at B = 1 a 10 s clip is
 // only 38 tiles of 32 frames, and one tile's MFMA work on one CU is the latency floor of a launch.
 static int pick_nj(const rvcmi_front* h, int B, int T) {
@@ -108,7 +94,7 @@ void launch_conv_nj(rvcmi_front* h, const char* name, FrConvArgs a, const ConvLa
     const int gy = (ctiles + NW * MI - 1) / (NW * MI);
     auto kern = k_fr_conv<OpT, CIN, MI, NJ, NW, EPI>;
     static std::atomic<unsigned long long> attr_done{0};  // one instantiation = one static; one bit per device
-    ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr_done);
+    ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done);
     const double flops = L.flops_per_pos * (double)a.T * B;
     h->prof.launch(name, flops, 0.0, st, [&] {
         hipLaunchKernelGGL(kern, dim3((a.T + TT - 1) / TT, gy, B), dim3(64 * NW), smem, st, a);
@@ -136,7 +122,7 @@ void launch_wn_nj(rvcmi_front* h, FrWnArgs a, const ConvLayer& Lin, const ConvLa
     const size_t smem = (size_t)(TT + a.ntaps - 1 + 2 + TT + 2) * Tile<H>::STRIDE + 2 * H * sizeof(float);
     auto kern = k_fr_wn<OpT, H, NJ, LAST>;
     static std::atomic<unsigned long long> attr_done{0};  // one instantiation = one static; one bit per device
-    ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr_done);
+    ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done);
     const double flops = (Lin.flops_per_pos + Lrs.flops_per_pos) * (double)a.T * B;
     static unsigned long long* stamps = nullptr;  // dev only
     const bool want_stamps = h->opt.on("FR_STAMPS");
@@ -176,7 +162,7 @@ void launch_wn_split(rvcmi_front* h, const FrWnArgs& w, const ConvLayer& Lin, co
             const size_t smem = (size_t)rows * Tile<H>::STRIDE + (size_t)(a.ntaps - 1) * 2 * 16 * 64 * sizeof(float);
             auto kern = k_fr_gate_ks<OpT, H, 1>;
             static std::atomic<unsigned long long> attr_done{0};
-            ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr_done);
+            ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done);
             h->prof.launch("flow_wn_gate", Lin.flops_per_pos * (double)a.T * B, 0.0, st, [&] {
                 hipLaunchKernelGGL(kern, dim3((a.T + 31) / 32, H / 32, B), dim3(64 * a.ntaps), smem, st, a);
             });
@@ -244,7 +230,7 @@ void launch_ffn_nj(rvcmi_front* h, FrFfnArgs a, const ConvLayer& L1, const ConvL
     const size_t smem = (size_t)(HR + a.ntaps - 1 + 2) * Tile<H>::STRIDE + (size_t)(HR + a.ntaps - 1 + 2) * Tile<F>::STRIDE;
     auto kern = k_fr_ffn<OpT, H, F, NJ1>;
     static std::atomic<unsigned long long> attr_done{0};  // one instantiation = one static; one bit per device
-    ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr_done);
+    ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done);
     const double flops = (L1.flops_per_pos + L2.flops_per_pos) * (double)a.T * B;
     h->prof.launch("enc_ffn_ln", flops, 0.0, st, [&] {
         hipLaunchKernelGGL(kern, dim3((a.T + TV - 1) / TV, B), dim3(64 * (H / 32)), smem, st, a);
@@ -269,7 +255,7 @@ void launch_ffn_split_nj(rvcmi_front* h, FrFfnArgs a, const ConvLayer& L1, const
     const size_t smem = (size_t)(HR + a.ntaps - 1 + 2) * Tile<H>::STRIDE + (size_t)(HR + a.ntaps - 1 + 2) * Tile<FS>::STRIDE;
     auto kern = k_fr_ffn_part<OpT, H, FS, NJ1>;
     static std::atomic<unsigned long long> attr_done{0};
-    ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr_done);
+    ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done);
     const double flops = (L1.flops_per_pos + L2.flops_per_pos) * (double)a.T * B;
     h->prof.launch("enc_ffn_part", flops, 0.0, st, [&] {
         hipLaunchKernelGGL(kern, dim3((a.T + TV - 1) / TV, B, FFN_SPLIT), dim3(64 * (H / 32)), smem, st, a);
@@ -495,11 +481,6 @@ void front_forward(rvcmi_front* h, int B, int T, const float* phone, const int64
     }
 }
 
-void upload_vec(DevBuf& d, const float* p, size_t n) {
-    d.alloc(n * sizeof(float));
-    HIP_CHECK(hipMemcpy(d.p, p, n * sizeof(float), hipMemcpyHostToDevice));
-}
-
 rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* weights, int n_weights, int device, int max_B, int max_T) {
     if (!cfg || !weights) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
     const rvcmi_front_config& c = *cfg;
@@ -516,8 +497,7 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
         RVCMI_FAIL(RVCMI_ERR_INVALID, "front: unsupported layer counts / kernel sizes");
     if (max_B < 1 || max_T < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "front: max_B/max_T must be positive");
     HIP_CHECK(hipSetDevice(device));
-    WeightMap wm;
-    for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+    WeightTable wm(weights, n_weights, "front_create");
     std::unique_ptr<rvcmi_front> h(new rvcmi_front);
     // (fp16x2 has one launch form per layer: only the tile height is an option there, see rvcmi_front_set_option)
     if (pair) h->opt.load_env({"FR_NJ"});
@@ -532,31 +512,31 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
     const int op = c.operand;
 
     {   // emb_phone: Linear(in, H) = 1x1 conv   encoders.py:142
-        const float* W = wdata(wm, "enc_p.emb_phone.weight", {H, IN});
-        const float* b = wdata(wm, "enc_p.emb_phone.bias", {H});
+        const float* W = wm.get("enc_p.emb_phone.weight", {H, IN});
+        const float* b = wm.get("enc_p.emb_phone.bias", {H});
         build_conv(h->emb, IN, H, 1, &one, &zero, 1, [&](int co, int ci, int, int) { return W[(size_t)co * IN + ci]; }, b, op);
-        if (c.use_f0) upload_vec(h->emb_pitch, wdata(wm, "enc_p.emb_pitch.weight", {256, H}), (size_t)256 * H);
+        if (c.use_f0) upload(h->emb_pitch, wm.get("enc_p.emb_pitch.weight", {256, H}), (size_t)256 * H * sizeof(float));
     }
     h->layers.resize(c.n_layers);
     for (int i = 0; i < c.n_layers; ++i) {
         AttnLayer& L = h->layers[i];
         const std::string a = "enc_p.encoder.attn_layers." + std::to_string(i) + ".";
-        const float* Wq = wdata(wm, a + "conv_q.weight", {H, H, 1});
-        const float* Wk = wdata(wm, a + "conv_k.weight", {H, H, 1});
-        const float* Wv = wdata(wm, a + "conv_v.weight", {H, H, 1});
+        const float* Wq = wm.get(a + "conv_q.weight", {H, H, 1});
+        const float* Wk = wm.get(a + "conv_k.weight", {H, H, 1});
+        const float* Wv = wm.get(a + "conv_v.weight", {H, H, 1});
         std::vector<float> bq(3 * H);
-        memcpy(bq.data(), wdata(wm, a + "conv_q.bias", {H}), H * 4);
-        memcpy(bq.data() + H, wdata(wm, a + "conv_k.bias", {H}), H * 4);
-        memcpy(bq.data() + 2 * H, wdata(wm, a + "conv_v.bias", {H}), H * 4);
+        memcpy(bq.data(), wm.get(a + "conv_q.bias", {H}), H * 4);
+        memcpy(bq.data() + H, wm.get(a + "conv_k.bias", {H}), H * 4);
+        memcpy(bq.data() + 2 * H, wm.get(a + "conv_v.bias", {H}), H * 4);
         build_conv(L.qkv, H, 3 * H, 1, &one, &zero, 1, [&](int co, int ci, int, int) {
             const float* W = co < H ? Wq : (co < 2 * H ? Wk : Wv);
             return W[(size_t)(co % H) * H + ci];
         }, bq.data(), op);
-        const float* Wo = wdata(wm, a + "conv_o.weight", {H, H, 1});
+        const float* Wo = wm.get(a + "conv_o.weight", {H, H, 1});
         build_conv(L.o, H, H, 1, &one, &zero, 1, [&](int co, int ci, int, int) { return Wo[(size_t)co * H + ci]; },
-                   wdata(wm, a + "conv_o.bias", {H}), op);
+                   wm.get(a + "conv_o.bias", {H}), op);
         // relative embeddings (attentions.py:45-54): keys as A fragments of one 32-row tile, values fp32
-        const float* Ek = wdata(wm, a + "emb_rel_k", {1, nb, dk});
+        const float* Ek = wm.get(a + "emb_rel_k", {1, nb, dk});
         const size_t rk_plane = (size_t)(dk / 16) * 512;
         std::vector<uint16_t> pk(rk_plane * (pair ? 2 : 1), 0);  // fp16x2: hi plane, lo plane
         for (int s = 0; s < dk / 16; ++s)
@@ -574,23 +554,22 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
                     }
                 }
             }
-        L.relk.alloc(pk.size() * 2);
-        HIP_CHECK(hipMemcpy(L.relk.p, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-        upload_vec(L.relv, wdata(wm, a + "emb_rel_v", {1, nb, dk}), (size_t)nb * dk);
+        upload(L.relk, pk);
+        upload(L.relv, wm.get(a + "emb_rel_v", {1, nb, dk}), (size_t)nb * dk * sizeof(float));
         const std::string n1 = "enc_p.encoder.norm_layers_1." + std::to_string(i) + ".";
         const std::string n2 = "enc_p.encoder.norm_layers_2." + std::to_string(i) + ".";
-        upload_vec(L.g1, wdata(wm, n1 + "gamma", {H}), H);
-        upload_vec(L.b1, wdata(wm, n1 + "beta", {H}), H);
-        upload_vec(L.g2, wdata(wm, n2 + "gamma", {H}), H);
-        upload_vec(L.b2, wdata(wm, n2 + "beta", {H}), H);
+        upload(L.g1, wm.get(n1 + "gamma", {H}), H * sizeof(float));
+        upload(L.b1, wm.get(n1 + "beta", {H}), H * sizeof(float));
+        upload(L.g2, wm.get(n2 + "gamma", {H}), H * sizeof(float));
+        upload(L.b2, wm.get(n2 + "beta", {H}), H * sizeof(float));
         const std::string f = "enc_p.encoder.ffn_layers." + std::to_string(i) + ".";
         const int ks = c.kernel_size;
-        const float* W1 = wdata(wm, f + "conv_1.weight", {FC, H, ks});
-        const float* W2 = wdata(wm, f + "conv_2.weight", {H, FC, ks});
+        const float* W1 = wm.get(f + "conv_1.weight", {FC, H, ks});
+        const float* W2 = wm.get(f + "conv_2.weight", {H, FC, ks});
         build_conv(L.f1, H, FC, 1, &ks, &zero, 1, [&](int co, int ci, int, int tap) { return W1[((size_t)co * H + ci) * ks + tap]; },
-                   wdata(wm, f + "conv_1.bias", {FC}), op);
+                   wm.get(f + "conv_1.bias", {FC}), op);
         build_conv(L.f2, FC, H, 1, &ks, &zero, 1, [&](int co, int ci, int, int tap) { return W2[((size_t)co * FC + ci) * ks + tap]; },
-                   wdata(wm, f + "conv_2.bias", {H}), op);
+                   wm.get(f + "conv_2.bias", {H}), op);
         if (FC % FFN_SPLIT == 0 && !pair) {
             const int FSl = FC / FFN_SPLIT;
             for (int sp = 0; sp < FFN_SPLIT; ++sp)  // conv_2 restricted to the input channels [sp * FSl, (sp + 1) * FSl): a conv of its own
@@ -604,9 +583,9 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
     };
     {   // proj: packed as (m tile, logs tile) pairs so that one wave holds both halves of a channel
         const int IC = c.inter_channels;
-        const float* W = wdata(wm, "enc_p.proj.weight", {2 * IC, H, 1});
+        const float* W = wm.get("enc_p.proj.weight", {2 * IC, H, 1});
         build_conv(h->proj, H, 2 * IC, 1, &one, &zero, 1, [&](int co, int ci, int, int) { return W[(size_t)paired(co, IC) * H + ci]; },
-                   wdata(wm, "enc_p.proj.bias", {2 * IC}), op);
+                   wm.get("enc_p.proj.bias", {2 * IC}), op);
     }
     // flow: coupling f runs after (n_flows - f) flips of the channel axis; the flips are folded into pre / post.
     h->flows.resize(c.flow_n_flows);
@@ -616,35 +595,35 @@ rvcmi_front* front_create(const rvcmi_front_config* cfg, const rvcmi_tensor* wei
         FlowLayer& FL = h->flows[f];
         const std::string p = "flow.flows." + std::to_string(2 * f) + ".";
         const bool odd = ((c.flow_n_flows - f) % 2) == 1;
-        const float* Wp = wdata(wm, p + "pre.weight", {H, half, 1});
+        const float* Wp = wm.get(p + "pre.weight", {H, half, 1});
         build_conv(FL.pre, IC, H, 1, &one, &zero, 1, [&](int co, int ph, int, int) {
             // logical x0[c] = physical channel c (even) / IC-1-c (odd)
             const int cl = odd ? IC - 1 - ph : ph;
             return cl < half ? Wp[(size_t)co * half + cl] : 0.f;
-        }, wdata(wm, p + "pre.bias", {H}), op);
+        }, wm.get(p + "pre.bias", {H}), op);
         for (int l = 0; l < c.flow_n_layers; ++l) {
             const bool last = l == c.flow_n_layers - 1;
-            const float* Wi = wdata(wm, p + "enc.in_layers." + std::to_string(l) + ".weight", {2 * H, H, fk});
+            const float* Wi = wm.get(p + "enc.in_layers." + std::to_string(l) + ".weight", {2 * H, H, fk});
             build_conv(FL.in[l], H, 2 * H, 1, &fk, &zero, 1,
                        [&](int co, int ci, int, int tap) { return Wi[((size_t)paired(co, H) * H + ci) * fk + tap]; },
-                       wdata(wm, p + "enc.in_layers." + std::to_string(l) + ".bias", {2 * H}), op);
+                       wm.get(p + "enc.in_layers." + std::to_string(l) + ".bias", {2 * H}), op);
             const int rsn = last ? H : 2 * H;
-            const float* Wr = wdata(wm, p + "enc.res_skip_layers." + std::to_string(l) + ".weight", {rsn, H, 1});
+            const float* Wr = wm.get(p + "enc.res_skip_layers." + std::to_string(l) + ".weight", {rsn, H, 1});
             build_conv(FL.rs[l], H, rsn, 1, &one, &zero, 1,
                        [&](int co, int ci, int, int) { return Wr[(size_t)(last ? co : paired(co, H)) * H + ci]; },
-                       wdata(wm, p + "enc.res_skip_layers." + std::to_string(l) + ".bias", {rsn}), op);
+                       wm.get(p + "enc.res_skip_layers." + std::to_string(l) + ".bias", {rsn}), op);
         }
         // post (mean only): output row o addresses physical channel phys_base + o
-        const float* Wo = wdata(wm, p + "post.weight", {half, H, 1});
-        const float* bo = wdata(wm, p + "post.bias", {half});
+        const float* Wo = wm.get(p + "post.weight", {half, H, 1});
+        const float* bo = wm.get(p + "post.bias", {half});
         std::vector<float> bperm(half);
         for (int o = 0; o < half; ++o) bperm[o] = bo[odd ? half - 1 - o : o];
         build_conv(FL.post, H, half, 1, &one, &zero, 1, [&](int o, int ci, int, int) { return Wo[(size_t)(odd ? half - 1 - o : o) * H + ci]; },
                    bperm.data(), op);
         FL.phys_base = odd ? 0 : half;
         if (c.gin_channels) {
-            const float* Wc = wdata(wm, p + "enc.cond_layer.weight", {gcn, c.gin_channels, 1});
-            const float* bc = wdata(wm, p + "enc.cond_layer.bias", {gcn});
+            const float* Wc = wm.get(p + "enc.cond_layer.weight", {gcn, c.gin_channels, 1});
+            const float* bc = wm.get(p + "enc.cond_layer.bias", {gcn});
             cw.insert(cw.end(), Wc, Wc + (size_t)gcn * c.gin_channels);
             cb.insert(cb.end(), bc, bc + gcn);
         }

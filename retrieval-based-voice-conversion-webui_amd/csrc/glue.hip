@@ -10,17 +10,6 @@
 
 using namespace rvcmi;
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device: set it once for every device a call is made on (a process-global
-// flag would leave the second GPU of a multi-GPU process without it).
-template <typename K>
-static void ensure_dyn_lds(K kernel, int bytes, std::atomic<unsigned long long>& done_mask) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done_mask.load(std::memory_order_acquire) & bit) return;
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done_mask.fetch_or(bit, std::memory_order_release);
-}
 static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0},
     g_attr_gate_stft{0}, g_attr_gate_idft{0};
 
@@ -28,8 +17,8 @@ static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola
 static void launch_phase_vocoder(const float* a, const float* b, const int* b_off, const float* fade_out, const float* fade_in, int n, float* out,
                                  double* bins, hipStream_t st) {
     const int nb = n / 2 + 1;
-    ensure_dyn_lds(k_pv_spectrum, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec);
-    ensure_dyn_lds(k_pv_synth, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth);
+    ensure_dyn_lds((const void*)k_pv_spectrum, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec);
+    ensure_dyn_lds((const void*)k_pv_synth, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth);
     hipLaunchKernelGGL(k_pv_spectrum, dim3((unsigned)std::min(256, (nb + 3) / 4)), dim3(256), (size_t)32 * n, st, a, b, b_off, fade_out,
                        fade_in, n, bins);
     hipLaunchKernelGGL(k_pv_synth, dim3((unsigned)((n + 63) / 64)), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st, a, b, b_off, fade_out,
@@ -46,15 +35,14 @@ static bool gate_layout(int B, int64_t n, int64_t nn, int n_fft, int hop, GateLa
     const int64_t F = 1 + n / hop, Fn = nn > 0 ? 1 + nn / hop : 0, K = n_fft / 2 + 1;
     const int64_t tiles = (F + GATE_FT - 1) / GATE_FT + (Fn + GATE_FT - 1) / GATE_FT;
     if (F > 65535 || tiles > 65535 || (int64_t)B > 65535) return false;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
-    g->x = o;       o = up(o + (size_t)B * F * K * 16);
-    g->xn = o;      o = up(o + (size_t)B * Fn * K * 16);
-    g->xmax = o;    o = up(o + (size_t)B * K * 8);
-    g->thresh = o;  o = up(o + (size_t)B * K * 8);
-    g->mask = o;    o = up(o + (size_t)B * F * K * 4);
-    g->frames = o;  o = up(o + (size_t)B * F * n_fft * 8);
-    g->total = o;
+    Carve c;
+    g->x = c.take((size_t)B * F * K * 16);
+    g->xn = c.take((size_t)B * Fn * K * 16);
+    g->xmax = c.take((size_t)B * K * 8);
+    g->thresh = c.take((size_t)B * K * 8);
+    g->mask = c.take((size_t)B * F * K * 4);
+    g->frames = c.take((size_t)B * F * n_fft * 8);
+    g->total = c.off;
     return true;
 }
 
@@ -196,8 +184,8 @@ int rvcmi_glue_spectral_gate(const float* x, int B, int64_t n, const float* xn, 
         const int64_t Lout = (int64_t)hop * (n / hop);
         const int lds = gate_lds_bytes(n_fft);
         hipStream_t st = (hipStream_t)stream;
-        ensure_dyn_lds(k_gate_stft, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_stft);
-        ensure_dyn_lds(k_gate_idft, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_idft);
+        ensure_dyn_lds((const void*)k_gate_stft, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_stft);
+        ensure_dyn_lds((const void*)k_gate_idft, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_idft);
         hipLaunchKernelGGL(k_gate_stft, dim3((unsigned)((K + 63) / 64), (unsigned)(tiles_x + tiles_n), (unsigned)B), dim3(256), (size_t)lds, st,
                            x, n, F, X, use_xn ? xn : x, use_xn ? nn : n, Fn, XN, tiles_x, n_fft, hop, window);
         hipLaunchKernelGGL(k_gate_stats, dim3((unsigned)((K + 63) / 64), (unsigned)B), dim3(1024), 0, st, (const double2*)X, F,
@@ -246,7 +234,7 @@ int rvcmi_glue_rmvpe_f0_key(const float* salience, int n, int nbins, float thred
         if (!in_lds) smem = 0;
         hipStream_t st = (hipStream_t)stream;
         hipLaunchKernelGGL(k_rmvpe_decode, dim3((n + 3) / 4), dim3(256), 0, st, salience, n, nbins, thred, scratch);
-        ensure_dyn_lds(k_f0_post, 160 * 1024, g_attr_f0);
+        ensure_dyn_lds((const void*)k_f0_post, 160 * 1024, g_attr_f0);
         // the host evaluates the scalars exactly as the reference does (python floats / math.log, rvc/f0/gen.py:18, 70-73)
         const double key_mul = std::pow(2.0, f0_up_key / 12.0);  // (an integral key: the same double as (double)int / 12.0)
         const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
@@ -266,7 +254,7 @@ int rvcmi_glue_f0_post_key(const double* f0, int n, double f0_up_key, int64_t* p
         size_t smem = (size_t)(2 * n) * sizeof(double);
         const bool in_lds = smem <= 160 * 1024;
         if (!in_lds) smem = 0;
-        ensure_dyn_lds(k_f0_post, 160 * 1024, g_attr_f0);
+        ensure_dyn_lds((const void*)k_f0_post, 160 * 1024, g_attr_f0);
         const double key_mul = std::pow(2.0, f0_up_key / 12.0);
         const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
         hipLaunchKernelGGL(k_f0_post, dim3(1), dim3(256), smem, (hipStream_t)stream, f0, n, n, 0, 0, key_mul, mel_min, mel_max, pitch, pitchf,
@@ -297,7 +285,7 @@ int rvcmi_glue_sola(const float* infer_wav, int64_t n, float* sola_buffer, int L
                        block_frame, Lb);
         const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
         if (smem > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "sola: buffer + search window too large");
-        ensure_dyn_lds(k_sola, 150 * 1024, g_attr_sola);  // + 2 KB static
+        ensure_dyn_lds((const void*)k_sola, 150 * 1024, g_attr_sola);  // + 2 KB static
         hipLaunchKernelGGL(k_sola, dim3(1), dim3(256), smem, (hipStream_t)stream, infer_wav, sola_buffer, Lb, Ls, fade_in, fade_out,
                            block_frame, out_block, offset_out);
         HIP_CHECK(hipGetLastError());
@@ -330,7 +318,7 @@ int rvcmi_glue_sola_pv(const float* infer_wav, int64_t n, float* sola_buffer, in
         float* pv = reinterpret_cast<float*>(scratch + 3 * nb);
         int* off = offset_out ? offset_out : reinterpret_cast<int*>(pv + Lb);
         hipStream_t st = (hipStream_t)stream;
-        ensure_dyn_lds(k_sola_search, 150 * 1024, g_attr_sola_search);
+        ensure_dyn_lds((const void*)k_sola_search, 150 * 1024, g_attr_sola_search);
         hipLaunchKernelGGL(k_sola_search, dim3(1), dim3(256), smem, st, infer_wav, (const float*)sola_buffer, Lb, Ls, off);
         launch_phase_vocoder(sola_buffer, infer_wav, off, fade_out, fade_in, Lb, pv, scratch, st);
         hipLaunchKernelGGL(k_sola_pv_stitch, dim3((unsigned)((block_frame + Lb + 255) / 256)), dim3(256), 0, st, infer_wav, (const int*)off,

@@ -187,9 +187,8 @@ static __global__ void __launch_bounds__(GNT) k_gru_seq(const half2v* __restrict
 
 struct rvcmi_gru {
     int device = 0, input = 0;
-    DevBuf wih, whh, bias, bhn, gx;
-    std::vector<DevBuf> retired;  // earlier, smaller projection workspaces: a captured graph may still point at one, so they live as long as the handle
-    size_t gx_rows = 0;
+    DevBuf wih, whh, bias, bhn;
+    GrowBuf gx;  // the input projection of all rows, fp32 [M][2 * GR]
 };
 
 extern "C" {
@@ -208,8 +207,7 @@ int rvcmi_gru_create(int input_size, int hidden_size, const float* w_ih, const f
         {   // W_ih of both directions as fp16, rows = the 2 * 768 stacked features
             std::vector<_Float16> w((size_t)2 * GR * I);
             for (size_t i = 0; i < w.size(); ++i) w[i] = (_Float16)w_ih[i];
-            h->wih.alloc(w.size() * 2);
-            HIP_CHECK(hipMemcpy(h->wih.p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
+            upload(h->wih, w);
         }
         {   // W_hh: thread (group, ks) holds rows 8 * group .. + 7, inputs 32 * ks .. + 31, as 16 fp16 pairs per row
             std::vector<_Float16> w((size_t)2 * GNT * 256);
@@ -218,8 +216,7 @@ int rvcmi_gru_create(int input_size, int hidden_size, const float* w_ih, const f
                     for (int r = 0; r < 8; ++r)
                         for (int k = 0; k < 32; ++k)
                             w[(((size_t)d * GNT + t) * 8 + r) * 32 + k] = (_Float16)w_hh[((size_t)d * GR + (t >> 3) * 8 + r) * GH + (t & 7) * 32 + k];
-            h->whh.alloc(w.size() * 2);
-            HIP_CHECK(hipMemcpy(h->whh.p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
+            upload(h->whh, w);
         }
         {   // b_ih + b_hh for the r and z gates (they add before the sigmoid); b_hn stays inside the r * (...) term
             std::vector<float> bc((size_t)2 * GR), bn((size_t)2 * GH);
@@ -228,10 +225,8 @@ int rvcmi_gru_create(int input_size, int hidden_size, const float* w_ih, const f
                     bc[(size_t)d * GR + f] = b_ih[(size_t)d * GR + f] + (f < 2 * GH ? b_hh[(size_t)d * GR + f] : 0.f);
                     if (f >= 2 * GH) bn[(size_t)d * GH + f - 2 * GH] = b_hh[(size_t)d * GR + f];
                 }
-            h->bias.alloc(bc.size() * 4);
-            HIP_CHECK(hipMemcpy(h->bias.p, bc.data(), bc.size() * 4, hipMemcpyHostToDevice));
-            h->bhn.alloc(bn.size() * 4);
-            HIP_CHECK(hipMemcpy(h->bhn.p, bn.data(), bn.size() * 4, hipMemcpyHostToDevice));
+            upload(h->bias, bc);
+            upload(h->bhn, bn);
         }
         *out = h.release();
     });
@@ -250,15 +245,11 @@ namespace {
 void gru_run(rvcmi_gru* h, int B, int T, size_t M, const int* seq_off, const void* x16, float* y, float* hn, void* stream) {
     DeviceGuard dg(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (M > h->gx_rows) {  // (grows with the largest row count seen -- B * T, or all packed rows of a ragged batch; such a call must be outside any capture)
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (h->gx.p) h->retired.push_back(std::move(h->gx));  // not freed: a graph captured at the smaller size replays into it
-        h->gx.alloc(M * 2 * GR * sizeof(float));
-        h->gx_rows = M;
-    }
+    // (grows with the largest row count seen -- B * T, or all packed rows of a ragged batch)
+    float* gx = (float*)h->gx.ensure(M * 2 * GR * sizeof(float), st);
     hipLaunchKernelGGL(k_gru_xproj, dim3((unsigned)((M + 31) / 32), 2 * GR / 128), dim3(256), 0, st, (const _Float16*)x16, h->wih.as<_Float16>(),
-                       h->bias.as<float>(), h->gx.as<float>(), (int)M, h->input);
-    hipLaunchKernelGGL(k_gru_seq, dim3(2, B), dim3(GNT), 0, st, h->whh.as<half2v>(), h->gx.as<float>(), h->bhn.as<float>(), y, hn, B, T, seq_off, (int)M);
+                       h->bias.as<float>(), gx, (int)M, h->input);
+    hipLaunchKernelGGL(k_gru_seq, dim3(2, B), dim3(GNT), 0, st, h->whh.as<half2v>(), gx, h->bhn.as<float>(), y, hn, B, T, seq_off, (int)M);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -23,8 +23,6 @@ namespace {
 constexpr int MAX_D = 1024, MAX_FFN = 4096, MAX_LAYERS = 64;
 constexpr long long MAX_ROWS = 1ll << 22;  // B * T
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct Layer {
     DevBuf wqkv, bqkv, wo, bo, g1, b1, w1, bf1, w2, bf2, g2, b2;
 };
@@ -37,20 +35,15 @@ struct Plan {
 Plan plan_of(int B, int T, int d, int ffn) {
     Plan p;
     const size_t M = (size_t)B * T;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align256(bytes);
-        return at;
-    };
-    p.off_qkv = take(3 * M * d * 2);
-    p.off_att = take(M * d * 2);
-    p.off_x1 = take(M * d * 4);
-    p.off_x1h = take(M * d * 2);
-    p.off_h = take(M * ffn * 2);
-    p.off_tmp[0] = take(M * d * 4);  // a layer's output on its way to the next (the model's dtype; fp32 is the larger)
-    p.off_tmp[1] = take(M * d * 4);
-    p.bytes = o;
+    Carve c;
+    p.off_qkv = c.take(3 * M * d * 2);
+    p.off_att = c.take(M * d * 2);
+    p.off_x1 = c.take(M * d * 4);
+    p.off_x1h = c.take(M * d * 2);
+    p.off_h = c.take(M * ffn * 2);
+    p.off_tmp[0] = c.take(M * d * 4);  // a layer's output on its way to the next (the model's dtype; fp32 is the larger)
+    p.off_tmp[1] = c.take(M * d * 4);
+    p.bytes = c.off;
     return p;
 }
 
@@ -122,35 +115,12 @@ int rvcmi_hubert_enc_create(const rvcmi_tensor* weights, int n_weights, int n_la
         if (heads < 1 || heads * HD != d) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_enc_create: %d heads of d = %d (the head dim must be 64)", heads, d);
         if (ffn < 64 || ffn > MAX_FFN || ffn % 64) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_enc_create: FFN width %d (a multiple of 64 up to %d)", ffn, MAX_FFN);
         if (!(ln_eps > 0.f) || !(ln_eps < 1.f)) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_enc_create: LayerNorm eps %g", (double)ln_eps);
-        std::map<std::string, const rvcmi_tensor*> by_name;
-        for (int i = 0; i < n_weights; ++i) {
-            if (!weights[i].name) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_enc_create: tensor %d has no name", i);
-            by_name[weights[i].name] = &weights[i];
-        }
-        size_t used = 0;
-        auto get = [&](const std::string& n, std::initializer_list<int64_t> shape) {
-            auto it = by_name.find(n);
-            if (it == by_name.end()) RVCMI_FAIL(RVCMI_ERR_MISSING, "hubert_enc_create: weight '%s' was not supplied", n.c_str());
-            const rvcmi_tensor* t = it->second;
-            bool ok = t->data && t->ndim == (int)shape.size();
-            int i = 0;
-            for (int64_t s : shape) ok = ok && i < 4 && t->shape[i++] == s;
-            if (!ok) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_enc_create: weight '%s' has an unexpected shape", n.c_str());
-            ++used;
-            return (const float*)t->data;
-        };
+        WeightTable wt(weights, n_weights, "hubert_enc_create");
         DeviceGuard dg(device);
         std::unique_ptr<rvcmi_hubert_enc> h(new rvcmi_hubert_enc());
         h->device = device, h->n_layers = n_layers, h->d = d, h->heads = heads, h->ffn = ffn, h->eps = ln_eps;
         h->layers.resize(n_layers);
-        auto up32 = [&](DevBuf& dst, const float* p, size_t n) {
-            dst.alloc(n * 4);
-            HIP_CHECK(hipMemcpy(dst.p, p, n * 4, hipMemcpyHostToDevice));
-        };
-        auto up16 = [&](DevBuf& dst, const std::vector<_Float16>& v) {
-            dst.alloc(v.size() * 2);
-            HIP_CHECK(hipMemcpy(dst.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-        };
+        auto up32 = [](DevBuf& dst, const float* p, size_t n) { upload(dst, p, n * 4); };
         auto to16 = [](std::vector<_Float16>& v, size_t at, const float* p, size_t n) {
             for (size_t i = 0; i < n; ++i) v[at + i] = (_Float16)p[i];
         };
@@ -162,27 +132,26 @@ int rvcmi_hubert_enc_create(const rvcmi_tensor* weights, int n_weights, int n_la
             std::vector<float> bqkv(3 * (size_t)d);
             const char* names[3] = {"q_proj", "k_proj", "v_proj"};
             for (int i = 0; i < 3; ++i) {
-                to16(wqkv, i * dd, get(pre + "self_attn." + names[i] + ".weight", {d, d}), dd);
-                memcpy(bqkv.data() + (size_t)i * d, get(pre + "self_attn." + names[i] + ".bias", {d}), (size_t)d * 4);
+                to16(wqkv, i * dd, wt.get(pre + "self_attn." + names[i] + ".weight", {d, d}), dd);
+                memcpy(bqkv.data() + (size_t)i * d, wt.get(pre + "self_attn." + names[i] + ".bias", {d}), (size_t)d * 4);
             }
-            up16(L.wqkv, wqkv);
-            up32(L.bqkv, bqkv.data(), bqkv.size());
-            to16(w, 0, get(pre + "self_attn.out_proj.weight", {d, d}), dd);
-            up16(L.wo, w);
-            up32(L.bo, get(pre + "self_attn.out_proj.bias", {d}), d);
-            up32(L.g1, get(pre + "self_attn_layer_norm.weight", {d}), d);
-            up32(L.b1, get(pre + "self_attn_layer_norm.bias", {d}), d);
-            to16(wf, 0, get(pre + "fc1.weight", {ffn, d}), df);
-            up16(L.w1, wf);
-            up32(L.bf1, get(pre + "fc1.bias", {ffn}), ffn);
-            to16(wf, 0, get(pre + "fc2.weight", {d, ffn}), df);
-            up16(L.w2, wf);
-            up32(L.bf2, get(pre + "fc2.bias", {d}), d);
-            up32(L.g2, get(pre + "final_layer_norm.weight", {d}), d);
-            up32(L.b2, get(pre + "final_layer_norm.bias", {d}), d);
+            upload(L.wqkv, wqkv);
+            upload(L.bqkv, bqkv);
+            to16(w, 0, wt.get(pre + "self_attn.out_proj.weight", {d, d}), dd);
+            upload(L.wo, w);
+            up32(L.bo, wt.get(pre + "self_attn.out_proj.bias", {d}), d);
+            up32(L.g1, wt.get(pre + "self_attn_layer_norm.weight", {d}), d);
+            up32(L.b1, wt.get(pre + "self_attn_layer_norm.bias", {d}), d);
+            to16(wf, 0, wt.get(pre + "fc1.weight", {ffn, d}), df);
+            upload(L.w1, wf);
+            up32(L.bf1, wt.get(pre + "fc1.bias", {ffn}), ffn);
+            to16(wf, 0, wt.get(pre + "fc2.weight", {d, ffn}), df);
+            upload(L.w2, wf);
+            up32(L.bf2, wt.get(pre + "fc2.bias", {d}), d);
+            up32(L.g2, wt.get(pre + "final_layer_norm.weight", {d}), d);
+            up32(L.b2, wt.get(pre + "final_layer_norm.bias", {d}), d);
         }
-        if (used != by_name.size())  // a relative-position table, a seventeenth tensor of a layer ...
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_enc_create: %d tensors were supplied, the recognised layers have %d", (int)by_name.size(), (int)used);
+        wt.require_all_used("layer stack");  // a relative-position table, a seventeenth tensor of a layer ...
         *out = h.release();
     });
 }

@@ -34,8 +34,6 @@ void layer_rows(int N, int* L) {
     for (int l = 1; l < NLAYERS; ++l) L[l] = (L[l - 1] - TAPS[l]) / 2 + 1;
 }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct Plan {
     int L[NLAYERS];
     int nchunk;
@@ -47,19 +45,14 @@ Plan plan_of(int B, int N) {
     Plan p;
     layer_rows(N, p.L);
     p.nchunk = (p.L[0] + ST_FRAMES - 1) / ST_FRAMES;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align256(bytes);
-        return at;
-    };
-    p.off_a = take((size_t)B * p.L[0] * HC * 2);  // outputs of layers 0, 2, 4
-    p.off_b = take((size_t)B * p.L[1] * HC * 2);  // outputs of layers 1, 3, 5
-    p.off_part = take((size_t)B * p.nchunk * ST_VALS * sizeof(double));
-    p.off_meanf = take((size_t)B * K0 * 4);
-    p.off_scale = take((size_t)B * HC * 4);
-    p.off_shift = take((size_t)B * HC * 4);
-    p.bytes = o;
+    Carve c;
+    p.off_a = c.take((size_t)B * p.L[0] * HC * 2);  // outputs of layers 0, 2, 4
+    p.off_b = c.take((size_t)B * p.L[1] * HC * 2);  // outputs of layers 1, 3, 5
+    p.off_part = c.take((size_t)B * p.nchunk * ST_VALS * sizeof(double));
+    p.off_meanf = c.take((size_t)B * K0 * 4);
+    p.off_scale = c.take((size_t)B * HC * 4);
+    p.off_shift = c.take((size_t)B * HC * 4);
+    p.bytes = c.off;
     return p;
 }
 
@@ -88,9 +81,6 @@ void gemm(const _Float16* x, const _Float16* w, void* out, int B, int Lin, int t
     else hipLaunchKernelGGL((k_hfe_gemm<false, false>), grid, dim3(256), 0, st, x, w, out, Lin, Lout, taps * HC, (const int*)nullptr, 0, 0);
 }
 
-// the handle's own workspace (ws_dev == NULL), grown to ``bytes``: such a call must be outside any capture
-char* own_workspace(rvcmi_hubert_fe* h, size_t bytes, hipStream_t st);
-
 // the launches of one forward; lens == NULL: dense (N is every item's length), else ragged (N = N_max, the strides)
 template <bool RAGGED>
 void enqueue(rvcmi_hubert_fe* h, const Plan& p, int B, size_t N, const int* lens, const void* x_dev, int x_is_half, void* out16_dev, char* ws, hipStream_t st);
@@ -100,20 +90,10 @@ void enqueue(rvcmi_hubert_fe* h, const Plan& p, int B, size_t N, const int* lens
 struct rvcmi_hubert_fe {
     int device = 0;
     DevBuf w0, gamma, beta, w[NLAYERS];  // w0: [512][10] fp32 holding the fp16-rounded values; w[1 .. 6]: packed fp16
-    DevBuf ws;                           // the handle's own workspace (forward with ws_dev == NULL)
-    std::vector<DevBuf> retired;         // earlier, smaller workspaces: a captured graph may still point at one, so they live as long as the handle
+    GrowBuf ws;                          // the handle's own workspace (forward with ws_dev == NULL)
 };
 
 namespace {
-
-char* own_workspace(rvcmi_hubert_fe* h, size_t bytes, hipStream_t st) {
-    if (bytes > h->ws.bytes) {  // (grows with the largest shape seen; such a call must be outside any capture)
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (h->ws.p) h->retired.push_back(std::move(h->ws));  // not freed: a graph captured at the smaller size replays into it
-        h->ws.alloc(bytes);
-    }
-    return h->ws.as<char>();
-}
 
 template <bool RAGGED>
 void enqueue(rvcmi_hubert_fe* h, const Plan& p, int B, size_t N, const int* lens, const void* x_dev, int x_is_half, void* out16_dev, char* ws, hipStream_t st) {
@@ -146,44 +126,20 @@ extern "C" {
 int rvcmi_hubert_fe_create(const rvcmi_tensor* weights, int n_weights, int device, rvcmi_hubert_fe** out) {
     return guarded([&] {
         if (!weights || n_weights < 1 || !out) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_create: null argument");
-        std::map<std::string, const rvcmi_tensor*> by_name;
-        for (int i = 0; i < n_weights; ++i) {
-            if (!weights[i].name) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_create: tensor %d has no name", i);
-            by_name[weights[i].name] = &weights[i];
-        }
-        size_t used = 0;
-        auto get = [&](const std::string& n, std::initializer_list<int64_t> shape) {
-            auto it = by_name.find(n);
-            if (it == by_name.end()) RVCMI_FAIL(RVCMI_ERR_MISSING, "hubert_fe_create: weight '%s' was not supplied", n.c_str());
-            const rvcmi_tensor* t = it->second;
-            bool ok = t->data && t->ndim == (int)shape.size();
-            int i = 0;
-            for (int64_t s : shape) ok = ok && i < 4 && t->shape[i++] == s;
-            if (!ok) RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_create: weight '%s' has an unexpected shape (a geometry this extractor does not serve)", n.c_str());
-            ++used;
-            return (const float*)t->data;
-        };
+        WeightTable wt(weights, n_weights, "hubert_fe_create");
         const float* wl[NLAYERS];
-        for (int l = 0; l < NLAYERS; ++l) wl[l] = get("conv_layers." + std::to_string(l) + ".0.weight", {HC, l ? HC : 1, TAPS[l]});
-        const float *g = get("conv_layers.0.2.weight", {HC}), *bt = get("conv_layers.0.2.bias", {HC});
-        if (used != by_name.size())  // a conv bias, an eighth layer, a norm behind another layer ...
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "hubert_fe_create: %d tensors were supplied, the recognised extractor has %d", (int)by_name.size(), (int)used);
+        for (int l = 0; l < NLAYERS; ++l) wl[l] = wt.get("conv_layers." + std::to_string(l) + ".0.weight", {HC, l ? HC : 1, TAPS[l]});
+        const float *g = wt.get("conv_layers.0.2.weight", {HC}), *bt = wt.get("conv_layers.0.2.bias", {HC});
+        wt.require_all_used("extractor");  // a conv bias, an eighth layer, a norm behind another layer ...
         DeviceGuard dg(device);
         std::unique_ptr<rvcmi_hubert_fe> h(new rvcmi_hubert_fe());
         h->device = device;
-        auto upload = [&](DevBuf& d, const void* p, size_t bytes) {
-            d.alloc(bytes);
-            HIP_CHECK(hipMemcpy(d.p, p, bytes, hipMemcpyHostToDevice));
-        };
         std::vector<float> w0((size_t)HC * K0);
         for (size_t i = 0; i < w0.size(); ++i) w0[i] = (float)(_Float16)wl[0][i];
-        upload(h->w0, w0.data(), w0.size() * 4);
+        upload(h->w0, w0);
         upload(h->gamma, g, HC * 4);
         upload(h->beta, bt, HC * 4);
-        for (int l = 1; l < NLAYERS; ++l) {
-            const std::vector<_Float16> p = pack_conv(wl[l], TAPS[l]);
-            upload(h->w[l], p.data(), p.size() * 2);
-        }
+        for (int l = 1; l < NLAYERS; ++l) upload(h->w[l], pack_conv(wl[l], TAPS[l]));
         *out = h.release();
     });
 }
@@ -211,7 +167,7 @@ int rvcmi_hubert_fe_forward(rvcmi_hubert_fe* h, int B, int64_t N, const void* x_
         const Plan p = plan_of(B, (int)N);
         DeviceGuard dg(h->device);
         hipStream_t st = (hipStream_t)stream;
-        char* ws = ws_dev ? (char*)ws_dev : own_workspace(h, p.bytes, st);
+        char* ws = ws_dev ? (char*)ws_dev : h->ws.ensure(p.bytes, st);
         enqueue<false>(h, p, B, (size_t)N, nullptr, x_dev, x_is_half, out16_dev, ws, st);
         HIP_CHECK(hipGetLastError());
     });
@@ -242,7 +198,7 @@ int rvcmi_hubert_fe_forward_ragged(rvcmi_hubert_fe* h, int B, int64_t N_max, con
         const Plan p = plan_of(B, (int)N_max);
         DeviceGuard dg(h->device);
         hipStream_t st = (hipStream_t)stream;
-        char* ws = ws_dev ? (char*)ws_dev : own_workspace(h, p.bytes, st);
+        char* ws = ws_dev ? (char*)ws_dev : h->ws.ensure(p.bytes, st);
         enqueue<true>(h, p, B, (size_t)N_max, lens_dev, x_dev, x_is_half, out16_dev, ws, st);
         HIP_CHECK(hipGetLastError());
     });
@@ -256,8 +212,7 @@ int rvcmi_hubert_fe_debug_conv(int taps, int B, int L_in, const float* w, const 
         hipStream_t st = (hipStream_t)stream;
         const std::vector<_Float16> p = pack_conv(w, taps);
         DevBuf wd;
-        wd.alloc(p.size() * 2);
-        HIP_CHECK(hipMemcpy(wd.p, p.data(), p.size() * 2, hipMemcpyHostToDevice));
+        upload(wd, p);
         gemm((const _Float16*)x16_dev, wd.as<_Float16>(), out32_dev, B, L_in, taps, true, st);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(st));

@@ -91,7 +91,7 @@ constexpr int RB_SPLIT_MAX_ROWS = 1024;      // C = 256
 constexpr int RB_SPLIT_MAX_ROWS_128 = 4096;  // C = 128 (a chunk's second stage: 3100 rows = 75 pair tiles of 3 x 40 us)
 
 // Weights of upsampling stage i: ups[i], noise_convs[i] and its resblocks.
-static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& wm, int i) {
+static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, WeightTable& wm, int i) {
     const int op = cfg->operand, C0 = cfg->upsample_initial_channel;
     s.cin = C0 >> i;
     s.cout = C0 >> (i + 1);
@@ -104,8 +104,8 @@ static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& 
     if (s.k - 2 * s.pad != s.u) RVCMI_FAIL(RVCMI_ERR_INVALID, "stage %d: k-u must be even (k=%d,u=%d)", i, s.k, s.u);
     {  // ups[i]: ConvTranspose1d(cin, cout, k, u, padding=(k-u)//2)   nsf.py:92-102
         // out[q*u + r] = sum_j x[q + off_r - j] * W[:, :, cm_r + j*u],  c = r + pad, off_r = c / u, cm_r = c % u
-        const rvcmi_tensor& w = wm.get("ups." + std::to_string(i) + ".weight", {s.cin, s.cout, s.k});
-        const rvcmi_tensor& b = wm.get("ups." + std::to_string(i) + ".bias", {s.cout});
+        const float* w = wm.get("ups." + std::to_string(i) + ".weight", {s.cin, s.cout, s.k});
+        const float* b = wm.get("ups." + std::to_string(i) + ".bias", {s.cout});
         int nt[16], off[16], cm[16];
         for (int r = 0; r < s.u; ++r) {
             const int c = r + s.pad;
@@ -113,12 +113,11 @@ static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& 
             cm[r] = c % s.u;
             nt[r] = (s.k - cm[r] + s.u - 1) / s.u;
         }
-        const float* wd = w.data;
         const int cout = s.cout, k = s.k, u = s.u;
         std::vector<int> cmv(cm, cm + s.u);
         build_conv(s.up, s.cin, s.cout, s.u, nt, off, -1,
-                   [=](int co, int ci, int p, int tap) { return wd[((size_t)ci * cout + co) * k + cmv[p] + tap * u]; },
-                   b.data, op);
+                   [=](int co, int ci, int p, int tap) { return w[((size_t)ci * cout + co) * k + cmv[p] + tap * u]; },
+                   b, op);
     }
     if (cfg->use_f0) {  // noise_convs[i]   nsf.py:103-115
         int sf = 1;
@@ -127,20 +126,19 @@ static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& 
         s.nk = last ? 1 : 2 * sf;
         s.ns = last ? 1 : sf;
         s.npad = last ? 0 : sf / 2;
-        const rvcmi_tensor& w = wm.get("noise_convs." + std::to_string(i) + ".weight", {s.cout, 1, s.nk});
-        const rvcmi_tensor& b = wm.get("noise_convs." + std::to_string(i) + ".bias", {s.cout});
+        const float* w = wm.get("noise_convs." + std::to_string(i) + ".weight", {s.cout, 1, s.nk});
+        const float* b = wm.get("noise_convs." + std::to_string(i) + ".bias", {s.cout});
         std::vector<float> wt((size_t)s.nk * s.cout);
         for (int co = 0; co < s.cout; ++co)
-            for (int j = 0; j < s.nk; ++j) wt[(size_t)j * s.cout + co] = w.data[(size_t)co * s.nk + j];
+            for (int j = 0; j < s.nk; ++j) wt[(size_t)j * s.cout + co] = w[(size_t)co * s.nk + j];
         upload(s.noise_w, wt);
-        upload(s.noise_b, std::vector<float>(b.data, b.data + s.cout));
+        upload(s.noise_b, b, s.cout * sizeof(float));
         if (op != RVCMI_OPERAND_F32 && !last && s.ns % 8 == 0 && s.ns <= 64) {
             const int cinp = s.ns <= 16 ? 16 : (s.ns <= 32 ? 32 : 64);
             int nt = 2, off = 0;
-            const float* wd = w.data;
             const int ns = s.ns, nkk = s.nk;
             build_conv(s.nz, cinp, s.cout, 1, &nt, &off, 1,
-                       [=](int co, int ci, int, int tap) { return ci < ns ? wd[(size_t)co * nkk + tap * ns + ci] : 0.f; }, b.data, op);
+                       [=](int co, int ci, int, int tap) { return ci < ns ? w[(size_t)co * nkk + tap * ns + ci] : 0.f; }, b, op);
             s.nz_mfma = true;
         } else if (op != RVCMI_OPERAND_F32 && s.nk >= 2 && s.nk <= 16 && s.ns % 2 == 0) {
             const int ctiles = (s.cout + 31) / 32;
@@ -150,12 +148,11 @@ static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& 
                     for (int e = 0; e < 8; ++e) {
                         const int co = ct * 32 + (lane & 31), kk = 8 * (lane >> 5) + e;
                         if (co < s.cout && kk < s.nk) {
-                            const float v = w.data[(size_t)co * s.nk + kk];
+                            const float v = w[(size_t)co * s.nk + kk];
                             pk[(size_t)ct * 512 + lane * 8 + e] = op == RVCMI_OPERAND_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
                         }
                     }
-            s.nz_k1_w.alloc(pk.size() * 2);
-            HIP_CHECK(hipMemcpy(s.nz_k1_w.p, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
+            upload(s.nz_k1_w, pk);
             s.nz_k1 = true;
         }
     }
@@ -172,14 +169,13 @@ static void build_stage(Stage& s, const rvcmi_nsf_config* cfg, const WeightMap& 
             const int C = s.cout;
             for (int which = 0; which < 2; ++which) {
                 const std::string nm = base + (which ? ".convs2." : ".convs1.") + std::to_string(m);
-                const rvcmi_tensor& w = wm.get(nm + ".weight", {C, C, k});
-                const rvcmi_tensor& b = wm.get(nm + ".bias", {C});
+                const float* w = wm.get(nm + ".weight", {C, C, k});
+                const float* b = wm.get(nm + ".bias", {C});
                 const int dil = which ? 1 : d;
                 int nt = k, off = -((k * dil - dil) / 2);  // get_padding, rvc/layers/utils.py:14
-                const float* wd = w.data;
                 ConvLayer& L2 = which ? s.rb[j][m].second : s.rb[j][m].first;
                 build_conv(L2, C, C, 1, &nt, &off, dil,
-                           [=](int co, int ci, int, int tap) { return wd[((size_t)co * C + ci) * k + tap]; }, b.data, op);
+                           [=](int co, int ci, int, int tap) { return w[((size_t)co * C + ci) * k + tap]; }, b, op);
             }
         }
     }
@@ -205,28 +201,26 @@ static void nsf_create(const rvcmi_nsf_config* cfg, const rvcmi_tensor* weights,
     h->max_B = max_B;
     h->max_T = max_T;
     const int op = cfg->operand;
-    WeightMap wm;
-    for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+    WeightTable wm(weights, n_weights, "nsf_create");
 
     const int C0 = cfg->upsample_initial_channel, inter = cfg->inter_channels;
     h->C0 = C0;
     {  // conv_pre: Conv1d(inter, C0, 7, padding=3)   nsf.py:84-86
-        const rvcmi_tensor& w = wm.get("conv_pre.weight", {C0, inter, 7});
-        const rvcmi_tensor& b = wm.get("conv_pre.bias", {C0});
-        const float* wd = w.data;
+        const float* w = wm.get("conv_pre.weight", {C0, inter, 7});
+        const float* b = wm.get("conv_pre.bias", {C0});
         int nt = 7, off = -3;
         build_conv(h->pre, inter, C0, 1, &nt, &off, 1,
-                   [=](int co, int ci, int, int tap) { return wd[((size_t)co * inter + ci) * 7 + tap]; }, b.data, op);
+                   [=](int co, int ci, int, int tap) { return w[((size_t)co * inter + ci) * 7 + tap]; }, b, op);
     }
     if (cfg->gin_channels) {  // cond: Conv1d(gin, C0, 1)   nsf.py:129-130
-        const rvcmi_tensor& w = wm.get("cond.weight", {C0, cfg->gin_channels, 1});
-        const rvcmi_tensor& b = wm.get("cond.bias", {C0});
-        upload(h->cond_w, std::vector<float>(w.data, w.data + (size_t)C0 * cfg->gin_channels));
-        upload(h->cond_b, std::vector<float>(b.data, b.data + C0));
+        const float* w = wm.get("cond.weight", {C0, cfg->gin_channels, 1});
+        const float* b = wm.get("cond.bias", {C0});
+        upload(h->cond_w, w, (size_t)C0 * cfg->gin_channels * sizeof(float));
+        upload(h->cond_b, b, C0 * sizeof(float));
     }
     if (cfg->use_f0) {  // m_source.l_linear: Linear(1,1)   nsf.py:51
-        h->lin_w = wm.get("m_source.l_linear.weight", {1, 1}).data[0];
-        h->lin_b = wm.get("m_source.l_linear.bias", {1}).data[0];
+        h->lin_w = wm.get("m_source.l_linear.weight", {1, 1})[0];
+        h->lin_b = wm.get("m_source.l_linear.bias", {1})[0];
     }
     int upp = 1;
     for (int i = 0; i < cfg->n_ups; ++i) upp *= cfg->upsample_rates[i];
@@ -242,10 +236,10 @@ static void nsf_create(const rvcmi_nsf_config* cfg, const rvcmi_tensor* weights,
     }
     h->c_last = C0 >> cfg->n_ups;
     {  // conv_post: Conv1d(ch, 1, 7, padding=3, bias=False)   nsf.py:126
-        const rvcmi_tensor& w = wm.get("conv_post.weight", {1, h->c_last, 7});
+        const float* w = wm.get("conv_post.weight", {1, h->c_last, 7});
         std::vector<float> wt((size_t)7 * h->c_last);
         for (int c = 0; c < h->c_last; ++c)
-            for (int j = 0; j < 7; ++j) wt[(size_t)j * h->c_last + c] = w.data[(size_t)c * 7 + j];
+            for (int j = 0; j < 7; ++j) wt[(size_t)j * h->c_last + c] = w[(size_t)c * 7 + j];
         upload(h->post_w, wt);
     }
     if (h->c_last & 3) RVCMI_FAIL(RVCMI_ERR_INVALID, "last stage channel count %d", h->c_last);

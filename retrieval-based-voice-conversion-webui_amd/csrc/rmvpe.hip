@@ -55,14 +55,10 @@ int rvcmi_mel_create(int n_fft, int hop, int win_length, int n_mels, const float
             band[2 * m] = hi ? lo : 0;
             band[2 * m + 1] = hi;
         }
-        h->window.alloc(win.size() * 8);
-        HIP_CHECK(hipMemcpy(h->window.p, win.data(), win.size() * 8, hipMemcpyHostToDevice));
-        h->tw.alloc(tw.size() * 8);
-        HIP_CHECK(hipMemcpy(h->tw.p, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
-        h->basisT.alloc(bt.size() * 4);
-        HIP_CHECK(hipMemcpy(h->basisT.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
-        h->band.alloc(band.size() * 4);
-        HIP_CHECK(hipMemcpy(h->band.p, band.data(), band.size() * 4, hipMemcpyHostToDevice));
+        upload(h->window, win);
+        upload(h->tw, tw);
+        upload(h->basisT, bt);
+        upload(h->band, band);
         *out = h.release();
     });
 }

@@ -40,7 +40,7 @@ struct Unit {
 struct Arena {
     std::vector<char> host;
     size_t push(const void* p, size_t bytes) {
-        const size_t o = (host.size() + 255) & ~(size_t)255;
+        const size_t o = align256(host.size());
         host.resize(o + bytes);
         memcpy(host.data() + o, p, bytes);
         return o;
@@ -176,22 +176,11 @@ struct rvcmi_unet {
 namespace {
 
 struct Loader {
-    std::map<std::string, const rvcmi_tensor*> by_name;
-    std::set<std::string> used;
+    WeightTable wt;
     Arena arena;
 
-    bool has(const std::string& n) const { return by_name.count(n) != 0; }
-    const float* get(const std::string& n, std::initializer_list<int64_t> shape) {
-        auto it = by_name.find(n);
-        if (it == by_name.end()) RVCMI_FAIL(RVCMI_ERR_MISSING, "unet_create: weight '%s' was not supplied", n.c_str());
-        const rvcmi_tensor* t = it->second;
-        bool ok = t->data && t->ndim == (int)shape.size();
-        int i = 0;
-        for (int64_t s : shape) ok = ok && i < 4 && t->shape[i++] == s;
-        if (!ok) RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: weight '%s' has an unexpected shape", n.c_str());
-        used.insert(n);
-        return t->data;
-    }
+    bool has(const std::string& n) const { return wt.has(n); }
+    const float* get(const std::string& n, std::initializer_list<int64_t> shape) { return wt.get(n, shape); }
     // eval-mode BatchNorm as y = x * scale + shift
     void bn(const std::string& p, int C, std::vector<float>& scale, std::vector<float>& shift) {
         const float *g = get(p + ".weight", {C}), *b = get(p + ".bias", {C}), *m = get(p + ".running_mean", {C}), *v = get(p + ".running_var", {C});
@@ -260,18 +249,14 @@ size_t run(const rvcmi_unet* h, int B, int T, const float* mel, float* out, char
     c.st = st;
     c.dry = dry;
     c.seq_off = seq_off_dev, c.nseq = nseq, c.R = T;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return (_Float16*)(ws + o);
-    };
+    Carve carve;
+    auto take = [&](size_t bytes) { return (_Float16*)(ws + carve.take(bytes)); };
     const int L = h->levels;
     const size_t full = (size_t)B * T * NMEL * h->base * 2;
     _Float16 *X0 = take(full), *X1 = take(full), *Tb = take(full), *Sb = take(full);
     std::vector<_Float16*> skip(L);
     for (int l = 0; l < L; ++l) skip[l] = take(((size_t)B * (T >> l) * (NMEL >> l) * ((size_t)h->base << l)) * 2);
-    c.part = (float*)(ws + off);
+    c.part = (float*)(ws + carve.off);
     auto other = [&](const _Float16* p) { return p == X0 ? X1 : X0; };
     auto unit = [&](const Unit& u, const _Float16* x0, int C0, const _Float16* x1, int C1, int H, int W, _Float16* dst) {
         conv(c, u.c1, x0, C0, x1, C1, B, H, W, 1, nullptr, Tb, OUT_NHWC16);
@@ -326,7 +311,7 @@ size_t run(const rvcmi_unet* h, int B, int T, const float* mel, float* out, char
     }
     conv(c, h->head, cur, C, nullptr, 0, B, H, W, 0, nullptr, out, OUT_HEAD32);
     if (!dry) HIP_CHECK(hipGetLastError());
-    return off + ((c.max_part + 255) & ~(size_t)255);
+    return carve.off + align256(c.max_part);
 }
 
 }  // namespace
@@ -336,19 +321,12 @@ extern "C" {
 int rvcmi_unet_create(const rvcmi_tensor* weights, int n_weights, int device, rvcmi_unet** out) {
     return guarded([&] {
         if (!weights || n_weights < 1 || !out) RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: null argument");
-        Loader ld;
-        int supplied = 0;
-        for (int i = 0; i < n_weights; ++i) {
-            if (!weights[i].name) RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: tensor %d has no name", i);
-            ld.by_name[weights[i].name] = &weights[i];
-            const std::string n = weights[i].name;
-            supplied += n.rfind("unet.", 0) == 0 || n.rfind("cnn.", 0) == 0;
-        }
+        Loader ld{WeightTable(weights, n_weights, "unet_create"), {}};
         std::unique_ptr<rvcmi_unet> h(new rvcmi_unet());
         h->device = device;
         const std::string w00 = "unet.encoder.layers.0.conv.0.conv.0.weight";
-        if (!ld.has(w00)) RVCMI_FAIL(RVCMI_ERR_MISSING, "unet_create: weight '%s' was not supplied", w00.c_str());
-        const rvcmi_tensor* t0 = ld.by_name[w00];
+        const rvcmi_tensor* t0 = ld.wt.find(w00);
+        if (!t0) RVCMI_FAIL(RVCMI_ERR_MISSING, "unet_create: missing weight tensor '%s'", w00.c_str());
         if (t0->ndim != 4 || t0->shape[1] != 1 || t0->shape[0] < 16 || t0->shape[0] > 4096 || t0->shape[0] % 16)
             RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: the first layer must map 1 channel to a multiple of 16");
         h->base = (int)t0->shape[0];
@@ -390,19 +368,17 @@ int rvcmi_unet_create(const rvcmi_tensor* weights, int n_weights, int device, rv
         if (cin != h->base) RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: the decoder ends with %d channels, not %d", cin, h->base);
         {
             const std::string wn = "cnn.weight";
-            if (!ld.has(wn)) RVCMI_FAIL(RVCMI_ERR_MISSING, "unet_create: weight 'cnn.weight' was not supplied");
-            const int hc = (int)ld.by_name[wn]->shape[0];
+            if (!ld.has(wn)) RVCMI_FAIL(RVCMI_ERR_MISSING, "unet_create: missing weight tensor 'cnn.weight'");
+            const int hc = (int)ld.wt.find(wn)->shape[0];
             if (hc < 1 || hc > 16) RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: a head of %d channels is not supported", hc);
             h->head.Cin = h->base, h->head.Cout = hc, h->head.mode = MODE_3X3;
             h->head.w = ld.arena.push_f16(pack_conv(ld.get(wn, {hc, h->base, 3, 3}), hc, h->base, 3));
             h->head.scale = ld.arena.push_f32(std::vector<float>(16, 1.f));
             h->head.shift = ld.arena.push_f32(padded16(ld.get("cnn.bias", {hc}), hc, 0.f));
         }
-        if ((int)ld.used.size() != supplied)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "unet_create: %d tensors under unet. / cnn. were supplied, the recognised network has %d", supplied, (int)ld.used.size());
+        ld.wt.require_all_used("network", {"unet.", "cnn."});  // (tensors under other prefixes belong to the rest of the f0 model)
         DeviceGuard dg(device);
-        h->arena.alloc(ld.arena.host.size());
-        HIP_CHECK(hipMemcpy(h->arena.p, ld.arena.host.data(), ld.arena.host.size(), hipMemcpyHostToDevice));
+        upload(h->arena, ld.arena.host);
         *out = h.release();
     });
 }
@@ -482,8 +458,7 @@ int rvcmi_unet_debug_op(int kind, int B, int H, int W, int C0, int C1, int Cout,
         L.scale = ar.push_f32(padded16(scale, Cout, 1.f));
         L.shift = ar.push_f32(padded16(shift, Cout, 0.f));
         DevBuf wd, part;
-        wd.alloc(ar.host.size());
-        HIP_CHECK(hipMemcpy(wd.p, ar.host.data(), ar.host.size(), hipMemcpyHostToDevice));
+        upload(wd, ar.host);
         c.wbase = wd.as<char>();
         if (one) {
             first(c, L, kind == 4 ? 9 : 1, (const float*)x0_dev, in_scale, in_shift, relu, (_Float16*)out_dev, B, H, W);

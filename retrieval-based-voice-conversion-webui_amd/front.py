@@ -54,12 +54,10 @@ class FrontHIP(torch.nn.Module):
             from .nsf import _warn_bf16
 
             _warn_bf16("encoder / flow: 1.4e-2 RMS on z")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.RvcmiError("the HIP front needs a GPU device (got %s); there is no CPU fallback" % device)
+        self.device = _lib.cuda_device(device, "the HIP front")
         self._weights = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in weights.items()
                          if k.startswith(("enc_p.", "flow."))}
-        self._handle = C.c_void_p(None)
+        self._handle = None
         self._max_B = self._max_T = 0
         self._ensure(max_B, max_T)
 
@@ -67,38 +65,18 @@ class FrontHIP(torch.nn.Module):
         if self._handle and B <= self._max_B and T <= self._max_T:
             return
         B, T = max(B, self._max_B), max(T, self._max_T)
-        self._destroy()
-        names = list(self._weights)
-        arr = (_lib.Tensor * len(names))()
-        keep = []
-        for i, k in enumerate(names):
-            t = self._weights[k]
-            kb = k.encode()
-            keep.append(kb)
-            arr[i].name, arr[i].data, arr[i].ndim = kb, t.data_ptr(), t.dim()
-            for j, s in enumerate(t.shape):
-                arr[i].shape[j] = s
+        if self._handle:
+            self._handle.close()
+        arr = _lib.pack_tensors(self._weights.items())
         cs = _lib.FrontConfig()
         for k in _CFG_KEYS:
             setattr(cs, k, int(self.cfg[k]))
         cs.operand = _lib.OPERANDS[self.operand]
         h = C.c_void_p(None)
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(_lib.lib().rvcmi_front_create(C.byref(cs), arr, len(names), idx, B, T, C.byref(h)))
-        self._handle, self._max_B, self._max_T = h, B, T
+        _lib.check(_lib.lib().rvcmi_front_create(C.byref(cs), arr, len(arr), self.device.index, B, T, C.byref(h)))
+        self._handle, self._max_B, self._max_T = _lib.Handle("rvcmi_front_destroy", h), B, T
         for k, v in getattr(self, "_options", {}).items():
             _lib.set_option(_lib.lib().rvcmi_front_set_option, self._handle, k, v)
-
-    def _destroy(self) -> None:
-        if getattr(self, "_handle", None):
-            _lib.lib().rvcmi_front_destroy(self._handle)
-            self._handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
 
     def reserve(self, max_B: int, max_T: int) -> "FrontHIP":
         self._ensure(max_B, max_T)
@@ -137,20 +115,18 @@ class FrontHIP(torch.nn.Module):
             raise ValueError("noise must be [B, %d, %d]" % (IC, T - fh))
         nz = noise.to(dev, torch.float32).contiguous()
         self._ensure(B, T)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+        ptr, stream = _lib.ptr, _lib.stream_ptr(dev)
         L = _lib.lib()
         with torch.cuda.device(dev):
             if tap is None:
                 out = torch.empty(B, IC, T - fh, device=dev, dtype=torch.float32)
-                _lib.check(L.rvcmi_front_forward(self._handle, B, T, ptr(ph), ptr(pi), ptr(ln), ptr(gf), ptr(nz), fh, ptr(out),
-                                                 C.c_void_p(stream)))
+                _lib.check(L.rvcmi_front_forward(self._handle, B, T, ptr(ph), ptr(pi), ptr(ln), ptr(gf), ptr(nz), fh, ptr(out), stream))
                 return out.to(out_dtype)
             cap = B * T * 192
             host = np.empty(cap, dtype=np.float32)
             shape = (C.c_int64 * 3)()
             _lib.check(L.rvcmi_front_debug_forward(self._handle, B, T, ptr(ph), ptr(pi), ptr(ln), ptr(gf), ptr(nz), fh, tap.encode(),
-                                                   host.ctypes.data_as(C.c_void_p), cap, shape, C.c_void_p(stream)))
+                                                   host.ctypes.data_as(C.c_void_p), cap, shape, stream))
             n = shape[0] * shape[1] * shape[2]
             return torch.from_numpy(host[:n].reshape(shape[0], shape[1], shape[2]).copy())
 

@@ -29,20 +29,6 @@ import torch
 from . import _lib
 
 
-def _dev(t: torch.Tensor, what: str) -> torch.device:
-    if t.device.type != "cuda":
-        raise _lib.RvcmiError("%s must live on the GPU (got %s); the glue has no CPU fallback" % (what, t.device))
-    return t.device
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _blend_expand_into(out: torch.Tensor, f: torch.Tensor, index, index_rate: float, pf: Optional[torch.Tensor], protect: float,
                        realtime_guard: bool) -> None:
     """out [p_len, d] (a contiguous row slice) <- x2(f [nq, d]), blended against ``index`` first when given, protect-mixed."""
@@ -58,10 +44,10 @@ def _blend_expand_into(out: torch.Tensor, f: torch.Tensor, index, index_rate: fl
                 raise _lib.RvcmiError("the index lives on %s, the features on %s: read the index on the pipeline's device "
                                       "(read_index(path, device=...))" % (index.device, dev))
             index.reserve(nq)
-            _lib.check(L.rvcmi_ivf_search_blend_expand(index._h, nq, _ptr(f), float(index_rate), 8, 1 if realtime_guard else 0,
-                                                       _ptr(pf), float(protect), p_len, _ptr(out), _stream(dev)))
+            _lib.check(L.rvcmi_ivf_search_blend_expand(index._h, nq, _lib.ptr(f), float(index_rate), 8, 1 if realtime_guard else 0,
+                                                       _lib.ptr(pf), float(protect), p_len, _lib.ptr(out), _lib.stream_ptr(dev)))
         else:
-            _lib.check(L.rvcmi_glue_expand_protect(_ptr(f), nq, d, 2, _ptr(pf), float(protect), p_len, _ptr(out), _stream(dev)))
+            _lib.check(L.rvcmi_glue_expand_protect(_lib.ptr(f), nq, d, 2, _lib.ptr(pf), float(protect), p_len, _lib.ptr(out), _lib.stream_ptr(dev)))
 
 
 def retrieve_blend_expand(feats: torch.Tensor, index, index_rate: float, pitchf: Optional[torch.Tensor] = None,
@@ -73,7 +59,7 @@ def retrieve_blend_expand(feats: torch.Tensor, index, index_rate: float, pitchf:
 
     ``skip_rows`` > 0 is the realtime form (rtrvc.py:167-185, 221-233): only ``feats[0][skip_rows:]`` is searched and
     blended (the rolling window's old frames keep their HuBERT features); the protect mix runs over all rows."""
-    dev = _dev(feats, "feats")
+    dev = _lib.on_gpu(feats, "feats")
     if feats.dim() != 3 or feats.shape[0] != 1:
         raise ValueError("feats must be [1, nq, d]")
     nq, d = int(feats.shape[1]), int(feats.shape[2])
@@ -101,7 +87,7 @@ def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.0
     """RMVPE salience [n, 360] -> (pitch int64 [1, p_len], pitchf float32 [1, p_len]) as ``Generator.calculate`` +
     pipeline.py:270-277 produce them.  ``f0_up_key``: an int or a float (the realtime GUI's key minus its formant shift); the factor is
     ``pow(2, f0_up_key / 12)`` in fp64 either way, as in rvc/f0/gen.py:18."""
-    dev = _dev(salience, "salience")
+    dev = _lib.on_gpu(salience, "salience")
     if salience.dim() != 2:
         raise ValueError("salience must be [n, bins]")
     s = salience.to(torch.float32).contiguous()
@@ -110,35 +96,35 @@ def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.0
     pitch = torch.empty(int(p_len), device=dev, dtype=torch.int64)
     pitchf = torch.empty(int(p_len), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_rmvpe_f0_key(_ptr(s), n, nb, float(thred), int(p_len), float(f0_up_key), _ptr(scratch), _ptr(pitch),
-                                                      _ptr(pitchf), _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_rmvpe_f0_key(_lib.ptr(s), n, nb, float(thred), int(p_len), float(f0_up_key), _lib.ptr(scratch), _lib.ptr(pitch),
+                                                      _lib.ptr(pitchf), _lib.stream_ptr(dev)))
     return pitch.unsqueeze(0), pitchf.unsqueeze(0)
 
 
 def f0_post(f0: torch.Tensor, f0_up_key=0) -> Tuple[torch.Tensor, torch.Tensor]:
     """f0 in Hz [n] (any estimator) -> (pitch int64 [1, n], pitchf float32 [1, n]): rvc/f0/gen.py post_process (``f0_up_key``: int or float)."""
-    dev = _dev(f0, "f0")
+    dev = _lib.on_gpu(f0, "f0")
     x = f0.reshape(-1).to(torch.float64).contiguous()
     n = int(x.numel())
     pitch = torch.empty(n, device=dev, dtype=torch.int64)
     pitchf = torch.empty(n, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_f0_post_key(_ptr(x), n, float(f0_up_key), _ptr(pitch), _ptr(pitchf), _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_f0_post_key(_lib.ptr(x), n, float(f0_up_key), _lib.ptr(pitch), _lib.ptr(pitchf), _lib.stream_ptr(dev)))
     return pitch.unsqueeze(0), pitchf.unsqueeze(0)
 
 
 def change_rms(data1: torch.Tensor, sr1: int, data2: torch.Tensor, sr2: int, rate: float) -> torch.Tensor:
     """``change_rms(audio, 16000, audio_opt, tgt_sr, rms_mix_rate)`` of pipeline.py:26-46,351 on the device, IN PLACE on
     ``data2`` (returned): ``data2 *= rms1**(1-rate) * max(rms2, 1e-6)**(rate-1)`` with half-second frame RMS envelopes."""
-    dev = _dev(data2, "data2")
+    dev = _lib.on_gpu(data2, "data2")
     for t, nm in ((data1, "data1"), (data2, "data2")):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1 or t.device != dev:
             raise ValueError("%s must be a contiguous 1-D float32 tensor on %s" % (nm, dev))
     n1, n2 = int(data1.numel()), int(data2.numel())
     scratch = torch.empty(2 + n1 // (int(sr1) // 2) + n2 // (int(sr2) // 2), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_change_rms(_ptr(data1), n1, int(sr1), _ptr(data2), n2, int(sr2), float(rate), _ptr(scratch),
-                                                    _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_change_rms(_lib.ptr(data1), n1, int(sr1), _lib.ptr(data2), n2, int(sr2), float(rate), _lib.ptr(scratch),
+                                                    _lib.stream_ptr(dev)))
     return data2
 
 
@@ -155,7 +141,7 @@ def cut_points(audio: torch.Tensor, window: int, t_center: int, t_query: int, re
     not float64 raises ``TypeError``: a cast would change the sums.  Enqueue-only; the caller reads the cuts back."""
     if audio.dtype != torch.float64:
         raise TypeError("audio must be float64 (got %s): the sums are defined on the float64 signal" % audio.dtype)
-    dev = _dev(audio, "audio")
+    dev = _lib.on_gpu(audio, "audio")
     if audio.dim() != 1 or not audio.is_contiguous():
         raise ValueError("audio must be a contiguous 1-D tensor")
     n, window, t_center, t_query = int(audio.numel()), int(window), int(t_center), int(t_query)
@@ -166,8 +152,8 @@ def cut_points(audio: torch.Tensor, window: int, t_center: int, t_query: int, re
     sums = torch.full((ncuts, 2 * max(t_query, 0)), float("nan"), device=dev, dtype=torch.float64) if return_sums else None
     scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        _lib.check(L.rvcmi_glue_cut_points(_ptr(audio), n, window, t_center, t_query, _ptr(cuts), ncuts, _ptr(sums), _ptr(scratch),
-                                           _stream(dev)))
+        _lib.check(L.rvcmi_glue_cut_points(_lib.ptr(audio), n, window, t_center, t_query, _lib.ptr(cuts), ncuts, _lib.ptr(sums), _lib.ptr(scratch),
+                                           _lib.stream_ptr(dev)))
     return (cuts, sums) if return_sums else cuts
 
 
@@ -302,7 +288,7 @@ def filtfilt_flat(flat: torch.Tensor, lengths, b, a, reflect_pad: int = 0):
             raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
         if pad < 0 or (pad and n <= pad):
             raise ValueError("reflect_pad = %d needs every item longer than it (got %d samples)" % (pad, n))
-    dev = _dev(flat, "x")  # (after the argument checks: they are scipy's and need no GPU)
+    dev = _lib.on_gpu(flat, "x")  # (after the argument checks: they are scipy's and need no GPU)
     B, total, max_len = len(lengths), int(flat.numel()), max(lengths)
     L = _lib.lib()
     nbytes = int(L.rvcmi_glue_filtfilt_scratch_bytes(B, total, order))
@@ -317,8 +303,8 @@ def filtfilt_flat(flat: torch.Tensor, lengths, b, a, reflect_pad: int = 0):
     scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     dptr = lambda v: v.ctypes.data_as(C.c_void_p)  # noqa: E731
     with torch.cuda.device(dev):
-        _lib.check(L.rvcmi_glue_filtfilt(_ptr(flat), 1 if flat.dtype == torch.float64 else 0, _ptr(offsets), B, max_len, total, dptr(bn), dptr(an),
-                                         dptr(zi), order, warm, _ptr(out), _ptr(out_pad), pad, _ptr(scratch), nbytes, _stream(dev)))
+        _lib.check(L.rvcmi_glue_filtfilt(_lib.ptr(flat), 1 if flat.dtype == torch.float64 else 0, _lib.ptr(offsets), B, max_len, total, dptr(bn), dptr(an),
+                                         dptr(zi), order, warm, _lib.ptr(out), _lib.ptr(out_pad), pad, _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
     outs = [out[starts[i]: starts[i + 1]] for i in range(B)]
     if not pad:
         return outs
@@ -376,12 +362,12 @@ def highpass16k(x, reflect_pad: int = 0, ref_module=None):
 
 def scale_int16_range(audio: torch.Tensor) -> torch.Tensor:
     """In place: ``audio *= 32768 / max(1, |audio|.max() / 0.99)`` (pipeline.py:355-359); returns ``audio``."""
-    dev = _dev(audio, "audio")
+    dev = _lib.on_gpu(audio, "audio")
     if audio.dtype != torch.float32 or not audio.is_contiguous():
         raise ValueError("audio must be a contiguous float32 tensor")
     scratch = torch.empty(256, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_scale_int16_range(_ptr(audio), audio.numel(), _ptr(scratch), _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_scale_int16_range(_lib.ptr(audio), audio.numel(), _lib.ptr(scratch), _lib.stream_ptr(dev)))
     return audio
 
 
@@ -391,7 +377,7 @@ def sola(infer_wav: torch.Tensor, sola_buffer: torch.Tensor, fade_in: torch.Tens
     ``sola_buffer`` in place (``return_offset=True`` also returns the chosen offset as a 1-element int32 tensor).
     ``use_pv=True`` is the GUI's phase-vocoder branch (gui.py:1081-1087): the same search, then the ``len(sola_buffer)``
     samples at the offset are cross-faded by ``phase_vocoder`` (four launches; the offset never leaves the device)."""
-    dev = _dev(infer_wav, "infer_wav")
+    dev = _lib.on_gpu(infer_wav, "infer_wav")
     for t, nm in ((infer_wav, "infer_wav"), (sola_buffer, "sola_buffer"), (fade_in, "fade_in"), (fade_out, "fade_out")):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
             raise ValueError("%s must be a contiguous float32 tensor on %s" % (nm, dev))
@@ -401,11 +387,11 @@ def sola(infer_wav: torch.Tensor, sola_buffer: torch.Tensor, fade_in: torch.Tens
     with torch.cuda.device(dev):
         if use_pv:
             scratch = torch.empty(3 * (Lb // 2 + 1) + Lb // 2 + 1, device=dev, dtype=torch.float64)
-            _lib.check(_lib.lib().rvcmi_glue_sola_pv(_ptr(infer_wav), infer_wav.numel(), _ptr(sola_buffer), Lb, int(search_frame), _ptr(fade_in),
-                                                     _ptr(fade_out), int(block_frame), _ptr(out), _ptr(off), _ptr(scratch), _stream(dev)))
+            _lib.check(_lib.lib().rvcmi_glue_sola_pv(_lib.ptr(infer_wav), infer_wav.numel(), _lib.ptr(sola_buffer), Lb, int(search_frame), _lib.ptr(fade_in),
+                                                     _lib.ptr(fade_out), int(block_frame), _lib.ptr(out), _lib.ptr(off), _lib.ptr(scratch), _lib.stream_ptr(dev)))
         else:
-            _lib.check(_lib.lib().rvcmi_glue_sola(_ptr(infer_wav), infer_wav.numel(), _ptr(sola_buffer), Lb, int(search_frame), _ptr(fade_in),
-                                                  _ptr(fade_out), int(block_frame), _ptr(out), _ptr(off), _stream(dev)))
+            _lib.check(_lib.lib().rvcmi_glue_sola(_lib.ptr(infer_wav), infer_wav.numel(), _lib.ptr(sola_buffer), Lb, int(search_frame), _lib.ptr(fade_in),
+                                                  _lib.ptr(fade_out), int(block_frame), _lib.ptr(out), _lib.ptr(off), _lib.stream_ptr(dev)))
     return (out, off) if return_offset else out
 
 
@@ -413,7 +399,7 @@ def phase_vocoder(a: torch.Tensor, b: torch.Tensor, fade_out: torch.Tensor, fade
     """``phase_vocoder(a, b, fade_out, fade_in)`` of gui.py:27-49 on the device (n = len(a) <= 4096): the windowed spectra of
     both signals, their summed magnitudes and wrapped phase difference, and the O(n^2 / 2) phase-interpolating synthesis, in
     fp64.  A bin whose spectrum is exactly zero has phase 0.  Returns a new float32 tensor [n]."""
-    dev = _dev(a, "a")
+    dev = _lib.on_gpu(a, "a")
     n = int(a.numel())
     for t, nm in ((a, "a"), (b, "b"), (fade_out, "fade_out"), (fade_in, "fade_in")):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.dim() != 1 or t.numel() != n:
@@ -421,8 +407,8 @@ def phase_vocoder(a: torch.Tensor, b: torch.Tensor, fade_out: torch.Tensor, fade
     out = torch.empty(n, device=dev, dtype=torch.float32)
     scratch = torch.empty(3 * (n // 2 + 1), device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_phase_vocoder(_ptr(a), _ptr(b), _ptr(fade_out), _ptr(fade_in), n, _ptr(out), _ptr(scratch),
-                                                       _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_phase_vocoder(_lib.ptr(a), _lib.ptr(b), _lib.ptr(fade_out), _lib.ptr(fade_in), n, _lib.ptr(out), _lib.ptr(scratch),
+                                                       _lib.stream_ptr(dev)))
     return out
 
 
@@ -430,7 +416,7 @@ def envelope_mix(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int, rms_
     """The realtime GUI's volume-envelope mix (gui.py:1023-1056), IN PLACE on ``infer_wav`` (returned): frame RMS of
     ``input_wav[:len(infer_wav)]`` and of ``infer_wav`` (frame 4 zc, hop zc), both interpolated with ``align_corners=True``,
     ``infer_wav *= pow(rms1 / max(rms2, 1e-3), 1 - rms_mix_rate)``.  Not ``change_rms``: that is the offline formula."""
-    dev = _dev(infer_wav, "infer_wav")
+    dev = _lib.on_gpu(infer_wav, "infer_wav")
     for t, nm in ((input_wav, "input_wav"), (infer_wav, "infer_wav")):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1 or t.device != dev:
             raise ValueError("%s must be a contiguous 1-D float32 tensor on %s" % (nm, dev))
@@ -441,8 +427,8 @@ def envelope_mix(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int, rms_
         raise ValueError("zc must be positive")
     scratch = torch.empty(2 * (1 + n // zc), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rvcmi_glue_envelope_mix(_ptr(input_wav), _ptr(infer_wav), n, zc, float(rms_mix_rate), _ptr(scratch),
-                                                      _stream(dev)))
+        _lib.check(_lib.lib().rvcmi_glue_envelope_mix(_lib.ptr(input_wav), _lib.ptr(infer_wav), n, zc, float(rms_mix_rate), _lib.ptr(scratch),
+                                                      _lib.stream_ptr(dev)))
     return infer_wav
 
 
@@ -453,14 +439,14 @@ def spectral_gate(x: torch.Tensor, xn: Optional[torch.Tensor], n_fft: int, hop: 
     contiguous float32, ``window`` [n_fft] float64 (the hann window zero-padded to the centre), ``smoothing_filter`` [nf, nt]
     float32 or None.  Returns a new float32 tensor [B, hop * (L // hop)].  STFT, statistics and overlap-add in fp64
     (rvcmi.h); n_fft must be even and <= 4096."""
-    dev = _dev(x, "x")
+    dev = _lib.on_gpu(x, "x")
     tensors = [(x, "x", torch.float32), (window, "window", torch.float64)]
     if xn is not None:
         tensors.append((xn, "xn", torch.float32))
     if smoothing_filter is not None:
         tensors.append((smoothing_filter, "smoothing_filter", torch.float32))
     for t, nm, dt in tensors:
-        _dev(t, nm)
+        _lib.on_gpu(t, nm)
         if t.device != dev:
             raise _lib.RvcmiError("%s lives on %s, x on %s" % (nm, t.device, dev))
         if t.dtype != dt or not t.is_contiguous():
@@ -481,7 +467,7 @@ def spectral_gate(x: torch.Tensor, xn: Optional[torch.Tensor], n_fft: int, hop: 
     out = torch.empty(B, hop * (n // hop) if hop > 0 else 0, device=dev, dtype=torch.float32)
     scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        _lib.check(L.rvcmi_glue_spectral_gate(_ptr(x), B, n, _ptr(xn), nn, int(n_fft), hop, _ptr(window), _ptr(smoothing_filter), nf, nt,
+        _lib.check(L.rvcmi_glue_spectral_gate(_lib.ptr(x), B, n, _lib.ptr(xn), nn, int(n_fft), hop, _lib.ptr(window), _lib.ptr(smoothing_filter), nf, nt,
                                               1 if nonstationary else 0, float(n_std_thresh), float(n_thresh_ns), float(temp_coeff),
-                                              int(n_movemean), float(prop_decrease), _ptr(out), _ptr(scratch), nbytes, _stream(dev)))
+                                              int(n_movemean), float(prop_decrease), _lib.ptr(out), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
     return out

@@ -15,6 +15,7 @@ Operands are fp16 (like the reference's own ``is_half`` RMVPE), accumulation, ga
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -28,10 +29,7 @@ class GRUHIP(torch.nn.Module):
         super().__init__()
         if not supports(gru):
             raise _lib.RvcmiError("GRUHIP: only nn.GRU(I, 256, num_layers=1, bias=True, batch_first=True, bidirectional=True) with I % 16 == 0")
-        p = next(gru.parameters())
-        dev = torch.device(device) if device is not None else p.device
-        if dev.type != "cuda":
-            raise _lib.RvcmiError("GRUHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
+        dev = _lib.cuda_device(device if device is not None else next(gru.parameters()).device, "GRUHIP")
         self.input_size, self.hidden_size = gru.input_size, gru.hidden_size
         self.batch_first, self.bidirectional, self.num_layers = True, True, 1
         self._device = dev
@@ -42,17 +40,9 @@ class GRUHIP(torch.nn.Module):
         w_ih, w_hh, b_ih, b_hh = both("weight_ih"), both("weight_hh"), both("bias_ih"), both("bias_hh")
         h = C.c_void_p()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rvcmi_gru_create(self.input_size, self.hidden_size, C.c_void_p(w_ih.data_ptr()), C.c_void_p(w_hh.data_ptr()),
-                                                   C.c_void_p(b_ih.data_ptr()), C.c_void_p(b_hh.data_ptr()), _lib.device_index(dev), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = self.__dict__.pop("_h", None)  # (not through nn.Module.__setattr__: it may be gone at interpreter shutdown)
-        if h:
-            try:
-                _lib.lib().rvcmi_gru_destroy(h)
-            except Exception:  # noqa  (interpreter shutdown)
-                pass
+            _lib.check(_lib.lib().rvcmi_gru_create(self.input_size, self.hidden_size, _lib.ptr(w_ih), _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh),
+                                                   dev.index, C.byref(h)))
+        self._h = _lib.Handle("rvcmi_gru_destroy", h)
 
     def flatten_parameters(self):  # (nn.GRU API the callers of a loaded checkpoint may use)
         pass
@@ -62,8 +52,7 @@ class GRUHIP(torch.nn.Module):
             raise _lib.RvcmiError("GRUHIP: h_0 must be None (zeros), as in rvc/f0/e2e.py:66")
         if x.dim() != 3 or x.shape[-1] != self.input_size:
             raise ValueError("GRUHIP: expected [B, T, %d], got %s" % (self.input_size, tuple(x.shape)))
-        if x.device.type != "cuda":
-            raise _lib.RvcmiError("GRUHIP input must live on the GPU (got %s)" % x.device)
+        _lib.require_on(x, self._device, "GRUHIP")  # (a launch on the handle's device with another device's stream and pointers otherwise)
         B, T = int(x.shape[0]), int(x.shape[1])
         H = self.hidden_size
         y = torch.empty(B, T, 2 * H, device=x.device, dtype=torch.float32)
@@ -71,8 +60,7 @@ class GRUHIP(torch.nn.Module):
         if B and T:
             x16 = x.detach().to(torch.float16).contiguous()
             with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().rvcmi_gru_forward(self._h, B, T, C.c_void_p(x16.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(hn.data_ptr()),
-                                                        C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+                _lib.check(_lib.lib().rvcmi_gru_forward(self._h, B, T, _lib.ptr(x16), _lib.ptr(y), _lib.ptr(hn), _lib.stream_ptr(x.device)))
         return y.to(x.dtype), hn.to(x.dtype)
 
 
@@ -97,28 +85,14 @@ def accelerate_f0_rmvpe(rmvpe) -> int:
     """What the rebound ``Pipeline.pipeline`` / ``RVC.infer`` do with the ``RMVPE`` object (rvc/f0/rmvpe.py) of their f0 generator, once:
     ``accelerate_rmvpe(rmvpe.model)`` unless ``RVCMI_RMVPE_GRU=0``.  The count is remembered on the object (``_rvcmi_gru``).  With the opt-in
     switch of ``unet.py`` on, also ``accelerate_rmvpe_unet(rmvpe.model)`` (count: ``_rvcmi_unet``)."""
-    import os
-
-    n = getattr(rmvpe, "_rvcmi_gru", None)
-    if n is None:
-        n = 0
-        net = getattr(rmvpe, "model", None)
-        if os.environ.get("RVCMI_RMVPE_GRU", "1") != "0" and isinstance(net, torch.nn.Module):
-            n = accelerate_rmvpe(net)
-        try:
-            rmvpe._rvcmi_gru = n
-        except Exception:  # noqa  (an object without a __dict__: try again next time)
-            pass
+    net = getattr(rmvpe, "model", None)
+    is_net = isinstance(net, torch.nn.Module)
+    n = _lib.once(rmvpe, "_rvcmi_gru", lambda: accelerate_rmvpe(net) if os.environ.get("RVCMI_RMVPE_GRU", "1") != "0" and is_net else 0)
     # opt-in (RVCMI_RMVPE_UNET=1 / install(rmvpe_unet=True), default off): the U-Net and head in front of the GRU on csrc/unet.hip; its own
     # count (_rvcmi_unet), so the switch can come on after the GRU swap was made
     from . import unet as _unet
 
-    if _unet.unet_on() and getattr(rmvpe, "_rvcmi_unet", None) is None:
-        net = getattr(rmvpe, "model", None)
-        m = _unet.accelerate_rmvpe_unet(net) if isinstance(net, torch.nn.Module) else 0
-        try:
-            rmvpe._rvcmi_unet = m
-        except Exception:  # noqa
-            pass
+    if _unet.unet_on():
+        _lib.once(rmvpe, "_rvcmi_unet", lambda: _unet.accelerate_rmvpe_unet(net) if is_net else 0)
     return n
 

@@ -26,7 +26,6 @@ LayerNorm, ``final_proj`` and the loop over the layers stay on torch.  Measured 
 from __future__ import annotations
 
 import ctypes as C
-import os
 import re
 import contextlib
 from typing import Dict, List, Optional, Sequence
@@ -56,14 +55,9 @@ HUBERT_BATCH_MAX_WASTE = 0.5
 HUBERT_BATCH_MAX_SAMPLES = 64 * 12 * 16000  # B * N_max of one group (the extractor's workspace takes ~310 bytes per sample): the largest shape the timing tool runs
 
 
-def hubert_on() -> bool:
-    env = os.environ.get("RVCMI_HUBERT_FE")
-    return env == "1" if env in ("0", "1") else bool(HUBERT_FE)
-
-
-def hubert_batch_on() -> bool:
-    env = os.environ.get("RVCMI_HUBERT_BATCH")
-    return hubert_on() and (env == "1" if env in ("0", "1") else bool(HUBERT_BATCH))
+_FE = _lib.Switch("RVCMI_HUBERT_FE", globals(), "HUBERT_FE")
+_BATCH = _lib.Switch("RVCMI_HUBERT_BATCH", globals(), "HUBERT_BATCH", base=_FE)
+hubert_on, hubert_batch_on = _FE.on, _BATCH.on
 
 
 def frames(n: int) -> int:
@@ -205,24 +199,15 @@ class HubertFrontHIP(torch.nn.Module):
 
     def __init__(self, state_dict, device):
         super().__init__()
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.RvcmiError("HubertFrontHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
-        dev = torch.device("cuda", _lib.device_index(dev))
-        keep = [(k, v.detach().float().cpu().contiguous()) for k, v in canonical_keys(state_dict).items() if v.is_floating_point() and 1 <= v.dim() <= 4]
-        if not keep:
+        dev = _lib.cuda_device(device, "HubertFrontHIP")
+        arr = _lib.pack_tensors((k, v.detach().float().cpu().contiguous()) for k, v in canonical_keys(state_dict).items()
+                                if v.is_floating_point() and 1 <= v.dim() <= 4)
+        if not len(arr):
             raise _lib.RvcmiError("HubertFrontHIP: no 'conv_layers.' weights in the state dict", code=_lib.ERR_INVALID)
-        arr = (_lib.Tensor * len(keep))()
-        for i, (k, v) in enumerate(keep):
-            arr[i].name = k.encode()
-            arr[i].data = v.data_ptr()
-            arr[i].ndim = v.dim()
-            for j, s in enumerate(v.shape):
-                arr[i].shape[j] = int(s)
         h = C.c_void_p()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rvcmi_hubert_fe_create(arr, len(keep), dev.index, C.byref(h)))
-        self._h = h
+            _lib.check(_lib.lib().rvcmi_hubert_fe_create(arr, len(arr), dev.index, C.byref(h)))
+        self._h = _lib.Handle("rvcmi_hubert_fe_destroy", h)
         self._device = dev
 
     @classmethod
@@ -239,14 +224,6 @@ class HubertFrontHIP(torch.nn.Module):
         if len(devs) != 1:
             raise _lib.RvcmiError("HubertFrontHIP: the module's parameters are on %d devices" % len(devs), code=_lib.ERR_INVALID)
         return cls(fe.state_dict(), next(iter(devs)))
-
-    def __del__(self):
-        h = self.__dict__.pop("_h", None)  # (not through nn.Module.__setattr__: it may be gone at interpreter shutdown)
-        if h:
-            try:
-                _lib.lib().rvcmi_hubert_fe_destroy(h)
-            except Exception:  # noqa  (interpreter shutdown)
-                pass
 
     def workspace_bytes(self, B: int, N: int) -> int:
         return int(_lib.lib().rvcmi_hubert_fe_workspace_bytes(self._h, int(B), int(N)))
@@ -283,10 +260,7 @@ class HubertFrontHIP(torch.nn.Module):
         lies behind them is not read.  -> the same transposed view as ``forward``, ``[B, 512, frames(N_max)]``: item ``i``'s first
         ``frames(lens[i])`` frames are bit-equal to ``forward`` of that item alone, the frames behind them exactly zero.  ``workspace``: as in
         ``forward`` (``workspace_bytes_ragged(B, N_max)`` bytes).  Inside a stream capture the lengths must have been used once before."""
-        if not torch.is_tensor(x) or x.device.type != "cuda":
-            raise _lib.RvcmiError("HubertFrontHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(x, "device", type(x)))
-        if x.device != self._device:
-            raise _lib.RvcmiError("HubertFrontHIP: the input is on %s, the weights on %s" % (x.device, self._device))
+        _lib.require_on(x, self._device, "HubertFrontHIP")
         if x.dim() != 2 or x.dtype not in (torch.float16, torch.float32):
             raise _lib.RvcmiError("HubertFrontHIP: expected an fp16 or fp32 [B, N_max], got %s %s" % (x.dtype, tuple(x.shape)), code=_lib.ERR_INVALID)
         lens = tuple(_lens_list(lens))
@@ -296,18 +270,12 @@ class HubertFrontHIP(torch.nn.Module):
                                   "longest equal to N_max)" % (list(lens[:8]), tuple(x.shape)), code=_lib.ERR_INVALID)
         x = x.detach().contiguous()
         out = torch.empty(B, frames(N), CHANNELS, device=x.device, dtype=torch.float16)
-        ws = 0
-        if workspace is not None:
-            need = self.workspace_bytes_ragged(B, N)
-            if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() < need or need == 0:
-                raise _lib.RvcmiError("HubertFrontHIP: the workspace must be %d uint8 on %s" % (need, x.device), code=_lib.ERR_INVALID)
-            ws = workspace.data_ptr()
+        ws = None if workspace is None else _lib.workspace_ptr(workspace, self.workspace_bytes_ragged(B, N), x.device, "HubertFrontHIP")
         host = (C.c_int * B)(*lens)
         dev = self._lens_dev(lens)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().rvcmi_hubert_fe_forward_ragged(self._h, B, N, host, C.c_void_p(dev.data_ptr()), C.c_void_p(x.data_ptr()),
-                                                                 1 if x.dtype == torch.float16 else 0, C.c_void_p(out.data_ptr()), C.c_void_p(ws),
-                                                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+            _lib.check(_lib.lib().rvcmi_hubert_fe_forward_ragged(self._h, B, N, host, _lib.ptr(dev), _lib.ptr(x), 1 if x.dtype == torch.float16 else 0,
+                                                                 _lib.ptr(out), ws, _lib.stream_ptr(x.device)))
         return out.to(x.dtype).transpose(1, 2)
 
     @contextlib.contextmanager
@@ -329,10 +297,7 @@ class HubertFrontHIP(torch.nn.Module):
         lens = self.__dict__.get("_ragged")
         if lens is not None:
             return self.forward_ragged(x, lens, workspace)
-        if not torch.is_tensor(x) or x.device.type != "cuda":
-            raise _lib.RvcmiError("HubertFrontHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(x, "device", type(x)))
-        if x.device != self._device:
-            raise _lib.RvcmiError("HubertFrontHIP: the input is on %s, the weights on %s" % (x.device, self._device))
+        _lib.require_on(x, self._device, "HubertFrontHIP")
         if x.dim() != 2 or x.dtype not in (torch.float16, torch.float32):
             raise _lib.RvcmiError("HubertFrontHIP: expected an fp16 or fp32 [B, N], got %s %s" % (x.dtype, tuple(x.shape)), code=_lib.ERR_INVALID)
         B, N = int(x.shape[0]), int(x.shape[1])
@@ -342,14 +307,10 @@ class HubertFrontHIP(torch.nn.Module):
         L = frames(N)
         x = x.detach().contiguous()
         out = torch.empty(B, max(L, 0), CHANNELS, device=x.device, dtype=torch.float16)
-        ws = 0
-        if workspace is not None:
-            if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() < self.workspace_bytes(B, N):
-                raise _lib.RvcmiError("HubertFrontHIP: the workspace must be %d uint8 on %s" % (self.workspace_bytes(B, N), x.device), code=_lib.ERR_INVALID)
-            ws = workspace.data_ptr()
+        ws = None if workspace is None else _lib.workspace_ptr(workspace, self.workspace_bytes(B, N), x.device, "HubertFrontHIP")
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().rvcmi_hubert_fe_forward(self._h, B, N, C.c_void_p(x.data_ptr()), 1 if x.dtype == torch.float16 else 0,
-                                                          C.c_void_p(out.data_ptr()), C.c_void_p(ws), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+            _lib.check(_lib.lib().rvcmi_hubert_fe_forward(self._h, B, N, _lib.ptr(x), 1 if x.dtype == torch.float16 else 0, _lib.ptr(out), ws,
+                                                          _lib.stream_ptr(x.device)))
         return out.to(x.dtype).transpose(1, 2)
 
 
@@ -361,8 +322,8 @@ def debug_conv(x16: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     wh = w.detach().float().cpu().contiguous()
     out = torch.empty(B, max((L_in - taps) // 2 + 1, 0), CHANNELS, device=x16.device, dtype=torch.float32)
     with torch.cuda.device(x16.device):
-        _lib.check(_lib.lib().rvcmi_hubert_fe_debug_conv(taps, B, L_in, C.c_void_p(wh.data_ptr()), C.c_void_p(x16.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                         _lib.device_index(x16.device), C.c_void_p(torch.cuda.current_stream(x16.device).cuda_stream)))
+        _lib.check(_lib.lib().rvcmi_hubert_fe_debug_conv(taps, B, L_in, _lib.ptr(wh), _lib.ptr(x16), _lib.ptr(out), _lib.device_index(x16.device),
+                                                         _lib.stream_ptr(x16.device)))
     return out
 
 
@@ -460,16 +421,7 @@ def restore_hubert(model) -> int:
 def accelerate_hubert_once(model) -> int:
     """What the conversion paths call in front of ``model.extract_features``: with the switch on, ``accelerate_hubert(model)`` once per
     model object (the count is remembered on it as ``_rvcmi_hubert_fe``); with it off, nothing."""
-    if not hubert_on():
-        return 0
-    n = getattr(model, "_rvcmi_hubert_fe", None)
-    if n is None:
-        n = accelerate_hubert(model)
-        try:
-            object.__setattr__(model, "_rvcmi_hubert_fe", n)
-        except Exception:  # noqa  (an object without a __dict__: the swap is looked for again next time, and found done)
-            pass
-    return n
+    return _lib.once(model, "_rvcmi_hubert_fe", lambda: accelerate_hubert(model)) if hubert_on() else 0
 
 
 # ---- the transformer's layers on csrc/hubert_enc.hip (opt-in: RVCMI_HUBERT_ENC=1 or rvc_amd.install(hubert_enc=True); default off; DESIGN.md 7.9) ----
@@ -482,9 +434,7 @@ _LAYER_TENSORS = tuple("%s.%s" % (m, p) for m in ("self_attn.q_proj", "self_attn
                                                   "fc1", "fc2", "final_layer_norm") for p in ("weight", "bias"))
 
 
-def hubert_enc_on() -> bool:
-    env = os.environ.get("RVCMI_HUBERT_ENC")
-    return env == "1" if env in ("0", "1") else bool(HUBERT_ENC)
+hubert_enc_on = _lib.Switch("RVCMI_HUBERT_ENC", globals(), "HUBERT_ENC").on
 
 
 def _layer_parts(m):
@@ -567,29 +517,16 @@ class HubertEncoderHIP:
     fp32), every layer's output rounded once to that dtype, so ``forward(first=0, n=2)`` is bit-equal to two calls of one layer."""
 
     def __init__(self, state_dicts, cfg, device):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.RvcmiError("HubertEncoderHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
-        dev = torch.device("cuda", _lib.device_index(dev))
-        keep = []
-        for i, sd in enumerate(state_dicts):
-            for k, v in sd.items():
-                if torch.is_tensor(v) and v.is_floating_point() and 1 <= v.dim() <= 4:
-                    keep.append(("layers.%d.%s" % (i, k), v.detach().float().cpu().contiguous()))
-        if not keep:
+        dev = _lib.cuda_device(device, "HubertEncoderHIP")
+        arr = _lib.pack_tensors(("layers.%d.%s" % (i, k), v.detach().float().cpu().contiguous()) for i, sd in enumerate(state_dicts) for k, v in sd.items()
+                                if torch.is_tensor(v) and v.is_floating_point() and 1 <= v.dim() <= 4)
+        if not len(arr):
             raise _lib.RvcmiError("HubertEncoderHIP: no layer weights", code=_lib.ERR_INVALID)
-        arr = (_lib.Tensor * len(keep))()
-        for i, (k, v) in enumerate(keep):
-            arr[i].name = k.encode()
-            arr[i].data = v.data_ptr()
-            arr[i].ndim = v.dim()
-            for j, s in enumerate(v.shape):
-                arr[i].shape[j] = int(s)
         h = C.c_void_p()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rvcmi_hubert_enc_create(arr, len(keep), len(state_dicts), int(cfg["d"]), int(cfg["heads"]), int(cfg["ffn"]),
+            _lib.check(_lib.lib().rvcmi_hubert_enc_create(arr, len(arr), len(state_dicts), int(cfg["d"]), int(cfg["heads"]), int(cfg["ffn"]),
                                                           float(cfg.get("eps", 1e-5)), dev.index, C.byref(h)))
-        self._h = h
+        self._h = _lib.Handle("rvcmi_hubert_enc_destroy", h)
         self._device = dev
         self.n_layers, self.d = len(state_dicts), int(cfg["d"])
         self._ws = None
@@ -612,14 +549,6 @@ class HubertEncoderHIP:
             raise _lib.RvcmiError("HubertEncoderHIP: the layers differ in geometry or device", code=_lib.ERR_INVALID)
         return cls([layer_state_dict(m) for m in modules], cfgs[0], cfgs[0]["device"] if device is None else device)
 
-    def __del__(self):
-        h = self.__dict__.pop("_h", None)
-        if h:
-            try:
-                _lib.lib().rvcmi_hubert_enc_destroy(h)
-            except Exception:  # noqa  (interpreter shutdown)
-                pass
-
     def workspace_bytes(self, B: int, T: int) -> int:
         return int(_lib.lib().rvcmi_hubert_enc_workspace_bytes(self._h, int(B), int(T)))
 
@@ -638,33 +567,25 @@ class HubertEncoderHIP:
         """Layers ``first .. first + n - 1`` (default: all from ``first``).  ``key_mask``: bool / uint8 ``[B, T]`` on the GPU, nonzero = a padded
         key no query attends to (padded QUERY rows are computed like any other, as torch does).  ``workspace``: a uint8 tensor of
         ``workspace_bytes(B, T)`` bytes; default: the object's own, which grows on the first call of a larger shape (not inside a capture)."""
-        if not torch.is_tensor(x) or x.device.type != "cuda":
-            raise _lib.RvcmiError("HubertEncoderHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(x, "device", type(x)))
-        if x.device != self._device:
-            raise _lib.RvcmiError("HubertEncoderHIP: the input is on %s, the weights on %s" % (x.device, self._device))
+        _lib.require_on(x, self._device, "HubertEncoderHIP")
         if x.dim() != 3 or x.dtype not in (torch.float16, torch.float32) or int(x.shape[2]) != self.d:
             raise _lib.RvcmiError("HubertEncoderHIP: expected an fp16 or fp32 [B, T, %d], got %s %s" % (self.d, x.dtype, tuple(x.shape)), code=_lib.ERR_INVALID)
         B, T = int(x.shape[0]), int(x.shape[1])
         n = self.n_layers - int(first) if n is None else int(n)
         x = x.detach().contiguous()
-        km = 0
+        km = None
         if key_mask is not None:
             if key_mask.device != x.device or tuple(key_mask.shape) != (B, T):
                 raise _lib.RvcmiError("HubertEncoderHIP: the key mask must be [B, T] = %s on %s" % ((B, T), x.device), code=_lib.ERR_INVALID)
             key_mask = (key_mask if key_mask.dtype in (torch.uint8, torch.bool) else key_mask != 0).contiguous()
             key_mask = key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
-            km = key_mask.data_ptr()
+            km = key_mask
         need = self.workspace_bytes(B, T)
-        if workspace is not None:
-            if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() < need or need == 0:
-                raise _lib.RvcmiError("HubertEncoderHIP: the workspace must be %d uint8 on %s" % (need, x.device), code=_lib.ERR_INVALID)
-        else:
-            workspace = self._own_workspace(need)
+        ws = _lib.ptr(self._own_workspace(need)) if workspace is None else _lib.workspace_ptr(workspace, need, x.device, "HubertEncoderHIP")
         out = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().rvcmi_hubert_enc_forward(self._h, int(first), n, B, T, C.c_void_p(x.data_ptr()), 1 if x.dtype == torch.float16 else 0,
-                                                           C.c_void_p(km), C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()),
-                                                           C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+            _lib.check(_lib.lib().rvcmi_hubert_enc_forward(self._h, int(first), n, B, T, _lib.ptr(x), 1 if x.dtype == torch.float16 else 0, _lib.ptr(km),
+                                                           _lib.ptr(out), ws, _lib.stream_ptr(x.device)))
         return out
 
     __call__ = forward
@@ -758,13 +679,4 @@ def restore_hubert_layers(model) -> int:
 def accelerate_hubert_layers_once(model) -> int:
     """What the conversion paths call next to ``accelerate_hubert_once``: with the switch on, ``accelerate_hubert_layers(model)`` once per
     model object (the count is remembered on it as ``_rvcmi_hubert_enc``); with it off, nothing."""
-    if not hubert_enc_on():
-        return 0
-    n = getattr(model, "_rvcmi_hubert_enc", None)
-    if n is None:
-        n = accelerate_hubert_layers(model)
-        try:
-            object.__setattr__(model, "_rvcmi_hubert_enc", n)
-        except Exception:  # noqa  (an object without a __dict__)
-            pass
-    return n
+    return _lib.once(model, "_rvcmi_hubert_enc", lambda: accelerate_hubert_layers(model)) if hubert_enc_on() else 0

@@ -166,6 +166,19 @@ def _rebind_gate(rebound) -> None:
             rebound.append((mod, "TorchGate", old))
 
 
+# The opt-in globals install() sets from its arguments and uninstall() puts back: (module, global, install() argument, default)
+_SWITCHES = (("pipeline", "DEVICE_PREP", "device_prep", False), ("unet", "RMVPE_UNET", "rmvpe_unet", False), ("rmvpe", "RMVPE_HIP", "rmvpe_hip", False),
+             ("hubert", "HUBERT_FE", "hubert_fe", False), ("hubert", "HUBERT_BATCH", "hubert_batch", False), ("hubert", "HUBERT_ENC", "hubert_enc", False),
+             ("synthesizer", "FRONT_OPERAND", "front_operand", None))
+
+
+def _set_switches(args: Optional[dict]) -> None:
+    """``args``: install()'s arguments; None: every global back to its default."""
+    for mod, name, arg, default in _SWITCHES:
+        v = default if args is None else args[arg]
+        setattr(importlib.import_module("." + mod, __package__), name, v if default is None else bool(v))
+
+
 def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss: bool = True, patch_pipeline: bool = True,
             patch_gui: bool = False, device_prep: bool = False, rmvpe_unet: bool = False, rmvpe_hip: bool = False,
             index_build: Optional[bool] = None, hubert_fe: bool = False, hubert_batch: bool = False,
@@ -191,6 +204,7 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
     (``hubert.accelerate_hubert_layers``: all layers or none), once per model object."""
     if _state.get("installed"):
         return
+    args = dict(locals())
     _syn.front_operand_choice(front_operand)  # a bad name raises here, before anything is rebound
     import rvc.synthesizer as rs  # the reference package must be importable: this IS the plug-in boundary
 
@@ -249,21 +263,7 @@ def install(operand: str = "fp16", front: bool = True, device=None, patch_faiss:
         _rebind_methods(rebound)
     if patch_gui:
         _rebind_gate(rebound)
-    from . import pipeline as _plm
-
-    from . import unet as _unet
-
-    _plm.DEVICE_PREP = bool(device_prep)  # last: an install() that raised above leaves the switch as it was
-    _unet.RMVPE_UNET = bool(rmvpe_unet)
-    from . import rmvpe as _rmvpe
-
-    _rmvpe.RMVPE_HIP = bool(rmvpe_hip)
-    from . import hubert as _hubert
-
-    _hubert.HUBERT_FE = bool(hubert_fe)
-    _hubert.HUBERT_BATCH = bool(hubert_batch)
-    _hubert.HUBERT_ENC = bool(hubert_enc)
-    _syn.FRONT_OPERAND = front_operand
+    _set_switches(args)  # last: an install() that raised above leaves the switches as they were
 
 
 def uninstall() -> None:
@@ -279,19 +279,5 @@ def uninstall() -> None:
             sys.modules.pop("faiss", None)
         else:
             sys.modules["faiss"] = _state["faiss_prev"]
-    from . import pipeline as _plm
-
-    from . import unet as _unet
-
-    _plm.DEVICE_PREP = False
-    _unet.RMVPE_UNET = False
-    from . import rmvpe as _rmvpe
-
-    _rmvpe.RMVPE_HIP = False
-    from . import hubert as _hubert
-
-    _hubert.HUBERT_FE = False
-    _hubert.HUBERT_BATCH = False
-    _hubert.HUBERT_ENC = False
-    _syn.FRONT_OPERAND = None
+    _set_switches(None)
     _state.clear()

@@ -114,8 +114,7 @@ class IVFFlatHIP:
         if keep.ndim != 2 or keep.shape[1] != d:
             raise ValueError("add: rows must be [n, %d], got %s" % (d, tuple(keep.shape)))  # faiss: assert d == self.d
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().rvcmi_ivf_add(h, int(keep.shape[0]), C.c_void_p(ptr), on_device, C.c_void_p(st)))
+            _lib.check(_lib.lib().rvcmi_ivf_add(h, int(keep.shape[0]), C.c_void_p(ptr), on_device, _lib.stream_ptr(self.device)))
 
     @classmethod
     def from_blob(cls, blob: torch.Tensor) -> "IVFFlatHIP":
@@ -123,7 +122,7 @@ class IVFFlatHIP:
         if blob.dtype != torch.uint8 or blob.device.type != "cuda" or not blob.is_contiguous():
             raise ValueError("blob must be a contiguous uint8 CUDA tensor")
         h = C.c_void_p(None)
-        _lib.check(_lib.lib().rvcmi_ivf_create_from_blob(C.c_void_p(blob.data_ptr()), blob.numel(), _idx(blob.device), 0,
+        _lib.check(_lib.lib().rvcmi_ivf_create_from_blob(_lib.ptr(blob), blob.numel(), _idx(blob.device), 0,
                                                          C.byref(h)))
         return cls(h, blob.device, keepalive=blob)
 
@@ -133,8 +132,7 @@ class IVFFlatHIP:
         _lib.check(_lib.lib().rvcmi_ivf_blob(self._h, C.byref(p), C.byref(n)))
         out = torch.empty(n.value, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().rvcmi_ivf_blob_copy(self._h, C.c_void_p(out.data_ptr()), n.value, C.c_void_p(st)))
+            _lib.check(_lib.lib().rvcmi_ivf_blob_copy(self._h, _lib.ptr(out), n.value, _lib.stream_ptr(self.device)))
         return out
 
     def __del__(self):
@@ -202,9 +200,7 @@ class IVFFlatHIP:
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().rvcmi_ivf_search(self._h, nq, C.c_void_p(xt.data_ptr()), int(k), C.c_void_p(D.data_ptr()),
-                                                   C.c_void_p(I.data_ptr()), C.c_void_p(st)))
+            _lib.check(_lib.lib().rvcmi_ivf_search(self._h, nq, _lib.ptr(xt), int(k), _lib.ptr(D), _lib.ptr(I), _lib.stream_ptr(self.device)))
         if is_np:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
@@ -217,9 +213,8 @@ class IVFFlatHIP:
         if feats.dim() != 2 or feats.shape[1] != self.d:
             raise ValueError("feats must be [nq, %d]" % self.d)
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().rvcmi_ivf_search_blend(self._h, feats.shape[0], C.c_void_p(feats.data_ptr()),
-                                                         float(index_rate), int(k), 1 if skip_if_short else 0, C.c_void_p(st)))
+            _lib.check(_lib.lib().rvcmi_ivf_search_blend(self._h, feats.shape[0], _lib.ptr(feats), float(index_rate), int(k), 1 if skip_if_short else 0,
+                                                         _lib.stream_ptr(self.device)))
         return feats
 
     def set_option(self, key: str, value=None) -> None:

@@ -79,9 +79,7 @@ class _HipGenerator(torch.nn.Module):
         _operand_code(operand)  # a bad name (or the front-only 'fp16x2') raises ValueError before anything else
         self.cfg = dict(cfg)
         self.operand = operand
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.RvcmiError("the HIP generator needs a GPU device (got %s); there is no CPU fallback" % device)
+        self.device = _lib.cuda_device(device, "the HIP generator")
         if operand == "bf16":
             _warn_bf16("generator: 2.0-2.8e-3 RMS on the waveform")
         self.upp = math.prod(cfg["upsample_rates"])
@@ -89,7 +87,7 @@ class _HipGenerator(torch.nn.Module):
         self.num_upsamples = len(cfg["upsample_rates"])
         # host fp32 copies (kept so the handle can be re-created with a larger workspace)
         self._weights = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in weights.items()}
-        self._handle = C.c_void_p(None)
+        self._handle = None
         self._max_B = self._max_T = 0
         self._ensure(max_B, max_T)
 
@@ -98,24 +96,13 @@ class _HipGenerator(torch.nn.Module):
         if self._handle and B <= self._max_B and T <= self._max_T:
             return
         B, T = max(B, self._max_B), max(T, self._max_T)
-        self._destroy()
-        names = list(self._weights)
-        arr = (_lib.Tensor * len(names))()
-        keep = []
-        for i, k in enumerate(names):
-            t = self._weights[k]
-            kb = k.encode()
-            keep.append(kb)
-            arr[i].name = kb
-            arr[i].data = t.data_ptr()
-            arr[i].ndim = t.dim()
-            for j, s in enumerate(t.shape):
-                arr[i].shape[j] = s
+        if self._handle:
+            self._handle.close()
+        arr = _lib.pack_tensors(self._weights.items())
         cs = _cfg_struct(self.cfg, self.operand)
         h = C.c_void_p(None)
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(_lib.lib().rvcmi_nsf_create(C.byref(cs), arr, len(names), idx, B, T, C.byref(h)))
-        self._handle, self._max_B, self._max_T = h, B, T
+        _lib.check(_lib.lib().rvcmi_nsf_create(C.byref(cs), arr, len(arr), self.device.index, B, T, C.byref(h)))
+        self._handle, self._max_B, self._max_T = _lib.Handle("rvcmi_nsf_destroy", h), B, T
         for k, v in getattr(self, "_options", {}).items():  # options survive a workspace re-creation
             _lib.set_option(_lib.lib().rvcmi_nsf_set_option, self._handle, k, v)
 
@@ -133,17 +120,6 @@ class _HipGenerator(torch.nn.Module):
             self._options.pop(key, None)
         else:
             self._options[key] = value
-
-    def _destroy(self) -> None:
-        if getattr(self, "_handle", None):
-            _lib.lib().rvcmi_nsf_destroy(self._handle)
-            self._handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
 
     def reserve(self, max_B: int, max_T: int) -> "_HipGenerator":
         """Pre-size the workspace (allocation happens here, never inside forward once sized)."""
@@ -200,21 +176,19 @@ class _HipGenerator(torch.nn.Module):
                 raise ValueError("lengths must lie in [1, %d]" % T)
             ln = lt.to(dev, torch.int32).contiguous()
         self._ensure(B, max(T, Te))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+        ptr, stream = _lib.ptr, _lib.stream_ptr(dev)
         nr = -1 if n_res is None else int(n_res)
         L = _lib.lib()
         with torch.cuda.device(dev):
             if tap is None:
                 out = torch.empty(B, 1, Te * self.upp, device=dev, dtype=torch.float32)
-                _lib.check(L.rvcmi_nsf_forward(self._handle, B, T, ptr(ln), ptr(xf), ptr(f0f), ptr(gf), ptr(nf), nr, ptr(out),
-                                               C.c_void_p(stream)))
+                _lib.check(L.rvcmi_nsf_forward(self._handle, B, T, ptr(ln), ptr(xf), ptr(f0f), ptr(gf), ptr(nf), nr, ptr(out), stream))
                 return out.to(out_dtype)
             cap = B * max(self.cfg["upsample_initial_channel"] * Te, Te * self.upp * 256)
             host = np.empty(cap, dtype=np.float32)
             shape = (C.c_int64 * 3)()
             _lib.check(L.rvcmi_nsf_debug_forward(self._handle, B, T, ptr(xf), ptr(f0f), ptr(gf), ptr(nf), nr, tap.encode(),
-                                                 host.ctypes.data_as(C.c_void_p), cap, shape, C.c_void_p(stream)))
+                                                 host.ctypes.data_as(C.c_void_p), cap, shape, stream))
             n = shape[0] * shape[1] * shape[2]
             return torch.from_numpy(host[:n].reshape(shape[0], shape[1], shape[2]).copy())
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
 from .ivf import IVFFlatHIP
 
 
@@ -365,11 +366,7 @@ DEVICE_PREP = False  # install(device_prep=True) sets it; RVCMI_DEVICE_PREP=1 / 
 DEVICE_PREP_MIN_SAMPLES = 24 * 16000
 
 
-def _device_prep_on() -> bool:
-    import os
-
-    env = os.environ.get("RVCMI_DEVICE_PREP")
-    return env == "1" if env in ("0", "1") else bool(DEVICE_PREP)
+_device_prep_on = _lib.Switch("RVCMI_DEVICE_PREP", globals(), "DEVICE_PREP").on
 
 
 def _device_prep(self, audios, dev):

@@ -70,14 +70,11 @@ class SincResample:
         n = int(x.shape[1])
         n_out = -(-self.new * n // self.orig)
         out = torch.empty(x.shape[0], n_out, device=x.device, dtype=torch.float32)
-        import ctypes as C
-
         with torch.cuda.device(x.device):
-            st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            st = _lib.stream_ptr(x.device)
             for r in range(x.shape[0]):
-                _lib.check(_lib.lib().rvcmi_glue_resample_poly(C.c_void_p(x[r].data_ptr()), n, C.c_void_p(self.kernel.data_ptr()), self.orig,
-                                                               self.new, int(self.kernel.shape[1]), self.width, C.c_void_p(out[r].data_ptr()),
-                                                               n_out, st))
+                _lib.check(_lib.lib().rvcmi_glue_resample_poly(_lib.ptr(x[r]), n, _lib.ptr(self.kernel), self.orig, self.new, int(self.kernel.shape[1]),
+                                                               self.width, _lib.ptr(out[r]), n_out, st))
         return out.reshape(shape[:-1] + (n_out,))
 
 

@@ -16,7 +16,6 @@ on the device.  The reference object is read, never changed.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -33,23 +32,13 @@ CACHE_ROWS = 512   # workspaces of calls with B * T_pad <= this stay with the ob
 RMVPE_HIP = False  # install(rmvpe_hip=True) sets it; RVCMI_RMVPE_HIP=1 / =0 overrides it per call
 
 
-def rmvpe_on() -> bool:
-    env = os.environ.get("RVCMI_RMVPE_HIP")
-    return env == "1" if env in ("0", "1") else bool(RMVPE_HIP)
-
-
 RMVPE_BATCH = False        # the group path of pipeline.convert_files (ONE f0_batch call per group); RVCMI_RMVPE_BATCH=1 / =0 overrides it per call.
                            # Off until tools/rmvpe_batch_time.py has been run: profiles/rmvpe_batch_time.json decides the default and the threshold
 RMVPE_BATCH_MIN_FILES = 2  # ... and with it on, a group takes that path from this many files to estimate
 
 
-def rmvpe_batch_on() -> bool:
-    env = os.environ.get("RVCMI_RMVPE_BATCH")
-    return rmvpe_on() and (env == "1" if env in ("0", "1") else bool(RMVPE_BATCH))
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+_HIP = _lib.Switch("RVCMI_RMVPE_HIP", globals(), "RMVPE_HIP")
+rmvpe_on, rmvpe_batch_on = _HIP.on, _lib.Switch("RVCMI_RMVPE_BATCH", globals(), "RMVPE_BATCH", base=_HIP).on
 
 
 def ragged_layout(frames: Sequence[int]) -> Tuple[List[int], int]:
@@ -113,18 +102,15 @@ class RMVPEHIP:
     """waveform at 16 kHz -> log-mel -> U-Net -> GRU -> salience -> (pitch, pitchf), every stage a HIP kernel of this project."""
 
     def __init__(self, n_fft: int, hop_length: int, win_length: int, clamp: float, mel_basis: torch.Tensor, is_half: bool, net, gru, linear, device):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.RvcmiError("RMVPEHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
-        dev = torch.device("cuda", _lib.device_index(dev))
+        dev = _lib.cuda_device(device, "RMVPEHIP")
         basis = mel_basis.detach().float().cpu().contiguous()
         if basis.dim() != 2 or basis.shape[1] != int(n_fft) // 2 + 1:
             raise _lib.RvcmiError("RMVPEHIP: mel_basis %s does not belong to n_fft %d" % (tuple(basis.shape), n_fft), code=_lib.ERR_INVALID)
         h = C.c_void_p()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rvcmi_mel_create(int(n_fft), int(hop_length), int(win_length), int(basis.shape[0]), _ptr(basis), float(clamp),
+            _lib.check(_lib.lib().rvcmi_mel_create(int(n_fft), int(hop_length), int(win_length), int(basis.shape[0]), _lib.ptr(basis), float(clamp),
                                                    dev.index, C.byref(h)))
-        self._h = h
+        self._h = _lib.Handle("rvcmi_mel_destroy", h)
         self.device, self.is_half, self.hop_length, self.n_fft = dev, bool(is_half), int(hop_length), int(n_fft)
         self.unet = net if isinstance(net, _unet.UNetHIP) else _unet.UNetHIP(net, dev)
         self.gru = gru if isinstance(gru, GRUHIP) else GRUHIP(gru, dev)
@@ -158,22 +144,11 @@ class RMVPEHIP:
                 return None
             raise
 
-    def __del__(self):
-        h = self.__dict__.pop("_h", None)
-        if h:
-            try:
-                _lib.lib().rvcmi_mel_destroy(h)
-            except Exception:  # noqa  (interpreter shutdown)
-                pass
-
     def frames(self, n: int) -> int:
         return int(_lib.lib().rvcmi_mel_frames(self._h, int(n)))
 
     def _wav(self, wav) -> torch.Tensor:
-        if not torch.is_tensor(wav) or wav.device.type != "cuda":
-            raise _lib.RvcmiError("RMVPEHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(wav, "device", type(wav)))
-        if wav.device != self.device:
-            raise _lib.RvcmiError("RMVPEHIP: the input is on %s, the weights on %s" % (wav.device, self.device))
+        _lib.require_on(wav, self.device, "RMVPEHIP")
         x = wav.detach().float()
         if x.dim() == 1:
             x = x.unsqueeze(0)
@@ -203,11 +178,8 @@ class RMVPEHIP:
             raise _lib.RvcmiError("RMVPEHIP: a %d-sample input is not longer than the reflection pad %d" % (n, self.n_fft // 2), code=_lib.ERR_INVALID)
         T_pad = 32 * ((T - 1) // 32 + 1)
         ws = ws if ws is not None else self._buffers(B, T_pad)
-        _lib.check(_lib.lib().rvcmi_mel_forward(self._h, B, n, _ptr(x), 1 if self.is_half else 0, T_pad, _ptr(ws["mel"]), self._stream()))
+        _lib.check(_lib.lib().rvcmi_mel_forward(self._h, B, n, _lib.ptr(x), 1 if self.is_half else 0, T_pad, _lib.ptr(ws["mel"]), _lib.stream_ptr(self.device)))
         return ws, T
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _salience(self, x: torch.Tensor) -> Tuple[torch.Tensor, int]:
         """-> ([B, T_pad, 360] fp32, T).  Up to ``CACHE_ROWS`` rows the tensor belongs to the object: the next call of the same shape overwrites it."""
@@ -215,11 +187,11 @@ class RMVPEHIP:
         with torch.cuda.device(self.device):
             ws, T = self._mel(x)
             B, T_pad = int(ws["mel"].shape[0]), int(ws["mel"].shape[1])
-            st = self._stream()
-            _lib.check(L.rvcmi_unet_forward(self.unet._h, B, T_pad, _ptr(ws["mel"]), _ptr(ws["feat"]), _ptr(ws["unet"]), st))
+            st = _lib.stream_ptr(self.device)
+            _lib.check(L.rvcmi_unet_forward(self.unet._h, B, T_pad, _lib.ptr(ws["mel"]), _lib.ptr(ws["feat"]), _lib.ptr(ws["unet"]), st))
             ws["x16"].copy_(ws["feat"])  # the fp32 -> fp16 cast GRUHIP.forward makes
-            _lib.check(L.rvcmi_gru_forward(self.gru._h, B, T_pad, _ptr(ws["x16"]), _ptr(ws["y"]), None, st))
-            _lib.check(L.rvcmi_rmvpe_head(_ptr(ws["y"]), B * T_pad, _ptr(self._w), _ptr(self._b), 1 if self.is_half else 0, _ptr(ws["sal"]), st))
+            _lib.check(L.rvcmi_gru_forward(self.gru._h, B, T_pad, _lib.ptr(ws["x16"]), _lib.ptr(ws["y"]), None, st))
+            _lib.check(L.rvcmi_rmvpe_head(_lib.ptr(ws["y"]), B * T_pad, _lib.ptr(self._w), _lib.ptr(self._b), 1 if self.is_half else 0, _lib.ptr(ws["sal"]), st))
         return ws["sal"], T
 
     def mel(self, wav: torch.Tensor) -> torch.Tensor:
@@ -273,17 +245,17 @@ class RMVPEHIP:
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             y = torch.empty(R, 2 * self.gru.hidden_size, device=dev, dtype=f32)
             sal = torch.empty(R, N_CLASS, device=dev, dtype=f32)
-            st, half = self._stream(), 1 if self.is_half else 0
+            st, half = _lib.stream_ptr(self.device), 1 if self.is_half else 0
             for i, x in enumerate(xs):
-                _lib.check(L.rvcmi_mel_forward(self._h, 1, int(x.shape[1]), _ptr(x), half, off[i + 1] - off[i],
+                _lib.check(L.rvcmi_mel_forward(self._h, 1, int(x.shape[1]), _lib.ptr(x), half, off[i + 1] - off[i],
                                                C.c_void_p(mel.data_ptr() + 4 * N_MELS * off[i]), st))
             mark("mel")
-            _lib.check(L.rvcmi_unet_forward_ragged(self.unet._h, nseq, off_host, _ptr(off_dev), _ptr(mel), _ptr(feat), _ptr(ws), st))
+            _lib.check(L.rvcmi_unet_forward_ragged(self.unet._h, nseq, off_host, _lib.ptr(off_dev), _lib.ptr(mel), _lib.ptr(feat), _lib.ptr(ws), st))
             mark("unet")
             x16 = feat.half()  # the fp32 -> fp16 cast GRUHIP.forward makes
-            _lib.check(L.rvcmi_gru_forward_ragged(self.gru._h, nseq, off_host, _ptr(off_dev), _ptr(x16), _ptr(y), None, st))
+            _lib.check(L.rvcmi_gru_forward_ragged(self.gru._h, nseq, off_host, _lib.ptr(off_dev), _lib.ptr(x16), _lib.ptr(y), None, st))
             mark("gru")
-            _lib.check(L.rvcmi_rmvpe_head(_ptr(y), R, _ptr(self._w), _ptr(self._b), half, _ptr(sal), st))
+            _lib.check(L.rvcmi_rmvpe_head(_lib.ptr(y), R, _lib.ptr(self._w), _lib.ptr(self._b), half, _lib.ptr(sal), st))
             mark("head")
         return sal, off, frames
 

@@ -17,7 +17,6 @@ BatchNorm / ReLU / residual epilogues fp32.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import re
 from typing import Dict, Optional, Tuple
 
@@ -29,9 +28,7 @@ N_MELS = 128
 RMVPE_UNET = False  # install(rmvpe_unet=True) sets it; RVCMI_RMVPE_UNET=1 / =0 overrides it per call
 
 
-def unet_on() -> bool:
-    env = os.environ.get("RVCMI_RMVPE_UNET")
-    return env == "1" if env in ("0", "1") else bool(RMVPE_UNET)
+unet_on = _lib.Switch("RVCMI_RMVPE_UNET", globals(), "RMVPE_UNET").on
 
 
 def _unit_keys(p: str, cin: int, cout: int, out: Dict[str, Tuple[int, ...]]) -> None:
@@ -120,27 +117,15 @@ class UNetHIP(torch.nn.Module):
 
     def __init__(self, state_dict, device):
         super().__init__()
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.RvcmiError("UNetHIP needs a GPU device (got %s); there is no CPU fallback" % dev)
-        dev = torch.device("cuda", _lib.device_index(dev))
-        keep = []
-        for k, v in state_dict.items():
-            if (k.startswith("unet.") or k.startswith("cnn.")) and torch.is_tensor(v) and v.is_floating_point() and 1 <= v.dim() <= 4:
-                keep.append((k, v.detach().float().cpu().contiguous()))
-        if not keep:
+        dev = _lib.cuda_device(device, "UNetHIP")
+        arr = _lib.pack_tensors((k, v.detach().float().cpu().contiguous()) for k, v in state_dict.items()
+                                if k.startswith(("unet.", "cnn.")) and torch.is_tensor(v) and v.is_floating_point() and 1 <= v.dim() <= 4)
+        if not len(arr):
             raise _lib.RvcmiError("UNetHIP: no 'unet.' / 'cnn.' weights in the state dict", code=_lib.ERR_INVALID)
-        arr = (_lib.Tensor * len(keep))()
-        for i, (k, v) in enumerate(keep):
-            arr[i].name = k.encode()
-            arr[i].data = v.data_ptr()
-            arr[i].ndim = v.dim()
-            for j, s in enumerate(v.shape):
-                arr[i].shape[j] = int(s)
         h = C.c_void_p()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rvcmi_unet_create(arr, len(keep), dev.index, C.byref(h)))
-        self._h = h
+            _lib.check(_lib.lib().rvcmi_unet_create(arr, len(arr), dev.index, C.byref(h)))
+        self._h = _lib.Handle("rvcmi_unet_destroy", h)
         self._device = dev
         self.head_channels = int(_lib.lib().rvcmi_unet_head_channels(h))
         self.geometry = geometry({k: tuple(v.shape) for k, v in state_dict.items() if torch.is_tensor(v)})
@@ -149,22 +134,11 @@ class UNetHIP(torch.nn.Module):
     def from_state_dict(cls, sd, device) -> "UNetHIP":
         return cls(sd, device)
 
-    def __del__(self):
-        h = self.__dict__.pop("_h", None)  # (not through nn.Module.__setattr__: it may be gone at interpreter shutdown)
-        if h:
-            try:
-                _lib.lib().rvcmi_unet_destroy(h)
-            except Exception:  # noqa  (interpreter shutdown)
-                pass
-
     def workspace_bytes(self, B: int, T: int) -> int:
         return int(_lib.lib().rvcmi_unet_workspace_bytes(self._h, int(B), int(T)))
 
     def forward(self, mel: torch.Tensor) -> torch.Tensor:
-        if not torch.is_tensor(mel) or mel.device.type != "cuda":
-            raise _lib.RvcmiError("UNetHIP input must live on the GPU (got %s); there is no CPU fallback" % getattr(mel, "device", type(mel)))
-        if mel.device != self._device:
-            raise _lib.RvcmiError("UNetHIP: the input is on %s, the weights on %s" % (mel.device, self._device))
+        _lib.require_on(mel, self._device, "UNetHIP")
         if mel.dim() != 4 or mel.shape[1] != 1 or mel.shape[3] != N_MELS or not mel.is_floating_point():
             raise _lib.RvcmiError("UNetHIP: expected a float [B, 1, T, %d], got %s %s" % (N_MELS, mel.dtype, tuple(mel.shape)), code=_lib.ERR_INVALID)
         B, T = int(mel.shape[0]), int(mel.shape[2])
@@ -176,8 +150,7 @@ class UNetHIP(torch.nn.Module):
         out = torch.empty(B, T, self.head_channels, N_MELS, device=mel.device, dtype=torch.float32)
         ws = torch.empty(nbytes, device=mel.device, dtype=torch.uint8)  # torch's caching allocator: no hipMalloc inside a capture
         with torch.cuda.device(mel.device):
-            _lib.check(_lib.lib().rvcmi_unet_forward(self._h, B, T, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                                     C.c_void_p(torch.cuda.current_stream(mel.device).cuda_stream)))
+            _lib.check(_lib.lib().rvcmi_unet_forward(self._h, B, T, _lib.ptr(x), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr(mel.device)))
         return out.to(mel.dtype).permute(0, 2, 1, 3)
 
 

@@ -446,6 +446,159 @@ def test_install_rebinds_names_without_editing_the_callers():
             del sys.modules[m]
 
 
+def _switch_globals():
+    """(module, global, default) of every opt-in ``install()`` sets."""
+    from rvc_amd import hubert, pipeline, rmvpe, synthesizer, unet
+
+    return [(pipeline, "DEVICE_PREP", False), (unet, "RMVPE_UNET", False), (rmvpe, "RMVPE_HIP", False), (hubert, "HUBERT_FE", False),
+            (hubert, "HUBERT_BATCH", False), (hubert, "HUBERT_ENC", False), (synthesizer, "FRONT_OPERAND", None)]
+
+
+def test_install_then_uninstall_leaves_every_switch_at_its_default():
+    """On the skeleton tree: install() with every opt-in on sets each module global, uninstall() puts each default back, and the table the
+    two walk covers exactly the globals listed here."""
+    import sys
+
+    inst = sys.modules["rvc_amd.install"]  # (the package's attribute of that name is the function)
+    skel = os.path.join(os.path.dirname(os.path.abspath(__file__)), "skeleton")
+    for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "infer")]:
+        del sys.modules[m]
+    sys.path.insert(0, skel)
+    try:
+        import rvc.synthesizer  # noqa  (the plug-in boundary install() imports)
+
+        assert sorted((m, g) for m, g, _a, _d in inst._SWITCHES) == sorted((mod.__name__.split(".")[-1], g) for mod, g, _d in _switch_globals())
+        assert all(getattr(mod, g) is d for mod, g, d in _switch_globals())
+        rvc_amd.install(patch_faiss=False, device_prep=True, rmvpe_unet=True, rmvpe_hip=True, hubert_fe=True, hubert_batch=True, hubert_enc=True,
+                        front_operand="fp16x2")
+        assert [getattr(mod, g) for mod, g, _d in _switch_globals()] == [True] * 6 + ["fp16x2"]
+        rvc_amd.uninstall()
+        assert all(getattr(mod, g) is d for mod, g, d in _switch_globals())
+        with pytest.raises(ValueError):  # raises before anything is rebound: the switches stay as they were
+            rvc_amd.install(patch_faiss=False, hubert_fe=True, front_operand="fp64")
+        assert all(getattr(mod, g) is d for mod, g, d in _switch_globals())
+    finally:
+        rvc_amd.uninstall()
+        sys.path.remove(skel)
+        for m in [m for m in sys.modules if m.split(".")[0] in ("rvc", "infer")]:
+            del sys.modules[m]
+
+
+def test_switch_env_overrides_the_global_and_anything_else_is_ignored(monkeypatch):
+    """The semantics of the six switch functions: ``"1"`` / ``"0"`` in the environment override the module global, any other value is
+    ignored, the global (what install() sets) decides otherwise; a batch switch is effective only together with its base."""
+    from rvc_amd import hubert, pipeline, rmvpe, unet
+
+    for mod, name, env, fn in ((hubert, "HUBERT_FE", "RVCMI_HUBERT_FE", "hubert_on"), (hubert, "HUBERT_ENC", "RVCMI_HUBERT_ENC", "hubert_enc_on"),
+                               (unet, "RMVPE_UNET", "RVCMI_RMVPE_UNET", "unet_on"), (rmvpe, "RMVPE_HIP", "RVCMI_RMVPE_HIP", "rmvpe_on"),
+                               (pipeline, "DEVICE_PREP", "RVCMI_DEVICE_PREP", "_device_prep_on")):
+        on = lambda: getattr(mod, fn)()  # noqa: E731  (looked up per call, as the callers do)
+        monkeypatch.delenv(env, raising=False)
+        assert on() is False
+        monkeypatch.setattr(mod, name, True)
+        assert on() is True
+        for v, want in (("0", False), ("1", True), ("", True), ("yes", True), ("2", True)):
+            monkeypatch.setenv(env, v)
+            assert on() is want, (env, v)
+        monkeypatch.setattr(mod, name, False)
+        for v, want in (("0", False), ("1", True), ("", False), ("true", False)):
+            monkeypatch.setenv(env, v)
+            assert on() is want, (env, v)
+        monkeypatch.delenv(env)
+    for mod, base, name, env_base, env, fn in ((hubert, "HUBERT_FE", "HUBERT_BATCH", "RVCMI_HUBERT_FE", "RVCMI_HUBERT_BATCH", "hubert_batch_on"),
+                                               (rmvpe, "RMVPE_HIP", "RMVPE_BATCH", "RVCMI_RMVPE_HIP", "RVCMI_RMVPE_BATCH", "rmvpe_batch_on")):
+        on = lambda: getattr(mod, fn)()  # noqa: E731
+        monkeypatch.setattr(mod, name, True)
+        assert on() is False  # the base is off
+        monkeypatch.setenv(env_base, "1")
+        assert on() is True
+        monkeypatch.setenv(env, "0")
+        assert on() is False
+        monkeypatch.setenv(env, "1")
+        monkeypatch.setenv(env_base, "0")
+        assert on() is False
+        monkeypatch.delenv(env_base)
+        monkeypatch.delenv(env)
+        monkeypatch.setattr(mod, base, True)
+        assert on() is True
+        monkeypatch.setattr(mod, name, False)
+        assert on() is False
+    # .value is the module global, both ways
+    sw = _lib.Switch("RVCMI_TEST_SWITCH", vars(hubert), "HUBERT_ENC")
+    assert sw.value is False
+    monkeypatch.setattr(hubert, "HUBERT_ENC", True)
+    assert sw.value is True and sw.on()
+    sw.value = False
+    assert hubert.HUBERT_ENC is False and not hubert.hubert_enc_on()
+
+
+def test_pack_tensors_round_trips_and_keeps_its_inputs_alive():
+    import gc
+
+    sd = {"a.weight": torch.arange(24, dtype=torch.float32).reshape(2, 3, 4), "b.bias": torch.ones(5), "c": torch.zeros(1, 2, 3, 4), "s": torch.tensor(2.0)}
+    want = [(k, tuple(v.shape), v.flatten().tolist()) for k, v in sd.items()]
+    arr = _lib.pack_tensors(sd.items())
+    del sd
+    gc.collect()
+    junk = [torch.full((24,), -1.0) for _ in range(64)]  # (would land in freed storage if the array did not hold the tensors)
+    assert len(arr) == len(want) and isinstance(arr[0], _lib.Tensor)
+    for a, (k, shape, vals) in zip(arr, want):
+        assert a.name == k.encode() and a.ndim == len(shape) and tuple(a.shape[:a.ndim]) == shape and all(s == 0 for s in a.shape[a.ndim:])
+        got = C.cast(a.data, C.POINTER(C.c_float * len(vals))).contents
+        assert list(got) == vals
+    assert [t.data_ptr() for _kb, t in arr.keep] == [a.data for a in arr]
+    del junk
+    assert len(_lib.pack_tensors([])) == 0
+    for bad in (torch.zeros(2, dtype=torch.float64), torch.zeros(4, 4).t(), torch.zeros(1, 1, 1, 1, 1)):
+        with pytest.raises(ValueError, match="'x'"):
+            _lib.pack_tensors([("x", bad)])
+
+
+def test_handle_closes_once_and_passes_as_its_pointer(monkeypatch):
+    import types
+
+    calls = []
+    monkeypatch.setattr(_lib, "lib", lambda: types.SimpleNamespace(rvcmi_stub_destroy=lambda p: calls.append(p.value)))
+    h = _lib.Handle("rvcmi_stub_destroy", C.c_void_p(0x1234))
+    assert h and C.c_void_p.from_param(h).value == 0x1234  # what ctypes does with an argument declared c_void_p
+    h.close()
+    h.close()
+    assert calls == [0x1234] and not h and C.c_void_p.from_param(h).value is None
+    del h
+    assert calls == [0x1234]
+    h = _lib.Handle("rvcmi_stub_destroy", C.c_void_p(0x5678))
+    del h  # collected while open: destroyed once
+    assert calls == [0x1234, 0x5678]
+    assert not _lib.Handle("rvcmi_stub_destroy", C.c_void_p(None))
+    monkeypatch.setattr(_lib, "lib", None)  # interpreter shutdown: the module's names are gone
+    h = _lib.Handle("rvcmi_stub_destroy", C.c_void_p(0x9))
+    del h  # must not raise (pytest turns an exception in __del__ into a warning-as-error under -W error; here it simply must stay silent)
+    assert calls == [0x1234, 0x5678]
+
+
+def test_input_checks_keep_their_texts():
+    """What a caller sees for a CPU tensor: the handles' text and the stateless entry points' text, both as before the helpers."""
+    from rvc_amd import glue
+
+    x = torch.zeros(4, 768)
+    with pytest.raises(_lib.RvcmiError, match=r"^HubertFrontHIP input must live on the GPU \(got cpu\); there is no CPU fallback$"):
+        _lib.require_on(x, torch.device("cuda", 0), "HubertFrontHIP")
+    with pytest.raises(_lib.RvcmiError, match=r"^feats must live on the GPU \(got cpu\); the glue has no CPU fallback$"):
+        glue.retrieve_blend_expand(x[None], None, 0.5)
+    with pytest.raises(_lib.RvcmiError, match=r"^GRUHIP needs a GPU device \(got cpu\); there is no CPU fallback$"):
+        _lib.cuda_device("cpu", "GRUHIP")
+
+
+def test_once_runs_its_function_once_per_object():
+    class Obj:
+        pass
+
+    o, n = Obj(), []
+    assert _lib.once(o, "_count", lambda: n.append(1) or 3) == 3 and _lib.once(o, "_count", lambda: n.append(1) or 4) == 3
+    assert n == [1] and o._count == 3
+    assert _lib.once(object(), "_count", lambda: 5) == 5  # nowhere to remember it: the value still comes back
+
+
 def test_bf16_operands_warn_before_anything_else():
     """operand='bf16' misses the 1e-3 bar: constructing with it warns -- even where the constructor then
     fails for lack of a GPU."""

@@ -312,6 +312,29 @@ def test_a_graph_captured_before_the_workspace_grew_still_replays(gpu):
     del graph
 
 
+def test_forward_refuses_a_cpu_input(gpu):
+    import rvc_amd
+
+    m = rvc_amd.GRUHIP(gc.module(gc.Case(1, 4, 384, 17)), device=gpu)
+    assert m._device == torch.device("cuda", torch.device(gpu).index if torch.device(gpu).index is not None else torch.cuda.current_device())
+    with pytest.raises(rvc_amd.RvcmiError, match="must live on the GPU"):
+        m(torch.zeros(1, 4, 384))
+    y, hn = m(torch.zeros(1, 4, 384, device=gpu))  # the handle goes on working
+    assert tuple(y.shape) == (1, 4, 512) and tuple(hn.shape) == (2, 1, 256) and bool(torch.isfinite(y).all())
+
+
+def test_forward_refuses_an_input_on_another_gpu(gpu):
+    """(A launch on the handle's device with a foreign stream and foreign pointers otherwise.)"""
+    import rvc_amd
+
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one GPU: no second device to hold the foreign input")
+    m = rvc_amd.GRUHIP(gc.module(gc.Case(1, 4, 384, 17)), device=gpu)
+    other = (m._device.index + 1) % torch.cuda.device_count()
+    with pytest.raises(rvc_amd.RvcmiError, match="the input is on cuda:%d, the weights on %s" % (other, m._device)):
+        m(torch.zeros(1, 4, 384, device="cuda:%d" % other))
+
+
 def test_gru_forward_rejects_more_sequences_than_the_grid_has_rows(gpu):
     """B > 65535 (grid y of one block per (direction, sequence)) is an argument error, found before the workspace is touched; the handle goes on
     working."""

@@ -129,6 +129,49 @@ def test_graph_captured_after_a_larger_eager_call_replays_bit_equal(gpu):
     assert torch.equal(y, fresh(xs))
 
 
+def test_a_graph_captured_before_the_workspace_grew_still_replays(gpu):
+    """The handle keeps the workspace it outgrows (``GrowBuf``): a forward captured at N = 800 on the handle's own workspace must replay unchanged
+    after an eager call at N = 4000 has replaced it.  The replay against an eager call on a second, fresh handle."""
+    import rvc_amd
+
+    sd = hc.state_dict(hc.weights(72), "fairseq")
+    hip = rvc_amd.HubertFrontHIP.from_state_dict(sd, gpu)  # (its own handle: the shared ones already hold larger workspaces)
+    g = torch.Generator().manual_seed(73)
+    static = torch.randn(1, 800, generator=g).to(gpu)
+    side = torch.cuda.Stream(gpu)
+    side.wait_stream(torch.cuda.current_stream(gpu))
+    with torch.cuda.stream(side):
+        hip(static)  # warm-up: the workspace is allocated here, outside the capture
+    torch.cuda.current_stream(gpu).wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        y_static = hip(static)
+    big = hip(torch.randn(1, 4000, generator=g).to(gpu))  # the workspace grows, outside any capture
+    torch.cuda.synchronize()
+    assert tuple(big.shape) == (1, 512, hc.frames(4000)) and bool(torch.isfinite(big).all())
+    x_new = torch.randn(1, 800, generator=g).to(gpu)
+    static.copy_(x_new)
+    graph.replay()
+    torch.cuda.synchronize()
+    y_want = rvc_amd.HubertFrontHIP.from_state_dict(sd, gpu)(x_new)
+    torch.cuda.synchronize()
+    assert tuple(y_static.shape) == (1, 512, 2) and torch.equal(y_static, y_want), "the replay after the growth differs from an eager call"
+    del graph
+
+
+def test_workspace_sizes_are_those_of_the_planner_before_the_shared_carve(gpu):
+    """``rvcmi_hubert_fe_workspace_bytes`` is ABI-visible.  The numbers are the offset planner's arithmetic worked by hand from the layer row
+    counts (each part rounded up to 256 bytes: two fp16 activation buffers, the fp64 partial statistics, mean filter, scale, shift)."""
+    from rvc_amd import _lib
+
+    hip = _hip(gpu, 70)
+    L = _lib.lib()
+    assert L.rvcmi_hubert_fe_workspace_bytes(hip._h, 1, 400) == 125952
+    assert L.rvcmi_hubert_fe_workspace_bytes(hip._h, 2, 16000) == 9837056
+    assert L.rvcmi_hubert_fe_workspace_bytes_ragged(hip._h, 3, 4000) == 3694592
+
+
 # ---------------------------------------------------------------- the module swap
 
 def _hf_model(gpu, **cfg):

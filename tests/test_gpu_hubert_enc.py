@@ -46,6 +46,21 @@ def test_one_layer_against_the_oracle(c):
     check(y.float().cpu().numpy(), hc.bars(c), hc.case_id(c))
 
 
+def test_workspace_sizes_are_those_of_the_planner_before_the_shared_carve():
+    """``rvcmi_hubert_enc_workspace_bytes`` is ABI-visible.  The numbers are the offset planner's arithmetic worked by hand for M = B T rows:
+    q / k / v (3 M d fp16), attention (M d fp16), the stream fp32 and fp16, the GELU output (M ffn fp16), two fp32 hand-over buffers, each
+    part rounded up to 256 bytes."""
+    base = encoder("base", 1)
+    assert (base.workspace_bytes(1, 1), base.workspace_bytes(2, 77)) == (23040, 3548160)
+    names = {"self_attn.q_proj": (64, 64), "self_attn.k_proj": (64, 64), "self_attn.v_proj": (64, 64), "self_attn.out_proj": (64, 64),
+             "self_attn_layer_norm": (64,), "fc1": (64, 64), "fc2": (64, 64), "final_layer_norm": (64,)}
+    sd = {}
+    for n, shape in names.items():
+        sd[n + ".weight"], sd[n + ".bias"] = torch.zeros(shape), torch.zeros(shape[0])
+    tiny = rvc_amd.HubertEncoderHIP.from_state_dicts([sd], dict(d=64, heads=1, ffn=64, eps=hc.EPS), DEV)
+    assert (tiny.workspace_bytes(1, 1), tiny.workspace_bytes(2, 77)) == (2048, 236544)
+
+
 @pytest.mark.parametrize("c", hc.STAGE_CASES, ids=hc.case_id)
 def test_gelu_output_against_the_oracle(c):
     """FFN-2's operand, read from the caller's workspace: where a wrong GELU would show (tests/hubert_enc_cases.py)."""

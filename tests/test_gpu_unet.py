@@ -230,6 +230,22 @@ def test_two_forwards_are_bit_identical(gpu):
         assert torch.equal(a, b), "T = %d" % T
 
 
+def test_workspace_sizes_are_those_of_the_planner_before_the_shared_carve(gpu):
+    """``rvcmi_unet_workspace_bytes`` is ABI-visible.  The numbers are the full network's (5 levels, 4 units, 4 intermediate layers, base 16)
+    worked by hand from the dry run's arithmetic: four full-size fp16 buffers, one skip tensor per level, then the largest split-K
+    partial buffer, each part rounded up to 256 bytes.  Sizes depend on the row count only: (2, 64) and the packed [32, 96] agree."""
+    import ctypes as C
+
+    import rvc_amd
+    from rvc_amd import _lib
+
+    hip = rvc_amd.UNetHIP.from_state_dict(uc.seeded_weights(uc.golden_keys(), 1), gpu)
+    L = _lib.lib()
+    assert L.rvcmi_unet_workspace_bytes(hip._h, 1, 32) == hip.workspace_bytes(1, 32) == 1368064
+    assert L.rvcmi_unet_workspace_bytes(hip._h, 2, 64) == 5472256
+    assert L.rvcmi_unet_workspace_bytes_ragged(hip._h, 2, (C.c_int * 3)(0, 32, 128)) == 5472256
+
+
 # ---------------------------------------------------------------- swap, graph, errors
 
 def _standin(gpu, seed=11, half=False, keys=None, **kw):

@@ -70,9 +70,9 @@ def main():
 
         def kernels():
             e0.record()
-            rvc_amd._lib.check(L.rvcmi_glue_cut_points(rvc_amd.glue._ptr(a64), audio.shape[0], 160, state.t_center, state.t_query,
-                                                       rvc_amd.glue._ptr(cuts), ncuts, None, rvc_amd.glue._ptr(scratch),
-                                                       rvc_amd.glue._stream(dev)))
+            rvc_amd._lib.check(L.rvcmi_glue_cut_points(rvc_amd._lib.ptr(a64), audio.shape[0], 160, state.t_center, state.t_query,
+                                                       rvc_amd._lib.ptr(cuts), ncuts, None, rvc_amd._lib.ptr(scratch),
+                                                       rvc_amd._lib.stream_ptr(dev)))
             e1.record()
             e1.synchronize()
             return cuts.tolist(), e0.elapsed_time(e1)

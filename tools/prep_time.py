@@ -128,8 +128,8 @@ def main():
 
         def kernels():
             e0.record()
-            rvc_amd._lib.check(L.rvcmi_glue_filtfilt(glue._ptr(flat), 0, glue._ptr(offsets), B, max(lens), total, d(bn), d(an), d(zi), order, warm,
-                                                     glue._ptr(out), glue._ptr(out_pad), pad, glue._ptr(scratch), nbytes, glue._stream(dev)))
+            rvc_amd._lib.check(L.rvcmi_glue_filtfilt(rvc_amd._lib.ptr(flat), 0, rvc_amd._lib.ptr(offsets), B, max(lens), total, d(bn), d(an), d(zi), order, warm,
+                                                     rvc_amd._lib.ptr(out), rvc_amd._lib.ptr(out_pad), pad, rvc_amd._lib.ptr(scratch), nbytes, rvc_amd._lib.stream_ptr(dev)))
             e1.record()
             e1.synchronize()
             return None, e0.elapsed_time(e1)
