@@ -6,6 +6,9 @@
     sizes, against the functional evaluator of tests/unet_cases.py in fp32 on the CPU.  Tolerance: measured each run, not fixed -- torch's own
     ``.half()`` evaluation of the same network on the GPU (what the reference runs with ``is_half``) has an RMS and a max-abs error against
     that fp32 result; the HIP path's may be at most TWICE those (a different summation order, fp16 storage of the skip tensors);
+  * every primitive of the full network on its own, fed the fp16 operands of the fp64 oracle with the kernel's rounding points
+    (oracle/unet_oracle.py), against the elementwise bound and the flip share of tests/unet_cases.py; the skip tensors and the output of whole
+    forwards against the same oracle at bars derived on the CPU (tests/test_cpu_unet.py);
   * determinism, the module swap, the realtime graph capture with the swap on, and the errors.
 """
 import ctypes as C
@@ -40,36 +43,7 @@ def _ints(g, shape, lo, hi):
     return torch.randint(lo, hi + 1, shape, generator=g).float()
 
 
-def _nhwc16(x, gpu):
-    return x.permute(0, 2, 3, 1).contiguous().to(gpu, torch.float16)
-
-
-def _op(gpu, kind, x0, x1, res, w, scale, shift, relu, cout, out_shape, ksplit=0, in_scale=1.0, in_shift=0.0, head=False):
-    """One primitive through ``rvcmi_unet_debug_op``; tensors in torch's NCHW fp32 on the CPU -> the result as NCHW fp32 on the CPU."""
-    from rvc_amd import _lib
-
-    B, _, H, W = x0.shape
-    one = kind in (4, 5)
-    d0 = x0[:, 0].contiguous().to(gpu) if one else _nhwc16(x0, gpu)
-    d1 = _nhwc16(x1, gpu) if x1 is not None else None
-    dr = _nhwc16(res, gpu) if res is not None else None
-    if head:
-        out = torch.full((B, H, cout, W), float("nan"), device=gpu, dtype=torch.float32)
-    else:
-        out = torch.full((out_shape[0], out_shape[2], out_shape[3], out_shape[1]), float("nan"), device=gpu, dtype=torch.float16)
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    wf = w.contiguous() if w is not None else None
-    sc = scale.contiguous() if scale is not None else None
-    sh = shift.contiguous() if shift is not None else None
-    _lib.check(_lib.lib().rvcmi_unet_debug_op(kind, B, H, W, 1 if one else x0.shape[1], x1.shape[1] if x1 is not None else 0, cout, ptr(wf), ptr(sc), ptr(sh),
-                                              int(relu), in_scale, in_shift, ptr(d0), ptr(d1), ptr(dr), ptr(out), ksplit, 0,
-                                              C.c_void_p(torch.cuda.current_stream(gpu).cuda_stream)))
-    torch.cuda.synchronize()
-    o = out.cpu()
-    return o.permute(0, 2, 1, 3).float() if head else o.permute(0, 3, 1, 2).float()
+_op = uc.debug_op  # one primitive through ``rvcmi_unet_debug_op``: NCHW fp32 on the CPU in, NCHW fp32 on the CPU out
 
 
 def _epilogue(y, scale, shift, relu, res):
@@ -87,10 +61,15 @@ def _same(got, want_fp32, what):
     assert torch.equal(got, want), "%s: %d of %d values differ, max |d| %.4g" % (what, int((got != want).sum()), got.numel(), float((got - want).abs().max()))
 
 
-@pytest.mark.parametrize("C,H,W,ksplit", [(16, 5, 7, 0), (32, 9, 6, 0), (64, 5, 7, 0), (64, 3, 4, 3), (512, 3, 4, 0), (512, 3, 4, 1), (512, 1, 4, 7)])
+@pytest.mark.parametrize("C,H,W,ksplit", [(16, 5, 7, 0), (32, 9, 6, 0), (64, 5, 7, 0), (64, 3, 4, 3), (512, 3, 4, 0), (512, 3, 4, 1), (512, 1, 4, 7),
+                                          (16, 5, 7, 1), (32, 9, 6, 1), (64, 5, 7, 1), (16, 5, 14, 0), (16, 5, 14, 1), (32, 5, 14, 0), (32, 5, 14, 1),
+                                          (128, 3, 4, 0), (128, 3, 4, 1), (256, 3, 4, 0), (256, 3, 4, 1)])
 def test_conv3x3_is_exact(C, H, W, ksplit, gpu):
     """3x3 convolution + scale / shift + ReLU + residual (added AFTER the ReLU), B = 2, borders in both axes, tiles that do not divide the
-    pixel count; the 512-channel cases with the forward's own K split, without one, and with an uneven one."""
+    pixel count; the 512-channel cases with the forward's own K split, without one, and with an uneven one.  ``ksplit=1``: the fused epilogue
+    with its residual inside k_unet_conv<1, 1> / <2, 1> / <2, 2> (at these sizes the forward's own choice, 0, is always a split for a 3x3 layer);
+    W = 14: 140 pixels, two blocks along the pixels for C = 16 and 32, the second one partial; C = 128 / 256: two / four blocks along the
+    channels."""
     g = torch.Generator().manual_seed(C + 7 * H + ksplit)
     x, w, res = _ints(g, (2, C, H, W), -3, 3), _ints(g, (C, C, 3, 3), -2, 2), _ints(g, (2, C, H, W), -4, 4)
     scale, shift = 2.0 ** -_ints(g, (C,), 3, 5), _ints(g, (C,), -3, 3)
@@ -114,9 +93,11 @@ def test_first_layer_applies_the_input_batchnorm_before_the_zero_padding(gpu):
     _same(_op(gpu, 5, x, None, None, w1, torch.ones(16), b1, False, 16, want1.shape, in_scale=0.5, in_shift=3.0), want1, "first 1x1")
 
 
-@pytest.mark.parametrize("C0,C1,Cout,k", [(32, 0, 16, 1), (16, 16, 16, 1), (64, 64, 64, 3), (16, 16, 16, 3), (256, 256, 256, 1)])
+@pytest.mark.parametrize("C0,C1,Cout,k", [(32, 0, 16, 1), (16, 16, 16, 1), (64, 64, 64, 3), (16, 16, 16, 3), (256, 256, 256, 1),
+                                          (48, 48, 48, 3), (48, 48, 48, 1)])
 def test_shortcut_and_two_source_read_are_exact(C0, C1, Cout, k, gpu):
-    """The 1x1 shortcut with its bias, and a convolution over cat(a, b) read from the two tensors in place."""
+    """The 1x1 shortcut with its bias, and a convolution over cat(a, b) read from the two tensors in place.  48 + 48: the second 32-channel
+    chunk of K straddles the two tensors."""
     g = torch.Generator().manual_seed(C0 + C1 + k)
     a = _ints(g, (2, C0, 5, 6), -3, 3)
     b = _ints(g, (2, C1, 5, 6), -3, 3) if C1 else None
@@ -135,9 +116,11 @@ def test_pool_is_exact(gpu):
     _same(_op(gpu, 3, x, None, None, None, None, None, False, 48, want.shape), want, "pool")
 
 
-@pytest.mark.parametrize("Cin,Cout,H,W,ksplit", [(32, 16, 3, 5, 0), (64, 32, 4, 4, 1), (512, 256, 1, 4, 0), (128, 64, 2, 3, 5)])
+@pytest.mark.parametrize("Cin,Cout,H,W,ksplit", [(32, 16, 3, 5, 0), (64, 32, 4, 4, 1), (512, 256, 1, 4, 0), (128, 64, 2, 3, 5),
+                                                 (32, 16, 3, 1, 0), (64, 32, 2, 1, 1)])
 def test_transposed_convolution_is_exact(Cin, Cout, H, W, ksplit, gpu):
-    """ConvTranspose2d(3x3, stride 2, padding 1, output_padding 1), weight [Cin, Cout, 3, 3], as four output phases + scale / shift + ReLU."""
+    """ConvTranspose2d(3x3, stride 2, padding 1, output_padding 1), weight [Cin, Cout, 3, 3], as four output phases + scale / shift + ReLU.
+    W = 1: every tap at x + 1 falls outside the image."""
     g = torch.Generator().manual_seed(Cin + H)
     x, w = _ints(g, (2, Cin, H, W), -3, 3), _ints(g, (Cin, Cout, 3, 3), -2, 2)
     scale, shift = 2.0 ** -_ints(g, (Cout,), 2, 4), _ints(g, (Cout,), -2, 2)
@@ -153,6 +136,52 @@ def test_head_writes_the_gru_layout_exactly(gpu):
     want = F.conv2d(x, w, bias, padding=1)
     got = _op(gpu, 6, x, None, None, w, torch.ones(3), bias, False, 3, want.shape, head=True)
     assert torch.equal(got, want)
+
+
+# ---------------------------------------------------------------- every layer against the fp16-operand fp64 oracle
+
+@pytest.mark.parametrize("ksplit", [0, 1])
+def test_every_primitive_teacher_forced_against_the_oracle(ksplit, gpu):
+    """Every primitive of the full network at (B, T) = (2, 32) -- both first-layer kernels, 3x3, 1x1, two-source reads, the five transposed
+    convolutions, the five pools, the head -- fed the oracle's own fp16 operands, so that nothing has cascaded, against the unrounded fp64
+    result: the elementwise bound and the flip share of tests/unet_cases.py (derived on the CPU, tests/test_cpu_unet.py).  Once with the
+    forward's own K split at this size, once with the fused epilogue that long inputs run."""
+    trace = uc.sweep_trace()
+    assert len(trace) == 134
+    bad, worst_flips, worst_excess = [], 0.0, 0.0
+    for rec in trace:
+        got = uc.run_record(gpu, rec, ksplit)
+        if not torch.isfinite(got).all():
+            bad.append("%s: non-finite output" % rec["name"])
+            continue
+        ck = uc.prim_check(got, rec)
+        worst_flips, worst_excess = max(worst_flips, ck["flips"]), max(worst_excess, ck["excess"])
+        if ck["violations"] or ck["flips"] > uc.FLIP_CAP:
+            bad.append("%s (kind %d, %s): %d of %d outside the elementwise bound, flip share %.3e, excess %.3e A" % (
+                rec["name"], rec["kind"], tuple(rec["y"].shape), ck["violations"], ck["n"], ck["flips"], ck["excess"]))
+    print("unet sweep ksplit=%d: largest flip share %.3e (cap %.0e), largest excess %.3e A (gamma %.3e)" % (ksplit, worst_flips, uc.FLIP_CAP, worst_excess,
+                                                                                                          uc.GAMMA))
+    assert not bad, "%d of %d primitives:\n%s" % (len(bad), len(trace), "\n".join(bad))
+
+
+@pytest.mark.parametrize("case", uc.WHOLE, ids=uc.case_id)
+def test_whole_network_and_skips_against_the_rounded_oracle(case, gpu):
+    """``rvcmi_unet_forward`` with the test's own workspace: the skip tensors it leaves there (``uc.skip_offsets``) and the head's output against
+    the fp64 oracle with the kernel's rounding points, at the derived bars.  What the per-primitive sweep cannot see is held to account here:
+    ``Loader::bn``, the weights' packing at create time, the buffer rotation of ``run()``."""
+    want = uc.whole_case(case)
+    got = uc.run_whole(gpu, case)
+    assert sorted(got) == sorted(want)
+    bad = []
+    for k in sorted(want):
+        b = want[k]
+        assert got[k].shape == b["y"].shape, k
+        rms, mx = uc.err(got[k], b["y"])
+        print("unet %s %s: rms %.3e (floor %.3e, bar %.3e) max %.3e (floor %.3e, bar %.3e)" % (uc.case_id(case), k, rms, b["floor_rms"], b["bar_rms"], mx,
+                                                                                            b["floor_max"], b["bar_max"]))
+        if not (torch.isfinite(got[k]).all() and rms <= b["bar_rms"] and mx <= b["bar_max"]):
+            bad.append("%s: rms %.3e against %.3e, max %.3e against %.3e" % (k, rms, b["bar_rms"], mx, b["bar_max"]))
+    assert not bad, "; ".join(bad)
 
 
 # ---------------------------------------------------------------- the whole network
