@@ -818,7 +818,8 @@ __device__ __forceinline__ void conv_prefetch(typename Op<OpT>::frag (&A)[NB][KG
 // last group ends in taps of zero weights.  `nks` = k-steps that carry real taps (taps * CC); the wave leaves the last group at the
 // first tap boundary at or behind it (wave-uniform), skipping the MFMAs, the B reads and the ring requests of the dead slots.
 // nks >= ntaps_p * CC runs the padded loop.
-template <typename OpT, int CIN, int MI, int NJ, int KGROUP, int NB, bool REAL = false>
+// JT0: first column tile that is computed (as in kconv, below): tiles 0 .. JT0-1 keep what acc held on entry.
+template <typename OpT, int CIN, int MI, int NJ, int KGROUP, int NB, bool REAL = false, int JT0 = 0>
 __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>::frag (&A)[NB][KGROUP][MI],
                                          const char* lds_lane, const OpT* wlane, long ct_stride, int ntaps_p, int roff,
                                          int dstep, int dbg = 0, int nks = 0) {
@@ -829,6 +830,8 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
     static_assert((CC >= KGROUP) ? (CC % KGROUP == 0) : (KGROUP % CC == 0), "k-group must tile a tap");
     static_assert(NB >= 2 && NB <= 4, "2..4 weight buffers");
     static_assert(KGROUP % 2 == 0, "the B ping-pong needs an even k-group");
+    static_assert(JT0 >= 0 && JT0 < NJ, "at least one column tile runs");
+    constexpr int NJA = NJ - JT0;  // column tiles that run
     constexpr int GPT = (CC >= KGROUP) ? CC / KGROUP : 1;  // k-groups per tap
     constexpr int TPG = (CC >= KGROUP) ? 1 : KGROUP / CC;  // taps per k-group
     const int NG = ntaps_p * CC / KGROUP;
@@ -841,7 +844,7 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
     auto readB = [&](frag(&B)[NJ], const char* base, int k) {
         const char* bp = base + koff(k);
 #pragma unroll
-        for (int jt = 0; jt < NJ; ++jt) B[jt] = *(const frag*)(bp + jt * 32 * STRIDE);
+        for (int jt = JT0; jt < NJ; ++jt) B[jt] = *(const frag*)(bp + jt * 32 * STRIDE);
     };
 
     const char* gb = lds_lane + roff * STRIDE;  // B base of the current group
@@ -854,7 +857,7 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
     // first k-step's B fragments, in ASCENDING tile order like every later k-step (the waitcnt pass merges the loop entry
     // with the back edge: a different order here makes it wait for lgkmcnt(0) at the head of every group)
 #pragma unroll
-    for (int jt = 0; jt < NJ; ++jt) {
+    for (int jt = JT0; jt < NJ; ++jt) {
         Bf[0][jt] = *(const frag*)(gb + koff(0) + jt * 32 * STRIDE);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -883,14 +886,14 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                        for (int jt = 0; jt < NJ; ++jt) {
-                            constexpr int NS = MI * NJ;
-                            const int i = mi * NJ + jt;
+                        for (int jt = JT0; jt < NJ; ++jt) {
+                            constexpr int NS = MI * NJA;
+                            const int i = mi * NJA + jt - JT0;
                             acc[mi][jt] = Op<OpT>::mfma(A[u][k][mi], Bf[k & 1][jt], acc[mi][jt]);
 #ifdef RVCMI_KLOOP_ABLATE  // tools/ubench/kloop.hip only: 1 = no weight loads, 2 = no B reads inside the loop
                             if (!(RVCMI_KLOOP_ABLATE & 2))
 #endif
-                            if (i < NJ) Bf[(k + 1) & 1][i] = *(const frag*)(nbp + i * 32 * STRIDE);
+                            if (i < NJA) Bf[(k + 1) & 1][JT0 + i] = *(const frag*)(nbp + (JT0 + i) * 32 * STRIDE);
 #ifdef RVCMI_KLOOP_ABLATE
                             if (!(RVCMI_KLOOP_ABLATE & 1))
 #endif
@@ -913,12 +916,12 @@ __device__ __forceinline__ void conv_run(f32x16 (&acc)[MI][NJ], typename Op<OpT>
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                        for (int jt = 0; jt < NJ; ++jt) acc[mi][jt] = Op<OpT>::mfma(A[u][k][mi], Bf[k & 1][jt], acc[mi][jt]);
+                        for (int jt = JT0; jt < NJ; ++jt) acc[mi][jt] = Op<OpT>::mfma(A[u][k][mi], Bf[k & 1][jt], acc[mi][jt]);
 #pragma unroll
-                    for (int i = 0; i < MI * NJ; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // 1 MFMA
-                        if (i < NJ) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);            // 1 DS read
-                        else if (i < NJ + MI) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
+                    for (int i = 0; i < MI * NJA; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                         // 1 MFMA
+                        if (i < NJA) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);            // 1 DS read
+                        else if (i < NJA + MI) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
                     }
                 }
 #endif
@@ -962,17 +965,21 @@ __device__ __forceinline__ void kconv_prefetch(typename Op<OpT>::frag (&A)[8][MI
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) A[kk][mi] = weight_load<OpT>(r, loff + kk * 1024, mi * ctb);
 }
-template <typename OpT, int CIN, int MI, int NJ, int STRIDE>
+// JT0: first column tile that is computed.  Tiles 0 .. JT0-1 keep what acc held on entry: no MFMA, no B read (k_rb_stream's first step of
+// a strip, whose leading tiles are pipeline fill).  The weight requests stay one per k-step, now behind (NJ - JT0) * MI MFMAs.
+template <typename OpT, int CIN, int MI, int NJ, int STRIDE, int JT0 = 0>
 __device__ __forceinline__ void kconv(f32x16 (&acc)[MI][NJ], typename Op<OpT>::frag (&A)[8][MI], unsigned lds_row, __amdgpu_buffer_rsrc_t r,
                                       unsigned loff, unsigned ctb, int ntaps, int dstep) {
     using frag = typename Op<OpT>::frag;
     constexpr int CC = CIN / 16, GPT = CC / 8;  // k-steps per tap, groups of 8 k-steps per tap
     static_assert(CIN % 128 == 0, "kconv: C_in must be a multiple of 128");
+    static_assert(JT0 >= 0 && JT0 < NJ, "kconv: at least one column tile runs");
+    constexpr int NJA = NJ - JT0;  // column tiles that run
     constexpr unsigned TS = 32u * STRIDE;
     auto ld = [](unsigned a) { return *(const __attribute__((address_space(3))) frag*)(size_t)a; };
     frag Bf[2][NJ];
 #pragma unroll
-    for (int jt = 0; jt < NJ; ++jt) {
+    for (int jt = JT0; jt < NJ; ++jt) {
         Bf[0][jt] = ld(lds_row + jt * TS);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -992,11 +999,11 @@ __device__ __forceinline__ void kconv(f32x16 (&acc)[MI][NJ], typename Op<OpT>::f
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int jt = 0; jt < NJ; ++jt) {
-                    constexpr int NS = MI * NJ;
-                    const int i = mi * NJ + jt;
+                for (int jt = JT0; jt < NJ; ++jt) {
+                    constexpr int NS = MI * NJA;
+                    const int i = mi * NJA + jt - JT0;
                     acc[mi][jt] = Op<OpT>::mfma(A[kk][mi], Bf[kk & 1][jt], acc[mi][jt]);
-                    if (i < NJ) Bf[(kk + 1) & 1][i] = ld((kk < 7 ? b0 + (unsigned)((kk + 1) * 32) : b1) + i * TS);
+                    if (i < NJA) Bf[(kk + 1) & 1][JT0 + i] = ld((kk < 7 ? b0 + (unsigned)((kk + 1) * 32) : b1) + (JT0 + i) * TS);
                     if (i >= NS - MI) A[kk][i - (NS - MI)] = weight_load<OpT>(r, loff + kk * 1024, soff + (unsigned)(i - (NS - MI)) * ctb);
                     __builtin_amdgcn_sched_barrier(0);
                 }

@@ -25,6 +25,10 @@ namespace {
 struct Geo {
     int MI, NJ, NCO, bpc;  // bpc = blocks per CU (k_rb_stream: one wave per SIMD, NCO * bpc = 4)
     double c0;             // planning: a block's time is steps x (k + c0) units
+    // A strip's first step, which skips its pipeline-fill column tiles (rb_stream_kernels.hpp rs_fill_tile), costs f x a full step:
+    // f = 0.79 / 0.84 / 0.96 at k = 11 / 7 / 3 (C = 128, NJ = 6, phase stamps of the headline launch with RS_FILL = 0 against the default,
+    // profiles/rb_stream_fill_time.json "stamps").  Pricing a block at (steps - 1 + f) x (k + c0) plans the SAME strips at the headline shape
+    // (122 / 81 / 52: the step counts 7 / 10 / 15 are what is quantised) and was not measured anywhere else, so the planner prices every step alike.
 };
 bool geo_for(int C, int nd, Geo& g, const Options& opt) {
     const bool sm = opt.geti("RS_SMALL", 1) != 0;
@@ -132,6 +136,7 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     const int slots1 = std::max(njobs, num_cus() * g.bpc / std::max(1, B));
     int nblocks = 0, side_rows = 0, min_steps = 1 << 30;
     int warm[3] = {0, 0, 0};
+    bool fill = nd > 1 && opt.geti("RS_FILL", 1) != 0;  // (nd = 1, the pair level: no gain measured, not instantiated)
     for (int j = 0; j < njobs; ++j) {
         const RbStreamDesc& d = jobs[j];
         RbStreamJob& J = a.job[j];
@@ -161,6 +166,13 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
             J.sh_off[m] = sx;
             sx += 2 * p2;
         }
+        // first step of a strip: the kernel starts pair m's convs at column tile rs_fill_inst = m + 1 (or 0).  That has to be pipeline fill
+        // (at or in front of the exact first needed tile) and must leave tiles NJ-2 and NJ-1, which feed the next step's histories
+        for (int m = 0; m < nd; ++m)
+            for (int c = 0; c < 2; ++c) {
+                const int inst = rs_fill_inst(m, g.NJ);
+                if (inst > rs_fill_tile(d.k, d.dil, nd, m, c) || inst > g.NJ - 2) fill = false;  // (no shape in use: every tile, as RS_FILL = 0)
+            }
         side_rows = std::max(side_rows, sx);
     }
     // Strips.  A block's time is steps x (per-step cost), steps = ceil((rows + warm-up) / R) and the per-step cost measured with
@@ -168,10 +180,10 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     // every resblock so that the slowest block finishes earliest (brute force over the splits of the slots; cached).
     int nst[3] = {1, 1, 1};
     {
-        struct Key { int C, nd, L, slots, R, k[3], n; };
+        struct Key { int C, nd, L, slots, R, k[3], n, c0_milli; };  // (all int: compared with memcmp)
         static std::mutex mu;
         static std::vector<std::pair<Key, std::array<int, 3>>> cache;
-        Key key{C, nd, L, slots1, R, {jobs[0].k, njobs > 1 ? jobs[1].k : 0, njobs > 2 ? jobs[2].k : 0}, njobs};
+        Key key{C, nd, L, slots1, R, {jobs[0].k, njobs > 1 ? jobs[1].k : 0, njobs > 2 ? jobs[2].k : 0}, njobs, (int)std::lround(g.c0 * 1000.0)};  // (c0: option RS_C0)
         bool hit = false;
         {
             std::lock_guard<std::mutex> lk(mu);
@@ -239,6 +251,7 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     a.lens = jobs[0].lens;
     a.lmul = jobs[0].lmul;
     if (jobs[0].y_half) a.flags |= 8;
+    if (fill) a.flags |= 32;
     if (jobs[0].x_half) {
         if (!(a.flags & 4) || !(C == 128 && nd == 3 && g.NJ == 6)) return false;  // fp16 input rows: only in the coalesced step IO of KL = 2
         a.flags |= 16;

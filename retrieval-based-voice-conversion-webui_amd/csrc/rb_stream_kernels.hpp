@@ -18,6 +18,8 @@
 // The schedule (row arithmetic, masks, history copies, tile shift) is modelled line by line in tools/model_rb_stream.py
 // and checked there against a direct evaluation of the resblock.
 #pragma once
+#include <type_traits>
+
 #include "nsf_kernels.hpp"
 
 namespace rvcmi {
@@ -26,6 +28,30 @@ constexpr int RS_HEAD = 62;   // first M row of the new X rows: 2*p2 (<= 10) row
 constexpr int RS_HROW = 10;   // first M row of the new H rows
 constexpr int RS_SLACK = 4;   // zero rows behind the tile: the last padded tap of conv1 may read p1 + p2 + dil - 32 <= 3 rows beyond
 constexpr int RS_MAXND = 3;
+
+// Pipeline fill of a strip's first step.  A strip starts HL = sum(p1_m + p2) rows early and every pair's output window lags its input
+// window by 32 rows, so in step 0 pair m's conv2 window starts at r0 - 32 (m + 1) and its conv1 (h) window p2 rows behind that.  The first
+// row of pair m's output that anything reads is S0 minus the halos of the LATER pairs (the last pair: S0 itself, the store descriptor
+// drops what lies in front); conv1's is p2 rows earlier.  Column tiles wholly in front of that row feed nothing: they are the LEADING
+// rows of the window, the histories of the next step are cut from the TRAILING ones (X: tiles NJ-2 and NJ-1, H: tile NJ-1).
+// Returns the first column tile holding a needed row -- independent of the strip (S0 cancels), of r0 < 0 and of the sequence end.
+// tools/model_rb_stream.py has the same arithmetic, checked against a brute-force dependency walk.
+inline int rs_fill_tile(int k, const int* dil, int nd, int m, int conv2) {
+    const int p2 = (k - 1) / 2;
+    int HL = nd * p2, later = 0;
+    for (int i = 0; i < nd; ++i) HL += dil[i] * (k - 1) / 2;
+    for (int i = m + 1; i < nd; ++i) later += dil[i] * (k - 1) / 2 + p2;
+    const int S0 = 0, r0 = S0 - HL;
+    const int need = S0 - later - (conv2 ? 0 : p2);                  // first needed row
+    const int win = r0 - 32 * (m + 1) + (conv2 ? 0 : p2);            // first row of the window
+    return (need - win) / 32;                                        // (need >= win: p1 >= p2 >= 0)
+}
+// The kernel rounds a conv's first tile DOWN to m + 1, which the 32-row lag alone gives pair m whatever k and the dilations are
+// (v2/48k: 12 of a first step's 36 conv-tiles against 14 / 13 / 12 exact at k = 11 / 7 / 3), so that the first step is straight-line
+// code with one K loop instantiation per conv.  (Selecting the instantiation at run time inside the one step body -- m + 1 and 4
+// for the last pair, chosen per job -- was built first: the accumulators then meet behind every conv from two or three K loops whose
+// VGPR / AGPR assignment differs, 90 -> 1279 v_accvgpr_read in the fp16-row instantiation and 87..106 spilled registers in four others.)
+constexpr int rs_fill_inst(int m, int NJ) { return m + 1 <= NJ - 2 ? m + 1 : 0; }
 
 struct RbStreamJob {
     const float* src;
@@ -53,7 +79,8 @@ struct RbStreamArgs {
     long bstride;
     int side_rows;  // rows of the side area (max over jobs)
     int flags;      // bit 2 (4) = lean K loop instantiation; bit 3 (8) = the dst streams are fp16 (pack4_h, nsf_kernels.hpp), same
-                    // element layout; bit 4 (16) = the src stream is fp16 (KL = 2 only)
+                    // element layout; bit 4 (16) = the src stream is fp16 (KL = 2 only); bit 5 (32) = a strip's first step skips its
+                    // pipeline-fill column tiles (rs_fill_tile)
     unsigned long long* ts;  // dev only (RVCMI_RS_STAMPS=1): per-wave cycle sums per phase, [block][wave][16]
 };
 
@@ -175,9 +202,10 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
         if constexpr (KL == 2) kconv_prefetch<OpT, MI>(A8, weight_rsrc(wl), loff, ctb);
         else conv_prefetch<OpT, C, MI, KG, NB>(A, wl + lane * 8, ct, J.k_p);
     };
-    auto run = [&](f32x16 (&acc)[MI][NJ], const char* lds_lane, const OpT* wl, long ct, unsigned ctb, int dstep) {
-        if constexpr (KL == 2) kconv<OpT, C, MI, NJ, STRIDE>(acc, A8, lds_address(lds_lane), weight_rsrc(wl), loff, ctb, J.k, dstep);
-        else conv_run<OpT, C, MI, NJ, KG, NB>(acc, A, lds_lane, wl + lane * 8, ct, J.k_p, 0, dstep);
+    auto run = [&](auto jt0c, f32x16 (&acc)[MI][NJ], const char* lds_lane, const OpT* wl, long ct, unsigned ctb, int dstep) {
+        constexpr int JT0 = decltype(jt0c)::value;  // first column tile that runs
+        if constexpr (KL == 2) kconv<OpT, C, MI, NJ, STRIDE, JT0>(acc, A8, lds_address(lds_lane), weight_rsrc(wl), loff, ctb, J.k, dstep);
+        else conv_run<OpT, C, MI, NJ, KG, NB, false, JT0>(acc, A, lds_lane, wl + lane * 8, ct, J.k_p, 0, dstep);
     };
     prefetch((const OpT*)J.w1[0] + (size_t)ct0 * J.ct1, J.ct1, ctb1);
     __syncthreads();
@@ -248,7 +276,10 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
     using lds_f32x4 = __attribute__((address_space(3))) f32x4;
     if constexpr (KL == 2) issue_loads(r0);
 
-    for (int step = 0; step < nsteps; ++step) {
+    // One step.  FILL (a strip's first step only, flags bit 5): every conv starts at its first column tile that is not pipeline fill.  The
+    // skipped tiles keep bias (+ residual), finite values that are published like any other and that no needed row reads.
+    auto do_step = [&](auto fillc, const int step) {
+        constexpr bool FILL = decltype(fillc)::value;
         f32x16 xin[MI][NJ];
         if constexpr (KL == 2) {
             bar();  // every thread is done with T (the previous step's row-wise reads for its stores)
@@ -321,8 +352,9 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             }
         }
         stamp(8);  // x loads issued
-#pragma unroll
-        for (int m = 0; m < ND; ++m) {
+        auto pair = [&](auto mc) {  // (m as a constant: it selects the K loop instantiations of the first step)
+            constexpr int m = decltype(mc)::value;
+            using jt0_t = std::integral_constant<int, FILL ? rs_fill_inst(m, NJ) : 0>;
             const int dil = J.dil[m];
             const int p1 = dil * (J.k - 1) / 2;
             const int Hx = 32 + p1 - p2;
@@ -415,7 +447,7 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
                             for (int e = 0; e < 4; ++e) hacc[mi][jt][4 * g + e] = bv[e];
                     }
             }
-            run(hacc, M + (size_t)(RS_HEAD - Hx + lrow) * STRIDE + (lane >> 5) * 16, w1l, J.ct1, ctb1, dil);
+            run(jt0_t{}, hacc, M + (size_t)(RS_HEAD - Hx + lrow) * STRIDE + (lane >> 5) * 16, w1l, J.ct1, ctb1, dil);
             prefetch(w2l, J.ct2, ctb2);  // in flight across the publish + barriers
             stamp(2);  // conv1
             bar();  // every wave is done reading X
@@ -464,7 +496,7 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
                             for (int e = 0; e < 4; ++e) res[mi][jt][4 * g + e] += bv[e];
                     }
             }
-            run(res, M + (size_t)(RS_HROW - 2 * p2 + lrow) * STRIDE + (lane >> 5) * 16, w2l, J.ct2, ctb2, 1);
+            run(jt0_t{}, res, M + (size_t)(RS_HROW - 2 * p2 + lrow) * STRIDE + (lane >> 5) * 16, w2l, J.ct2, ctb2, 1);
             {  // next conv1's weights (next pair, or pair 0 of the next step)
                 const int mn = (m + 1 < ND) ? m + 1 : 0;
                 prefetch((const OpT*)J.w1[mn] + (size_t)ct0 * J.ct1, J.ct1, ctb1);
@@ -476,7 +508,11 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                 for (int jt = 0; jt < NJ; ++jt) xin[mi][jt] = res[mi][jt];
-        }
+        };
+        pair(std::integral_constant<int, 0>{});
+        if constexpr (ND > 1) pair(std::integral_constant<int, 1>{});
+        if constexpr (ND > 2) pair(std::integral_constant<int, 2>{});
+        static_assert(ND <= 3, "pair calls above");
         // ---- store the rows of this strip ------------------------------------------------------------------------------
         if constexpr (KL == 2) {
             const int wout = r0 - 32 * ND + step * R;
@@ -559,7 +595,17 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             }
         }
         stamp(9);  // stores issued
+    };
+    // the first step is peeled, so that the steps behind it are the one loop they were.  Whole resblocks only: the pair-level form (ND = 1)
+    // runs where strips are long (large batches) and measured no gain from its one tile of three (rb_stream_launch never sets the flag there)
+    int step0 = 0;
+    if constexpr (ND > 1) {
+        if (a.flags & 32) {
+            do_step(std::true_type{}, 0);
+            step0 = 1;
+        }
     }
+    for (int step = step0; step < nsteps; ++step) do_step(std::false_type{}, step);
     if (stamps && lane < 12) {
         unsigned long long v = 0;
 #pragma unroll

@@ -112,7 +112,8 @@ class _HipGenerator(torch.nn.Module):
         conv_post by the register-staged kernel / by LDS-DMA with the next tile in flight (default), ``POST_DBG`` (timing ablations); ``RBF_PAD_TAP`` 0 / 1 = the fused ResBlock kernel at C <= 32 stops its K loops behind the real taps
         (default) / also multiplies the zero taps that round k = 11, 7, 3 up to whole k-groups of 12, 8, 4 (the loop before, kept so that a test can
         hold the two against each other bit for bit); ``RBF32_TALL`` 1 / 0 = 768-row tiles for that kernel at C = 32 always / never, unset = from
-        four blocks per compute unit on; these two take 0 or 1 only, another value is an error; an unknown key is an error); ``None`` restores the default.  The library reads ``RVCMI_<KEY>`` only when a handle is created."""
+        four blocks per compute unit on; these two take 0 or 1 only, another value is an error; ``RS_FILL`` 0 = the streaming ResBlock kernel computes every column tile in a strip's first step too,
+        unset / 1 = it skips the leading tiles that only fill the pipeline (same bits); an unknown key is an error); ``None`` restores the default.  The library reads ``RVCMI_<KEY>`` only when a handle is created."""
         _lib.set_option(_lib.lib().rvcmi_nsf_set_option, self._handle, key, value)  # raises on a key this handle does not honour
         if not hasattr(self, "_options"):
             self._options = {}
