@@ -1447,6 +1447,7 @@ int rvcmi_nsf_set_option(rvcmi_nsf* h, const char* key, double value) {
         if (!h || !key) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
         if ((!strcmp(key, "RBF_PAD_TAP") || !strcmp(key, "RBF32_TALL")) && value == value && value != 0.0 && value != 1.0)
             RVCMI_FAIL(RVCMI_ERR_INVALID, "option '%s' takes 0 or 1", key);
+        if (!strcmp(key, "RS_MFMA") && value == value && value != 16.0 && value != 32.0) RVCMI_FAIL(RVCMI_ERR_INVALID, "option 'RS_MFMA' takes 16 or 32");
         if (!h->opt.set(key, value)) RVCMI_FAIL(RVCMI_ERR_INVALID, "unknown option '%s' for this handle", key);
     });
 }

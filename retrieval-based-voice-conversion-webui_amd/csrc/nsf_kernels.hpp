@@ -604,12 +604,18 @@ struct Op<__bf16> {
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
+    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
 };
 template <>
 struct Op<_Float16> {
     using frag = f16x8;
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
     }
 };
 
@@ -1014,6 +1020,78 @@ __device__ __forceinline__ void kconv(f32x16 (&acc)[MI][NJ], typename Op<OpT>::f
     }
 }
 
+// ---- the lean K loop on v_mfma_f32_16x16x32 (k_rb_stream, option RS_MFMA) ------------------------------------------------------
+// The same sum over the same LDS tile and the same packed weights [co_tile][k_step][lane][8] in steps of 32 k; the chip holds a
+// higher clock on this shape (tools/ubench/kloop2.hip `shape`).  A wave's 32 channels x 32 NJ rows are 2 channel
+// halves x 2 NJ column tiles of 16 rows; per 32 k a tile's B fragment is ONE ds_read_b128 and feeds both halves' MFMAs.
+//   B  lane l = (q, n) = (l / 16, l % 16) reads row mfma16_row(n) of the tile and the 8 channels of 16-byte chunk
+//      mfma16_chunk(q) of the 32: which 8 channels sit in which K-block of the instruction is free as long as A agrees, and
+//      the tile's rows may stand in any column order that the D lanes then follow.  Chunks {0, 2, 1, 3} and even rows on columns
+//      0-3, 12-15, odd rows on 4-11 give every ds_read_b128 lane group ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, + 32) 16
+//      distinct 16-byte slots with rows of 17 slots; the natural order puts two lanes of each group on one slot
+//      (tools/model_rb_stream.py mfma16_*, tests/test_cpu_rb_stream_mfma16.py).
+//   A  half h, K-block q = channels 16 h + n of k-step 2 s + (q & 1), 8-k block q >> 1: lanes 32 (q >> 1) + 16 h + n of that
+//      k-step's packed fragment, whole 256-byte runs (mfma16_loff + s * 2048 + h * 256).  Ring slot A[2 s + h].
+//   D  lane (q, n) holds row mfma16_row(n) and channels 16 h + 4 q + e: four consecutive channels of one row, as before.
+// B fragments are refilled IN PLACE behind their second MFMA (the next use is 2 * (2 NJ - JT0) - 2 MFMAs later), so the buffer
+// stays at 2 NJ fragments.  JT0 counts 16-row tiles.
+__host__ __device__ constexpr int mfma16_row(int n) { return n < 4 ? 2 * n : n < 12 ? 2 * n - 7 : 2 * n - 16; }
+__host__ __device__ constexpr int mfma16_chunk(int q) { return ((q & 1) << 1) | (q >> 1); }
+__device__ __forceinline__ unsigned mfma16_loff(int lane) {
+    const int q = lane >> 4, n = lane & 15;
+    return (unsigned)(((q & 1) * 64 + (q >> 1) * 32 + n) * 16);
+}
+template <typename OpT, int MI>
+__device__ __forceinline__ void kconv16_prefetch(typename Op<OpT>::frag (&A)[8][MI], __amdgpu_buffer_rsrc_t r, unsigned loff, unsigned ctb) {
+    static_assert(MI == 1, "kconv16: one 32-channel tile per wave");
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) A[2 * s + h][0] = weight_load<OpT>(r, loff + s * 2048 + h * 256, 0);
+}
+template <typename OpT, int CIN, int MI, int NJ, int STRIDE, int JT0 = 0>
+__device__ __forceinline__ void kconv16(f32x4 (&acc)[2 * MI][2 * NJ], typename Op<OpT>::frag (&A)[8][MI], unsigned lds_row,
+                                        __amdgpu_buffer_rsrc_t r, unsigned loff, unsigned ctb, int ntaps, int dstep) {
+    using frag = typename Op<OpT>::frag;
+    constexpr int CC = CIN / 16, GPT = CC / 8, NT = 2 * NJ;
+    static_assert(CIN % 128 == 0, "kconv16: C_in must be a multiple of 128");
+    static_assert(MI == 1, "kconv16: one 32-channel tile per wave");
+    static_assert(JT0 >= 0 && JT0 < NT, "kconv16: at least one column tile runs");
+    constexpr unsigned TS = 16u * STRIDE;
+    auto ld = [](unsigned a) { return *(const __attribute__((address_space(3))) frag*)(size_t)a; };
+    frag Bf[NT];
+#pragma unroll
+    for (int jt = JT0; jt < NT; ++jt) {
+        Bf[jt] = ld(lds_row + jt * TS);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const unsigned dS = (unsigned)(dstep * STRIDE);
+    const int ngroups = ntaps * GPT;
+    const unsigned slast = (unsigned)(ngroups - 1) * 8192u;
+    unsigned soff = ngroups > 1 ? 8192u : 0u;
+    int gi = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        const unsigned nrow = (gi + 1 == GPT) ? lds_row - (unsigned)((GPT - 1) * 256) + dS : lds_row + 256u;
+        unsigned b0 = lds_row, b1 = nrow;  // (opaque, as in kconv)
+        asm volatile("" : "+v"(b0), "+v"(b1));
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+            for (int jt = JT0; jt < NT; ++jt)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    acc[h][jt] = Op<OpT>::mfma16(A[2 * s + h][0], Bf[jt], acc[h][jt]);
+                    if (h == 1) Bf[jt] = ld((s < 3 ? b0 + (unsigned)((s + 1) * 64) : b1) + jt * TS);
+                    if (jt == NT - 1) A[2 * s + h][0] = weight_load<OpT>(r, loff + s * 2048 + h * 256, soff);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+        }
+        lds_row = nrow;
+        gi = (gi + 1 == GPT) ? 0 : gi + 1;
+        soff = soff < slast ? soff + 8192u : soff;
+    }
+}
+
 template <typename OpT, int CIN, int MI, int NJ, int KGROUP = ::rvcmi::KGROUP, int NB = 2>
 __device__ __forceinline__ void conv_core(f32x16 (&acc)[MI][NJ], const char* lds_lane, const OpT* wlane,
                                           long ct_stride, int ntaps_p, int roff, int dstep) {
@@ -1313,6 +1391,18 @@ __device__ __forceinline__ void publish_operand(char* base, const f32x16 (&acc)[
                         pack4_lrelu<OpT, MASK>(t[4 * g + 0], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3], rowmask[jt]);
                 }
             }
+}
+
+// ... of the 16x16x32 shape (kconv16): tiles of 16 channels x 16 rows, one register quad each
+template <typename OpT, int MIH, int NT, int STRIDE, bool MASK>
+__device__ __forceinline__ void publish_operand16(char* base, const f32x4 (&acc)[MIH][NT], const unsigned (&rowmask)[NT]) {
+#pragma unroll
+    for (int mi = 0; mi < MIH; ++mi)
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) {
+            const f32x4& t = acc[mi][jt];
+            *(uint2*)(base + jt * 16 * STRIDE + mi * 16 * 2) = pack4_lrelu<OpT, MASK>(t[0], t[1], t[2], t[3], rowmask[jt]);
+        }
 }
 
 // Block barrier that orders LDS traffic ONLY: __syncthreads() carries a workgroup release fence over global memory too, i.e. an

@@ -22,6 +22,12 @@ namespace {
 #define RS_KL_DEFAULT 2  // measured (r3k): 0.641 -> 0.623 ms per clip at B = 1 with the planning constant below, 0.614 -> 0.605 at B = 16
 #endif
 
+// MFMA shape of the lean-K-loop instantiations (C = 128, whole resblocks, NJ = 6), option RS_MFMA = 16 / 32: v_mfma_f32_16x16x32 holds a
+// higher clock than 32x32x16 on this chip at the same traffic
+#ifndef RS_MFMA_DEFAULT
+#define RS_MFMA_DEFAULT 16
+#endif
+
 struct Geo {
     int MI, NJ, NCO, bpc;  // bpc = blocks per CU (k_rb_stream: one wave per SIMD, NCO * bpc = 4)
     double c0;             // planning: a block's time is steps x (k + c0) units
@@ -46,13 +52,13 @@ bool geo_for(int C, int nd, Geo& g, const Options& opt) {
 
 // nblocks < 0: only make sure the > 64 KB dynamic-LDS attribute is set on the current device (once per device and instantiation;
 // done at handle creation so that a first forward inside a stream capture does not have to)
-template <typename OpT, int C, int MI, int NJ, int NCO, int ND, int KG = 4, int NB = 2, int OCC = 1, int KL = 1, int XH = 0>
+template <typename OpT, int C, int MI, int NJ, int NCO, int ND, int KG = 4, int NB = 2, int OCC = 1, int KL = 1, int XH = 0, int SH = 32>
 void launch_inst(const RbStreamArgs& a, int nblocks, int B, size_t smem, hipStream_t st) {
     static std::atomic<unsigned long long> attr_done{0};
     int dev = 0;
     HIP_CHECK(hipGetDevice(&dev));
     const unsigned long long bit = 1ull << (dev & 63);
-    auto kern = &k_rb_stream<OpT, C, MI, NJ, NCO, ND, KG, NB, OCC, KL, XH>;
+    auto kern = &k_rb_stream<OpT, C, MI, NJ, NCO, ND, KG, NB, OCC, KL, XH, SH>;
     if (!(attr_done.load() & bit)) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_done.fetch_or(bit);
@@ -77,6 +83,10 @@ void launch_t(int C, int nd, int NJ, const RbStreamArgs& a, int nblocks, int B, 
     if (C == 256 && nd == 1 && NJ == 3) return launch_inst<OpT, 256, 2, 3, 4, 1>(a, nblocks, B, smem, st);
     if (C == 128 && nd == 3 && NJ == 8) return launch_inst<OpT, 128, 1, 8, 4, 3>(a, nblocks, B, smem, st);
     // (weight ring 3 / 4 groups deep instead of 2: 65 / 129 spilled registers, 0.70 -> 0.77 / 0.89 ms -- measured, not kept)
+    if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4) && (a.flags & 64)) {  // lean K loop on v_mfma_f32_16x16x32: fp16 / fp32 input rows
+        if (a.flags & 16) return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2, 1, 16>(a, nblocks, B, smem, st);
+        return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2, 0, 16>(a, nblocks, B, smem, st);
+    }
     if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4) && (a.flags & 16))
         return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2, 1>(a, nblocks, B, smem, st);  // lean K loop, fp16 input rows
     if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4)) return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2>(a, nblocks, B, smem, st);  // lean K loop
@@ -97,7 +107,7 @@ void rb_stream_prepare() {
         launch_t<__bf16>(128, 3, nj, a, -1, 1, 0, nullptr);
         launch_t<_Float16>(128, 3, nj, a, -1, 1, 0, nullptr);
     }
-    for (int fl : {4, 4 | 16}) {  // the lean-K-loop instantiations of NJ = 6: fp32 / fp16 input rows
+    for (int fl : {4, 4 | 16, 4 | 64, 4 | 16 | 64}) {  // the lean-K-loop instantiations of NJ = 6: fp32 / fp16 input rows, both MFMA shapes
         a.flags = fl;
         launch_t<__bf16>(128, 3, 6, a, -1, 1, 0, nullptr);
         launch_t<_Float16>(128, 3, 6, a, -1, 1, 0, nullptr);
@@ -180,10 +190,11 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     // every resblock so that the slowest block finishes earliest (brute force over the splits of the slots; cached).
     int nst[3] = {1, 1, 1};
     {
-        struct Key { int C, nd, L, slots, R, k[3], n, c0_milli; };  // (all int: compared with memcmp)
+        struct Key { int C, nd, L, slots, R, k[3], n, c0_milli, mfma; };  // (all int: compared with memcmp)
         static std::mutex mu;
         static std::vector<std::pair<Key, std::array<int, 3>>> cache;
-        Key key{C, nd, L, slots1, R, {jobs[0].k, njobs > 1 ? jobs[1].k : 0, njobs > 2 ? jobs[2].k : 0}, njobs, (int)std::lround(g.c0 * 1000.0)};  // (c0: option RS_C0)
+        Key key{C, nd, L, slots1, R, {jobs[0].k, njobs > 1 ? jobs[1].k : 0, njobs > 2 ? jobs[2].k : 0}, njobs, (int)std::lround(g.c0 * 1000.0),
+                opt.geti("RS_MFMA", RS_MFMA_DEFAULT)};  // (c0: option RS_C0)
         bool hit = false;
         {
             std::lock_guard<std::mutex> lk(mu);
@@ -250,6 +261,7 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     if (opt.geti("RS_KL", RS_KL_DEFAULT) == 2 && (double)L * C * 4.0 < 2147483648.0) a.flags = 4;
     a.lens = jobs[0].lens;
     a.lmul = jobs[0].lmul;
+    if ((a.flags & 4) && C == 128 && nd == 3 && g.NJ == 6 && opt.geti("RS_MFMA", RS_MFMA_DEFAULT) == 16) a.flags |= 64;
     if (jobs[0].y_half) a.flags |= 8;
     if (fill) a.flags |= 32;
     if (jobs[0].x_half) {
@@ -297,8 +309,8 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
                 ++cnt;
             }
             if (!cnt) continue;
-            fprintf(stderr, "[rs stamps] C=%d nd=%d NJ=%d k=%d strips=%d len=%d steps/blk=%.1f  cycles per PAIR-step:", C, nd, g.NJ, a.job[j].k,
-                    a.job[j].nstrips, a.job[j].strip_len, steps / cnt);
+            fprintf(stderr, "[rs stamps] C=%d nd=%d NJ=%d k=%d strips=%d len=%d mfma=%d steps/blk=%.1f  cycles per PAIR-step:", C, nd, g.NJ, a.job[j].k,
+                    a.job[j].nstrips, a.job[j].strip_len, (a.flags & 64) ? 16 : 32, steps / cnt);
             for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.0f", names[i], sum[i] / (steps * nd));
             fprintf(stderr, " | per step: xload %.0f store %.0f | slowest wave total %.0f cycles\n", sum[8] / steps, sum[9] / steps, tot_max);
         }

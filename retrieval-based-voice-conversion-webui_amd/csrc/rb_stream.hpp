@@ -28,8 +28,9 @@ void rb_stream_prepare();
 bool rb_stream_supported(int operand, int C, int nd);
 // Option keys read from `opt` (dev / tests): RS_SMALL (0 = the larger time tiles), RS_KL (2 = k_rb_stream with the lean K loop
 // kconv), RS_C0 (planning constant), RS_STAMPS (print phase stamps; syncs), RS_FILL (0 = a strip's first step computes its pipeline-fill
-// column tiles too, as every later step does; unset / 1 = skips them).
-inline void rb_stream_load_env(Options& opt) { opt.load_env({"RS_SMALL", "RS_KL", "RS_C0", "RS_STAMPS", "RS_FILL"}); }
+// column tiles too, as every later step does; unset / 1 = skips them), RS_MFMA (16 / 32: the MFMA shape of the lean-K-loop instantiations, v_mfma_f32_16x16x32 / 32x32x16; the shape that ran is
+// in the line RS_STAMPS prints, "mfma=16").
+inline void rb_stream_load_env(Options& opt) { opt.load_env({"RS_SMALL", "RS_KL", "RS_C0", "RS_STAMPS", "RS_FILL", "RS_MFMA"}); }
 // Plans strips for `B` utterances of `L` rows and launches ONE kernel covering all `njobs` resblocks.  Returns false
 // (nothing launched) when the strips would be too short for the persistent walk to pay and `force` is not set.
 // `dry_run`: plan only (same return value), launch nothing.

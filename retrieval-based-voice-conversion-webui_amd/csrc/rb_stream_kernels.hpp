@@ -6,7 +6,8 @@
 //   * each pair's output window lags its input window by exactly 32 rows (>= p1 + p2, the rows a pair cannot produce
 //     yet).  32 rows = one MFMA column tile, so the fp32 residual  x' = conv2(h) + x  needs no data movement: output tile
 //     jt adds input tile jt-1, which the SAME lane of the same wave already holds in registers (tile NJ-1 is carried to
-//     the next step).  The fp32 residual stream therefore never leaves the register file between the pairs;
+//     the next step).  The fp32 residual stream therefore never leaves the register file between the pairs
+//     (on the 16x16x32 shape, SH = 16 below, a column tile is 16 rows and the lag two tiles: jt adds jt-2, two tiles are carried);
 //   * with ND = 3 all pairs of a resblock run back to back on the resident rows: ONE read and ONE write of the stream
 //     per resblock, no overlap-save recomputation (k_rb_full computes R rows to keep R - 2*HL).  With ND = 1 the same
 //     code is the pair-level kernel for channel counts whose three histories do not fit (C = 256).
@@ -80,7 +81,7 @@ struct RbStreamArgs {
     int side_rows;  // rows of the side area (max over jobs)
     int flags;      // bit 2 (4) = lean K loop instantiation; bit 3 (8) = the dst streams are fp16 (pack4_h, nsf_kernels.hpp), same
                     // element layout; bit 4 (16) = the src stream is fp16 (KL = 2 only); bit 5 (32) = a strip's first step skips its
-                    // pipeline-fill column tiles (rs_fill_tile)
+                    // pipeline-fill column tiles (rs_fill_tile); bit 6 (64) = the K loops run on v_mfma_f32_16x16x32 (SH = 16)
     unsigned long long* ts;  // dev only (RVCMI_RS_STAMPS=1): per-wave cycle sums per phase, [block][wave][16]
 };
 
@@ -96,11 +97,20 @@ __device__ __forceinline__ void rs_copy_rows(char* dst, const char* src, int row
 // KL = 2: the lean K loop kconv (nsf_kernels.hpp) instead of conv_prefetch / conv_run
 // XH = 1 (with KL = 2): the src stream is fp16 (a.flags bit 4) -- its own instantiation: as a runtime switch the fp32 and the fp16 row
 // registers of the step prefetch were both live (472 -> 512 registers + 16 spilled)
-template <typename OpT, int C, int MI, int NJ, int NCO, int ND, int KG, int NB, int OCC = 1, int KL = 1, int XH = 0>
+// SH: the MFMA shape of the K loops, 32 = v_mfma_f32_32x32x16 (kconv / conv_run), 16 = v_mfma_f32_16x16x32 (kconv16, KL = 2 only).
+// Accumulator, residual and carry tiles are acc_t[MIH][NTL]: tiles of CT channels x TR rows holding NG register quads per lane, each
+// quad four consecutive channels (8 g + half4 of the tile) of the lane's row lrow.
+//   SH = 32: f32x16[MI][NJ], 32 x 32, 4 quads, lrow = lane % 32, half4 = 4 (lane / 32)
+//   SH = 16: f32x4[2 MI][2 NJ], 16 x 16, 1 quad, lrow = mfma16_row(lane % 16), half4 = 4 (lane / 16)   (nsf_kernels.hpp kconv16)
+// The 32-row lag of a pair is LAG = 32 / TR column tiles.
+template <typename OpT, int C, int MI, int NJ, int NCO, int ND, int KG, int NB, int OCC = 1, int KL = 1, int XH = 0, int SH = 32>
 static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs a) {
     using TL = Tile<C>;
     using frag = typename Op<OpT>::frag;
     using o4 = __attribute__((ext_vector_type(4))) OpT;
+    static_assert(SH == 32 || (SH == 16 && KL == 2 && MI == 1), "the 16x16x32 shape runs in the lean K loop only");
+    using acc_t = std::conditional_t<SH == 32, f32x16, f32x4>;
+    constexpr int TR = SH, CT = SH, LAG = 32 / TR, NTL = NJ * LAG, MIH = MI * LAG, NG = SH == 32 ? 4 : 1;
     constexpr int STRIDE = TL::STRIDE;
     constexpr int NT = 64 * NCO;
     constexpr int R = 32 * NJ;
@@ -150,8 +160,9 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
 
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // wave: scalar (SGPR weight bases)
     const int ct0 = wave * MI;               // first 32-channel output tile of this wave
-    const int half4 = 4 * (lane >> 5);
-    const int lrow = lane & 31;
+    const int half4 = SH == 32 ? 4 * (lane >> 5) : 4 * (lane >> 4);
+    const int lrow = SH == 32 ? lane & 31 : mfma16_row(lane & 15);
+    auto bchunk = [&] { return SH == 32 ? (lane >> 5) * 16 : mfma16_chunk(lane >> 4) * 16; };  // this lane's B chunk inside a k-step / 32 k, in bytes
 
     // ---- zero the whole LDS image once (histories start empty, slack rows stay zero), stage the biases ----------------
     {
@@ -186,26 +197,39 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             __syncthreads();
         }
     };
-    f32x16 carry[ND][MI];
+    acc_t carry[ND][MIH][LAG];
 #pragma unroll
     for (int m = 0; m < ND; ++m)
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
+        for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) carry[m][mi][e] = 0.f;
+            for (int j = 0; j < LAG; ++j)
+#pragma unroll
+                for (int e = 0; e < 4 * NG; ++e) carry[m][mi][j][e] = 0.f;
 
     frag A[NB][KG][MI];  // weight register ring, requested one phase ahead of its use
     frag A8[8][MI];      // ... of the lean loop (KL = 2)
-    const unsigned loff = (unsigned)lane * 16u;
+    const unsigned loff = SH == 32 ? (unsigned)lane * 16u : mfma16_loff(lane);
     const unsigned ctb1 = (unsigned)(J.ct1 * 2), ctb2 = (unsigned)(J.ct2 * 2);
     auto prefetch = [&](const OpT* wl, long ct, unsigned ctb) {  // wl: this wave's first output-channel tile (wave-uniform)
-        if constexpr (KL == 2) kconv_prefetch<OpT, MI>(A8, weight_rsrc(wl), loff, ctb);
+        if constexpr (SH == 16) kconv16_prefetch<OpT, MI>(A8, weight_rsrc(wl), loff, ctb);
+        else if constexpr (KL == 2) kconv_prefetch<OpT, MI>(A8, weight_rsrc(wl), loff, ctb);
         else conv_prefetch<OpT, C, MI, KG, NB>(A, wl + lane * 8, ct, J.k_p);
     };
-    auto run = [&](auto jt0c, f32x16 (&acc)[MI][NJ], const char* lds_lane, const OpT* wl, long ct, unsigned ctb, int dstep) {
+    auto run = [&](auto jt0c, acc_t (&acc)[MIH][NTL], const char* lds_lane, const OpT* wl, long ct, unsigned ctb, int dstep) {
         constexpr int JT0 = decltype(jt0c)::value;  // first column tile that runs
-        if constexpr (KL == 2) kconv<OpT, C, MI, NJ, STRIDE, JT0>(acc, A8, lds_address(lds_lane), weight_rsrc(wl), loff, ctb, J.k, dstep);
+        if constexpr (SH == 16) kconv16<OpT, C, MI, NJ, STRIDE, JT0>(acc, A8, lds_address(lds_lane), weight_rsrc(wl), loff, ctb, J.k, dstep);
+        else if constexpr (KL == 2) kconv<OpT, C, MI, NJ, STRIDE, JT0>(acc, A8, lds_address(lds_lane), weight_rsrc(wl), loff, ctb, J.k, dstep);
         else conv_run<OpT, C, MI, NJ, KG, NB, false, JT0>(acc, A, lds_lane, wl + lane * 8, ct, J.k_p, 0, dstep);
+    };
+    auto publish = [&](char* base, const acc_t (&acc)[MIH][NTL], const unsigned (&rowmask)[NTL], bool interior) {
+        if constexpr (SH == 16) {
+            if (interior) publish_operand16<OpT, MIH, NTL, STRIDE, false>(base, acc, rowmask);
+            else publish_operand16<OpT, MIH, NTL, STRIDE, true>(base, acc, rowmask);
+        } else {
+            if (interior) publish_operand<OpT, C, MI, NJ, STRIDE, false>(base, acc, rowmask);
+            else publish_operand<OpT, C, MI, NJ, STRIDE, true>(base, acc, rowmask);
+        }
     };
     prefetch((const OpT*)J.w1[0] + (size_t)ct0 * J.ct1, J.ct1, ctb1);
     __syncthreads();
@@ -271,7 +295,8 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             xr[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_src, v0[it / 8] + (unsigned)((it % 8) * (C * 4)), 0, 0));
         }
     };
-    // D-layout addresses of this lane inside T: tiles 0..2 from one base register, 3..5 from a second (16-bit offset fields)
+    // D-layout addresses of this lane inside T: the first NTH tiles from one base register, the rest from a second (16-bit offset fields)
+    constexpr int NTH = NTL / 2;
     const unsigned dl_lds = lds_address(T) + (unsigned)(lrow * TSTR + (ct0 * 32 + half4) * 4);
     using lds_f32x4 = __attribute__((address_space(3))) f32x4;
     if constexpr (KL == 2) issue_loads(r0);
@@ -280,7 +305,7 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
     // skipped tiles keep bias (+ residual), finite values that are published like any other and that no needed row reads.
     auto do_step = [&](auto fillc, const int step) {
         constexpr bool FILL = decltype(fillc)::value;
-        f32x16 xin[MI][NJ];
+        acc_t xin[MIH][NTL];
         if constexpr (KL == 2) {
             bar();  // every thread is done with T (the previous step's row-wise reads for its stores)
             if constexpr (xhf) {
@@ -298,12 +323,12 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
                     unsigned b0 = dlh_lds;
                     asm volatile("" : "+v"(b0));
 #pragma unroll
-                    for (int jt = 0; jt < NJ; ++jt)
+                    for (int jt = 0; jt < NTL; ++jt)
 #pragma unroll
-                        for (int mi = 0; mi < MI; ++mi)
+                        for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                const h4 v = *(const lds_h4*)(size_t)(b0 + (unsigned)(jt * 32 * TSTRH + (mi * 32 + 8 * g) * 2));
+                            for (int g = 0; g < NG; ++g) {
+                                const h4 v = *(const lds_h4*)(size_t)(b0 + (unsigned)(jt * TR * TSTRH + (mi * CT + 8 * g) * 2));
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) xin[mi][jt][4 * g + e] = (float)v[e];
                             }
@@ -317,15 +342,15 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             }
             bar();
             {
-                unsigned b0 = dl_lds, b1 = dl_lds + (unsigned)(3 * 32 * TSTR);
+                unsigned b0 = dl_lds, b1 = dl_lds + (unsigned)(NTH * TR * TSTR);
                 asm volatile("" : "+v"(b0), "+v"(b1));
 #pragma unroll
-                for (int jt = 0; jt < NJ; ++jt)
+                for (int jt = 0; jt < NTL; ++jt)
 #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
+                    for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const f32x4 v = *(const lds_f32x4*)(size_t)((jt < 3 ? b0 : b1) + (unsigned)((jt % 3) * 32 * TSTR + (mi * 32 + 8 * g) * 4));
+                        for (int g = 0; g < NG; ++g) {
+                            const f32x4 v = *(const lds_f32x4*)(size_t)((jt < NTH ? b0 : b1) + (unsigned)((jt % NTH) * TR * TSTR + (mi * CT + 8 * g) * 4));
 #pragma unroll
                             for (int e = 0; e < 4; ++e) xin[mi][jt][4 * g + e] = v[e];
                         }
@@ -354,7 +379,7 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
         stamp(8);  // x loads issued
         auto pair = [&](auto mc) {  // (m as a constant: it selects the K loop instantiations of the first step)
             constexpr int m = decltype(mc)::value;
-            using jt0_t = std::integral_constant<int, FILL ? rs_fill_inst(m, NJ) : 0>;
+            using jt0_t = std::integral_constant<int, FILL ? LAG * rs_fill_inst(m, NJ) : 0>;  // (in column tiles of TR rows)
             const int dil = J.dil[m];
             const int p1 = dil * (J.k - 1) / 2;
             const int Hx = 32 + p1 - p2;
@@ -386,33 +411,32 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             }
             rs_copy_rows<STRIDE, NT>(M + (size_t)(RS_HROW - 2 * p2) * STRIDE, sideH, 2 * p2);
             {
-                unsigned rowmask[NJ];
+                unsigned rowmask[NTL];
 #pragma unroll
-                for (int jt = 0; jt < NJ; ++jt) {
-                    const int t = wm + jt * 32 + lrow;
+                for (int jt = 0; jt < NTL; ++jt) {
+                    const int t = wm + jt * TR + lrow;
                     rowmask[jt] = (t >= 0 && t < L) ? 0xffffffffu : 0u;
                 }
                 char* xw = M + (size_t)(RS_HEAD + lrow) * STRIDE + (ct0 * 32 + half4) * 2;
-                if (interior) publish_operand<OpT, C, MI, NJ, STRIDE, false>(xw, xin, rowmask);
-                else publish_operand<OpT, C, MI, NJ, STRIDE, true>(xw, xin, rowmask);
+                publish(xw, xin, rowmask, interior);
                 if constexpr (KL == 2) {
 #pragma unroll
                     for (int it = 0; it < NIT; ++it) {
                         const int i = min(it * RPI + lane / WCH, Hx - 1);
                         *(uint4*)(M + (size_t)(RS_HEAD - Hx + i) * STRIDE + ct0 * 64 + (lane % WCH) * 16) = hb[it];
                     }
-                    // dual write: new rows [R - Hx, R) -> history rows [0, Hx)   (Hx <= 52 < 64: tiles NJ-2 and NJ-1 only)
+                    // dual write: new rows [R - Hx, R) -> history rows [0, Hx)   (Hx <= 52 < 64: the tiles of the last 64 rows only)
 #pragma unroll
-                    for (int jt = NJ - 2; jt < NJ; ++jt) {
-                        const int srow = jt * 32 + lrow - (R - Hx);
+                    for (int jt = NTL - 2 * LAG; jt < NTL; ++jt) {
+                        const int srow = jt * TR + lrow - (R - Hx);
                         char* tw = (srow >= 0 ? sideX + (size_t)srow * STRIDE : dump) + (ct0 * 32 + half4) * 2;
                         // (the same expression as the publish above, mask variant included: the packed words are reused, not recomputed)
 #pragma unroll
-                        for (int mi = 0; mi < MI; ++mi)
+                        for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                const f32x16& t = xin[mi][jt];
-                                *(uint2*)(tw + (mi * 32 + 8 * g) * 2) =
+                            for (int g = 0; g < NG; ++g) {
+                                const acc_t& t = xin[mi][jt];
+                                *(uint2*)(tw + (mi * CT + 8 * g) * 2) =
                                     interior ? pack4_lrelu<OpT, false>(t[4 * g + 0], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3], 0u)
                                              : pack4_lrelu<OpT, true>(t[4 * g + 0], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3], rowmask[jt]);
                             }
@@ -420,34 +444,36 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
                 }
             }
             // residual tiles of this pair's output window (= input window - 32 rows): pure register renaming
-            f32x16 res[MI][NJ];
+            acc_t res[MIH][NTL];
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                res[mi][0] = carry[m][mi];
+            for (int mi = 0; mi < MIH; ++mi) {
 #pragma unroll
-                for (int jt = 1; jt < NJ; ++jt) res[mi][jt] = xin[mi][jt - 1];
-                carry[m][mi] = xin[mi][NJ - 1];
+                for (int jt = 0; jt < LAG; ++jt) res[mi][jt] = carry[m][mi][jt];
+#pragma unroll
+                for (int jt = LAG; jt < NTL; ++jt) res[mi][jt] = xin[mi][jt - LAG];
+#pragma unroll
+                for (int jt = 0; jt < LAG; ++jt) carry[m][mi][jt] = xin[mi][NTL - LAG + jt];
             }
             stamp(0);  // phase A (waits for the x loads when m == 0)
             bar();
             stamp(1);
 
             // ---- conv1 (dilated): h rows [a_m, a_m + R), a_m = wm - 32 + p2 ---------------------------------------------
-            f32x16 hacc[MI][NJ];
+            acc_t hacc[MIH][NTL];
             {
                 const float* bl = bias_l + (m * 2 + 0) * CP + ct0 * 32 + half4;
 #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
+                for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 bv = *(const f32x4*)(bl + mi * 32 + 8 * g);
+                    for (int g = 0; g < NG; ++g) {
+                        const f32x4 bv = *(const f32x4*)(bl + mi * CT + 8 * g);
 #pragma unroll
-                        for (int jt = 0; jt < NJ; ++jt)
+                        for (int jt = 0; jt < NTL; ++jt)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) hacc[mi][jt][4 * g + e] = bv[e];
                     }
             }
-            run(jt0_t{}, hacc, M + (size_t)(RS_HEAD - Hx + lrow) * STRIDE + (lane >> 5) * 16, w1l, J.ct1, ctb1, dil);
+            run(jt0_t{}, hacc, M + (size_t)(RS_HEAD - Hx + lrow) * STRIDE + bchunk(), w1l, J.ct1, ctb1, dil);
             prefetch(w2l, J.ct2, ctb2);  // in flight across the publish + barriers
             stamp(2);  // conv1
             bar();  // every wave is done reading X
@@ -457,26 +483,28 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             if constexpr (KL != 2) rs_copy_rows<STRIDE, NT>(sideX, M + (size_t)(RS_HEAD + R - Hx) * STRIDE, Hx);
             {
                 const int am = wm - 32 + p2;
-                unsigned rowmask[NJ];
+                unsigned rowmask[NTL];
 #pragma unroll
-                for (int jt = 0; jt < NJ; ++jt) {
-                    const int t = am + jt * 32 + lrow;
+                for (int jt = 0; jt < NTL; ++jt) {
+                    const int t = am + jt * TR + lrow;
                     rowmask[jt] = (t >= 0 && t < L) ? 0xffffffffu : 0u;
                 }
                 char* hw = M + (size_t)(RS_HROW + lrow) * STRIDE + (ct0 * 32 + half4) * 2;
-                if (interior) publish_operand<OpT, C, MI, NJ, STRIDE, false>(hw, hacc, rowmask);
-                else publish_operand<OpT, C, MI, NJ, STRIDE, true>(hw, hacc, rowmask);
-                // the last 2*p2 rows of the new h rows are next step's H head
-                const int srow = lrow - (32 - 2 * p2);
-                char* tw = (srow >= 0 ? sideH + (size_t)srow * STRIDE : dump) + (ct0 * 32 + half4) * 2;
+                publish(hw, hacc, rowmask, interior);
+                // the last 2*p2 rows of the new h rows are next step's H head (2*p2 <= 10: the tiles of the last 32 rows only)
 #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
+                for (int jt = NTL - LAG; jt < NTL; ++jt) {
+                    const int srow = jt * TR + lrow - (R - 2 * p2);
+                    char* tw = (srow >= 0 ? sideH + (size_t)srow * STRIDE : dump) + (ct0 * 32 + half4) * 2;
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x16& t = hacc[mi][NJ - 1];
-                        *(uint2*)(tw + (mi * 32 + 8 * g) * 2) =
-                            pack4_lrelu<OpT, true>(t[4 * g + 0], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3], rowmask[NJ - 1]);
-                    }
+                    for (int mi = 0; mi < MIH; ++mi)
+#pragma unroll
+                        for (int g = 0; g < NG; ++g) {
+                            const acc_t& t = hacc[mi][jt];
+                            *(uint2*)(tw + (mi * CT + 8 * g) * 2) =
+                                pack4_lrelu<OpT, true>(t[4 * g + 0], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3], rowmask[jt]);
+                        }
+                }
             }
             stamp(4);  // phase B
             bar();
@@ -486,17 +514,17 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             {
                 const float* bl = bias_l + (m * 2 + 1) * CP + ct0 * 32 + half4;
 #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
+                for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 bv = *(const f32x4*)(bl + mi * 32 + 8 * g);
+                    for (int g = 0; g < NG; ++g) {
+                        const f32x4 bv = *(const f32x4*)(bl + mi * CT + 8 * g);
 #pragma unroll
-                        for (int jt = 0; jt < NJ; ++jt)
+                        for (int jt = 0; jt < NTL; ++jt)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) res[mi][jt][4 * g + e] += bv[e];
                     }
             }
-            run(jt0_t{}, res, M + (size_t)(RS_HROW - 2 * p2 + lrow) * STRIDE + (lane >> 5) * 16, w2l, J.ct2, ctb2, 1);
+            run(jt0_t{}, res, M + (size_t)(RS_HROW - 2 * p2 + lrow) * STRIDE + bchunk(), w2l, J.ct2, ctb2, 1);
             {  // next conv1's weights (next pair, or pair 0 of the next step)
                 const int mn = (m + 1 < ND) ? m + 1 : 0;
                 prefetch((const OpT*)J.w1[mn] + (size_t)ct0 * J.ct1, J.ct1, ctb1);
@@ -505,9 +533,9 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
             bar();  // every wave is done reading H
             stamp(7);
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
+            for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                for (int jt = 0; jt < NJ; ++jt) xin[mi][jt] = res[mi][jt];
+                for (int jt = 0; jt < NTL; ++jt) xin[mi][jt] = res[mi][jt];
         };
         pair(std::integral_constant<int, 0>{});
         if constexpr (ND > 1) pair(std::integral_constant<int, 1>{});
@@ -526,12 +554,12 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
                     unsigned b0 = dlh_lds;
                     asm volatile("" : "+v"(b0));
 #pragma unroll
-                    for (int jt = 0; jt < NJ; ++jt)
+                    for (int jt = 0; jt < NTL; ++jt)
 #pragma unroll
-                        for (int mi = 0; mi < MI; ++mi)
+                        for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                            for (int g = 0; g < 4; ++g)
-                                *(lds_u2*)(size_t)(b0 + (unsigned)(jt * 32 * TSTRH + (mi * 32 + 8 * g) * 2)) = __builtin_bit_cast(
+                            for (int g = 0; g < NG; ++g)
+                                *(lds_u2*)(size_t)(b0 + (unsigned)(jt * TR * TSTRH + (mi * CT + 8 * g) * 2)) = __builtin_bit_cast(
                                     u32x2_t, pack4_h(xin[mi][jt][4 * g + 0], xin[mi][jt][4 * g + 1], xin[mi][jt][4 * g + 2], xin[mi][jt][4 * g + 3]));
                 }
                 bar();
@@ -547,16 +575,16 @@ static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs
                 }
             } else {
             {
-                unsigned b0 = dl_lds, b1 = dl_lds + (unsigned)(3 * 32 * TSTR);
+                unsigned b0 = dl_lds, b1 = dl_lds + (unsigned)(NTH * TR * TSTR);
                 asm volatile("" : "+v"(b0), "+v"(b1));
 #pragma unroll
-                for (int jt = 0; jt < NJ; ++jt)
+                for (int jt = 0; jt < NTL; ++jt)
 #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
+                    for (int mi = 0; mi < MIH; ++mi)
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) {
+                        for (int g = 0; g < NG; ++g) {
                             const f32x4 v = {xin[mi][jt][4 * g + 0], xin[mi][jt][4 * g + 1], xin[mi][jt][4 * g + 2], xin[mi][jt][4 * g + 3]};
-                            *(lds_f32x4*)(size_t)((jt < 3 ? b0 : b1) + (unsigned)((jt % 3) * 32 * TSTR + (mi * 32 + 8 * g) * 4)) = v;
+                            *(lds_f32x4*)(size_t)((jt < NTH ? b0 : b1) + (unsigned)((jt % NTH) * TR * TSTR + (mi * CT + 8 * g) * 4)) = v;
                         }
             }
             bar();

@@ -113,7 +113,8 @@ class _HipGenerator(torch.nn.Module):
         (default) / also multiplies the zero taps that round k = 11, 7, 3 up to whole k-groups of 12, 8, 4 (the loop before, kept so that a test can
         hold the two against each other bit for bit); ``RBF32_TALL`` 1 / 0 = 768-row tiles for that kernel at C = 32 always / never, unset = from
         four blocks per compute unit on; these two take 0 or 1 only, another value is an error; ``RS_FILL`` 0 = the streaming ResBlock kernel computes every column tile in a strip's first step too,
-        unset / 1 = it skips the leading tiles that only fill the pipeline (same bits); an unknown key is an error); ``None`` restores the default.  The library reads ``RVCMI_<KEY>`` only when a handle is created."""
+        unset / 1 = it skips the leading tiles that only fill the pipeline (same bits); ``RS_MFMA`` 16 / 32 = the MFMA shape of that kernel's lean K loop,
+        ``v_mfma_f32_16x16x32`` (default) / ``32x32x16`` (the same products summed in another order), another value is an error; an unknown key is an error); ``None`` restores the default.  The library reads ``RVCMI_<KEY>`` only when a handle is created."""
         _lib.set_option(_lib.lib().rvcmi_nsf_set_option, self._handle, key, value)  # raises on a key this handle does not honour
         if not hasattr(self, "_options"):
             self._options = {}
