@@ -306,6 +306,18 @@ int rvcmi_ivf_search_blend_expand(rvcmi_ivf* h, int64_t nq, const float* feats_d
                                   int skip_if_short, const float* pitchf_dev, float protect, int64_t p_len,
                                   float* out_dev, void* stream);
 
+/* rvcmi_ivf_search_blend_expand for a bank of S realtime sessions that share the index (feats_dev [S, nq, d], pitchf_dev
+ * [S, p_len] or NULL, out_dev [S, p_len, d], all contiguous): per session, rows [0, skip_rows) are expanded un-blended and rows
+ * [skip_rows, nq) are searched and blended -- what two single-session calls on the two row ranges compute, bit for bit.  All
+ * S * (nq - skip_rows) searched rows go through ONE search; the launch count does not depend on S.  The realtime guard
+ * (skip_if_short != 0; rtrvc.py:172-180 is a per-call condition, and a call is one talker's block) is evaluated PER SESSION:
+ * the result ids are reduced into one flag per session after the search, so a session whose rows probe a list shorter than k
+ * keeps its own features and leaves the others' blend alone.  1 <= S <= 65535, 0 <= skip_rows <= nq, p_len <= 2 * nq.
+ * The handle keeps the packed query rows and the flags (grown on demand, like rvcmi_ivf_reserve).                            */
+int rvcmi_ivf_search_blend_expand_batch(rvcmi_ivf* h, int S, int64_t nq, int64_t skip_rows, const float* feats_dev,
+                                        float index_rate, int k, int skip_if_short, const float* pitchf_dev, float protect,
+                                        int64_t p_len, float* out_dev, void* stream);
+
 /* index.reconstruct_n(i0, n) -> out_host [n,d] rows in id order (pipeline.py:215).             */
 int rvcmi_ivf_reconstruct_n(const rvcmi_ivf* h, int64_t i0, int64_t n, float* out_host);
 
@@ -469,6 +481,43 @@ size_t rvcmi_glue_filtfilt_scratch_bytes(int B, int64_t total, int order);
  * rolloff 0.99).  n_out = ceil(new * n / orig) for the whole signal.  PARITY UNPINNED: torchaudio is not installable offline. */
 int rvcmi_glue_resample_poly(const float* x_dev, int64_t n, const float* kernel_dev, int orig, int new_, int K, int width,
                              float* out_dev, int64_t n_out, void* stream);
+
+/* ---- the realtime block for a bank of S sessions (rvc_amd.RealtimeBank) ----------------------------------------------------
+ * Each call below is its single-stream namesake applied to S signals at once: the same device code per session (the kernels
+ * share their bodies), so session s's results equal a single-stream call on its row bit for bit, and the number of launches
+ * does not depend on S.  Every per-session array is given with a ROW STRIDE in elements (`*_stride`): session s's row starts
+ * at base + s * stride, and a row may be a slice of a longer rolling buffer (stride >= the row's length, else
+ * RVCMI_ERR_INVALID).  Rows of one output array must not overlap.  1 <= S <= 65535.  Tables (resample kernel, fades) are shared. */
+
+/* rvcmi_glue_resample_poly per row: x_dev rows of n samples -> out_dev rows of n_out samples. */
+int rvcmi_glue_resample_poly_batch(int S, const float* x_dev, int64_t x_stride, int64_t n, const float* kernel_dev, int orig,
+                                   int new_, int K, int width, float* out_dev, int64_t out_stride, int64_t n_out, void* stream);
+
+/* rvcmi_glue_sola per session: one offset search per session (one block each, the chunk head and the previous tail staged in
+ * LDS: 2 Lb + Ls floats <= 150 KB), sola_buffer_dev [S rows of Lb] updated in place, out_block_dev [S rows of block_frame],
+ * offset_out_dev [S] (optional, contiguous).                                                                              */
+int rvcmi_glue_sola_batch(int S, const float* infer_wav_dev, int64_t wav_stride, int64_t n, float* sola_buffer_dev,
+                          int64_t buf_stride, int Lb, int Ls, const float* fade_in_dev, const float* fade_out_dev,
+                          int block_frame, float* out_block_dev, int64_t out_stride, int* offset_out_dev, void* stream);
+
+/* rvcmi_glue_sola_pv per session (four launches for the whole bank).  Lb <= 4096.
+ * scratch_dev: S * P doubles with P = 3 * (Lb/2 + 1) + Lb/2 + 1; session s owns [s * P, (s + 1) * P), laid out as the
+ * single-stream call's scratch: bins [3 * (Lb/2 + 1)] doubles | phase-vocoder result [Lb] floats | the offset (one int, used
+ * when offset_out_dev is NULL).                                                                                            */
+int rvcmi_glue_sola_pv_batch(int S, const float* infer_wav_dev, int64_t wav_stride, int64_t n, float* sola_buffer_dev,
+                             int64_t buf_stride, int Lb, int Ls, const float* fade_in_dev, const float* fade_out_dev,
+                             int block_frame, float* out_block_dev, int64_t out_stride, int* offset_out_dev,
+                             double* scratch_dev, void* stream);
+
+/* rvcmi_glue_envelope_mix per session, IN PLACE on wav_dev rows of n samples against input_dev rows (their first n samples).
+ * scratch_dev: S * 2 * (1 + n / zc) floats (per session: the input's envelope, then the output's).                         */
+int rvcmi_glue_envelope_mix_batch(int S, const float* input_dev, int64_t in_stride, float* wav_dev, int64_t wav_stride,
+                                  int64_t n, int zc, double rate, float* scratch_dev, void* stream);
+
+/* rvcmi_glue_expand_protect per session (the bank without retrieval): feats_dev [S, nq, d], pitchf_dev [S, p_len] or NULL,
+ * out_dev [S, p_len, d], contiguous.                                                                                       */
+int rvcmi_glue_expand_protect_batch(int S, const float* feats_dev, int64_t nq, int d, int reps, const float* pitchf_dev,
+                                    float protect, int64_t p_len, float* out_dev, void* stream);
 
 /* ---- beyond SURVEY.md section 8: the recurrent layer of the RMVPE f0 network -----------------------------------------------
  * Stands in for the `nn.GRU(384, 256, num_layers=1, batch_first=True, bidirectional=True)` of rvc/f0/e2e.py:50-67 (E2E.BiGRU, the

@@ -96,6 +96,8 @@ SYMBOLS = [
     ("rvcmi_ivf_search", C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P]),
     ("rvcmi_ivf_search_blend", C.c_int, [_P, C.c_int64, _P, C.c_float, C.c_int, C.c_int, _P]),
     ("rvcmi_ivf_search_blend_expand", C.c_int, [_P, C.c_int64, _P, C.c_float, C.c_int, C.c_int, _P, C.c_float, C.c_int64, _P, _P]),
+    ("rvcmi_ivf_search_blend_expand_batch", C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_float, C.c_int, C.c_int, _P, C.c_float,
+                                                      C.c_int64, _P, _P]),
     ("rvcmi_ivf_reconstruct_n", C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     ("rvcmi_ivf_blob", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     ("rvcmi_ivf_centroids", C.c_int, [_P, _P]),
@@ -116,6 +118,12 @@ SYMBOLS = [
     ("rvcmi_glue_phase_vocoder", C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("rvcmi_glue_sola_pv", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     ("rvcmi_glue_envelope_mix", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P]),
+    ("rvcmi_glue_resample_poly_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int64, _P]),
+    ("rvcmi_glue_sola_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P, _P]),
+    ("rvcmi_glue_sola_pv_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P, _P,
+                                           _P]),
+    ("rvcmi_glue_envelope_mix_batch", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_double, _P, _P]),
+    ("rvcmi_glue_expand_protect_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_float, C.c_int64, _P, _P]),
     ("rvcmi_glue_spectral_gate", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                            C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P, _P, C.c_size_t, _P]),
     ("rvcmi_glue_spectral_gate_scratch_bytes", C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),

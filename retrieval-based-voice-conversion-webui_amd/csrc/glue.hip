@@ -11,7 +11,7 @@
 using namespace rvcmi;
 
 static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0},
-    g_attr_gate_stft{0}, g_attr_gate_idft{0};
+    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_sola_b{0}, g_attr_sola_search_b{0}, g_attr_pv_spec_b{0}, g_attr_pv_synth_b{0};
 
 // The phase-vocoder launches on a device-resident b (b_off: optional device offset into b); out [n] may not alias a or b.
 static void launch_phase_vocoder(const float* a, const float* b, const int* b_off, const float* fade_out, const float* fade_in, int n, float* out,
@@ -351,6 +351,124 @@ int rvcmi_glue_resample_poly(const float* x, int64_t n, const float* kernel, int
         if (n_out == 0) return;
         hipLaunchKernelGGL(k_resample_poly, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n, kernel, orig, new_, K,
                            width, out, n_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// ---- the block DSP for a bank of S sessions: the single-stream bodies, session index in the grid (glue_kernels.hpp) --------------------
+#define RVCMI_BANK_MAX_S 65535  // a session is blockIdx.y (or blockIdx.x of a one-block-per-session launch)
+
+int rvcmi_glue_resample_poly_batch(int S, const float* x, int64_t x_stride, int64_t n, const float* kernel, int orig, int new_, int K, int width,
+                                   float* out, int64_t out_stride, int64_t n_out, void* stream) {
+    return guarded([&] {
+        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "resample_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
+        if (!x || !kernel || !out || n < 1 || orig < 1 || new_ < 1 || K < 1 || width < 0 || n_out < 0)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "resample_batch: bad argument");
+        if (x_stride < n || out_stride < n_out)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "resample_batch: row stride %lld / %lld shorter than the row %lld / %lld", (long long)x_stride,
+                       (long long)out_stride, (long long)n, (long long)n_out);
+        if (n_out == 0) return;
+        hipLaunchKernelGGL(k_resample_poly_batch, dim3((unsigned)((n_out + 255) / 256), (unsigned)S), dim3(256), 0, (hipStream_t)stream, x, x_stride,
+                           n, kernel, orig, new_, K, width, out, out_stride, n_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// what rvcmi_glue_sola and rvcmi_glue_sola_pv check, plus the bank's own arguments
+static void check_sola_batch(const char* who, int S, const float* infer_wav, int64_t wav_stride, int64_t n, const float* sola_buffer,
+                             int64_t buf_stride, int Lb, int Ls, const float* fade_in, const float* fade_out, int block_frame, const float* out_block,
+                             int64_t out_stride) {
+    if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: S = %d outside [1, %d]", who, S, RVCMI_BANK_MAX_S);
+    if (!infer_wav || !sola_buffer || !fade_in || !fade_out || !out_block || Lb < 1 || Ls < 0 || block_frame < 1)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
+    if ((int64_t)Ls + block_frame + Lb > n)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: chunk of %lld samples is shorter than search %d + block %d + buffer %d", who, (long long)n, Ls, block_frame, Lb);
+    if (wav_stride < n || buf_stride < Lb || out_stride < block_frame)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a row stride (%lld, %lld, %lld) is shorter than its row (%lld, %d, %d)", who, (long long)wav_stride,
+                   (long long)buf_stride, (long long)out_stride, (long long)n, Lb, block_frame);
+    if ((size_t)(2 * (int64_t)Lb + Ls) * sizeof(float) > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "%s: buffer + search window too large", who);
+}
+
+int rvcmi_glue_sola_batch(int S, const float* infer_wav, int64_t wav_stride, int64_t n, float* sola_buffer, int64_t buf_stride, int Lb, int Ls,
+                          const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
+                          void* stream) {
+    return guarded([&] {
+        check_sola_batch("sola_batch", S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block, out_stride);
+        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
+        ensure_dyn_lds((const void*)k_sola_batch, 150 * 1024, g_attr_sola_b);  // + 2 KB static
+        hipLaunchKernelGGL(k_sola_batch, dim3((unsigned)S), dim3(256), smem, (hipStream_t)stream, infer_wav, wav_stride, sola_buffer, buf_stride, Lb, Ls,
+                           fade_in, fade_out, block_frame, out_block, out_stride, offset_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_sola_pv_batch(int S, const float* infer_wav, int64_t wav_stride, int64_t n, float* sola_buffer, int64_t buf_stride, int Lb, int Ls,
+                             const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
+                             double* scratch, void* stream) {
+    return guarded([&] {
+        check_sola_batch("sola_pv_batch", S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block,
+                         out_stride);
+        if (!scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv_batch: bad argument");
+        if (Lb > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv_batch: cross-fade buffer of %d samples exceeds %d", Lb, RVCMI_PV_MAX_N);
+        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
+        // scratch: S slices of P = 3 * (Lb/2 + 1) + Lb/2 + 1 doubles, session s at s * P, each laid out as rvcmi_glue_sola_pv's:
+        //   bins [3 * (Lb/2 + 1)] doubles | pv result [Lb] floats | offset (when offset_out is NULL)
+        const int nb = Lb / 2 + 1;
+        const int64_t per = 3 * (int64_t)nb + Lb / 2 + 1;
+        float* pv = reinterpret_cast<float*>(scratch + 3 * nb);
+        const int* off = offset_out ? offset_out : reinterpret_cast<int*>(pv + Lb);
+        const int64_t off_stride = offset_out ? 1 : 2 * per;  // in ints
+        hipStream_t st = (hipStream_t)stream;
+        ensure_dyn_lds((const void*)k_sola_search_batch, 150 * 1024, g_attr_sola_search_b);
+        ensure_dyn_lds((const void*)k_pv_spectrum_batch, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec_b);
+        ensure_dyn_lds((const void*)k_pv_synth_batch, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth_b);
+        hipLaunchKernelGGL(k_sola_search_batch, dim3((unsigned)S), dim3(256), smem, st, infer_wav, wav_stride, (const float*)sola_buffer, buf_stride, Lb,
+                           Ls, const_cast<int*>(off), off_stride);
+        // a = the session's sola_buffer row, b = its chunk at its own offset (launch_phase_vocoder's two launches, session in grid.y)
+        hipLaunchKernelGGL(k_pv_spectrum_batch, dim3((unsigned)std::min(256, (nb + 3) / 4), (unsigned)S), dim3(256), (size_t)32 * Lb, st,
+                           (const float*)sola_buffer, buf_stride, infer_wav, wav_stride, off, off_stride, fade_out, fade_in, Lb, scratch, per);
+        hipLaunchKernelGGL(k_pv_synth_batch, dim3((unsigned)((Lb + 63) / 64), (unsigned)S), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st,
+                           (const float*)sola_buffer, buf_stride, infer_wav, wav_stride, off, off_stride, fade_out, fade_in, Lb, (const double*)scratch,
+                           per, pv, 2 * per);
+        hipLaunchKernelGGL(k_sola_pv_stitch_batch, dim3((unsigned)((block_frame + Lb + 255) / 256), (unsigned)S), dim3(256), 0, st, infer_wav, wav_stride,
+                           off, off_stride, (const float*)pv, 2 * per, Lb, block_frame, out_block, out_stride, sola_buffer, buf_stride);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_envelope_mix_batch(int S, const float* input, int64_t in_stride, float* wav, int64_t wav_stride, int64_t n, int zc, double rate,
+                                  float* scratch, void* stream) {
+    return guarded([&] {
+        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
+        if (!input || !wav || !scratch || n < 1 || zc < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: bad argument");
+        if (in_stride < n || wav_stride < n)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: row stride %lld / %lld shorter than the row %lld", (long long)in_stride,
+                       (long long)wav_stride, (long long)n);
+        const int64_t nf64 = 1 + n / zc;
+        if (nf64 > (1 << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: too many frames");
+        const int nf = (int)nf64;
+        hipStream_t st = (hipStream_t)stream;
+        // scratch [S][2][nf]: session s's input envelope, then its output envelope
+        hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf, (unsigned)S), dim3(256), 0, st, input, in_stride, n, 4 * zc, zc, nf, scratch, (int64_t)2 * nf);
+        hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf, (unsigned)S), dim3(256), 0, st, (const float*)wav, wav_stride, n, 4 * zc, zc, nf, scratch + nf,
+                           (int64_t)2 * nf);
+        const float e = (float)(1.0 - rate);
+        hipLaunchKernelGGL(k_envelope_mix_batch, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, st, wav, wav_stride, n,
+                           (const float*)scratch, nf, e);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// The bank's retrieval-free expansion (index_rate == 0 / no index): rvcmi_glue_expand_protect per session, one launch.
+int rvcmi_glue_expand_protect_batch(int S, const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
+                                    float* out, void* stream) {
+    return guarded([&] {
+        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "expand_protect_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
+        if (!feats || !out || nq < 0 || d < 1 || reps < 1 || p_len < 0 || p_len > nq * reps)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "expand_protect_batch: bad argument (nq %lld d %d reps %d p_len %lld)", (long long)nq, d, reps, (long long)p_len);
+        if (!nq || !p_len) return;
+        hipLaunchKernelGGL(k_blend_expand_batch, dim3((unsigned)nq, (unsigned)S), dim3(256), 0, (hipStream_t)stream, feats, nullptr, nullptr, nullptr, d,
+                           0, (int64_t)0, 0.f, 0.f, nullptr, 0, nq, (int64_t)0, pitchf, protect, p_len, reps, out);
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -22,19 +22,17 @@ namespace rvcmi {
 //   out[t] = x * pf + feats0[t/2] * (1 - pf),  pf = pitchf[t] >= 1 ? 1 : protect         (pipeline.py:153-158)
 // One block per QUERY row (both of its output frames): the blended row is computed once, in registers.
 // P == nullptr: no retrieval (index_rate == 0 / no index): the row is the input row.
-static __global__ void __launch_bounds__(256) k_blend_expand(const float* __restrict__ feats, const float* __restrict__ D,
-                                                             const int64_t* __restrict__ P, const float* __restrict__ vecs,
-                                                             int d, int k, int64_t pos_last, float rate, float omr,
-                                                             const int* __restrict__ any_short, int skip_if_short,
-                                                             const float* __restrict__ pitchf, float protect, int64_t p_len,
-                                                             int reps, float* __restrict__ out) {
+// The body: query row qi of feats [nq, d] -> output frames qi * reps .. of out [p_len, d]; D / P are the row's own k results (read
+// only when blend).  Shared by k_blend_expand and k_blend_expand_batch: one arithmetic, whoever launches it.
+__device__ __forceinline__ void blend_expand_row(const float* __restrict__ feats, const float* __restrict__ D, const int64_t* __restrict__ P,
+                                                 const float* __restrict__ vecs, int d, int k, int64_t pos_last, float rate, float omr,
+                                                 bool blend, const float* __restrict__ pitchf, float protect, int64_t p_len, int reps,
+                                                 float* __restrict__ out, int64_t qi) {
 #pragma clang fp contract(off)
-    const int64_t qi = blockIdx.x;
-    const bool blend = P != nullptr && !(skip_if_short && *any_short);
     float w[8];
     if (blend) {
         for (int s = 0; s < k; ++s) {
-            const float inv = div_rn(1.0f, D[qi * k + s]);
+            const float inv = div_rn(1.0f, D[s]);
             w[s] = mul_rn(inv, inv);
         }
         float sum;
@@ -53,7 +51,7 @@ static __global__ void __launch_bounds__(256) k_blend_expand(const float* __rest
         if (blend) {
             float acc = 0.f;
             for (int s = 0; s < k; ++s) {
-                int64_t p = P[qi * k + s];
+                int64_t p = P[s];
                 if (p < 0) p = pos_last;
                 const float prod = mul_rn(vecs[p * d + e], w[s]);
                 acc = s == 0 ? prod : add_rn(acc, prod);
@@ -71,6 +69,58 @@ static __global__ void __launch_bounds__(256) k_blend_expand(const float* __rest
             out[t * d + e] = o;
         }
     }
+}
+
+static __global__ void __launch_bounds__(256) k_blend_expand(const float* __restrict__ feats, const float* __restrict__ D,
+                                                             const int64_t* __restrict__ P, const float* __restrict__ vecs,
+                                                             int d, int k, int64_t pos_last, float rate, float omr,
+                                                             const int* __restrict__ any_short, int skip_if_short,
+                                                             const float* __restrict__ pitchf, float protect, int64_t p_len,
+                                                             int reps, float* __restrict__ out) {
+    const int64_t qi = blockIdx.x;
+    const bool blend = P != nullptr && !(skip_if_short && *any_short);
+    blend_expand_row(feats, blend ? D + qi * k : nullptr, blend ? P + qi * k : nullptr, vecs, d, k, pos_last, rate, omr, blend, pitchf,
+                     protect, p_len, reps, out, qi);
+}
+
+// The realtime guard per SESSION (rtrvc.py:172-180 is a per-call condition; in a bank a call is one session's block):
+// flags[s] = 1 when any of session s's m * k result ids is negative.  One block per session.
+static __global__ void __launch_bounds__(256) k_session_short(const int64_t* __restrict__ I, int64_t per_session, int* __restrict__ flags) {
+    __shared__ int any;
+    if (threadIdx.x == 0) any = 0;
+    __syncthreads();
+    const int64_t* row = I + (int64_t)blockIdx.x * per_session;
+    int mine = 0;
+    for (int64_t i = threadIdx.x; i < per_session; i += 256) mine |= row[i] < 0 ? 1 : 0;
+    if (mine) atomicOr(&any, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) flags[blockIdx.x] = any;
+}
+
+// The searched rows of every session, feats [S, nq, d] rows [skip, nq), packed into q [S * (nq - skip), d] for ONE search.
+static __global__ void __launch_bounds__(256) k_gather_tail_rows(const float* __restrict__ feats, int64_t nq, int64_t skip, int d,
+                                                                 float* __restrict__ q) {
+    const int64_t m = nq - skip;
+    const int64_t r = blockIdx.x, s = blockIdx.y;
+    const float* src = feats + (s * nq + skip + r) * d;
+    float* dst = q + (s * m + r) * d;
+    for (int e = threadIdx.x; e < d; e += 256) dst[e] = src[e];
+}
+
+// k_blend_expand for a bank: grid (nq, S).  Row qi < skip of a session is expanded un-blended; row qi >= skip uses result row
+// s * (nq - skip) + qi - skip of the one search and blends unless the session's flag is set (skip_if_short).  P == nullptr: no
+// retrieval at all.  feats [S, nq, d], pitchf [S, p_len] or nullptr, out [S, p_len, d].
+static __global__ void __launch_bounds__(256) k_blend_expand_batch(const float* __restrict__ feats, const float* __restrict__ D,
+                                                                   const int64_t* __restrict__ P, const float* __restrict__ vecs, int d,
+                                                                   int k, int64_t pos_last, float rate, float omr,
+                                                                   const int* __restrict__ flags, int skip_if_short, int64_t nq,
+                                                                   int64_t skip, const float* __restrict__ pitchf, float protect,
+                                                                   int64_t p_len, int reps, float* __restrict__ out) {
+    const int64_t qi = blockIdx.x, s = blockIdx.y;
+    const bool blend = P != nullptr && qi >= skip && !(skip_if_short && flags[s]);
+    const int64_t ri = s * (nq - skip) + (qi - skip);
+    blend_expand_row(feats + s * nq * d, blend ? D + ri * k : nullptr, blend ? P + ri * k : nullptr, vecs, d, k, pos_last, rate, omr, blend,
+                     pitchf ? pitchf + s * p_len : nullptr, protect, p_len, reps, out + s * p_len * d, qi);
 }
 
 // RMVPE._to_local_average_cents + _decode (rmvpe.py:119-164): one wave per frame.
@@ -293,15 +343,13 @@ __device__ __forceinline__ int sola_search(const float* xs, const float* bs, int
     return ri[0];
 }
 
-static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
-                                                     const float* __restrict__ fade_in, const float* __restrict__ fade_out,
-                                                     int block, float* __restrict__ out, int* __restrict__ offset_out) {
+// One block's whole stitch of one signal (sl: the dynamic LDS, 2 Lb + Ls floats): the body of k_sola and k_sola_batch.
+__device__ __forceinline__ void sola_block(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
+                                           const float* __restrict__ fade_in, const float* __restrict__ fade_out, int block,
+                                           float* __restrict__ out, int* __restrict__ offset_out, float* sl, float* rv, int* ri) {
 #pragma clang fp contract(off)
-    extern __shared__ float sl[];
     float* xs = sl;             // [Lb + Ls]
     float* bs = sl + Lb + Ls;   // [Lb]
-    __shared__ float rv[256];
-    __shared__ int ri[256];
     for (int i = threadIdx.x; i < Lb + Ls; i += 256) xs[i] = x[i];
     for (int i = threadIdx.x; i < Lb; i += 256) bs[i] = buf[i];
     __syncthreads();
@@ -315,17 +363,37 @@ static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x
     for (int i = threadIdx.x; i < Lb; i += 256) buf[i] = y(block + i);  // old tail is in LDS: safe to overwrite
 }
 
+static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
+                                                     const float* __restrict__ fade_in, const float* __restrict__ fade_out,
+                                                     int block, float* __restrict__ out, int* __restrict__ offset_out) {
+    extern __shared__ float sl[];
+    __shared__ float rv[256];
+    __shared__ int ri[256];
+    sola_block(x, buf, Lb, Ls, fade_in, fade_out, block, out, offset_out, sl, rv, ri);
+}
+
+// A bank of S signals, one block per session (blockIdx.x); every per-session array has a row stride in elements (a row may be a
+// slice of a longer rolling buffer).  fade_in / fade_out are shared.  offset_out [S] (optional).
+static __global__ void __launch_bounds__(256) k_sola_batch(const float* __restrict__ x, int64_t x_stride, float* __restrict__ buf,
+                                                           int64_t buf_stride, int Lb, int Ls, const float* __restrict__ fade_in,
+                                                           const float* __restrict__ fade_out, int block, float* __restrict__ out,
+                                                           int64_t out_stride, int* __restrict__ offset_out) {
+    extern __shared__ float sl[];
+    __shared__ float rv[256];
+    __shared__ int ri[256];
+    const int64_t s = blockIdx.x;
+    sola_block(x + s * x_stride, buf + s * buf_stride, Lb, Ls, fade_in, fade_out, block, out + s * out_stride,
+               offset_out ? offset_out + s : nullptr, sl, rv, ri);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The GUI's use_pv branch (gui.py:1076-1087): the same search, then x[off : off + Lb] is cross-faded with the previous tail by
 // the phase vocoder below instead of the sin^2 fade.  Four launches: search -> pv spectrum -> pv synthesis (into scratch) ->
 // stitch; the offset stays in device memory between them.
-static __global__ void __launch_bounds__(256) k_sola_search(const float* __restrict__ x, const float* __restrict__ buf, int Lb, int Ls,
-                                                            int* __restrict__ offset_out) {
-    extern __shared__ float sl[];
+__device__ __forceinline__ void sola_search_block(const float* __restrict__ x, const float* __restrict__ buf, int Lb, int Ls,
+                                                  int* __restrict__ offset_out, float* sl, float* rv, int* ri) {
     float* xs = sl;             // [Lb + Ls]
     float* bs = sl + Lb + Ls;   // [Lb]
-    __shared__ float rv[256];
-    __shared__ int ri[256];
     for (int i = threadIdx.x; i < Lb + Ls; i += 256) xs[i] = x[i];
     for (int i = threadIdx.x; i < Lb; i += 256) bs[i] = buf[i];
     __syncthreads();
@@ -333,16 +401,49 @@ static __global__ void __launch_bounds__(256) k_sola_search(const float* __restr
     if (threadIdx.x == 0) *offset_out = off;
 }
 
+static __global__ void __launch_bounds__(256) k_sola_search(const float* __restrict__ x, const float* __restrict__ buf, int Lb, int Ls,
+                                                            int* __restrict__ offset_out) {
+    extern __shared__ float sl[];
+    __shared__ float rv[256];
+    __shared__ int ri[256];
+    sola_search_block(x, buf, Lb, Ls, offset_out, sl, rv, ri);
+}
+
+// One block per session (blockIdx.x), rows by stride; offset_out [S].
+static __global__ void __launch_bounds__(256) k_sola_search_batch(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ buf,
+                                                                  int64_t buf_stride, int Lb, int Ls, int* __restrict__ offset_out,
+                                                                  int64_t off_stride) {
+    extern __shared__ float sl[];
+    __shared__ float rv[256];
+    __shared__ int ri[256];
+    const int64_t s = blockIdx.x;
+    sola_search_block(x + s * x_stride, buf + s * buf_stride, Lb, Ls, offset_out + s * off_stride, sl, rv, ri);
+}
+
 // out <- y[:block], buf <- y[block : block + Lb] with y = x[off:], y[:Lb] = pv.  buf is not read here (the pv launches have
 // consumed it), so any number of blocks may write it.
-static __global__ void __launch_bounds__(256) k_sola_pv_stitch(const float* __restrict__ x, const int* __restrict__ offset, const float* __restrict__ pv,
-                                                               int Lb, int block, float* __restrict__ out, float* __restrict__ buf) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void sola_pv_stitch_at(const float* __restrict__ x, const int* __restrict__ offset, const float* __restrict__ pv,
+                                                  int Lb, int block, float* __restrict__ out, float* __restrict__ buf, int i) {
     if (i >= block + Lb) return;
     const int off = *offset;
     const float v = i < Lb ? pv[i] : x[off + i];
     if (i < block) out[i] = v;
     else buf[i - block] = v;
+}
+
+static __global__ void __launch_bounds__(256) k_sola_pv_stitch(const float* __restrict__ x, const int* __restrict__ offset, const float* __restrict__ pv,
+                                                               int Lb, int block, float* __restrict__ out, float* __restrict__ buf) {
+    sola_pv_stitch_at(x, offset, pv, Lb, block, out, buf, blockIdx.x * 256 + threadIdx.x);
+}
+
+// Session blockIdx.y; pv and offset live in the session's slice of the scratch (strides in floats / ints).
+static __global__ void __launch_bounds__(256) k_sola_pv_stitch_batch(const float* __restrict__ x, int64_t x_stride, const int* __restrict__ offset,
+                                                                     int64_t off_stride, const float* __restrict__ pv, int64_t pv_stride, int Lb,
+                                                                     int block, float* __restrict__ out, int64_t out_stride,
+                                                                     float* __restrict__ buf, int64_t buf_stride) {
+    const int64_t s = blockIdx.y;
+    sola_pv_stitch_at(x + s * x_stride, offset + s * off_stride, pv + s * pv_stride, Lb, block, out + s * out_stride, buf + s * buf_stride,
+                      blockIdx.x * 256 + threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -361,10 +462,10 @@ static __global__ void __launch_bounds__(256) k_sola_pv_stitch(const float* __re
 // Spectrum: one wave per bin (grid-strided), lanes over samples.  LDS: the twiddle table (cos, sin)(2 pi m / n) built with
 // sincospi (the quarter points are exact) and the windowed inputs, 32 n bytes.  bins: absab [nb] | phia [nb] | d / n [nb].
 // b_off (optional): b is read at b + *b_off (the SOLA offset, which never leaves the device).
-static __global__ void __launch_bounds__(256) k_pv_spectrum(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
-                                                            const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
-                                                            double* __restrict__ bins) {
-    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+// (bx, gx: the block's index and the block count over the bins of ONE signal -- blockIdx.x / gridDim.x in both launch forms)
+__device__ __forceinline__ void pv_spectrum_block(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
+                                                  const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                  double* __restrict__ bins, double* pv_sm, int bx, int gx) {
     double2* tw = reinterpret_cast<double2*>(pv_sm);   // [n]
     double2* xy = tw + n;                              // [n]: (a w, b w)
     const float* bp = b + (b_off ? *b_off : 0);
@@ -378,7 +479,7 @@ static __global__ void __launch_bounds__(256) k_pv_spectrum(const float* __restr
     }
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < nb; k += gridDim.x * 4) {
+    for (int k = bx * 4 + (threadIdx.x >> 6); k < nb; k += gx * 4) {
         double ra = 0.0, ia = 0.0, rb = 0.0, ib = 0.0;
         int m = (k * lane) % n;              // (k * i) mod n, i = lane + 64 j   (k * i < 2^31 for n <= 4096)
         const int step = (k * 64) % n;
@@ -411,13 +512,30 @@ static __global__ void __launch_bounds__(256) k_pv_spectrum(const float* __restr
     }
 }
 
+static __global__ void __launch_bounds__(256) k_pv_spectrum(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
+                                                            const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                            double* __restrict__ bins) {
+    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+    pv_spectrum_block(a, b, b_off, fade_out, fade_in, n, bins, pv_sm, blockIdx.x, gridDim.x);
+}
+
+// Session blockIdx.y: a / b rows by stride, b_off and bins in the session's slice of the scratch (strides in ints / doubles).
+static __global__ void __launch_bounds__(256) k_pv_spectrum_batch(const float* __restrict__ a, int64_t a_stride, const float* __restrict__ b,
+                                                                  int64_t b_stride, const int* __restrict__ b_off, int64_t off_stride,
+                                                                  const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                                  double* __restrict__ bins, int64_t bins_stride) {
+    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+    const int64_t s = blockIdx.y;
+    pv_spectrum_block(a + s * a_stride, b + s * b_stride, b_off + s * off_stride, fade_out, fade_in, n, bins + s * bins_stride, pv_sm,
+                      blockIdx.x, gridDim.x);
+}
+
 // Synthesis: a block owns 64 consecutive samples (one per lane); its 16 waves split the bins, staged in LDS, and their
 // partial sums are added in a fixed order.  Argument per term: 2 pi ((k t) mod n) / n + (d[k] / n) t + phia[k] in fp64,
 // reduced by 2 pi rint(arg / 2 pi) into [-pi, pi] before the fp32 cosine; products and sums in fp64, one rounding at the end.
-static __global__ void __launch_bounds__(1024) k_pv_synth(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
-                                                          const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
-                                                          const double* __restrict__ bins, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+__device__ __forceinline__ void pv_synth_block(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
+                                               const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                               const double* __restrict__ bins, float* __restrict__ out, double* pv_sm, int bx) {
     const int nb = n / 2 + 1;
     double* ab = pv_sm;             // [nb]
     double* ph = ab + nb;           // [nb]
@@ -426,7 +544,7 @@ static __global__ void __launch_bounds__(1024) k_pv_synth(const float* __restric
     for (int i = threadIdx.x; i < 3 * nb; i += 1024) pv_sm[i] = bins[i];
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int t = blockIdx.x * 64 + lane;
+    const int t = bx * 64 + lane;
     const int tt = t < n ? t : 0;
     const double two_pi = 2.0 * M_PI, inv_two_pi = 1.0 / (2.0 * M_PI), w_n = 2.0 * M_PI / (double)n, td = (double)tt;
     int m = (wv * tt) % n;                  // (k * t) mod n for k = wv + 16 j
@@ -451,6 +569,24 @@ static __global__ void __launch_bounds__(1024) k_pv_synth(const float* __restric
     }
 }
 
+static __global__ void __launch_bounds__(1024) k_pv_synth(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
+                                                          const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                          const double* __restrict__ bins, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+    pv_synth_block(a, b, b_off, fade_out, fade_in, n, bins, out, pv_sm, blockIdx.x);
+}
+
+static __global__ void __launch_bounds__(1024) k_pv_synth_batch(const float* __restrict__ a, int64_t a_stride, const float* __restrict__ b,
+                                                                int64_t b_stride, const int* __restrict__ b_off, int64_t off_stride,
+                                                                const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
+                                                                const double* __restrict__ bins, int64_t bins_stride, float* __restrict__ out,
+                                                                int64_t out_stride) {
+    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
+    const int64_t s = blockIdx.y;
+    pv_synth_block(a + s * a_stride, b + s * b_stride, b_off + s * off_stride, fade_out, fade_in, n, bins + s * bins_stride,
+                   out + s * out_stride, pv_sm, blockIdx.x);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The realtime GUI's envelope mix (gui.py:1023-1056), in place on wav [n]:
 //   rms1, rms2 = librosa.feature.rms(input[:n] / wav, frame_length = 4 zc, hop_length = zc)   (k_frame_rms below)
@@ -470,13 +606,25 @@ __device__ __forceinline__ float interp_linear_ac(const float* __restrict__ r, i
     return add_rn(mul_rn(l0, r[i0]), mul_rn(l1, r[i1]));
 }
 
-static __global__ void __launch_bounds__(256) k_envelope_mix(float* __restrict__ wav, int64_t n, const float* __restrict__ rms1,
-                                                             const float* __restrict__ rms2, int nf, float e) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void envelope_mix_at(float* __restrict__ wav, int64_t n, const float* __restrict__ rms1,
+                                                const float* __restrict__ rms2, int nf, float e, int64_t t) {
     if (t >= n) return;
     const float r1 = interp_linear_ac(rms1, nf, n + 1, t);
     const float r2 = fmaxf(interp_linear_ac(rms2, nf, n + 1, t), 1e-3f);
     wav[t] = mul_rn(wav[t], powf(div_rn(r1, r2), e));
+}
+
+static __global__ void __launch_bounds__(256) k_envelope_mix(float* __restrict__ wav, int64_t n, const float* __restrict__ rms1,
+                                                             const float* __restrict__ rms2, int nf, float e) {
+    envelope_mix_at(wav, n, rms1, rms2, nf, e, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// Session blockIdx.y: wav rows by stride; rms [S][2][nf] (the session's two envelopes side by side).
+static __global__ void __launch_bounds__(256) k_envelope_mix_batch(float* __restrict__ wav, int64_t wav_stride, int64_t n,
+                                                                   const float* __restrict__ rms, int nf, float e) {
+    const int64_t s = blockIdx.y;
+    const float* r = rms + s * 2 * nf;
+    envelope_mix_at(wav + s * wav_stride, n, r, r + nf, nf, e, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -488,10 +636,8 @@ static __global__ void __launch_bounds__(256) k_envelope_mix(float* __restrict__
 // The frame energy is accumulated in fp64 (numpy sums the float32 squares in float32; its summation order for this strided
 // view is not pinned by anything in the reference, see oracle/glue_oracle.py:change_rms) and rounded to fp32 before the sqrt.
 // ------------------------------------------------------------------------------------------------
-static __global__ void __launch_bounds__(256) k_frame_rms(const float* __restrict__ y, int64_t n, int frame, int hop, int nframes,
-                                                          float* __restrict__ rms) {
-    __shared__ double red[256];
-    const int f = blockIdx.x;
+__device__ __forceinline__ void frame_rms_block(const float* __restrict__ y, int64_t n, int frame, int hop, int nframes,
+                                                float* __restrict__ rms, double* red, int f) {
     if (f >= nframes) return;
     const int64_t lo = (int64_t)f * hop - frame / 2;
     double acc = 0.0;
@@ -509,6 +655,20 @@ static __global__ void __launch_bounds__(256) k_frame_rms(const float* __restric
         __syncthreads();
     }
     if (threadIdx.x == 0) rms[f] = sqrtf((float)(red[0] / (double)frame));
+}
+
+static __global__ void __launch_bounds__(256) k_frame_rms(const float* __restrict__ y, int64_t n, int frame, int hop, int nframes,
+                                                          float* __restrict__ rms) {
+    __shared__ double red[256];
+    frame_rms_block(y, n, frame, hop, nframes, rms, red, blockIdx.x);
+}
+
+// Session blockIdx.y: y rows by stride, rms rows by rms_stride floats.
+static __global__ void __launch_bounds__(256) k_frame_rms_batch(const float* __restrict__ y, int64_t y_stride, int64_t n, int frame, int hop,
+                                                                int nframes, float* __restrict__ rms, int64_t rms_stride) {
+    __shared__ double red[256];
+    const int64_t s = blockIdx.y;
+    frame_rms_block(y + s * y_stride, n, frame, hop, nframes, rms + s * rms_stride, red, blockIdx.x);
 }
 
 __device__ __forceinline__ float interp_linear_1d(const float* __restrict__ r, int nin, int64_t nout, int64_t o) {
@@ -539,9 +699,8 @@ static __global__ void __launch_bounds__(256) k_change_rms(float* __restrict__ d
 // xpad = x padded with `width` zeros in front (and zeros behind), k < K = 2*width + of.  One thread per output sample, fp32,
 // taps added in ascending k (torchaudio's F.conv1d leaves the order to the backend).  HBM/latency-bound: n_out * K MACs,
 // K ~ 430 for the 423 -> 400 ratio of a +1 semitone shift at 40 kHz; the 400 x 437 coefficient table stays in L2.
-static __global__ void __launch_bounds__(256) k_resample_poly(const float* __restrict__ x, int64_t n, const float* __restrict__ w, int of, int nf,
-                                                       int K, int width, float* __restrict__ out, int64_t n_out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void resample_poly_at(const float* __restrict__ x, int64_t n, const float* __restrict__ w, int of, int nf, int K,
+                                                 int width, float* __restrict__ out, int64_t n_out, int64_t i) {
     if (i >= n_out) return;
     const int64_t j = i / nf;
     const int p = (int)(i - j * nf);
@@ -554,6 +713,19 @@ static __global__ void __launch_bounds__(256) k_resample_poly(const float* __res
         acc = fmaf(wp[k], xv, acc);
     }
     out[i] = acc;
+}
+
+static __global__ void __launch_bounds__(256) k_resample_poly(const float* __restrict__ x, int64_t n, const float* __restrict__ w, int of, int nf,
+                                                       int K, int width, float* __restrict__ out, int64_t n_out) {
+    resample_poly_at(x, n, w, of, nf, K, width, out, n_out, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// Session blockIdx.y: x and out rows by stride, one coefficient table.
+static __global__ void __launch_bounds__(256) k_resample_poly_batch(const float* __restrict__ x, int64_t x_stride, int64_t n,
+                                                                    const float* __restrict__ w, int of, int nf, int K, int width,
+                                                                    float* __restrict__ out, int64_t out_stride, int64_t n_out) {
+    const int64_t s = blockIdx.y;
+    resample_poly_at(x + s * x_stride, n, w, of, nf, K, width, out + s * out_stride, n_out, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 }  // namespace rvcmi

@@ -39,6 +39,8 @@ struct rvcmi_ivf {
     int64_t cap_nq = 0;
     int cap_nprobe = 0;
     DevBuf assign, P, Dtmp, Itmp, flag, cdist, cscore, qcnt, qperm;
+    DevBuf bank_q, bank_flags;  // rvcmi_ivf_search_blend_expand_batch: the sessions' searched rows packed for one search, and flags [S]
+    int64_t bank_cap_rows = 0, bank_cap_S = 0;
     int64_t cap_chunk = 0;  // queries per coarse-score chunk (bounds the nq x nlist fp32 scratch)
     // list-major scan (ivf_lm_kernels.hpp): row norms + statistics (once per handle), score scratch and work items (per capacity)
     DevBuf lm_rn, lm_S, lm_items, lm_n, lm_qinfo;
@@ -649,6 +651,43 @@ int rvcmi_ivf_search_blend_expand(rvcmi_ivf* h, int64_t nq, const float* feats, 
             hipLaunchKernelGGL(k_blend_expand, dim3((unsigned)nq), dim3(256), 0, st, feats, h->Dtmp.as<float>(), h->P.as<int64_t>(),
                                h->vecs(), d, k, h->hdr.pos_last, rate, omr, h->flag.as<int>(), skip_if_short, pitchf, protect,
                                p_len, 2, out);
+        });
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int rvcmi_ivf_search_blend_expand_batch(rvcmi_ivf* h, int S, int64_t nq, int64_t skip_rows, const float* feats, float index_rate, int k,
+                                        int skip_if_short, const float* pitchf, float protect, int64_t p_len, float* out, void* stream) {
+    return guarded([&] {
+        if (!h || !feats || !out) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
+        if (S < 1 || S > 65535) RVCMI_FAIL(RVCMI_ERR_INVALID, "S = %d outside [1, 65535]", S);
+        if (nq < 1 || nq > 0x7fffffff || skip_rows < 0 || skip_rows > nq)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "nq %lld / skip_rows %lld out of range", (long long)nq, (long long)skip_rows);
+        if (p_len < 0 || p_len > 2 * nq) RVCMI_FAIL(RVCMI_ERR_INVALID, "p_len %lld outside [0, 2*nq]", (long long)p_len);
+        if (p_len == 0) return;
+        hipStream_t st = (hipStream_t)stream;
+        const int64_t m = nq - skip_rows, rows = (int64_t)S * m;
+        const int d = h->hdr.d;
+        DeviceGuard dg(h->device);
+        if (rows > 0) {
+            reserve(h, rows);
+            if (rows > h->bank_cap_rows) {
+                h->bank_q.alloc((size_t)rows * d * 4);
+                h->bank_cap_rows = rows;
+            }
+            if (S > h->bank_cap_S) {
+                h->bank_flags.alloc((size_t)S * 4);
+                h->bank_cap_S = S;
+            }
+            // every session's rows [skip_rows, nq) packed -> ONE search over S * m rows -> the guard reduced per session
+            hipLaunchKernelGGL(k_gather_tail_rows, dim3((unsigned)m, (unsigned)S), dim3(256), 0, st, feats, nq, skip_rows, d, h->bank_q.as<float>());
+            search(h, rows, h->bank_q.as<float>(), k, h->Dtmp.as<float>(), h->Itmp.as<int64_t>(), st);
+            hipLaunchKernelGGL(k_session_short, dim3((unsigned)S), dim3(256), 0, st, (const int64_t*)h->Itmp.as<int64_t>(), m * k, h->bank_flags.as<int>());
+        }
+        const float rate = index_rate, omr = (float)(1.0 - (double)index_rate);
+        h->prof.launch("ivf_blend_x2", 2.0 * rows * k * d, (double)rows * d * 4 * (1 + k) + (double)S * p_len * d * 4, st, [&] {
+            hipLaunchKernelGGL(k_blend_expand_batch, dim3((unsigned)nq, (unsigned)S), dim3(256), 0, st, feats, (const float*)h->Dtmp.as<float>(),
+                               rows > 0 ? (const int64_t*)h->P.as<int64_t>() : nullptr, h->vecs(), d, k, h->hdr.pos_last, rate, omr,
+                               (const int*)h->bank_flags.as<int>(), skip_if_short, nq, skip_rows, pitchf, protect, p_len, 2, out);
         });
         HIP_CHECK(hipGetLastError());
     });

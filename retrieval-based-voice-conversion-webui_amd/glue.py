@@ -16,6 +16,11 @@ and of the realtime GUI's block (gui.py:934-1090, assembled by ``realtime.Realti
     phase_vocoder(a, b, fade_out, fade_in)                                    gui.py:27-49
     spectral_gate(x, xn, n_fft, hop, window, smoothing_filter, ...)           torchgate.py (gui.py:974-992, 1015-1022)
 
+and their forms for a bank of S realtime sessions (``realtime.RealtimeBank``; per session bit-equal, launch count independent of S):
+
+    retrieve_blend_expand_batch(feats [S, nq, d], index, ..., skip_rows)       one search, the realtime guard per session
+    sola_batch(infer_wav [S, n], sola_buffer [S, Lb], ...) / envelope_mix_batch(input_wav [S, .], infer_wav [S, n], zc, rate)
+
 All take and return CUDA (ROCm) tensors and enqueue on the current stream; a CPU tensor raises (no fallback).
 """
 from __future__ import annotations
@@ -81,6 +86,44 @@ def retrieve_blend_expand(feats: torch.Tensor, index, index_rate: float, pitchf:
     else:
         _blend_expand_into(out, f, index, index_rate, pf, protect, realtime_guard)
     return out.unsqueeze(0).to(feats.dtype)
+
+
+def retrieve_blend_expand_batch(feats: torch.Tensor, index, index_rate: float, pitchf: Optional[torch.Tensor] = None,
+                                protect: float = 0.5, p_len: Optional[int] = None, realtime_guard: bool = True,
+                                skip_rows: int = 0) -> torch.Tensor:
+    """``retrieve_blend_expand(..., skip_rows=...)`` for a bank of ``S`` realtime sessions: ``feats`` [S, nq, d] -> [S, p_len, d]
+    (``pitchf`` [S, >= p_len], used when ``protect < 0.5``).  Row ``s`` equals the single-session call on ``feats[s:s+1]`` bit for
+    bit, with one difference that is the point: the realtime guard is evaluated per session, so one talker whose frames probe a
+    short list does not switch retrieval off for the others.  All ``S * (nq - skip_rows)`` searched rows go through one search;
+    the launch count does not depend on ``S``."""
+    dev = _lib.on_gpu(feats, "feats")
+    if feats.dim() != 3 or feats.shape[0] < 1:
+        raise ValueError("feats must be [S, nq, d] with S >= 1")
+    S, nq, d = int(feats.shape[0]), int(feats.shape[1]), int(feats.shape[2])
+    p_len = 2 * nq if p_len is None else min(int(p_len), 2 * nq)
+    f = feats.to(torch.float32).contiguous()
+    pf = None
+    if pitchf is not None and protect < 0.5:
+        if pitchf.dim() != 2 or pitchf.shape[0] != S or pitchf.shape[1] < p_len:
+            raise ValueError("pitchf must be [%d, >= %d], got %s" % (S, p_len, tuple(pitchf.shape)))
+        pf = pitchf[:, :p_len].to(dev, torch.float32).contiguous()
+    out = torch.empty(S, p_len, d, device=dev, dtype=torch.float32)
+    h = max(0, min(int(skip_rows), nq))
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        if index is not None and index_rate != 0:
+            if d != index.d:
+                raise ValueError("index mistatch")  # the reference's message (pipeline.py:128)
+            if _lib.device_index(index.device) != _lib.device_index(dev):
+                raise _lib.RvcmiError("the index lives on %s, the features on %s: read the index on the pipeline's device "
+                                      "(read_index(path, device=...))" % (index.device, dev))
+            index.reserve(S * (nq - h))
+            _lib.check(L.rvcmi_ivf_search_blend_expand_batch(index._h, S, nq, h, _lib.ptr(f), float(index_rate), 8, 1 if realtime_guard else 0,
+                                                             _lib.ptr(pf), float(protect), p_len, _lib.ptr(out), _lib.stream_ptr(dev)))
+        else:
+            _lib.check(L.rvcmi_glue_expand_protect_batch(S, _lib.ptr(f), nq, d, 2, _lib.ptr(pf), float(protect), p_len, _lib.ptr(out),
+                                                         _lib.stream_ptr(dev)))
+    return out.to(feats.dtype)
 
 
 def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.03) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -393,6 +436,66 @@ def sola(infer_wav: torch.Tensor, sola_buffer: torch.Tensor, fade_in: torch.Tens
             _lib.check(_lib.lib().rvcmi_glue_sola(_lib.ptr(infer_wav), infer_wav.numel(), _lib.ptr(sola_buffer), Lb, int(search_frame), _lib.ptr(fade_in),
                                                   _lib.ptr(fade_out), int(block_frame), _lib.ptr(out), _lib.ptr(off), _lib.stream_ptr(dev)))
     return (out, off) if return_offset else out
+
+
+def bank_rows(t: torch.Tensor, name: str, dev=None):
+    """``t`` as the batched block DSP takes a per-session array: 2-D float32 on the GPU, unit stride along a row; the rows may be
+    slices of longer rolling buffers (row stride >= row length, which any such view has).  -> (S, row length, row stride)."""
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("%s must be a 2-D float32 tensor [S, n] with contiguous rows" % name)
+    if dev is not None and t.device != dev:
+        raise ValueError("%s must live on %s" % (name, dev))
+    if t.shape[0] < 1:
+        raise ValueError("%s: a bank has at least one session (got S = 0)" % name)
+    return int(t.shape[0]), int(t.shape[1]), int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+
+
+def sola_batch(infer_wav: torch.Tensor, sola_buffer: torch.Tensor, fade_in: torch.Tensor, fade_out: torch.Tensor, block_frame: int,
+               search_frame: int, use_pv: bool = False):
+    """``sola`` for a bank: ``infer_wav`` [S, n] and ``sola_buffer`` [S, Lb] (updated in place), rows of either may be views into
+    longer buffers.  -> (out [S, block_frame], offsets int32 [S]); session ``s`` equals ``sola`` on its rows bit for bit.  One
+    launch (four with ``use_pv``) whatever ``S``."""
+    dev = _lib.on_gpu(infer_wav, "infer_wav")
+    S, n, ws = bank_rows(infer_wav, "infer_wav")
+    Sb, Lb, bs = bank_rows(sola_buffer, "sola_buffer", dev)
+    if Sb != S:
+        raise ValueError("infer_wav has %d sessions, sola_buffer %d" % (S, Sb))
+    for t, nm in ((fade_in, "fade_in"), (fade_out, "fade_out")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != Lb:
+            raise ValueError("%s must be a contiguous float32 tensor of %d samples on %s" % (nm, Lb, dev))
+    out = torch.empty(S, int(block_frame), device=dev, dtype=torch.float32)
+    off = torch.empty(S, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        if use_pv:
+            scratch = torch.empty(S * (3 * (Lb // 2 + 1) + Lb // 2 + 1), device=dev, dtype=torch.float64)
+            _lib.check(L.rvcmi_glue_sola_pv_batch(S, _lib.ptr(infer_wav), ws, n, _lib.ptr(sola_buffer), bs, Lb, int(search_frame), _lib.ptr(fade_in),
+                                                  _lib.ptr(fade_out), int(block_frame), _lib.ptr(out), int(block_frame), _lib.ptr(off), _lib.ptr(scratch),
+                                                  _lib.stream_ptr(dev)))
+        else:
+            _lib.check(L.rvcmi_glue_sola_batch(S, _lib.ptr(infer_wav), ws, n, _lib.ptr(sola_buffer), bs, Lb, int(search_frame), _lib.ptr(fade_in),
+                                               _lib.ptr(fade_out), int(block_frame), _lib.ptr(out), int(block_frame), _lib.ptr(off), _lib.stream_ptr(dev)))
+    return out, off
+
+
+def envelope_mix_batch(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int, rms_mix_rate: float) -> torch.Tensor:
+    """``envelope_mix`` for a bank, IN PLACE on ``infer_wav`` [S, n] (returned) against the first ``n`` samples of the rows of
+    ``input_wav`` [S, >= n]; rows may be views into longer buffers.  Three launches whatever ``S``; bit-equal per session."""
+    dev = _lib.on_gpu(infer_wav, "infer_wav")
+    S, n, ws = bank_rows(infer_wav, "infer_wav")
+    Si, ni, ins = bank_rows(input_wav, "input_wav", dev)
+    if Si != S:
+        raise ValueError("infer_wav has %d sessions, input_wav %d" % (S, Si))
+    if ni < n:
+        raise ValueError("input_wav has %d samples, infer_wav %d" % (ni, n))
+    zc = int(zc)
+    if zc < 1:
+        raise ValueError("zc must be positive")
+    scratch = torch.empty(S * 2 * (1 + n // zc), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_envelope_mix_batch(S, _lib.ptr(input_wav), ins, _lib.ptr(infer_wav), ws, n, zc, float(rms_mix_rate),
+                                                            _lib.ptr(scratch), _lib.stream_ptr(dev)))
+    return infer_wav
 
 
 def phase_vocoder(a: torch.Tensor, b: torch.Tensor, fade_out: torch.Tensor, fade_in: torch.Tensor) -> torch.Tensor:

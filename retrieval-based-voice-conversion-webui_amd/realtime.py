@@ -77,6 +77,22 @@ class SincResample:
                                                                self.width, _lib.ptr(out[r]), n_out, st))
         return out.reshape(shape[:-1] + (n_out,))
 
+    def batch(self, wav: torch.Tensor) -> torch.Tensor:
+        """``wav`` [S, n] float32 whose rows may be views into longer buffers -> [S, ceil(new * n / orig)]: ONE launch for all
+        rows (``__call__`` issues one per row), each row bit-equal to ``__call__`` on it."""
+        if wav.device.type != "cuda":
+            raise _lib.RvcmiError("SincResample input must live on the GPU (no CPU fallback)")
+        S, n, stride = glue.bank_rows(wav, "wav")
+        if self.orig == self.new:
+            return wav
+        n_out = -(-self.new * n // self.orig)
+        out = torch.empty(S, n_out, device=wav.device, dtype=torch.float32)
+        with torch.cuda.device(wav.device):
+            _lib.check(_lib.lib().rvcmi_glue_resample_poly_batch(S, _lib.ptr(wav), stride, n, _lib.ptr(self.kernel), self.orig, self.new,
+                                                                 int(self.kernel.shape[1]), self.width, _lib.ptr(out), n_out, n_out,
+                                                                 _lib.stream_ptr(wav.device)))
+        return out
+
 
 class PitchCache:
     """``cache_pitch`` / ``cache_pitchf`` of rtrvc.py:63-66 and their per-block update (rtrvc.py:213-217)."""
@@ -169,6 +185,91 @@ class RealtimeVC:
                 self._resample[upp_res] = SincResample(upp_res, self.tgt_sr // 100, self.device)
             audio = self._resample[upp_res](audio[:, : return_length * upp_res].contiguous())
         return audio.squeeze()
+
+
+class RealtimeVCBatch:
+    """``RealtimeVC`` for a bank of ``S`` live sessions that share the model, the index, ``index_rate`` and ``protect``; each has its
+    own pitch cache and speaker id.  One ``infer`` is one block of EVERY session: one roll of the ``[S, 1024]`` caches, one
+    retrieval call (``glue.retrieve_blend_expand_batch``: one search over all sessions' new frames, the realtime guard per
+    session) and one ``net_g.infer`` at batch ``S``.  The launch count does not depend on ``S``.
+
+    ``formant_shift`` must be 0: a shift changes ``return_length2`` per session, i.e. asks for a ragged partial decode."""
+
+    def __init__(self, net_g, sessions: int, index=None, index_rate: float = 0.0, device="cuda:0", if_f0: int = 1, tgt_sr: int = 48000,
+                 formant_shift: float = 0.0, window: int = 160, cache_size: int = 1024):
+        if int(sessions) < 1:
+            raise ValueError("a bank has at least one session (got %d)" % int(sessions))
+        if formant_shift != 0:
+            raise ValueError("RealtimeVCBatch serves formant_shift = 0 only (got %r): a shift makes return_length2 differ per session" % (formant_shift,))
+        self.net_g, self.index, self.index_rate = net_g, index, float(index_rate)
+        self.S, self.device = int(sessions), torch.device(device)
+        self.if_f0, self.tgt_sr, self.window = int(if_f0), int(tgt_sr), int(window)
+        self.pitch = torch.zeros(self.S, cache_size, device=self.device, dtype=torch.long)
+        self.pitchf = torch.zeros(self.S, cache_size, device=self.device, dtype=torch.float32)
+        self._sid_host, self._sid = None, None
+        self._lengths = {}
+
+    def set_index_rate(self, new_index_rate):
+        self.index_rate = float(new_index_rate)
+
+    def set_formant(self, new_formant):
+        if new_formant != 0:
+            raise ValueError("RealtimeVCBatch serves formant_shift = 0 only (got %r)" % (new_formant,))
+
+    def reset(self, i: int) -> None:
+        """Session ``i``'s pitch cache back to zeros (a new talker takes the slot)."""
+        self.pitch[int(i)].zero_()
+        self.pitchf[int(i)].zero_()
+
+    def _sids(self, sid) -> torch.Tensor:
+        host = [int(sid)] * self.S if np.isscalar(sid) else [int(v) for v in sid]
+        if len(host) != self.S:
+            raise ValueError("sid must hold %d values, got %d" % (self.S, len(host)))
+        if host != self._sid_host:   # uploaded when a session's speaker changes, not per block
+            self._sid_host, self._sid = host, torch.tensor(host, dtype=torch.long, device=self.device)
+        return self._sid
+
+    def infer(self, feats: torch.Tensor, n_input_samples: int, block_frame_16k: int, skip_head: int, return_length: int,
+              pitch: Optional[torch.Tensor] = None, pitchf: Optional[torch.Tensor] = None, protect: float = 1.0, sid=0) -> torch.Tensor:
+        """``feats`` [S, n, d] (HuBERT of every session's rolling window), ``pitch`` / ``pitchf`` [S, m] (the estimator's output per
+        session; ``None`` for a model without f0), ``sid``: one id or ``S`` of them.  Returns the block's waveforms [S, L]; row ``i``
+        is what ``RealtimeVC.infer`` gives session ``i`` alone, to the batch invariance of ``net_g.infer``."""
+        if feats.dim() != 3 or feats.shape[0] != self.S:
+            raise ValueError("feats must be [%d, n, d], got %s" % (self.S, tuple(feats.shape)))
+        feats = torch.cat((feats, feats[:, -1:, :]), 1)                                   # rtrvc.py:163
+        p_len = int(n_input_samples) // self.window                                       # :189
+        return_length2 = int(return_length)                                               # :190-191 at formant_shift 0
+        pf = pitchf if (protect < 0.5 and pitch is not None and pitchf is not None) else None   # :224
+        if pf is not None and (pf.dim() != 2 or pf.shape[1] != p_len):
+            raise RuntimeError("protect < 0.5 needs pitchf of exactly p_len = %d frames per session (got %s), as the reference's broadcast at "
+                               "infer/lib/rtrvc.py:229 does" % (p_len, tuple(pf.shape)))
+        cache_pitch = cache_pitchf = None
+        if self.if_f0 == 1:
+            if pitch is None or pitchf is None:
+                raise ValueError("an f0 model needs the block's pitch / pitchf")
+            if pitch.dim() != 2 or pitch.shape[0] != self.S or pitchf.shape != pitch.shape:
+                raise ValueError("pitch / pitchf must be [%d, m], got %s / %s" % (self.S, tuple(pitch.shape), tuple(pitchf.shape)))
+            shift = int(block_frame_16k) // self.window                                   # :213-217, every session at once
+            n = int(pitch.shape[1])
+            if n < 5 or n - 4 > self.pitch.shape[1]:
+                raise ValueError("pitch block of %d frames does not fit the cache" % n)
+            if shift > 0:
+                self.pitch[:, :-shift] = self.pitch[:, shift:].clone()
+                self.pitchf[:, :-shift] = self.pitchf[:, shift:].clone()
+            self.pitch[:, 4 - n:] = pitch[:, 3:-1].to(self.device, torch.long)
+            self.pitchf[:, 4 - n:] = pitchf[:, 3:-1].to(self.device, torch.float32)
+            cache_pitch, cache_pitchf = self.pitch[:, -p_len:], self.pitchf[:, -p_len:] * return_length2 / return_length   # :216-219
+        use_index = self.index is not None and self.index_rate > 0                        # :167
+        phone = glue.retrieve_blend_expand_batch(feats, self.index if use_index else None, self.index_rate if use_index else 0.0,
+                                                 pf, protect if pf is not None else 1.0, p_len, realtime_guard=True,
+                                                 skip_rows=int(skip_head) // 2)            # :167-185, 221-233
+        lengths = self._lengths.get(p_len)
+        if lengths is None:
+            lengths = self._lengths[p_len] = torch.full((self.S,), p_len, dtype=torch.long, device=self.device)
+        with torch.no_grad():
+            audio = self.net_g.infer(phone, lengths, self._sids(sid), pitch=cache_pitch, pitchf=cache_pitchf, skip_head=skip_head,
+                                     return_length=return_length, return_length2=return_length2)   # :236-247
+        return audio.squeeze(1).float()
 
 
 def stream_geometry(samplerate: int, block_time: float = 0.25, crossfade_time: float = 0.05, extra_time: float = 2.5) -> dict:
@@ -422,3 +523,191 @@ def rvc_infer_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, ret
                 accelerate_f0_rmvpe(self.f0_gen.rmvpe)   # (beyond SURVEY 8) at least the network's GRU, once the generator has loaded it
             pitch, pitchf = self._get_f0(input_wav[-n:], key, method=f0method)
     return rt.infer(feats, int(input_wav.shape[0]), block_frame_16k, skip_head, return_length, pitch=pitch, pitchf=pitchf, protect=protect)
+
+
+def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, return_length, f0method, protect: float = 1.0,
+                        keys=None, sids=None, rt: Optional[RealtimeVCBatch] = None) -> torch.Tensor:
+    """``rvc_infer_hip`` for ``S`` sessions of one voice: ``input_wav`` [S, n16] (every session's rolling 16 kHz window) -> [S, L].
+    HuBERT runs once on the ``[S, n16]`` batch (equal lengths: the padding mask is all-false), the RMVPE network once on the
+    ``[S, .]`` f0 windows; only the salience decode is per session, with that session's key (``keys``, default the object's
+    ``f0_up_key``; ``sids`` default 0).  ``rt``: the ``RealtimeVCBatch`` that holds the sessions' pitch caches (default: one kept on
+    the object).  Not served, and refused: a precomputed ``(pitch, pitchf)`` tuple, an index object that is not ours, a formant shift."""
+    from .ivf import IVFFlatHIP
+
+    index = getattr(self, "index", None)
+    if isinstance(f0method, tuple) or (index is not None and not isinstance(index, IVFFlatHIP)):
+        raise TypeError("rvc_infer_batch_hip serves neither a precomputed (pitch, pitchf) tuple nor a foreign index object")
+    if input_wav.dim() != 2 or input_wav.shape[0] < 1:
+        raise ValueError("input_wav must be [S, n16] with S >= 1, got %s" % (tuple(input_wav.shape),))
+    if getattr(self, "formant_shift", 0) != 0:
+        raise ValueError("a bank serves formant_shift = 0 only (got %r)" % (self.formant_shift,))
+    S = int(input_wav.shape[0])
+    keys = [self.f0_up_key] * S if keys is None else list(keys)
+    sids = [0] * S if sids is None else list(sids)
+    if len(keys) != S or len(sids) != S:
+        raise ValueError("keys / sids must hold one value per session (%d)" % S)
+    if rt is None:
+        rt = getattr(self, "_rvcmi_rt_bank", None)
+        if rt is None or rt.net_g is not self.net_g or rt.S != S:
+            rt = self._rvcmi_rt_bank = RealtimeVCBatch(self.net_g, S, index=index, index_rate=self.index_rate, device=self.device,
+                                                       if_f0=self.if_f0, tgt_sr=self.tgt_sr, window=self.window)
+    elif rt.S != S:
+        raise ValueError("the RealtimeVCBatch holds %d sessions, input_wav %d" % (rt.S, S))
+    rt.index, rt.index_rate = index, float(self.index_rate)
+    with torch.no_grad():                                           # rtrvc.py:142-162, all sessions at once
+        feats = input_wav.half() if self.is_half else input_wav.float()
+        feats = feats.to(self.device)
+        mask = torch.zeros(feats.shape, dtype=torch.bool, device=feats.device)
+        from .hubert import accelerate_hubert_layers_once, accelerate_hubert_once
+
+        accelerate_hubert_once(self.hubert)
+        accelerate_hubert_layers_once(self.hubert)
+        logits = self.hubert.extract_features(source=feats, padding_mask=mask, output_layer=9 if self.version == "v1" else 12)
+        feats = self.hubert.final_proj(logits[0]) if self.version == "v1" else logits[0]
+    pitch = pitchf = None
+    if self.if_f0 == 1:                                             # rtrvc.py:203-212
+        from .pipeline import RMVPE_THRED, _torch_rmvpe
+        from .rmvpe import for_generator, rmvpe_on
+
+        n = f0_extractor_frame(block_frame_16k, f0method, self.window)
+        w = input_wav[:, -n:]
+        m = int(w.shape[1]) // self.window
+        r = _torch_rmvpe(self) if (f0method == "rmvpe" and getattr(self, "f0_gen", None) is not None) else None
+        if r is not None:
+            hip = for_generator(self.f0_gen, r) if rmvpe_on() else None
+            if hip is not None:
+                sal = hip.salience_batch([w[s].float().to(hip.device) for s in range(S)])
+            else:
+                from .gru import accelerate_f0_rmvpe
+
+                accelerate_f0_rmvpe(r)
+                with torch.no_grad():
+                    hidden = r._mel2hidden(r.mel_extractor(w.float().to(r.device), center=True))
+                sal = [hidden[s].float() for s in range(S)]
+            got = [glue.rmvpe_f0(sal[s], m, keys[s] if (hip is not None or not float(keys[s]).is_integer()) else int(keys[s]), RMVPE_THRED)
+                   for s in range(S)]                              # the only S-proportional launches of the block
+        else:
+            got = []
+            for s in range(S):
+                p, pf = self._get_f0(input_wav[s, -n:], keys[s], method=f0method)
+                got.append((p.reshape(1, -1), pf.reshape(1, -1)))
+        pitch = torch.cat([g[0].to(self.device) for g in got], 0)
+        pitchf = torch.cat([g[1].to(self.device) for g in got], 0)
+    return rt.infer(feats, int(input_wav.shape[1]), block_frame_16k, skip_head, return_length, pitch=pitch, pitchf=pitchf, protect=protect,
+                    sid=sids)
+
+
+class RealtimeBank:
+    """``S`` live streams of ONE voice in one pass per block: a bank of ``RealtimeStream`` sessions that share the model, the index,
+    the sample rate and the block geometry.  Each session has its own rolling buffers, SOLA tail, input gate, pitch cache, speaker
+    id and pitch key:
+
+        bank = RealtimeBank(rvc, sessions=S, samplerate=48000, use_pv=True)
+        out = bank.process(blocks)     # host float32 [S, block_frame] -> device float32 [S, block_frame]
+        bank.set_key(i, key); bank.set_sid(i, sid); bank.reset(i)
+        bank.last_offsets              # device int32 [S]: every session's SOLA offset of the last block
+
+    Per block: the input gate (host, per session), ONE host-to-device copy of the ``[S, m]`` block, then on the device the 16 kHz
+    resample, ``rvc_infer_batch_hip`` (HuBERT, f0, retrieval and ``net_g.infer`` at batch ``S``), the ``tgt_sr -> samplerate`` resample,
+    the envelope mix and the SOLA stitch, each as ONE set of launches for all sessions (``rvcmi_glue_*_batch``).  Nothing is read back.
+    Every DSP step is bit-equal, per session, to ``RealtimeStream``'s.  ``rvc`` is an ``rtrvc.RVC``-like object; one that has an
+    ``infer_batch(input_wav_res [S, n16], block_frame_16k, skip_head, return_length, f0method, keys, sids)`` method is asked instead
+    of ``rvc_infer_batch_hip``.
+
+    Not served, and refused by the constructor: the noise-reduction boxes, the monitor mode ``function="im"``; a formant shift is
+    refused at the first block.  The step is eager: it is not captured into a hipGraph."""
+
+    def __init__(self, rvc, sessions: int, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05,
+                 extra_time: float = 2.5, threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe",
+                 device=None, I_noise_reduce: bool = False, O_noise_reduce: bool = False, function: str = "vc", protect: float = 1.0):
+        if int(sessions) < 1:
+            raise ValueError("a bank has at least one session (got %d)" % int(sessions))
+        if I_noise_reduce or O_noise_reduce:
+            raise ValueError("RealtimeBank does not serve noise reduction (I_noise_reduce / O_noise_reduce); use RealtimeStream")
+        if function != "vc":
+            raise ValueError("RealtimeBank serves function=\"vc\" only (got %r); the monitor mode is RealtimeStream's" % (function,))
+        if rvc is None:
+            raise ValueError("RealtimeBank needs an rvc object")
+        self.rvc, self.S = rvc, int(sessions)
+        self.tgt_sr = int(rvc.tgt_sr)
+        self.samplerate = self.tgt_sr if samplerate is None else int(samplerate)
+        self.block_time, self.crossfade_time, self.extra_time = block_time, crossfade_time, extra_time
+        self.threhold, self.rms_mix_rate, self.use_pv, self.f0method = threhold, float(rms_mix_rate), bool(use_pv), f0method
+        self.protect = float(protect)
+        if device is None:
+            device = getattr(rvc, "device", None) or "cuda:0"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.RvcmiError("RealtimeBank runs on the GPU (got %s); there is no CPU fallback" % self.device)
+        for k, v in stream_geometry(self.samplerate, block_time, crossfade_time, extra_time).items():
+            setattr(self, k, v)
+        S, f32 = self.S, torch.float32
+        self.input_wav = torch.zeros(S, self.input_wav_len, device=self.device, dtype=f32)
+        self.input_wav_res = torch.zeros(S, self.input_wav_res_len, device=self.device, dtype=f32)
+        self.rms_buffer = np.zeros((S, 4 * self.zc), dtype="float32")
+        self.sola_buffer = torch.zeros(S, self.sola_buffer_frame, device=self.device, dtype=f32)
+        fade_in = torch.sin(0.5 * np.pi * torch.linspace(0.0, 1.0, steps=self.sola_buffer_frame, dtype=torch.float32)) ** 2   # gui.py:841-855
+        self.fade_in_window = fade_in.to(self.device)
+        self.fade_out_window = (1 - fade_in).to(self.device)
+        self.resampler = SincResample(self.samplerate, 16000, self.device)
+        self.resampler2 = SincResample(self.tgt_sr, self.samplerate, self.device) if self.tgt_sr != self.samplerate else None
+        self.keys = [getattr(rvc, "f0_up_key", 0)] * S
+        self.sids = [0] * S
+        self.vc = None            # the sessions' RealtimeVCBatch (pitch caches), made at the first block of a real rvc object
+        self.last_offsets = None  # device int32 [S]
+
+    def set_key(self, i: int, key) -> None:
+        self.keys[int(i)] = key
+
+    def set_sid(self, i: int, sid: int) -> None:
+        self.sids[int(i)] = int(sid)
+
+    def reset(self, i: int) -> None:
+        """Session ``i``'s state back to zeros (a new talker takes the slot); the other sessions are not touched."""
+        i = int(i)
+        if not 0 <= i < self.S:
+            raise IndexError("session %d of %d" % (i, self.S))
+        for t in (self.input_wav, self.input_wav_res, self.sola_buffer):
+            t[i].zero_()
+        self.rms_buffer[i] = 0
+        if self.vc is not None:
+            self.vc.reset(i)
+
+    def _infer(self) -> torch.Tensor:
+        args = (self.input_wav_res, self.block_frame_16k, self.skip_head, self.return_length, self.f0method)
+        if hasattr(self.rvc, "infer_batch"):
+            return self.rvc.infer_batch(*args, keys=list(self.keys), sids=list(self.sids))
+        if self.vc is None or self.vc.net_g is not self.rvc.net_g:
+            if getattr(self.rvc, "formant_shift", 0) != 0:
+                raise ValueError("a bank serves formant_shift = 0 only (got %r)" % (self.rvc.formant_shift,))
+            self.vc = RealtimeVCBatch(self.rvc.net_g, self.S, index=getattr(self.rvc, "index", None), index_rate=self.rvc.index_rate,
+                                      device=self.device, if_f0=self.rvc.if_f0, tgt_sr=self.tgt_sr, window=getattr(self.rvc, "window", 160))
+        return rvc_infer_batch_hip(self.rvc, *args, protect=self.protect, keys=self.keys, sids=self.sids, rt=self.vc)
+
+    def process(self, blocks) -> torch.Tensor:
+        x = np.asarray(blocks, dtype=np.float32)
+        if x.ndim != 2 or x.shape != (self.S, self.block_frame):
+            raise ValueError("a bank block is [%d, %d] (sessions, samples), got %s" % (self.S, self.block_frame, x.shape))
+        if self.threhold > -60:   # the input gate stays on the host, per session (gui.py:950-963)
+            x = np.stack([input_gate(x[s], self.rms_buffer[s], self.zc, self.threhold) for s in range(self.S)])
+        m = int(x.shape[1])
+        blk, blk16, zc = self.block_frame, self.block_frame_16k, self.zc
+        self.input_wav[:, :-blk] = self.input_wav[:, blk:].clone()
+        self.input_wav[:, -m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)   # the block's one host-to-device copy
+        self.input_wav_res[:, :-blk16] = self.input_wav_res[:, blk16:].clone()
+        self.input_wav_res[:, -160 * (m // zc + 1):] = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
+        infer_wav = self._infer()
+        if infer_wav.dim() != 2 or infer_wav.shape[0] != self.S:
+            raise ValueError("the model returned %s for %d sessions" % (tuple(infer_wav.shape), self.S))
+        if infer_wav.dtype != torch.float32:
+            infer_wav = infer_wav.float()
+        if self.resampler2 is not None:
+            infer_wav = self.resampler2.batch(infer_wav if infer_wav.stride(1) == 1 else infer_wav.contiguous())
+        if not infer_wav.is_contiguous():
+            infer_wav = infer_wav.contiguous()
+        if self.rms_mix_rate < 1:
+            n = int(infer_wav.shape[1])
+            glue.envelope_mix_batch(self.input_wav[:, self.extra_frame: self.extra_frame + n], infer_wav, zc, self.rms_mix_rate)
+        out, self.last_offsets = glue.sola_batch(infer_wav, self.sola_buffer, self.fade_in_window, self.fade_out_window, blk,
+                                                 self.sola_search_frame, use_pv=self.use_pv)
+        return out
