@@ -8,6 +8,7 @@
 * ``post_process``        rvc/f0/gen.py:10-41, constants :70-73,131-132
 * ``scale_int16_range``   infer/modules/vc/pipeline.py:355-359
 * ``sola``                gui.py:1057-1090 (the non-phase-vocoder branch)
+* ``envelope_mix``        gui.py:1023-1056
 
 ``oracle/make_golden.py`` pins the f0 functions to the reference's own implementations (``F0Predictor``, ``RMVPE``
 methods, ``post_process`` with numba stubbed out) on seeded inputs and stores the results in ``tests/golden/glue_f0.npz``.
@@ -94,8 +95,8 @@ def interpolate_f0(f0: np.ndarray) -> np.ndarray:
     return data
 
 
-def post_process(f0: np.ndarray, f0_up_key: int):
-    """gen.py:18,34-41 with f0_min/f0_max = 50/1100 (:70-71) -> (f0_coarse int, f0 float64)."""
+def post_process_mel(f0: np.ndarray, f0_up_key):
+    """gen.py:18,34-40: the shifted f0 and its clamped mel value BEFORE ``np.rint`` (what decides the coarse bin)."""
     f0_mel_min = 1127 * math.log(1 + 50 / 700)
     f0_mel_max = 1127 * math.log(1 + 1100 / 700)
     f0 = np.multiply(f0, pow(2, f0_up_key / 12))
@@ -103,6 +104,12 @@ def post_process(f0: np.ndarray, f0_up_key: int):
     f0_mel[f0_mel > 0] = (f0_mel[f0_mel > 0] - f0_mel_min) * 254 / (f0_mel_max - f0_mel_min) + 1
     f0_mel[f0_mel <= 1] = 1
     f0_mel[f0_mel > 255] = 255
+    return f0_mel, f0
+
+
+def post_process(f0: np.ndarray, f0_up_key):
+    """gen.py:18,34-41 with f0_min/f0_max = 50/1100 (:70-71) -> (f0_coarse int, f0 float64)."""
+    f0_mel, f0 = post_process_mel(f0, f0_up_key)
     return np.rint(f0_mel).astype(np.int32), f0
 
 
@@ -145,6 +152,19 @@ def change_rms(data1: np.ndarray, sr1: int, data2: np.ndarray, sr2: int, rate: f
     out = np.array(data2, dtype=np.float32)
     out *= (torch.pow(rms1, torch.tensor(1 - rate)) * torch.pow(rms2, torch.tensor(rate - 1))).numpy()
     return out
+
+
+def envelope_mix(inp: np.ndarray, wav: np.ndarray, zc: int, rate: float) -> np.ndarray:
+    """gui.py:1029-1056 with ``frame_rms`` above (librosa restated, UNPINNED) and torch's own interpolate / pow."""
+    n = wav.shape[0]
+    rms1 = torch.from_numpy(frame_rms(inp[:n], 4 * zc, zc)[None])
+    rms1 = F.interpolate(rms1.unsqueeze(0), size=n + 1, mode="linear", align_corners=True)[0, 0, :-1]
+    rms2 = torch.from_numpy(frame_rms(wav, 4 * zc, zc)[None])
+    rms2 = F.interpolate(rms2.unsqueeze(0), size=n + 1, mode="linear", align_corners=True)[0, 0, :-1]
+    rms2 = torch.max(rms2, torch.zeros_like(rms2) + 1e-3)
+    out = torch.from_numpy(wav.copy())
+    out *= torch.pow(rms1 / rms2, torch.tensor(1 - rate))
+    return out.numpy()
 
 
 def scale_int16_range(audio: np.ndarray) -> np.ndarray:

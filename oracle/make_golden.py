@@ -494,7 +494,8 @@ def glue_case(name: str = "glue_f0"):
     """The f0 chain of the REFERENCE itself -- RMVPE._to_local_average_cents/_decode (rvc/f0/rmvpe.py:119-164),
     F0Predictor._resize_f0/_interpolate_f0 (rvc/f0/f0.py:31-78), post_process (rvc/f0/gen.py:10-41, numba stubbed to a
     pass-through) -- on seeded salience maps with voiced/unvoiced runs, edge layouts included.  The oracle restatement is
-    checked against them, inputs and outputs are stored."""
+    checked against them, inputs and outputs are stored.  A second fixture, ``<name>_patterns``, holds the same functions' results on
+    every voiced / unvoiced pattern of 1 .. 7 frames (tests/glue_cases.py; tests/test_cpu_glue.py holds the oracle to it)."""
     import types
 
     sys.path.insert(0, REF)
@@ -561,6 +562,32 @@ def glue_case(name: str = "glue_f0"):
         out[cname + "::pitchf"] = pitchf
     np.savez_compressed(os.path.join(GOLD, name + ".npz"), **out)
     print("%-28s %d cases, oracle == reference bit-exact  (%d KB)" % (name, len(cases), os.path.getsize(os.path.join(GOLD, name + ".npz")) // 1024))
+
+    # Second fixture: EVERY voiced / unvoiced pattern of 1 .. 7 frames (tests/glue_cases.py: single-peak salience rows, nine target lengths,
+    # an integral and a fractional key) through the same reference functions.  Stored: what defines the inputs (frame count, voiced mask,
+    # target length and key per case, the peak bins and height) and the results, concatenated (case c = [off[c], off[c + 1])).
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import glue_cases
+
+    pc = glue_cases.rmvpe_pattern_cases()
+    pitch_all, pitchf_all, off = [], [], [0]
+    dec_rows = rm._decode(glue_cases.pattern_salience(glue_cases.PATTERN_MAX_N, (1 << glue_cases.PATTERN_MAX_N) - 1), thred=0.03)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for n, mask, p_len, key in pc:
+            sal = glue_cases.pattern_salience(n, mask)
+            f0a = rm._decode(sal.copy(), thred=0.03)
+            assert np.array_equal(f0a, np.where([(mask >> i) & 1 for i in range(n)], dec_rows[:n], 0.0)), (n, mask)
+            f0r = fp._interpolate_f0(fp._resize_f0(f0a, p_len))[0]
+            coarse, f0k = post_process(100, f0r.copy(), key, 1, 1127 * log(1 + 50 / 700), 1127 * log(1 + 1100 / 700), None)
+            pitch_all.append(coarse[:p_len].astype(np.int64))
+            pitchf_all.append(f0k[:p_len].astype(np.float32))
+            off.append(off[-1] + p_len)
+    pname = name + "_patterns"
+    np.savez_compressed(os.path.join(GOLD, pname + ".npz"), bins=np.array(glue_cases.PATTERN_BINS, np.int64), peak=np.float32(glue_cases.PATTERN_PEAK),
+                        n=np.array([c[0] for c in pc], np.int64), mask=np.array([c[1] for c in pc], np.int64),
+                        p_len=np.array([c[2] for c in pc], np.int64), key=np.array([c[3] for c in pc], np.float64),
+                        decoded_hz=dec_rows, off=np.array(off, np.int64), pitch=np.concatenate(pitch_all), pitchf=np.concatenate(pitchf_all))
+    print("%-28s %d cases, %d frames  (%d KB)" % (pname, len(pc), off[-1], os.path.getsize(os.path.join(GOLD, pname + ".npz")) // 1024))
 
 
 def mute_case(name: str = "mute_hubert"):

@@ -4,7 +4,6 @@ RealtimeStream over restated audio_infer blocks (tests/golden/gui_stream_*.npz).
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import load_golden
 from oracle import glue_oracle
@@ -70,19 +69,6 @@ def test_sola_pv_is_the_search_plus_the_phase_vocoder(blk, Lb, Ls, true_off, gpu
     assert torch.equal(y_p[Lb:], wav_d[off + Lb: off + blk + Lb])
 
 
-def _envelope_mix_cpu(inp, wav, zc, rate):
-    """gui.py:1029-1056 with the frame RMS of oracle/glue_oracle.py (librosa restated, UNPINNED) and torch's own interpolate / pow."""
-    n = wav.shape[0]
-    rms1 = torch.from_numpy(glue_oracle.frame_rms(inp[:n], 4 * zc, zc)[None])
-    rms1 = F.interpolate(rms1.unsqueeze(0), size=n + 1, mode="linear", align_corners=True)[0, 0, :-1]
-    rms2 = torch.from_numpy(glue_oracle.frame_rms(wav, 4 * zc, zc)[None])
-    rms2 = F.interpolate(rms2.unsqueeze(0), size=n + 1, mode="linear", align_corners=True)[0, 0, :-1]
-    rms2 = torch.max(rms2, torch.zeros_like(rms2) + 1e-3)
-    out = torch.from_numpy(wav.copy())
-    out *= torch.pow(rms1 / rms2, torch.tensor(1 - rate))
-    return out.numpy()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("rate", [0.0, 0.25, 0.8])
 @pytest.mark.parametrize("zc,n", [(400, 12000), (480, 7200), (441, 6174)])
@@ -98,7 +84,7 @@ def test_envelope_mix_matches_the_gui_expression(rate, zc, n, gpu):
     wav = (0.2 * rng.standard_normal(n)).astype(np.float32)
     wav[n // 2: n // 2 + 7 * zc] = 0.0
     wav[n // 2 + 7 * zc: n // 2 + 9 * zc] *= 1e-4
-    ref = _envelope_mix_cpu(inp, wav, zc, rate)
+    ref = glue_oracle.envelope_mix(inp, wav, zc, rate)
     w = torch.from_numpy(wav).to(gpu)
     got = rvc_amd.glue.envelope_mix(torch.from_numpy(inp).to(gpu), w, zc, rate)
     assert got.data_ptr() == w.data_ptr()

@@ -69,10 +69,16 @@ def wrapped_d_margin(a, b, fo, fi) -> float:
     return float(np.min(np.abs(u - np.round(u))))
 
 
+# the sizes of the GUI's geometries, then the edges (tests/test_gpu_glue_edges.py): windows that are all zero (n <= 2), odd / even Nyquist
+# handling where one bin is a large share of them, the wave and block widths of the kernels +- 1, the size limit and one under it
+PV_SIZES = ((1280, 32000), (1600, 40000), (1920, 48000), (1323, 44100))
+PV_EDGE_SIZES = tuple((n, 48000) for n in (1, 2, 3, 4, 5, 63, 64, 65, 4095, 4096))
+
+
 def pv_fixture():
     pv, pv_raw = load_phase_vocoder(True), load_phase_vocoder(False)
     out = {}
-    for n, sr in ((1280, 32000), (1600, 40000), (1920, 48000), (1323, 44100)):
+    for n, sr in PV_SIZES + PV_EDGE_SIZES:
         fi, fo = fade_windows(n)
         out["n%d_fade_in" % n], out["n%d_fade_out" % n] = fi.numpy(), fo.numpy()
         seed = n
