@@ -163,6 +163,35 @@ int rvcmi_nsf_profile_enable(rvcmi_nsf* h, int enable);
 int rvcmi_nsf_set_option(rvcmi_nsf* h, const char* key, double value);
 int rvcmi_nsf_profile_read(rvcmi_nsf* h, rvcmi_kernel_stat* stats, int capacity, int* n, int reset);
 
+/* How the last forward of a handle ran each upsampling stage's ResBlocks (tests and tools; product code does not call this).
+ * One record per stage the forward reached, written by the forward itself from the values it launched with.  Every field is an int. */
+enum { RVCMI_RB_F32_CHAIN = 0, RVCMI_RB_SPLIT = 1, RVCMI_RB_STREAM = 2, RVCMI_RB_FULL = 3, RVCMI_RB_PAIR = 4 };
+typedef struct {
+    int path;          /* RVCMI_RB_*: conv by conv in fp32 / output-channel-split convs per pair level / whole ResBlocks on the streaming
+                        * kernel / whole ResBlocks fused, one launch / one launch per pair level                                       */
+    int C;             /* channels of the stage                                                                                        */
+    int B, rows;       /* batch items, rows per item (T x the upsample rates so far)                                                   */
+    int x0_half;       /* the upsampler's output, the ResBlocks' input, is stored as fp16                                              */
+    int y_half;        /* the ResBlocks' output streams are stored as fp16                                                             */
+    int tile_rows;     /* FULL, PAIR: rows a block computes (a ResBlock keeps tile_rows minus its halo of them)                        */
+    int tile_waves;    /* FULL: waves per block                                                                                        */
+    int n_rb;          /* STREAM, FULL, PAIR: ResBlocks described below, in launch order (largest kernel size first)                   */
+    int k[RVCMI_MAX_RB];          /* kernel size                                                                                       */
+    int tiles[RVCMI_MAX_RB];      /* FULL, PAIR: tiles per item (PAIR: of every pair level); STREAM: strips per item                   */
+    int strip_len[RVCMI_MAX_RB];  /* STREAM: rows per strip, strips x strip_len >= rows                                                */
+    int stream_nj;     /* STREAM: the kernel advances 32 x stream_nj rows per step                                                     */
+    int stream_mfma;   /* STREAM: MFMA shape of its K loops, 16 (v_mfma_f32_16x16x32) or 32 (32x32x16)                                 */
+    int stream_fill_skip;  /* STREAM: a strip's first step skips its pipeline-fill column tiles                                        */
+    int pair_streamed; /* PAIR: bit m set = pair level m ran on the streaming kernel's pair-level form                                 */
+    int num_cus;       /* compute units the planner saw                                                                                */
+} rvcmi_nsf_stage_plan;
+/* Copies the *n records of the last forward to out[0 .. *n).  A capacity smaller than the number of records is
+ * RVCMI_ERR_INVALID and writes nothing, neither out nor *n (RVCMI_MAX_UPS always suffices).  A handle that has not run a forward reports *n = 0.
+ *   - A forward that ended at a debug tap (rvcmi_nsf_debug_forward) reports the stages planned up to the tap; of a stage whose
+ *     ResBlocks did not run ("up<i>") the fields from tile_rows to pair_streamed are zero.
+ *   - Replaying a captured graph runs no host code of the forward: the record stays that of the capturing call.               */
+int rvcmi_nsf_last_plan(const rvcmi_nsf* h, rvcmi_nsf_stage_plan* out, int capacity, int* n);
+
 /* ------------------------------------------------------------------------------------------- */
 /* Synthesizer front: enc_p + prior sampling + flow^-1              */
 /* ------------------------------------------------------------------------------------------- */

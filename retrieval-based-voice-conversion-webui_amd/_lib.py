@@ -55,6 +55,15 @@ class KernelStat(C.Structure):
                 ("bytes", C.c_double)]
 
 
+class NsfStagePlan(C.Structure):  # rvcmi_nsf_stage_plan: ints only
+    _fields_ = [(n, C.c_int) for n in ("path", "C", "B", "rows", "x0_half", "y_half", "tile_rows", "tile_waves", "n_rb")] + [
+        (n, C.c_int * RVCMI_MAX_RB) for n in ("k", "tiles", "strip_len")] + [
+        (n, C.c_int) for n in ("stream_nj", "stream_mfma", "stream_fill_skip", "pair_streamed", "num_cus")]
+
+
+RB_PATHS = ("F32_CHAIN", "SPLIT", "STREAM", "FULL", "PAIR")  # RVCMI_RB_*
+
+
 # every symbol include/rvcmi.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -70,6 +79,7 @@ SYMBOLS = [
     ("rvcmi_nsf_set_option", C.c_int, [_P, C.c_char_p, C.c_double]),
     ("rvcmi_nsf_profile_enable", C.c_int, [_P, C.c_int]),
     ("rvcmi_nsf_profile_read", C.c_int, [_P, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int), C.c_int]),
+    ("rvcmi_nsf_last_plan", C.c_int, [_P, C.POINTER(NsfStagePlan), C.c_int, C.POINTER(C.c_int)]),
     ("rvcmi_front_create", C.c_int, [C.POINTER(FrontConfig), C.POINTER(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     ("rvcmi_front_destroy", C.c_int, [_P]),
     ("rvcmi_front_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
@@ -223,7 +233,7 @@ def build(verbose: bool = True, force: bool = False) -> str:
             # nsf.hip alone, none with this option; the 512-register kernels keep their overflow in AGPRs
             cmd[1:1] = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
         for d_ in os.environ.get("RVCMI_DEFINES", "").split():
-            cmd.insert(1, "-D" + d_)  # dev: geometry experiments, e.g. RVCMI_DEFINES="RBF32_NWV=8"
+            cmd.insert(1, "-D" + d_)  # dev: geometry experiments, e.g. RVCMI_DEFINES="RB256_NJ=3"
         if os.environ.get("RVCMI_DEV_STAMPS"):
             cmd.insert(1, "-DRVCMI_DEV_STAMPS")  # per-phase s_memtime stamps in the fused kernels (RVCMI_DBG=32)
         if verbose:

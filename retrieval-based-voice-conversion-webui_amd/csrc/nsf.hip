@@ -69,6 +69,9 @@ struct rvcmi_nsf {
     DevBuf P, X0, Ya[RVCMI_MAX_RB], Yb[RVCMI_MAX_RB], H, NZ, har, har2, x2, phase, condv, dbg;
     size_t ws_bytes = 0;
     Profiler prof;
+    // what the last forward planned, per stage it reached (rvcmi_nsf_last_plan)
+    rvcmi_nsf_stage_plan last_plan[RVCMI_MAX_UPS];
+    int n_plan = 0;
     // dev / test options (common.hpp Options): RB_STREAM (absent = auto, 1 = streaming resblock kernels whenever supported, 0 = never),
     // NO_RB_SPLIT, Y_F16, X0_F16, X0_F16_NOSTREAM, POST_DMA, POST_DBG, RBF_PAD_TAP, RBF32_TALL, DBG (timing-ablation bit mask: results are WRONG when
     // non-zero) and
@@ -341,7 +344,6 @@ template <typename OpT>
 static void set_lds_rb();
 template <typename OpT>
 static void set_lds_ups();
-template <typename OpT>
 static void set_lds_rbf();
 static void set_lds_limits() {
     set_lds_all<__bf16>();
@@ -350,8 +352,7 @@ static void set_lds_limits() {
     set_lds_rb<_Float16>();
     set_lds_ups<__bf16>();
     set_lds_ups<_Float16>();
-    set_lds_rbf<__bf16>();
-    set_lds_rbf<_Float16>();
+    set_lds_rbf();
 }
 
 
@@ -458,102 +459,67 @@ static void set_lds_ups() {
 }
 
 // ---- fully fused resblock (C <= 64) ----------------------------------------------------------------
-#ifndef RBF32_NJ
-#define RBF32_NJ 3
-#define RBF32_OCC 2
-#endif
-template <int C> struct RbFullGeom;
-// C=64 uses 3 column tiles per wave (R = 384): x(96) + h(96) accumulators + operands stay under 512 registers without spills
-// (NJ = 4 spilled ~100 registers to scratch)
-#ifndef RBF64_NWV
-#define RBF64_NWV 8
-#endif
-#if RBF64_NWV == 8
-// C=64: 8 waves (2 per SIMD) x 64 rows = R 512: the co-resident wave hides the K loop's issue overhead, and the
-// larger tile wastes less on overlap-save than R = 384 (x+h accumulators: 64+64 registers per wave)
-template <> struct RbFullGeom<64> { static constexpr int MI = 2, NJ = 2, KG = 4, OCC = 2, NWV = 8; };
-#else
-template <> struct RbFullGeom<64> { static constexpr int MI = 2, NJ = 3, KG = 4, OCC = 1, NWV = 4; };
-#endif
-// C <= 32: R = 384 keeps the two operand tiles at 68 KB and the kernel under 256 registers => 2 blocks per CU, so one
-// block's load / publish / store phases overlap the other's MFMA phases (worth more than the extra overlap-save waste of a
-// 512-row tile of four waves, which is what it was measured against).  Long launches at C = 32 take the 768-row class below:
-// the same eight waves per CU as ONE block, the same work and registers per wave, 648 / 696 / 744 kept rows of 768 instead of
-// 264 / 312 / 360 of 384.
-#ifndef RBF32_NWV
-#define RBF32_NWV 4
-#endif
-template <> struct RbFullGeom<32> { static constexpr int MI = 1, NJ = RBF32_NJ, KG = 4, OCC = RBF32_OCC, NWV = RBF32_NWV; };
-template <> struct RbFullGeom<16> { static constexpr int MI = 1, NJ = RBF32_NJ, KG = 4, OCC = RBF32_OCC, NWV = RBF32_NWV; };
-static int rbf_rows(int C) { return C == 64 ? RbFullGeom<64>::NWV * 32 * RbFullGeom<64>::NJ : RBF32_NWV * 32 * RBF32_NJ; }
-// weight-prefetch depth (register buffers): the 8-wave geometry has 256 registers per wave, a 2-deep ring fits without spills
-template <int C>
-constexpr int rbf_nb() { return RbFullGeom<C>::NWV == 8 ? 2 : 3; }
-template <typename OpT, int C>
-static void launch_rbf_inst(const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st) {
-    using G = RbFullGeom<C>;
-    constexpr int R = G::NWV * 32 * G::NJ;
-    const size_t smem = (size_t)(R + 2 * RBF_G + R + 2 * RBF_G2) * Tile<C>::STRIDE + 3 * 2 * 32 * G::MI * 4 + 512;  // + bias vectors + dev phase stamps
-    hipLaunchKernelGGL((k_rb_full<OpT, C, G::MI, G::NJ, G::KG, rbf_nb<C>(), G::OCC, G::NWV>), dim3(tiles, nj, B), dim3(64 * G::NWV), smem, st, ra);
-}
-// C = 64 on a launch of a few tiles (a realtime chunk's 6200 rows = 44 tiles of 512 rows on 256 CUs, the launch as long as ONE k = 11 tile:
-// 50 us): 256-row tiles of four waves -- 107 blocks, each half as long.  Two accumulator sets of 64 registers + a 3-deep ring: no spills.
-constexpr int RBF64S_NJ = 2, RBF64S_NWV = 4, RBF64S_ROWS = RBF64S_NWV * 32 * RBF64S_NJ;
-// (the same 256-row geometry for C <= 32, two blocks per CU: a chunk's 12 400 rows are 122 tiles of 384 rows, 214 of 256)
-template <typename OpT, int C>
-static void launch_rbf_small(const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st) {
-    constexpr int R = RBF64S_ROWS, MI = C == 64 ? 2 : 1, OCCS = C == 64 ? 1 : 2;
-    const size_t smem = (size_t)(R + 2 * RBF_G + R + 2 * RBF_G2) * Tile<C>::STRIDE + 3 * 2 * 32 * MI * 4 + 512;
-    hipLaunchKernelGGL((k_rb_full<OpT, C, MI, RBF64S_NJ, 4, 3, OCCS, RBF64S_NWV>), dim3(tiles, nj, B), dim3(64 * RBF64S_NWV), smem, st, ra);
-}
-// C = 32 on a launch of many tiles: 768-row tiles of eight waves, one block per CU (X | H: 129 KB of LDS)
-constexpr int RBF32T_NJ = 3, RBF32T_NWV = 8, RBF32T_NB = 3, RBF32T_ROWS = RBF32T_NWV * 32 * RBF32T_NJ;
-template <typename OpT>
-static void launch_rbf_tall(const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st) {
-    constexpr int R = RBF32T_ROWS;
-    const size_t smem = (size_t)(R + 2 * RBF_G + R + 2 * RBF_G2) * Tile<32>::STRIDE + 3 * 2 * 32 * 4 + 1024;
-    hipLaunchKernelGGL((k_rb_full<OpT, 32, 1, RBF32T_NJ, 4, RBF32T_NB, 1, RBF32T_NWV>), dim3(tiles, nj, B), dim3(64 * RBF32T_NWV), smem, st, ra);
-}
-template <typename OpT>
-static void launch_rbf_t(int C, const RbFullArgs& ra, int tiles, int nj, int B, hipStream_t st, bool small64, bool tall32) {
-    if (tall32 && C == 32) return launch_rbf_tall<OpT>(ra, tiles, nj, B, st);
-    if (small64 && C == 64) return launch_rbf_small<OpT, 64>(ra, tiles, nj, B, st);
-    if (small64 && C == 32) return launch_rbf_small<OpT, 32>(ra, tiles, nj, B, st);
-    switch (C) {
-        case 64: return launch_rbf_inst<OpT, 64>(ra, tiles, nj, B, st);
-        case 32: return launch_rbf_inst<OpT, 32>(ra, tiles, nj, B, st);
-        case 16: return launch_rbf_inst<OpT, 16>(ra, tiles, nj, B, st);
-        default: RVCMI_FAIL(RVCMI_ERR_INVALID, "fused resblock: unsupported channel count %d", C);
+// One launch of k_rb_full for the whole stage; the tile classes it is instantiated for are the rows of RBF_CLASSES below.
+// `ra` == nullptr: only set the > 64 KB dynamic-LDS attribute of the instantiation (set_lds_limits).
+template <typename OpT, int C, int MI, int NJ, int NB, int OCC, int NWV>
+static void launch_rbf(size_t smem, const RbFullArgs* ra, int tiles, int nj, int B, hipStream_t st) {
+    auto kern = &k_rb_full<OpT, C, MI, NJ, /*KG*/ 4, NB, OCC, NWV>;
+    if (!ra) {
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        return;
     }
+    hipLaunchKernelGGL(kern, dim3(tiles, nj, B), dim3(64 * NWV), smem, st, *ra);
 }
-template <typename OpT>
+struct RbFullClass {
+    int C, rows, waves;      // rows = waves x 32 NJ: what a block computes; a resblock keeps rows - 2 halo of them
+    int MI, NJ, NB, OCC;     // the template parameters: NB = weight-prefetch depth (register buffers), OCC = blocks per CU
+    size_t lds_bytes;        // X | H operand tiles + bias vectors + the bytes reserved for the dev phase stamps
+    void (*launch[2])(size_t, const RbFullArgs*, int, int, int, hipStream_t);  // bf16, fp16 operands
+};
+#define RBF_CLASS(C_, MI_, NJ_, NB_, OCC_, NWV_, STAMP_B_)                                                                     \
+    {C_, NWV_ * 32 * NJ_, NWV_, MI_, NJ_, NB_, OCC_,                                                                           \
+     (size_t)(2 * (NWV_ * 32 * NJ_) + 2 * RBF_G + 2 * RBF_G2) * Tile<C_>::STRIDE + 3 * 2 * 32 * MI_ * 4 + STAMP_B_,            \
+     {&launch_rbf<__bf16, C_, MI_, NJ_, NB_, OCC_, NWV_>, &launch_rbf<_Float16, C_, MI_, NJ_, NB_, OCC_, NWV_>}}
+static constexpr RbFullClass RBF_CLASSES[] = {
+    // The default classes.  C = 64, 512 rows: 8 waves (2 per SIMD) x 64 rows: the co-resident wave hides the K loop's issue overhead, and the larger
+    // tile wastes less on overlap-save than 384 rows (x + h accumulators: 64 + 64 registers per wave; 256 registers per wave, a 2-deep ring fits)
+    RBF_CLASS(64, 2, 2, 2, 2, 8, 512),
+    // C <= 32, 384 rows: keeps the two operand tiles at 68 KB and the kernel under 256 registers => 2 blocks per CU, so one block's load /
+    // publish / store phases overlap the other's MFMA phases (worth more than the extra overlap-save waste of a 512-row tile of four waves,
+    // which is what it was measured against)
+    RBF_CLASS(32, 1, 3, 3, 2, 4, 512),
+    RBF_CLASS(16, 1, 3, 3, 2, 4, 512),
+    // 256 rows, for a launch of a few tiles.  C = 64 (a realtime chunk's 6200 rows = 44 tiles of 512 rows on 256 CUs, the launch as long as ONE
+    // k = 11 tile: 50 us): four waves -- 107 blocks, each half as long; two accumulator sets of 64 registers + a 3-deep ring: no spills.
+    RBF_CLASS(64, 2, 2, 3, 1, 4, 512),
+    // C = 32, two blocks per CU: a chunk's 12 400 rows are 122 tiles of 384 rows, 214 of 256
+    RBF_CLASS(32, 1, 2, 3, 2, 4, 512),
+    // C = 32, 768 rows, for a launch of many tiles: the same eight waves per CU as ONE block (X | H: 129 KB of LDS), the same work and registers
+    // per wave, 648 / 696 / 744 kept rows of 768 instead of 264 / 312 / 360 of 384
+    RBF_CLASS(32, 1, 3, 3, 1, 8, 1024),
+};
+#undef RBF_CLASS
+constexpr int RBF_SMALL_ROWS = 256, RBF_TALL_ROWS = 768;
+static int rbf_default_rows(int C) { return C == 64 ? 512 : 384; }
+static const RbFullClass* rbf_class(int C, int rows) {
+    for (const RbFullClass& c : RBF_CLASSES)
+        if (c.C == C && c.rows == rows) return &c;
+    RVCMI_FAIL(RVCMI_ERR_INVALID, "fused resblock: no %d-row tile class for channel count %d", rows, C);
+}
 static void set_lds_rbf() {
-#define RBF_ATTR(C_)                                                                                                        \
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, C_, RbFullGeom<C_>::MI, RbFullGeom<C_>::NJ, RbFullGeom<C_>::KG, rbf_nb<C_>(), RbFullGeom<C_>::OCC, RbFullGeom<C_>::NWV>), \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RBF_ATTR(64) RBF_ATTR(32) RBF_ATTR(16)
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, 64, 2, RBF64S_NJ, 4, 3, 1, RBF64S_NWV>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, 32, 1, RBF64S_NJ, 4, 3, 2, RBF64S_NWV>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rb_full<OpT, 32, 1, RBF32T_NJ, 4, RBF32T_NB, 1, RBF32T_NWV>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#undef RBF_ATTR
+    for (const RbFullClass& c : RBF_CLASSES)
+        for (auto launch : c.launch) launch(c.lds_bytes, nullptr, 0, 0, 0, nullptr);
 }
 
+// A three-way option: 0 = never, 1 = always, absent (or anything else) = 2, the planner decides.
+static int tri_mode(const rvcmi_nsf* h, const char* key) {
+    const int v = h->opt.has(key) ? h->opt.geti(key, 2) : 2;
+    return v == 0 || v == 1 ? v : 2;
+}
 // option RBF32_TALL: absent = auto (plan_stage), 1 = the 768-row class at C = 32 always, 0 = never.
-static int rbf32_tall_mode(const rvcmi_nsf* h) {
-    if (!h->opt.has("RBF32_TALL")) return 2;
-    const int v = h->opt.geti("RBF32_TALL", 2);
-    return v == 0 ? 0 : (v == 1 ? 1 : 2);
-}
-
+static int rbf32_tall_mode(const rvcmi_nsf* h) { return tri_mode(h, "RBF32_TALL"); }
 // option RB_STREAM: absent = auto (streaming kernel when the strips are long enough), 1 = always when supported, 0 = never.
-static int rb_stream_mode(const rvcmi_nsf* h) {
-    if (!h->opt.has("RB_STREAM")) return 2;
-    const int v = h->opt.geti("RB_STREAM", 2);
-    return v == 0 ? 0 : (v == 1 ? 1 : 2);
-}
+static int rb_stream_mode(const rvcmi_nsf* h) { return tri_mode(h, "RB_STREAM"); }
 
 // Option Y_F16 (default 1): the whole-ResBlock kernels (k_rb_stream ND = 3, k_rb_full) write their output streams Ya[j] as fp16
 // and the next stage's k_ups / k_post read them as such (nsf_kernels.hpp pack4_h).  0 = fp32 streams (round 3).
@@ -752,6 +718,7 @@ struct Fwd {
     const float* har;    // excitation [B][Te * upp] (use_f0)
     hipStream_t st;
     TapRequest* tr;
+    rvcmi_nsf_stage_plan* rec;  // the running stage's record in the handle (rvcmi_nsf_last_plan)
     bool want(const char* w) const { return tr && strcmp(tr->what, w) == 0; }
 };
 
@@ -774,13 +741,14 @@ using RbLevels = std::vector<std::pair<ConvLayer, ConvLayer>>;  // one resblock:
 //   STREAM     whole resblocks on the streaming kernel (rb_stream_kernels.hpp): persistent blocks walk strips of the time axis
 //   FULL       whole resblocks fused, x resident in registers (C <= 64): ONE launch for the stage   residuals.py:68-85
 //   PAIR       one launch per pair level (k_rb_pair, or at C = 256 the streaming kernel with ND = 1 where its planner takes it)
-enum class RbPath { F32_CHAIN, SPLIT, STREAM, FULL, PAIR };
+enum class RbPath { F32_CHAIN = RVCMI_RB_F32_CHAIN, SPLIT = RVCMI_RB_SPLIT, STREAM = RVCMI_RB_STREAM, FULL = RVCMI_RB_FULL, PAIR = RVCMI_RB_PAIR };
 struct StagePlan {
     RbPath path;
     bool x0_half;     // the upsampler writes X0 as fp16
     bool stage_half;  // the resblocks write their output streams as fp16
-    bool small64;     // FULL: 256-row tiles (launch_rbf_small)
-    bool tall32;      // FULL, C = 32: 768-row tiles (launch_rbf_tall); never together with small64
+    const RbFullClass* full;  // FULL: the tile class (a row of RBF_CLASSES)
+    RbStreamPlan stream;      // STREAM: the launch, planned, with the flops and bytes the profiler books for it
+    double flops, bytes;
 };
 
 static float* ydst(rvcmi_nsf* h, size_t j, size_t m) { return (m & 1) ? h->Yb[j].as<float>() : h->Ya[j].as<float>(); }
@@ -859,7 +827,7 @@ static StagePlan plan_stage(const Fwd& f, const Stage& s, long L, int lm) {
     // once per stage; the stream itself stays fp32 inside the kernels): +1.1e-4 RMS on the full-clip golden, measured on the oracle and
     // gated by the same 5e-4 test.  0 = fp32 X0.
     const bool x0h = yh && h->opt.geti("X0_F16", 1) != 0;
-    StagePlan p = {RbPath::PAIR, false, false, false, false};
+    StagePlan p{RbPath::PAIR};
     if (op == RVCMI_OPERAND_F32) {
         p.path = RbPath::F32_CHAIN;
         return p;
@@ -876,18 +844,25 @@ static StagePlan plan_stage(const Fwd& f, const Stage& s, long L, int lm) {
     bool stream = mode != 0 && nk <= 3 && rb_stream_supported(op, C, 3);
     for (int j = 0; j < nk; ++j) stream = stream && s.rb[j].size() == 3;
     if (stream) {
-        // a dry run of the planner: it refuses short strips, and fp16 input rows outside the kernel form that reads them (option RS_KL)
+        // the planner refuses short strips, and fp16 input rows outside the kernel form that reads them (option RS_KL)
         auto plans = [&](bool xhalf) {
             RbStreamDesc sd[3];
-            double flops = 0, bytes = 0;
-            stream_jobs(f, s, L, lm, xhalf, yh, sd, flops, bytes);
-            return rb_stream_launch(op, C, 3, sd, nk, (int)L, f.B, L * C, mode == 1, f.st, h->opt, true);
+            p.flops = p.bytes = 0;
+            stream_jobs(f, s, L, lm, xhalf, yh, sd, p.flops, p.bytes);
+            p.stream = rb_stream_plan(op, C, 3, sd, nk, (int)L, f.B, L * C, mode == 1, h->opt);
+            return p.stream.ok;
         };
         const bool xh = x0h && !h->opt.on("X0_F16_NOSTREAM") && plans(true);
-        if (xh || plans(false)) return {RbPath::STREAM, xh, yh, false, false};
+        if (xh || plans(false)) {
+            p.path = RbPath::STREAM;
+            p.x0_half = xh;
+            p.stage_half = yh;
+            return p;
+        }
     }
     if (C <= 64 && max_levels(s) <= 3) {
-        p = {RbPath::FULL, x0h, yh, false, false};
+        const int R0 = rbf_default_rows(C);
+        p = {RbPath::FULL, x0h, yh, rbf_class(C, R0)};
         // (C = 64) short launches take 256-row tiles: at 512 rows they would be fewer blocks than half the CUs (halo of the k = 11
         // resblock: 120 rows either way -- the small tiles keep 136 of 256 rows)
         if (C == 64 || C == 32) {
@@ -895,19 +870,17 @@ static StagePlan plan_stage(const Fwd& f, const Stage& s, long L, int lm) {
             bool fits768 = true;
             for (int j = 0; j < nk; ++j) {
                 const int HL = rbf_halo(s.rb[j]);
-                blocks512 += (L + (rbf_rows(C) - 2 * HL) - 1) / (rbf_rows(C) - 2 * HL) * f.B;
-                if (RBF64S_ROWS - 2 * HL < RBF64S_ROWS / 4) blocks512 = 1 << 30;  // (halo too large for the small tile)
-                blocks768 += (L + (RBF32T_ROWS - 2 * HL) - 1) / (RBF32T_ROWS - 2 * HL) * f.B;
-                fits768 = fits768 && RBF32T_ROWS - 2 * HL >= RBF32T_ROWS / 4;
+                blocks512 += (L + (R0 - 2 * HL) - 1) / (R0 - 2 * HL) * f.B;
+                if (RBF_SMALL_ROWS - 2 * HL < RBF_SMALL_ROWS / 4) blocks512 = 1 << 30;  // (halo too large for the small tile)
+                blocks768 += (L + (RBF_TALL_ROWS - 2 * HL) - 1) / (RBF_TALL_ROWS - 2 * HL) * f.B;
+                fits768 = fits768 && RBF_TALL_ROWS - 2 * HL >= RBF_TALL_ROWS / 4;
             }
-            p.small64 = blocks512 < num_cus() / 2 * (C == 64 ? 1 : 2);
+            const bool small = blocks512 < num_cus() / 2 * (C == 64 ? 1 : 2);
             // (C = 32) long launches take 768-row tiles, one block of eight waves per CU: a quarter of the rows of a 384-row tile is halo,
             // 3 to 16 % of a 768-row one.  From four blocks per CU on, so that the tail of the launch (blocks twice as long) stays short.
-            if (C == 32 && fits768) {
-                const int tall = rbf32_tall_mode(h);
-                p.tall32 = tall == 1 || (tall == 2 && !p.small64 && blocks768 >= 4L * num_cus());
-                if (p.tall32) p.small64 = false;
-            }
+            const int tall = C == 32 && fits768 ? rbf32_tall_mode(h) : 0;
+            if (tall == 1 || (tall == 2 && !small && blocks768 >= 4L * num_cus())) p.full = rbf_class(C, RBF_TALL_ROWS);
+            else if (small) p.full = rbf_class(C, RBF_SMALL_ROWS);
         }
     }
     return p;
@@ -1190,19 +1163,25 @@ static void rb_split(const Fwd& f, const Stage& s, long L, int lm, const float**
     }
 }
 
-static void rb_stream(const Fwd& f, const Stage& s, const StagePlan& p, long L, int lm, const float** src) {
+static void rb_stream(const Fwd& f, const Stage& s, const StagePlan& p, const float** src) {
     rvcmi_nsf* h = f.h;
-    const int C = s.cout, nk = (int)s.rb.size();
-    RbStreamDesc sd[3];
-    double flops = 0, bytes = 0;
-    stream_jobs(f, s, L, lm, p.x0_half, p.stage_half, sd, flops, bytes);
+    const int nk = (int)s.rb.size();
     char nm[48];
-    snprintf(nm, sizeof(nm), "rb_stream_c%d", C);
-    h->prof.launch(nm, flops, bytes, f.st, [&] {
-        rb_stream_launch(f.op, C, 3, sd, nk, (int)L, f.B, L * C, rb_stream_mode(h) == 1, f.st, h->opt);
-    });
+    snprintf(nm, sizeof(nm), "rb_stream_c%d", s.cout);
+    h->prof.launch(nm, p.flops, p.bytes, f.st, [&] { rb_stream_run(p.stream, f.st, h->opt); });
     HIP_CHECK(hipGetLastError());
-    for (int j = 0; j < nk; ++j) src[j] = h->Ya[j].as<float>();
+    rvcmi_nsf_stage_plan& r = *f.rec;
+    r.n_rb = nk;
+    r.stream_nj = p.stream.NJ;
+    r.stream_mfma = p.stream.mfma();
+    r.stream_fill_skip = p.stream.fill_skip();
+    for (int j = 0; j < nk; ++j) {
+        const RbStreamJob& J = p.stream.args.job[j];
+        r.k[j] = J.k;
+        r.tiles[j] = J.nstrips;
+        r.strip_len[j] = J.strip_len;
+        src[j] = h->Ya[j].as<float>();
+    }
 }
 
 static void rb_full(const Fwd& f, const Stage& s, const StagePlan& p, long L, int lm, const float** src) {
@@ -1220,7 +1199,11 @@ static void rb_full(const Fwd& f, const Stage& s, const StagePlan& p, long L, in
     ra.yh = p.stage_half ? 1 : 0;
     ra.xh = p.x0_half ? 1 : 0;
     ra.pad_tap = h->opt.geti("RBF_PAD_TAP", 0) != 0 ? 1 : 0;
-    const int R = p.tall32 ? RBF32T_ROWS : (p.small64 ? RBF64S_ROWS : rbf_rows(C));
+    const int R = p.full->rows;
+    rvcmi_nsf_stage_plan& r = *f.rec;
+    r.tile_rows = R;
+    r.tile_waves = p.full->waves;
+    r.n_rb = nk;
     int order[RVCMI_MAX_RB];
     rb_order(s, order);
     int max_tiles = 0;
@@ -1239,20 +1222,16 @@ static void rb_full(const Fwd& f, const Stage& s, const StagePlan& p, long L, in
         if (J.tvalid < R / 4) RVCMI_FAIL(RVCMI_ERR_INVALID, "resblock halo too large for the fused kernel");
         J.ntiles = (int)((L + J.tvalid - 1) / J.tvalid);
         max_tiles = std::max(max_tiles, J.ntiles);
+        r.k[oj] = J.k;
+        r.tiles[oj] = J.ntiles;
         bytes += (double)B * L * C * ((p.stage_half ? 2 : 4) + (p.x0_half ? 2 : 4));
         src[j] = J.dst;
     }
     const size_t nblk = (size_t)max_tiles * nk * B;
     if (ra.dbg & 32) ra.ts = stamp_buffer(h, nblk * 8 * 16, f.st);
-    h->prof.launch(nm, flops, bytes, f.st, [&] {
-        if (f.op == RVCMI_OPERAND_BF16) launch_rbf_t<__bf16>(C, ra, max_tiles, nk, B, f.st, p.small64, p.tall32);
-        else launch_rbf_t<_Float16>(C, ra, max_tiles, nk, B, f.st, p.small64, p.tall32);
-    });
+    h->prof.launch(nm, flops, bytes, f.st, [&] { p.full->launch[f.op == RVCMI_OPERAND_BF16 ? 0 : 1](p.full->lds_bytes, &ra, max_tiles, nk, B, f.st); });
     HIP_CHECK(hipGetLastError());
-    if (ra.dbg & 32) {  // waves per block: the stamp rows of a tile
-        const int nwv = p.tall32 ? RBF32T_NWV : (p.small64 ? RBF64S_NWV : (C == 64 ? RbFullGeom<64>::NWV : RBF32_NWV));
-        print_stamps(h, nm, ra, nk, max_tiles, nwv, 16, nblk, f.st);
-    }
+    if (ra.dbg & 32) print_stamps(h, nm, ra, nk, max_tiles, p.full->waves, 16, nblk, f.st);  // (waves per block: the stamp rows of a tile)
 }
 
 // One launch per pair level, heaviest kernel size first.  At C = 256 the streaming kernel (ND = 1) takes a level where its planner accepts it.
@@ -1265,7 +1244,8 @@ static void rb_pair(const Fwd& f, const Stage& s, long L, int lm, const float** 
     snprintf(nms, sizeof(nms), "rb_stream1_c%d", C);
     int order[RVCMI_MAX_RB];
     rb_order(s, order);
-    constexpr int NWp = 8;  // upper bound of waves per block across the pair-kernel geometries (stamp rows)
+    rvcmi_nsf_stage_plan& r = *f.rec;
+    r.tile_rows = rb_rows(C);
     for (size_t m = 0; m < max_levels(s); ++m) {
         RbPairArgs ra;
         memset(&ra, 0, sizeof(ra));
@@ -1296,13 +1276,22 @@ static void rb_pair(const Fwd& f, const Stage& s, long L, int lm, const float** 
             J.ntiles = (int)((L + J.tt2 - 1) / J.tt2);
             max_tiles = std::max(max_tiles, J.ntiles);
             max_rows = std::max(max_rows, rb_rows(C) + (J.k_p - 1) * J.dil);
+            if (m == 0) {  // (a resblock's tiles are those of its kernel size at every level)
+                r.k[r.n_rb] = J.k;
+                r.tiles[r.n_rb++] = J.ntiles;
+            }
         }
+        constexpr int NWp = 8;  // upper bound of waves per block across the pair-kernel geometries (stamp rows)
         const size_t nblk = (size_t)max_tiles * nj * B;
         if (ra.dbg & 32) ra.ts = stamp_buffer(h, nblk * NWp * 8, f.st);
-        bool streamed = false;
-        if (mode != 0 && rb_stream_supported(op, C, 1) && rb_stream_launch(op, C, 1, sd, nj, (int)L, B, L * C, mode == 1, f.st, h->opt, true))
-            h->prof.launch(nms, flops, bytes, f.st, [&] { streamed = rb_stream_launch(op, C, 1, sd, nj, (int)L, B, L * C, mode == 1, f.st, h->opt); });
-        if (!streamed) h->prof.launch(nm, flops, bytes, f.st, [&] { launch_rb_pair(op, C, ra, max_tiles, nj, B, max_rows, f.st); });
+        RbStreamPlan sp{};
+        if (mode != 0 && rb_stream_supported(op, C, 1)) sp = rb_stream_plan(op, C, 1, sd, nj, (int)L, B, L * C, mode == 1, h->opt);
+        if (sp.ok) {
+            h->prof.launch(nms, flops, bytes, f.st, [&] { rb_stream_run(sp, f.st, h->opt); });
+            r.pair_streamed |= 1 << m;
+        } else {
+            h->prof.launch(nm, flops, bytes, f.st, [&] { launch_rb_pair(op, C, ra, max_tiles, nj, B, max_rows, f.st); });
+        }
         if ((ra.dbg & 32) && m == 0) print_stamps(h, nm, ra, nj, max_tiles, NWp, 8, nblk, f.st);  // (pair level 0)
         for (int j = 0; j < nk; ++j)
             if (dsts[j]) src[j] = dsts[j];
@@ -1375,7 +1364,8 @@ static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float
         RVCMI_FAIL(RVCMI_ERR_NOMEM, "shape B=%d T=%d n_res=%d exceeds handle limits (max_B=%d max_T=%d)", B, T, n_res,
                    h->max_B, h->max_T);
     HIP_CHECK(hipSetDevice(h->device));
-    Fwd f{h, c.operand, B, Te, lens, nullptr, st, tr};
+    Fwd f{h, c.operand, B, Te, lens, nullptr, st, tr, nullptr};
+    h->n_plan = 0;
     if (c.use_f0 && excitation(f, T, f0, noise)) return;
     Act a = conv_pre(f, x, T, g);
     if (f.want("pre")) return copy_tap_cl(h, a.y[0], B, Te, h->C0, tr, st);
@@ -1385,6 +1375,10 @@ static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float
         const long L = a.L * s.u;
         const int lm = a.lm * s.u, C = s.cout;
         const StagePlan p = plan_stage(f, s, L, lm);
+        f.rec = &h->last_plan[i];
+        *f.rec = {(int)p.path, C, B, (int)L, p.x0_half, p.stage_half};  // (the resblock functions add what they launch with)
+        f.rec->num_cus = num_cus();
+        h->n_plan = i + 1;
         if (f.op == RVCMI_OPERAND_F32) ups_f32(f, s, a, L, lm);
         else ups_mfma(f, s, a, p, L, lm);
         snprintf(nm, sizeof(nm), "up%d", i);
@@ -1394,7 +1388,7 @@ static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float
         switch (p.path) {
             case RbPath::F32_CHAIN: rb_f32_chain(f, s, L, lm, src); break;
             case RbPath::SPLIT: rb_split(f, s, L, lm, src); break;
-            case RbPath::STREAM: rb_stream(f, s, p, L, lm, src); break;
+            case RbPath::STREAM: rb_stream(f, s, p, src); break;
             case RbPath::FULL: rb_full(f, s, p, L, lm, src); break;
             case RbPath::PAIR: rb_pair(f, s, L, lm, src); break;
         }
@@ -1455,6 +1449,14 @@ int rvcmi_nsf_profile_enable(rvcmi_nsf* h, int enable) {
     return guarded([&] {
         if (!h) RVCMI_FAIL(RVCMI_ERR_INVALID, "null handle");
         h->prof.enabled = enable != 0;
+    });
+}
+int rvcmi_nsf_last_plan(const rvcmi_nsf* h, rvcmi_nsf_stage_plan* out, int capacity, int* n) {
+    return guarded([&] {
+        if (!h || !n || (!out && h->n_plan)) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
+        if (capacity < h->n_plan) RVCMI_FAIL(RVCMI_ERR_INVALID, "capacity %d for the %d stages of the last forward", capacity, h->n_plan);
+        std::copy(h->last_plan, h->last_plan + h->n_plan, out);
+        *n = h->n_plan;
     });
 }
 int rvcmi_nsf_profile_read(rvcmi_nsf* h, rvcmi_kernel_stat* stats, int capacity, int* n, int reset) {

@@ -120,24 +120,17 @@ bool rb_stream_supported(int operand, int C, int nd) {
     return operand != RVCMI_OPERAND_F32 && geo_for(C, nd, g, Options());
 }
 
-static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C, int nd, const RbStreamDesc* jobs, int njobs, int L, int B,
-                       long bstride, hipStream_t st, const Options& opt, bool dry_run);
-
-bool rb_stream_launch(int operand, int C, int nd, const RbStreamDesc* jobs, int njobs, int L, int B, long bstride, bool force,
-                      hipStream_t st, const Options& opt, bool dry_run) {
+RbStreamPlan rb_stream_plan(int operand, int C, int nd, const RbStreamDesc* jobs, int njobs, int L, int B, long bstride, bool force, const Options& opt) {
+    RbStreamPlan p;
+    memset(&p, 0, sizeof(p));
     Geo g;
-    if (operand == RVCMI_OPERAND_F32 || njobs < 1 || njobs > 3) return false;
-    if (!geo_for(C, nd, g, opt)) return false;
+    if (operand == RVCMI_OPERAND_F32 || njobs < 1 || njobs > 3) return p;
+    if (!geo_for(C, nd, g, opt)) return p;
     // auto mode: only where the persistent walk measured faster than the tile kernels -- C = 128 (whole resblocks) from 4 steps
     // per block; C = 256 (pair level) only with long strips (large batches).
-    return launch_geo(g, force ? 0 : (C == 128 ? 4 : 8), operand, C, nd, jobs, njobs, L, B, bstride, st, opt, dry_run);
-}
-
-static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C, int nd, const RbStreamDesc* jobs, int njobs, int L, int B,
-                       long bstride, hipStream_t st, const Options& opt, bool dry_run) {
+    const int min_steps_required = force ? 0 : (C == 128 ? 4 : 8);
     const int R = 32 * g.NJ;
-    RbStreamArgs a;
-    memset(&a, 0, sizeof(a));
+    RbStreamArgs& a = p.args;
     a.njobs = njobs;
     a.B = B;
     a.L = L;
@@ -167,7 +160,7 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
             J.dil[m] = d.dil[m];
             const int p1 = d.dil[m] * (d.k - 1) / 2;
             if (p1 + p2 > 32 || 2 * p2 > RS_HROW || p1 + p2 + d.dil[m] - 32 > RS_SLACK || 32 + p1 - p2 > RS_HEAD - RS_HROW)
-                return false;  // halo larger than the 32-row lag / the head room of the tile: not this kernel
+                return p;  // halo larger than the 32-row lag / the head room of the tile: not this kernel
             warm[j] += p1;
             J.sx_off[m] = sx;
             sx += 32 + p1 - p2;
@@ -265,10 +258,10 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     if (jobs[0].y_half) a.flags |= 8;
     if (fill) a.flags |= 32;
     if (jobs[0].x_half) {
-        if (!(a.flags & 4) || !(C == 128 && nd == 3 && g.NJ == 6)) return false;  // fp16 input rows: only in the coalesced step IO of KL = 2
+        if (!(a.flags & 4) || !(C == 128 && nd == 3 && g.NJ == 6)) return p;  // fp16 input rows: only in the coalesced step IO of KL = 2
         a.flags |= 16;
     }
-    if (min_steps < min_steps_required) return false;
+    if (min_steps < min_steps_required) return p;
     const size_t smem = (size_t)(RS_HEAD + R + RS_SLACK + side_rows + 1) * (2 * C + 16) + (size_t)nd * 2 * C * sizeof(float);
     // k_rb_stream with KL = 2 (lean K loop + coalesced step IO): [side | dump | biases | M ...] with the fp32 transposition tile
     // T (R rows x (4 C + 16) bytes) starting at M and running over its end (rb_stream_kernels.hpp)
@@ -278,18 +271,32 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
     if (kl2 && smem_kl2 > (size_t)160 * 1024) RVCMI_FAIL(RVCMI_ERR_INVALID, "rb_stream: LDS image %zu B too large (C=%d)", smem_kl2, C);
     if (smem > (size_t)160 * 1024 / g.bpc)
         RVCMI_FAIL(RVCMI_ERR_INVALID, "rb_stream: LDS image %zu B too large for %d block(s) per CU (C=%d)", smem, g.bpc, C);
-    if (dry_run) return true;
+    p.ok = true;
+    p.operand = operand;
+    p.C = C;
+    p.nd = nd;
+    p.NJ = g.NJ;
+    p.NCO = g.NCO;
+    p.nblocks = nblocks;
+    p.lds_bytes = kl2 ? smem_kl2 : smem;
+    return p;
+}
+
+void rb_stream_run(const RbStreamPlan& p, hipStream_t st, const Options& opt) {
+    if (!p.ok) RVCMI_FAIL(RVCMI_ERR_INVALID, "rb_stream: the plan was refused");
+    RbStreamArgs a = p.args;
+    const int B = a.B, njobs = a.njobs;
     // dev only: option RS_STAMPS prints the per-phase cycle breakdown of every launch (synchronises; never set it in a timed run)
     const bool want_stamps = opt.on("RS_STAMPS");
     unsigned long long* ts = nullptr;
-    const size_t nts = (size_t)nblocks * B * g.NCO * 16;
+    const size_t nts = (size_t)p.nblocks * B * p.NCO * 16;
     if (want_stamps) {
         HIP_CHECK(hipMalloc(&ts, nts * 8));
         HIP_CHECK(hipMemsetAsync(ts, 0, nts * 8, st));
         a.ts = ts;
     }
-    if (operand == RVCMI_OPERAND_BF16) launch_t<__bf16>(C, nd, g.NJ, a, nblocks, B, kl2 ? smem_kl2 : smem, st);
-    else launch_t<_Float16>(C, nd, g.NJ, a, nblocks, B, kl2 ? smem_kl2 : smem, st);
+    if (p.operand == RVCMI_OPERAND_BF16) launch_t<__bf16>(p.C, p.nd, p.NJ, a, p.nblocks, B, p.lds_bytes, st);
+    else launch_t<_Float16>(p.C, p.nd, p.NJ, a, p.nblocks, B, p.lds_bytes, st);
     if (want_stamps) {
         HIP_CHECK(hipStreamSynchronize(st));
         std::vector<unsigned long long> h(nts);
@@ -299,23 +306,22 @@ static bool launch_geo(const Geo& g, int min_steps_required, int operand, int C,
         for (int j = 0; j < njobs; ++j) {
             double sum[10] = {0}, steps = 0, tot_max = 0;
             long cnt = 0;
-            for (size_t w = 0; w < (size_t)nblocks * B * g.NCO; ++w) {
-                const unsigned long long* p = &h[w * 16];
-                if ((int)p[11] != j || !p[10]) continue;
+            for (size_t w = 0; w < (size_t)p.nblocks * B * p.NCO; ++w) {
+                const unsigned long long* q = &h[w * 16];
+                if ((int)q[11] != j || !q[10]) continue;
                 double tot = 0;
-                for (int i = 0; i < 10; ++i) { sum[i] += (double)p[i]; tot += (double)p[i]; }
+                for (int i = 0; i < 10; ++i) { sum[i] += (double)q[i]; tot += (double)q[i]; }
                 tot_max = std::max(tot_max, tot);
-                steps += (double)p[10];
+                steps += (double)q[10];
                 ++cnt;
             }
             if (!cnt) continue;
-            fprintf(stderr, "[rs stamps] C=%d nd=%d NJ=%d k=%d strips=%d len=%d mfma=%d steps/blk=%.1f  cycles per PAIR-step:", C, nd, g.NJ, a.job[j].k,
-                    a.job[j].nstrips, a.job[j].strip_len, (a.flags & 64) ? 16 : 32, steps / cnt);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.0f", names[i], sum[i] / (steps * nd));
+            fprintf(stderr, "[rs stamps] C=%d nd=%d NJ=%d k=%d strips=%d len=%d mfma=%d steps/blk=%.1f  cycles per PAIR-step:", p.C, p.nd, p.NJ, a.job[j].k,
+                    a.job[j].nstrips, a.job[j].strip_len, p.mfma(), steps / cnt);
+            for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.0f", names[i], sum[i] / (steps * p.nd));
             fprintf(stderr, " | per step: xload %.0f store %.0f | slowest wave total %.0f cycles\n", sum[8] / steps, sum[9] / steps, tot_max);
         }
     }
-    return true;
 }
 
 }  // namespace rvcmi

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "rb_stream_args.hpp"
 
 namespace rvcmi {
 
@@ -28,13 +29,26 @@ void rb_stream_prepare();
 bool rb_stream_supported(int operand, int C, int nd);
 // Option keys read from `opt` (dev / tests): RS_SMALL (0 = the larger time tiles), RS_KL (2 = k_rb_stream with the lean K loop
 // kconv), RS_C0 (planning constant), RS_STAMPS (print phase stamps; syncs), RS_FILL (0 = a strip's first step computes its pipeline-fill
-// column tiles too, as every later step does; unset / 1 = skips them), RS_MFMA (16 / 32: the MFMA shape of the lean-K-loop instantiations, v_mfma_f32_16x16x32 / 32x32x16; the shape that ran is
-// in the line RS_STAMPS prints, "mfma=16").
+// column tiles too, as every later step does; unset / 1 = skips them), RS_MFMA (16 / 32: the MFMA shape of the lean-K-loop instantiations, v_mfma_f32_16x16x32 / 32x32x16; the shape a launch
+// takes is RbStreamPlan::mfma()).
 inline void rb_stream_load_env(Options& opt) { opt.load_env({"RS_SMALL", "RS_KL", "RS_C0", "RS_STAMPS", "RS_FILL", "RS_MFMA"}); }
-// Plans strips for `B` utterances of `L` rows and launches ONE kernel covering all `njobs` resblocks.  Returns false
-// (nothing launched) when the strips would be too short for the persistent walk to pay and `force` is not set.
-// `dry_run`: plan only (same return value), launch nothing.
-bool rb_stream_launch(int operand, int C, int nd, const RbStreamDesc* jobs, int njobs, int L, int B, long bstride, bool force,
-                      hipStream_t st, const Options& opt, bool dry_run = false);
+// One launch of the kernel, planned: strips for `B` utterances of `L` rows, ONE grid covering all `njobs` resblocks.
+struct RbStreamPlan {
+    bool ok;            // false: refused (halo too large for the tile, fp16 input rows outside the kernel form that reads them, or strips too short
+                        // for the persistent walk to pay and `force` not set); nothing below is meaningful then
+    RbStreamArgs args;  // per job k, nstrips and strip_len; flags
+    int operand, C, nd;
+    int NJ, NCO;        // the instantiation's class: steps of 32 * NJ rows, blocks of NCO waves
+    int nblocks;        // per utterance: the grid is nblocks * B blocks
+    size_t lds_bytes;   // dynamic LDS of the launch
+    bool lean() const { return (args.flags & 4) != 0; }       // the lean K loop (KL = 2)
+    bool y_half() const { return (args.flags & 8) != 0; }
+    bool x_half() const { return (args.flags & 16) != 0; }
+    bool fill_skip() const { return (args.flags & 32) != 0; }
+    int mfma() const { return (args.flags & 64) ? 16 : 32; }  // MFMA shape of the K loops
+};
+RbStreamPlan rb_stream_plan(int operand, int C, int nd, const RbStreamDesc* jobs, int njobs, int L, int B, long bstride, bool force, const Options& opt);
+// Launches exactly that (accepted) plan.  `opt` is read for RS_STAMPS only.
+void rb_stream_run(const RbStreamPlan& p, hipStream_t st, const Options& opt);
 
 }  // namespace rvcmi

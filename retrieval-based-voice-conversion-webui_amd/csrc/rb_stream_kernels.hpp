@@ -22,13 +22,13 @@
 #include <type_traits>
 
 #include "nsf_kernels.hpp"
+#include "rb_stream_args.hpp"
 
 namespace rvcmi {
 
 constexpr int RS_HEAD = 62;   // first M row of the new X rows: 2*p2 (<= 10) rows of H head + Hx (<= 52) rows of X head in front
 constexpr int RS_HROW = 10;   // first M row of the new H rows
 constexpr int RS_SLACK = 4;   // zero rows behind the tile: the last padded tap of conv1 may read p1 + p2 + dil - 32 <= 3 rows beyond
-constexpr int RS_MAXND = 3;
 
 // Pipeline fill of a strip's first step.  A strip starts HL = sum(p1_m + p2) rows early and every pair's output window lags its input
 // window by 32 rows, so in step 0 pair m's conv2 window starts at r0 - 32 (m + 1) and its conv1 (h) window p2 rows behind that.  The first
@@ -53,37 +53,6 @@ inline int rs_fill_tile(int k, const int* dil, int nd, int m, int conv2) {
 // for the last pair, chosen per job -- was built first: the accumulators then meet behind every conv from two or three K loops whose
 // VGPR / AGPR assignment differs, 90 -> 1279 v_accvgpr_read in the fp16-row instantiation and 87..106 spilled registers in four others.)
 constexpr int rs_fill_inst(int m, int NJ) { return m + 1 <= NJ - 2 ? m + 1 : 0; }
-
-struct RbStreamJob {
-    const float* src;
-    float* dst;
-    const void* w1[RS_MAXND];
-    const void* w2[RS_MAXND];
-    const float* b1[RS_MAXND];
-    const float* b2[RS_MAXND];
-    long ct1, ct2;       // packed elements per 32-channel output tile
-    int k, k_p;          // real / padded taps
-    int dil[RS_MAXND];
-    int blk0;            // first blockIdx.x of this job
-    int nstrips;
-    int strip_len;       // output rows per strip
-    int sx_off[RS_MAXND];  // LDS row offset of pair m's X history inside the side area
-    int sh_off[RS_MAXND];  // ... and of its H history
-};
-struct RbStreamArgs {
-    RbStreamJob job[3];
-    int njobs;
-    int B;          // utterances; the grid is (sum of nstrips) * B blocks
-    int L;
-    const int* lens;  // ragged batch (nsf_kernels.hpp item_rows)
-    int lmul;
-    long bstride;
-    int side_rows;  // rows of the side area (max over jobs)
-    int flags;      // bit 2 (4) = lean K loop instantiation; bit 3 (8) = the dst streams are fp16 (pack4_h, nsf_kernels.hpp), same
-                    // element layout; bit 4 (16) = the src stream is fp16 (KL = 2 only); bit 5 (32) = a strip's first step skips its
-                    // pipeline-fill column tiles (rs_fill_tile); bit 6 (64) = the K loops run on v_mfma_f32_16x16x32 (SH = 16)
-    unsigned long long* ts;  // dev only (RVCMI_RS_STAMPS=1): per-wave cycle sums per phase, [block][wave][16]
-};
 
 // cooperative LDS -> LDS copy of `rows` operand rows (whole 16-byte words, pad included)
 // (a batched variant -- 4 reads in flight, then 4 predicated writes -- measured SLOWER: phase A 3.5k -> 5.7k cycles)

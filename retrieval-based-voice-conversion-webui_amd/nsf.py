@@ -108,7 +108,9 @@ class _HipGenerator(torch.nn.Module):
 
     def set_option(self, key: str, value=None) -> None:
         """Dev / test option of this handle (``rvcmi_nsf_set_option``: e.g. ``RB_STREAM`` 0 / 1 pins the ResBlock kernel family,
-        ``NO_RB_SPLIT``, ``RS_SMALL``, ``RS_KL``, ``Y_F16``, ``X0_F16`` / ``X0_F16_NOSTREAM``, ``DBG``; round 6: ``POST_DMA`` 0 / 1 =
+        ``NO_RB_SPLIT``, ``RS_SMALL``, ``RS_KL``, ``Y_F16``, ``X0_F16`` / ``X0_F16_NOSTREAM``, ``DBG`` (timing-ablation bit mask, results are WRONG when non-zero;
+        bit 32 = phase stamps, which the kernels take in ``RVCMI_DEV_STAMPS`` builds only), ``RS_STAMPS`` (dev: the streaming kernel's phase breakdown, synchronises); what a forward
+        made of them is ``last_plan()``; round 6: ``POST_DMA`` 0 / 1 =
         conv_post by the register-staged kernel / by LDS-DMA with the next tile in flight (default), ``POST_DBG`` (timing ablations); ``RBF_PAD_TAP`` 0 / 1 = the fused ResBlock kernel at C <= 32 stops its K loops behind the real taps
         (default) / also multiplies the zero taps that round k = 11, 7, 3 up to whole k-groups of 12, 8, 4 (the loop before, kept so that a test can
         hold the two against each other bit for bit); ``RBF32_TALL`` 1 / 0 = 768-row tiles for that kernel at C = 32 always / never, unset = from
@@ -200,6 +202,20 @@ class _HipGenerator(torch.nn.Module):
 
     def profile_read(self, reset: bool = True) -> List[dict]:
         return _lib.read_stats(_lib.lib().rvcmi_nsf_profile_read, self._handle, reset)
+
+    def last_plan(self) -> List[dict]:
+        """How the last forward on this handle ran each stage's ResBlocks (``rvcmi_nsf_last_plan``): one dict per stage it reached, the
+        fields of ``rvcmi_nsf_stage_plan`` with ``path`` as its name and the per-ResBlock arrays cut to ``n_rb``.  A debug tap reports
+        the stages up to the tap; a graph replay keeps the capturing call's record."""
+        buf, n = (_lib.NsfStagePlan * _lib.RVCMI_MAX_UPS)(), C.c_int(0)
+        _lib.check(_lib.lib().rvcmi_nsf_last_plan(self._handle, buf, len(buf), C.byref(n)))
+        out = []
+        for r in buf[:n.value]:
+            d = {k: getattr(r, k) for k, _ in r._fields_}
+            d.update(path=_lib.RB_PATHS[r.path], x0_half=bool(r.x0_half), y_half=bool(r.y_half), stream_fill_skip=bool(r.stream_fill_skip),
+                     **{k: list(d[k])[:r.n_rb] for k in ("k", "tiles", "strip_len")})
+            out.append(d)
+        return out
 
 
 def config_from_reference(dec: torch.nn.Module) -> dict:

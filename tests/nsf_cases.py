@@ -26,9 +26,10 @@ Sizes, from the constants of the headers (rows = B x L, L = T x the product of t
   SPLIT_ROWS_128 = 96      rows per block of the SPLIT path at C = 128 (nsf.hip conv_ks_nj(128) x 32)
   UPS_TQ0 = 64             input rows per block of k_ups at C_in = 512 (nsf.hip ups_mfma: nj = 2, four channel waves); 32 at C_in = 256, 64 at 128
   RB_ROWS = 128            k_rb_pair's tile: 128 - (k - 1) valid rows per tile (nsf_kernels.hpp RB_ROWS, nsf.hip rb_rows)
-  RB_SPLIT_MAX_ROWS = 1024 / RB_SPLIT_MAX_ROWS_128 = 4096: the SPLIT path ends above these rows (nsf.hip:99-100)
-  RBF64S_ROWS = 256        k_rb_full's small tile, 256 - 2 * halo valid rows (halo 60 / 36 / 12 for k = 11 / 7 / 3: 136 / 184 / 232)
-  rbf_rows(64) = 512, rbf_rows(32) = rbf_rows(16) = 384: its large tiles, taken from num_cus() / 2 (C = 64) or num_cus() (C = 32) blocks (plan_stage)
+  RB_SPLIT_MAX_ROWS = 1024 / RB_SPLIT_MAX_ROWS_128 = 4096: the SPLIT path ends above these rows (nsf.hip plan_stage)
+  RBF_SMALL_ROWS = 256     k_rb_full's small tile, 256 - 2 * halo valid rows (halo 60 / 36 / 12 for k = 11 / 7 / 3: 136 / 184 / 232)
+  rbf_rows(64) = 512, rbf_rows(32) = rbf_rows(16) = 384: its default tiles, taken from num_cus() / 2 (C = 64) or num_cus() (C = 32) blocks (plan_stage)
+  RBF_TALL_ROWS = 768      its tall tile at C = 32, taken from 4 x num_cus() blocks of 768 rows on (option RBF32_TALL: 1 always, 0 never)
   RS_HEAD = 62, R = 32 * NJ = 192 (RS_SMALL = 1) / 256 (RS_SMALL = 0) rows per step of k_rb_stream; the strip planner (rb_stream.hip launch_geo) cuts
                            an utterance into at most L / R strips per resblock: a forced launch at T = 24 (2880 rows) is up to 15 strips of two steps each
                            (one step of rows, one of warm-up), T = 1, 2, 3 are single strips of 120, 240, 360 rows against the 192-row step
@@ -37,18 +38,15 @@ tiles per kernel size, a sequence that ends inside the first tile, inside the se
 118 / 122 / 126, 136 / 184 / 232 or 192 rows, because no shipped config has an L of those sizes.  The tiles that ARE hit exactly: conv_pre's and SPLIT's
 32 rows (T = 31, 32, 33), k_ups' 64 input rows (T = 63, 64, 65), the SPLIT thresholds, and k_rb_full's block-count threshold (T = 76 / 77, 54 / 55).
 
-Which kernel ran is OBSERVED, not computed: the ResBlock family from the profiler's kernel names, k_rb_full's tile height from the tile counts the
-library prints per resblock under option DBG = 32 (nsf.hip print_stamps: tiles = ceil(L / (R - 2 halo)) names R wherever the two heights give
-different counts -- always from 137 rows on; below that both heights are ONE tile per resblock and the class is reported as computed).
+Which kernel ran is REPORTED by the forward whose output is compared: the path, k_rb_full's tile class, the tile / strip counts and the stream dtypes
+of every stage come from ``gen.last_plan()`` (include/rvcmi.h rvcmi_nsf_last_plan), and the profiler's kernel names must agree with the reported path.
+The rules below (``expected_paths``, ``stream_plan``, ``full_tile_counts``) restate the planner independently and are held against the report in every case.
 """
 import collections
-import contextlib
 import functools
 import math
 import os
-import re
 import sys
-import tempfile
 
 import torch
 
@@ -63,7 +61,7 @@ CONFIGS["nof0_v2_48k"] = GenConfig(**{**vars(nsf_oracle.CONFIGS["v2_48k"]), "use
 
 MI355X_CUS = 256  # what the CPU tests plan with; the GPU test asks the device
 RB_SPLIT_MAX_ROWS, RB_SPLIT_MAX_ROWS_128 = 1024, 4096
-RBF64S_ROWS = 256
+RBF_SMALL_ROWS, RBF_TALL_ROWS = 256, 768
 CONV_TILE_SMALL, UPS_TQ0, RB_ROWS = 32, 64, 128
 
 # 2 x the largest perturbed / floor ratio (RMS or max-abs) seen over CPU_TABLE x 2 perturbation seeds, rounded up to the next half.  Per kind of layer,
@@ -84,7 +82,7 @@ def kind_of(name):
 # opts: the handle options that pin the path, as a sorted tuple of (key, value).  kind: "synth" (oracle/synth.py's draws), "voiced" (f0 > 0
 # everywhere), "unvoiced" (f0 = 0), "zero" (z = 0 and f0 = 0).  wgain: conv_pre and ups weights and biases x wgain (larger activations at every
 # stage, coarser fp16 ulp).  layers: None = every layer, else the layers compared (long cases: only the stage under test gets an oracle).
-# want: ((stage, path), ...) the path the case is there for, asserted on the device ("FULL256" / "FULL512" name k_rb_full's tile class).
+# want: ((stage, path), ...) the path the case is there for, asserted on the device ("FULL256" / "FULL384" / "FULL512" / "FULL768" name k_rb_full's tile class by its rows).
 Case = collections.namedtuple("Case", "cfg B T seed opts operand wgain kind layers want", defaults=(0, (), "fp16", 1.0, "synth", None, ()))
 
 
@@ -123,8 +121,8 @@ STREAM_CASES = tuple(Case("v2_48k", 1, 24, 50 + 2 * s + k, O(RB_STREAM=1, RS_SMA
 # (L = 240 T; valid rows 392 / 440 / 488) is 77, with 256 blocks of 384 rows at stage 3 (L = 480 T; 264 / 312 / 360) it is 55; one frame less is the small
 # tile at its largest launch
 FULL_CASES = (Case("v2_48k", 1, 76, 61, layers=("stage2",), want=((2, "FULL256"),)), Case("v2_48k", 1, 77, 62, layers=("stage2",), want=((2, "FULL512"),)),
-              Case("v2_48k", 1, 54, 63, layers=("stage3",), want=((3, "FULL256"),)), Case("v2_48k", 1, 55, 64, layers=("stage3", "post"), want=((3, "FULL512"),)),
-              Case("v2_48k", 1, 80, 65, layers=("up2", "stage2", "up3", "stage3", "post"), want=((2, "FULL512"), (3, "FULL512"))))
+              Case("v2_48k", 1, 54, 63, layers=("stage3",), want=((3, "FULL256"),)), Case("v2_48k", 1, 55, 64, layers=("stage3", "post"), want=((3, "FULL384"),)),
+              Case("v2_48k", 1, 80, 65, layers=("up2", "stage2", "up3", "stage3", "post"), want=((2, "FULL512"), (3, "FULL384"))))
 # stream options off the default, conv_post's two kernels at C = 32 and C = 16
 OPTION_CASES = (Case("v2_48k", 1, 24, 70, O(Y_F16=0)), Case("v2_48k", 1, 24, 71, O(X0_F16=0)), Case("v2_48k", 1, 24, 72, O(POST_DMA=0)),
                 Case("v2_48k", 1, 24, 73, O(POST_DMA=1)), Case("v1_32k", 1, 16, 74, O(POST_DMA=0)), Case("v1_32k", 1, 16, 75, O(POST_DMA=1)))
@@ -186,7 +184,7 @@ def cpu_har(c):
         return nsf_oracle.har_source(weights(c.cfg, c.seed, c.wgain), x["f0"], cfg.upp, cfg.sr, x["noise"])
 
 
-# ---- plan_stage restated (nsf.hip:845-897): which ResBlock path a stage takes and what its streams are stored as ------------------------------
+# ---- plan_stage restated (nsf.hip plan_stage): which ResBlock path a stage takes and what its streams are stored as ------------------------------
 
 def _rbf_halo(k, dils):
     return (k - 1) // 2 * (sum(dils) + len(dils))
@@ -205,8 +203,8 @@ def stage_rows(cfg, T):
 
 
 def expected_paths(cfg, B, T, opts, ncu=MI355X_CUS):
-    """-> per stage "SPLIT" / "STREAM" / "FULL256" / "FULL512" / "PAIR", or None where the streaming planner decides (RB_STREAM unset, C = 128
-    beyond the SPLIT rows: it takes the stage from 4 steps per block, which the device's profile then shows)"""
+    """-> per stage "SPLIT" / "STREAM" / "FULL<tile rows>" / "PAIR", or None where the streaming planner decides (RB_STREAM unset, C = 128
+    beyond the SPLIT rows: it takes the stage from 4 steps per block, else the stage runs pair by pair)"""
     o = dict(opts)
     mode = {None: 2, 0: 0, 1: 1}.get(o.get("RB_STREAM"), 2)
     nk = cfg.num_kernels
@@ -219,17 +217,24 @@ def expected_paths(cfg, B, T, opts, ncu=MI355X_CUS):
         elif mode != 0 and C == 128 and nk == 3 and all(len(d) == 3 for d in cfg.resblock_dilation_sizes):
             out.append("STREAM" if mode == 1 else None)
         elif C <= 64:
-            small = False
+            R = rbf_rows(C)
             if C in (64, 32):
-                blocks = 0
+                blocks, blocks_tall, fits_tall = 0, 0, True
                 for k, d in zip(cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes):
                     HL = _rbf_halo(k, d)
                     v = rbf_rows(C) - 2 * HL
                     blocks += (L + v - 1) // v * B
-                    if RBF64S_ROWS - 2 * HL < RBF64S_ROWS // 4:
+                    if RBF_SMALL_ROWS - 2 * HL < RBF_SMALL_ROWS // 4:
                         blocks = 1 << 30
+                    blocks_tall += -(-L // (RBF_TALL_ROWS - 2 * HL)) * B
+                    fits_tall = fits_tall and RBF_TALL_ROWS - 2 * HL >= RBF_TALL_ROWS // 4
                 small = blocks < ncu // 2 * (1 if C == 64 else 2)
-            out.append("FULL256" if small else "FULL512")
+                tall = {None: 2, 0: 0, 1: 1}.get(o.get("RBF32_TALL"), 2) if C == 32 and fits_tall else 0
+                if tall == 1 or (tall == 2 and not small and blocks_tall >= 4 * ncu):
+                    R = RBF_TALL_ROWS
+                elif small:
+                    R = RBF_SMALL_ROWS
+            out.append("FULL%d" % R)
         else:
             out.append("PAIR")
     return out
@@ -243,10 +248,10 @@ def stream_plan(paths, opts):
     x0, y = [], []
     for p in paths:
         if p == "STREAM":
-            # fp16 input rows only in the lean-K-loop kernel with the coalesced step IO (rb_stream.hip:254-261: RS_KL = 2 and the 192-row steps)
+            # fp16 input rows only in the lean-K-loop kernel with the coalesced step IO (rb_stream.hip rb_stream_plan: RS_KL = 2 and the 192-row steps)
             x0.append(x0h and not o.get("X0_F16_NOSTREAM") and o.get("RS_KL", 2) == 2 and o.get("RS_SMALL", 1) != 0)
             y.append(yh)
-        elif p in ("FULL256", "FULL512"):
+        elif p.startswith("FULL"):
             x0.append(x0h)
             y.append(yh)
         else:
@@ -260,62 +265,50 @@ def full_tile_counts(cfg, L, R):
     return {k: -(-L // (R - 2 * _rbf_halo(k, d))) for k, d in zip(cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes)}
 
 
-@contextlib.contextmanager
-def captured_stderr_fd():
-    """What the library's C code prints to fd 2 inside the block -> the yielded list gets one string"""
+def pair_tile_counts(cfg, L):
+    """{k: tiles} k_rb_pair launches per resblock and pair level: ceil(L / (RB_ROWS - (k - 1))) (nsf.hip rb_pair J.ntiles)"""
+    return {k: -(-L // (RB_ROWS - (k - 1))) for k in cfg.resblock_kernel_sizes}
+
+
+KERNELS_OF = {"F32_CHAIN": ("rb_c%d",), "SPLIT": ("rb_split_c%d",), "STREAM": ("rb_stream_c%d",), "FULL": ("rb_full_c%d",),
+              "PAIR": ("rb_pair_c%d", "rb_stream1_c%d")}  # (rb_stream1: a pair level on the streaming kernel)
+
+
+def paths_from_plan(cfg, plan, names):
+    """-> the path each stage took as the forward reported it (``gen.last_plan()``), k_rb_full's as "FULL<tile rows>", after asserting that the kernel
+    names the profiler recorded for the same forward are those of the reported paths"""
+    assert len(plan) == len(cfg.upsample_rates), plan
     out = []
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            yield out
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-            tmp.seek(0)
-            out.append(tmp.read().decode(errors="replace"))
-
-
-TILE_LINE = re.compile(r"\[rvcmi ts\] rb_full_c(\d+) k=(\d+) tiles=(\d+):")
-
-
-def printed_tile_counts(text):
-    """-> {C: {k: tiles}} from the lines rb_full prints under option DBG = 32 (nsf.hip print_stamps)"""
-    out = {}
-    for C, k, n in TILE_LINE.findall(text):
-        out.setdefault(int(C), {})[int(k)] = int(n)
+    for i, r in enumerate(plan):
+        C = cfg.upsample_initial_channel >> (i + 1)
+        assert r["C"] == C, (i, r)
+        ran = {p for p, nms in KERNELS_OF.items() for nm in nms if nm % C in names}
+        assert ran == {r["path"]}, "stage %d (C = %d) reports %s, the profiler saw %s" % (i, C, r["path"], sorted(names))
+        if r["path"] == "PAIR":
+            levels = max(len(d) for d in cfg.resblock_dilation_sizes)
+            assert ("rb_stream1_c%d" % C in names) == (r["pair_streamed"] != 0) and ("rb_pair_c%d" % C in names) == (r["pair_streamed"] != (1 << levels) - 1), (r, sorted(names))
+        out.append("FULL%d" % r["tile_rows"] if r["path"] == "FULL" else r["path"])
     return out
 
 
-def paths_from_profile(cfg, names, tiles, B, T, ncu):
-    """-> (paths, observed).  The path each stage took, from the kernel names a profiled forward recorded (nsf.hip: rb_split_c<C>, rb_stream_c<C>,
-    rb_full_c<C>, rb_pair_c<C> / rb_stream1_c<C> = the pair level on the streaming kernel).  k_rb_full has ONE name for both tile heights: its class comes
-    from ``tiles`` (``printed_tile_counts`` of a forward under DBG = 32) -- the height whose tile counts are the printed ones.  Where both heights give the
-    printed counts (every resblock in one tile) the class is plan_stage's rule restated at this device's CU count and ``observed[i]`` is False; the rule
-    must never contradict what was printed."""
-    rule = expected_paths(cfg, B, T, (("RB_STREAM", 0), ("NO_RB_SPLIT", 1)), ncu)  # (with both off every C <= 64 stage shows its FULL class)
-    out, observed = [], []
-    for i, L in enumerate(stage_rows(cfg, T)):
-        C = cfg.upsample_initial_channel >> (i + 1)
-        got = [p for p, nm in (("SPLIT", "rb_split_c%d"), ("STREAM", "rb_stream_c%d"), ("FULL", "rb_full_c%d"), ("PAIR", "rb_pair_c%d"), ("PAIR", "rb_stream1_c%d"))
-               if nm % C in names]
-        got = sorted(set(got))
-        assert len(got) == 1, "stage %d (C = %d): kernels %s" % (i, C, sorted(names))
-        if got[0] != "FULL":
-            out.append(got[0])
-            observed.append(True)
-            continue
-        assert C in tiles, "stage %d: rb_full_c%d ran but printed no tile counts (%s)" % (i, C, tiles)
-        heights = {"FULL512": rbf_rows(C)}
-        if C in (64, 32):
-            heights["FULL256"] = RBF64S_ROWS
-        fits = sorted(cls for cls, R in heights.items() if full_tile_counts(cfg, L, R) == tiles[C])
-        assert fits, "stage %d: rb_full_c%d printed tiles %s, neither tile height gives them at L = %d" % (i, C, tiles[C], L)
-        assert rule[i] in fits, "stage %d: rb_full_c%d printed tiles %s = %s, plan_stage restated says %s" % (i, C, tiles[C], fits, rule[i])
-        out.append(fits[0] if len(fits) == 1 else rule[i])
-        observed.append(len(fits) == 1)
-    return out, observed
+def check_plan(c, plan, paths, ncu):
+    """The report of case ``c``'s forward against the restated rules: paths, stream dtypes, tile and strip counts"""
+    cfg, cid = CONFIGS[c.cfg], case_id(c)
+    for i, p in c.want:
+        assert paths[i] == p, "%s: stage %d ran on %s, the case is there for %s" % (cid, i, paths[i], p)
+    for i, p in enumerate(expected_paths(cfg, c.B, c.T, c.opts, ncu)):
+        assert p == paths[i] if p is not None else paths[i] in ("STREAM", "PAIR"), "%s: stage %d ran on %s, plan_stage restated says %s" % (cid, i, paths[i], p)
+    x0h, yh = stream_plan(paths, c.opts)
+    assert (tuple(r["x0_half"] for r in plan), tuple(r["y_half"] for r in plan)) == (x0h, yh), "%s: stream dtypes %s, restated %s" % (cid, plan, (x0h, yh))
+    for r, L in zip(plan, stage_rows(cfg, c.T)):
+        assert (r["B"], r["rows"], r["num_cus"]) == (c.B, L, ncu), (cid, r)
+        tiles = dict(zip(r["k"], r["tiles"]))
+        if r["path"] == "FULL":
+            assert tiles == full_tile_counts(cfg, L, r["tile_rows"]), (cid, r)
+        elif r["path"] == "PAIR":
+            assert r["tile_rows"] == RB_ROWS and tiles == pair_tile_counts(cfg, L), (cid, r)
+        elif r["path"] == "STREAM":
+            assert sorted(r["k"]) == sorted(cfg.resblock_kernel_sizes) and all(n * s >= L > (n - 1) * s for n, s in zip(r["tiles"], r["strip_len"])), (cid, r)
 
 
 # ---- errors and bars ---------------------------------------------------------------------------------------------------------------------
@@ -353,17 +346,18 @@ def half_out(name, x0_half, y_half):
     return False
 
 
-def make_layers(c, paths, arith, perturb=None, operand="case"):
-    x0h, yh = stream_plan(paths, c.opts)
+def make_layers(c, paths, arith, perturb=None, operand="case", halves=None):
+    """halves: (x0_half, y_half) per stage as a forward reported them; None = the restated rule"""
+    x0h, yh = halves or stream_plan(paths, c.opts)
     return lo.Layers(CONFIGS[c.cfg], weights(c.cfg, c.seed, c.wgain), arith, c.operand if operand == "case" else operand, x0h, yh, perturb)
 
 
-def layer_bars(c, paths, name, taps):
+def layer_bars(c, paths, name, taps, halves=None):
     """The fp64 oracle of layer ``name`` applied to ``taps`` (whatever feeds it), its fp32 evaluation on the same input, and the bars."""
-    x0h, yh = stream_plan(paths, c.opts)
+    x0h, yh = halves or stream_plan(paths, c.opts)
     with torch.no_grad():
-        y64 = lo.apply_layer(make_layers(c, paths, "f64"), name, taps)
-        y32 = lo.apply_layer(make_layers(c, paths, "f32"), name, taps)
+        y64 = lo.apply_layer(make_layers(c, paths, "f64", halves=halves), name, taps)
+        y32 = lo.apply_layer(make_layers(c, paths, "f32", halves=halves), name, taps)
     return {"y": y64, "y32": y32, **bars_of(y32, y64, half_out(name, x0h, yh), kind_of(name))}
 
 
@@ -401,9 +395,9 @@ def cpu_chain(c):
 # ---- one case on the device (tests/test_gpu_nsf_layers.py, tools/nsf_parity.py) -----------------------------------------------------------
 
 def device_case(c, device, items=False):
-    """Run case ``c`` on ``device``: pin the options, take the waveform of a plain forward (profiled: which ResBlock kernels ran) and every tap the
-    case's layers need -- each fetched twice, bit-equal -- and compare every layer's tap with the fp64 oracle of that layer applied to the DEVICE's
-    previous tap.  -> (record, wave, handle); record = {"case", "paths", "paths_observed", "full_tiles", "kernels", "layers": [{"layer", "item", "rms", "max",
+    """Run case ``c`` on ``device``: pin the options, take the waveform of a plain forward (profiled, and its own report of how it ran: ``check_plan``)
+    and every tap the case's layers need -- each fetched twice, bit-equal -- and compare every layer's tap with the fp64 oracle of that layer applied to
+    the DEVICE's previous tap.  -> (record, wave, handle); record = {"case", "paths", "plan", "kernels", "layers": [{"layer", "item", "rms", "max",
     floor / bar fields}]} holds plain data only; ``items``: per batch item."""
     import rvc_amd
 
@@ -424,21 +418,10 @@ def device_case(c, device, items=False):
     wave = run().cpu()
     names = {s["name"] for s in gen.profile_read()}
     gen.profile(False)
-    # k_rb_full's tile height: one more forward under DBG = 32, which makes rb_full print its tile counts per resblock and changes nothing else
-    # (the phase stamps it also asks for are compiled in by RVCMI_DEV_STAMPS builds only)
-    gen.set_option("DBG", 32)
-    with captured_stderr_fd() as printed:
-        wave_dbg = run().cpu()
-    gen.set_option("DBG", None)
-    assert torch.equal(wave, wave_dbg), "%s: the forward under DBG = 32 is not the plain forward" % case_id(c)
-    tiles = printed_tile_counts(printed[0])
-    ncu = torch.cuda.get_device_properties(device).multi_processor_count
-    paths, observed = paths_from_profile(cfg, names, tiles, c.B, c.T, ncu)
-    for i, p in c.want:
-        assert paths[i] == p and observed[i], "%s: stage %d ran on %s (%s), the case is there for %s (kernels: %s, tiles: %s)" % (
-            case_id(c), i, paths[i], "observed" if observed[i] else "computed: both tile heights give the printed counts", p, sorted(names), tiles)
-    for i, p in enumerate(expected_paths(cfg, c.B, c.T, c.opts, ncu)):
-        assert p is None or p == paths[i], "%s: stage %d ran on %s, plan_stage restated says %s" % (case_id(c), i, paths[i], p)
+    plan = gen.last_plan()
+    paths = paths_from_plan(cfg, plan, names)
+    check_plan(c, plan, paths, torch.cuda.get_device_properties(device).multi_processor_count)
+    halves = tuple(r["x0_half"] for r in plan), tuple(r["y_half"] for r in plan)
     layers = layer_list(c)
     need = sorted({t for n in layers for t in feeds(cfg, n)} | set(layers) - {"post"} - {"z", "g"})
     taps = {"z": x["z"], "g": x["g"]}
@@ -457,13 +440,12 @@ def device_case(c, device, items=False):
     for name in layers:
         for b in (range(c.B) if items else (None,)):
             sl = (lambda t: t) if b is None else (lambda t: None if t is None else t[b:b + 1])
-            lb = layer_bars(c, paths, name, {k: sl(taps.get(k)) for k in feeds(cfg, name)})
+            lb = layer_bars(c, paths, name, {k: sl(taps.get(k)) for k in feeds(cfg, name)}, halves)
             got = sl(taps[name])
             assert got.shape == lb["y"].shape, (name, got.shape, lb["y"].shape)
             rms, mx = err(got, lb["y"])
             out.append({"layer": name, "item": b, "rms": rms, "max": mx, **{k: lb[k] for k in ("floor_rms", "floor_max", "bar_rms", "bar_max")},
                         "rms_ratio": rms / lb["floor_rms"] if lb["floor_rms"] else None, "max_ratio": mx / lb["floor_max"] if lb["floor_max"] else None,
                         "within_bars": bool(rms <= lb["bar_rms"] and mx <= lb["bar_max"])})
-    rec = {"case": case_id(c), "paths": paths, "paths_observed": observed, "full_tiles": {"c%d" % C: {"k%d" % k: n for k, n in t.items()} for C, t in tiles.items()},
-           "kernels": sorted(n for n in names if n.startswith("rb_") or n == "conv_post"), "layers": out}
+    rec = {"case": case_id(c), "paths": paths, "plan": plan, "kernels": sorted(n for n in names if n.startswith("rb_") or n == "conv_post"), "layers": out}
     return rec, wave, gen

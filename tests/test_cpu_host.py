@@ -38,6 +38,16 @@ def test_struct_layout_matches_the_header():
     assert C.sizeof(_lib.KernelStat) == 48 + 8 + 8 + 8 + 8
     assert C.sizeof(_lib.Tensor) == 8 + 8 + 8 + 32
     assert C.sizeof(_lib.FrontConfig) == 4 * 15  # rvcmi_front_config: 15 ints
+    # rvcmi_nsf_stage_plan: ints only, in the header's order -- 9 scalars, 3 arrays of RVCMI_MAX_RB, 5 scalars
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rvcmi.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\} rvcmi_nsf_stage_plan;", src).group(1)
+    decls = [d.strip() for d in body.split(";") if d.strip()]
+    assert all(d.startswith("int ") for d in decls), decls
+    fields = [(n.strip().split("[")[0], "[" in n) for d in decls for n in d[4:].split(",")]
+    assert fields == [(n, hasattr(t, "_length_")) for n, t in _lib.NsfStagePlan._fields_]
+    assert all(t._length_ == _lib.RVCMI_MAX_RB for _, t in _lib.NsfStagePlan._fields_ if hasattr(t, "_length_"))
+    assert C.sizeof(_lib.NsfStagePlan) == 4 * (9 + 3 * 4 + 5)
+    assert [(n, str(i)) for i, n in enumerate(_lib.RB_PATHS)] == re.findall(r"RVCMI_RB_([A-Z0-9_]+) = (\d+)", src) and len(_lib.RB_PATHS) == 5
 
 
 def test_fails_loudly_without_a_gpu_and_on_bad_input(tmp_path):

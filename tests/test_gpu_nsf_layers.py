@@ -3,8 +3,8 @@
 
 Layer n's oracle is applied to the tap the device itself produced for layer n - 1 ("har", "pre", "up<i>", "stage<i>" of ``debug_tap``; the last layer's
 output is the waveform of a plain forward), so a failing layer names the kernel: conv_pre, k_ups (+ the noise conv's route), the ResBlock path the case
-pins (SPLIT, PAIR, STREAM, FULL with 256- or 512-row tiles), conv_post's two kernels.  What ran is observed and asserted: the family from the
-profiler's kernel names, k_rb_full's tile height from the tile counts the library prints under option DBG = 32 (one name covers both heights).
+pins (SPLIT, PAIR, STREAM, FULL with each of its tile classes), conv_post's two kernels.  What ran is reported by the compared forward itself
+(``gen.last_plan()``) and asserted: against the case's ``want``, the restated planning rules and the profiler's kernel names (tests/nsf_cases.py check_plan).
 Every tap is fetched twice and must be bit-equal; the plain forward is run before and after the tap calls and must be bit-equal too.  The tap calls end a
 forward early and copy what the kernels stored; that they ARE the real run is pinned by the last layer: conv_post's oracle applied to the "stage<last>"
 tap must give the plain forward's waveform to a few fp32 ulps (the bar of "post").
@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 def _within_bars(r):
     """Prints every layer's ratios to its floor, then asserts both bars of every layer."""
-    print("%s: paths %s (observed: %s; rb_full tiles %s) kernels %s" % (r["case"], r["paths"], r["paths_observed"], r["full_tiles"], r["kernels"]))
+    print("%s: paths %s kernels %s plan %s" % (r["case"], r["paths"], r["kernels"], r["plan"]))
     bad = []
     for e in r["layers"]:
         what = e["layer"] if e["item"] is None else "%s[%d]" % (e["layer"], e["item"])

@@ -5,7 +5,7 @@ BIT-equality between two code paths on the same device, inputs and handle.
   leaves the last group behind the real taps, option RBF_PAD_TAP = 1 keeps the padded loop.  The skipped products are exact zeros, so the only
   difference the addend can make is -0.0 against +0.0, which ``torch.equal`` counts as equal.
 * The 768-row tile class of C = 32 (option RBF32_TALL: 1 always, 0 never, absent = from 4 x num_cus() blocks of 768 rows on).  A taller tile changes
-  no element's summation order.  Which class ran is observed from the tile counts printed under DBG = 32, as tests/nsf_cases.py does.
+  no element's summation order.  Which class ran is reported by the forward whose output is compared (``gen.last_plan()``), as tests/nsf_cases.py does.
 
 The parity yardstick stays tests/test_gpu_nsf_layers.py and the goldens.
 """
@@ -35,13 +35,12 @@ def _gen(c, gpu):
     return gen, (lambda: gen(*args, noise=noise).cpu()), (lambda what: gen.debug_tap(what, *args, noise=noise))
 
 
-def _stage3_tiles(gen, run):
-    """-> (the waveform of a forward under DBG = 32, {k: tiles} rb_full printed for C = 32)"""
-    gen.set_option("DBG", 32)
-    with nc.captured_stderr_fd() as printed:
-        wave = run()
-    gen.set_option("DBG", None)
-    return wave, nc.printed_tile_counts(printed[0]).get(32)
+def _stage3(gen, run):
+    """-> (the waveform of a plain forward, the tile rows and {k: tiles} that forward reports for stage 3: k_rb_full at C = 32)"""
+    wave = run()
+    r = gen.last_plan()[3]
+    assert (r["path"], r["C"]) == ("FULL", 32), r
+    return wave, r["tile_rows"], dict(zip(r["k"], r["tiles"]))
 
 
 @pytest.mark.parametrize("operand", ("fp16", "bf16"))
@@ -50,10 +49,10 @@ def test_real_taps_equal_the_padded_loop_c32(T, operand, gpu):
     """v2_48k stage 3 (C = 32): T = 24 runs on the 256-row class, T = 55 on the 384-row class with several tiles per kernel size"""
     c = nc.Case("v2_48k", 1, T, 200 + T, operand=operand)
     gen, run, tap = _gen(c, gpu)
-    _, tiles = _stage3_tiles(gen, run)
+    wave, rows, tiles = _stage3(gen, run)
     L = nc.stage_rows(nc.CONFIGS[c.cfg], T)[3]
-    assert tiles == nc.full_tile_counts(nc.CONFIGS[c.cfg], L, 256 if T == 24 else 384), tiles
-    got = {"stage3": tap("stage3"), "wave": run()}
+    assert rows == (256 if T == 24 else 384) and tiles == nc.full_tile_counts(nc.CONFIGS[c.cfg], L, rows), (rows, tiles)
+    got = {"stage3": tap("stage3"), "wave": wave}
     gen.set_option("RBF_PAD_TAP", 1)
     want = {"stage3": tap("stage3"), "wave": run()}
     gen.set_option("RBF_PAD_TAP", None)
@@ -89,18 +88,18 @@ def test_tall_tiles_equal_the_default_class(T, gpu):
     cfg = nc.CONFIGS[c.cfg]
     gen, run, tap = _gen(c, gpu)
     gen.set_option("RBF32_TALL", 0)
-    want = {"stage3": tap("stage3"), "wave": run()}
-    _, tiles0 = _stage3_tiles(gen, run)
+    want = {"stage3": tap("stage3")}
+    want["wave"], rows0, tiles0 = _stage3(gen, run)
     gen.set_option("RBF32_TALL", 1)
-    got = {"stage3": tap("stage3"), "wave": run()}
-    wave_dbg, tiles = _stage3_tiles(gen, run)
+    got = {"stage3": tap("stage3")}
+    got["wave"], rows, tiles = _stage3(gen, run)
+    assert (rows0, rows) == (nc.RBF_SMALL_ROWS, RBF32T_ROWS)
     L = nc.stage_rows(cfg, T)[3]
     halo = {k: nc._rbf_halo(k, d) for k, d in zip(cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes)}
     assert halo == {3: 12, 7: 36, 11: 60}
     assert tiles == {k: -(-L // (RBF32T_ROWS - 2 * h)) for k, h in halo.items()}, tiles
-    assert tiles0 == nc.full_tile_counts(cfg, L, nc.RBF64S_ROWS), tiles0  # (a launch this short: the 256-row class when the tall one is off)
+    assert tiles0 == nc.full_tile_counts(cfg, L, nc.RBF_SMALL_ROWS), tiles0  # (a launch this short: the 256-row class when the tall one is off)
     assert tiles != tiles0
-    assert torch.equal(wave_dbg, got["wave"]), "the forward under DBG = 32 is not the plain forward"
     for k in got:
         assert bool(torch.isfinite(got[k]).all()) and got[k].abs().max() > 0
         assert torch.equal(got[k], want[k]), "%s: 768-row tiles differ from the default class, max %.3e" % (k, nc.err(got[k], want[k])[1])
@@ -134,18 +133,19 @@ def test_tall_tiles_ragged_batch(gpu):
 
 def test_tall_tiles_auto_rule(gpu):
     """plan_stage restated: the 768-row class from 4 x num_cus() blocks on.  T = 80 (38 400 rows at stage 3) is 60 + 56 + 52 = 168 blocks of 768 rows:
-    with no option set the 384-row class stays, and RBF32_TALL = 1 shows that the printed counts can tell the two apart"""
+    with no option set the 384-row class stays, and RBF32_TALL = 1 reports the other class and other counts"""
     c = nc.Case("v2_48k", 1, 80, 240)
     cfg = nc.CONFIGS[c.cfg]
     gen, run, _ = _gen(c, gpu)
     L = nc.stage_rows(cfg, c.T)[3]
     ncu = torch.cuda.get_device_properties(gpu).multi_processor_count
     assert sum(nc.full_tile_counts(cfg, L, RBF32T_ROWS).values()) == 168 < 4 * ncu
-    wave, tiles = _stage3_tiles(gen, run)
-    assert tiles == nc.full_tile_counts(cfg, L, 384), tiles
+    wave, rows, tiles = _stage3(gen, run)
+    assert rows == 384 and tiles == nc.full_tile_counts(cfg, L, 384), (rows, tiles)
+    assert nc.expected_paths(cfg, c.B, c.T, c.opts, ncu)[3] == "FULL384"
     gen.set_option("RBF32_TALL", 1)
-    wave_tall, tiles_tall = _stage3_tiles(gen, run)
-    assert tiles_tall == nc.full_tile_counts(cfg, L, RBF32T_ROWS) != tiles, tiles_tall
+    wave_tall, rows_tall, tiles_tall = _stage3(gen, run)
+    assert rows_tall == RBF32T_ROWS and tiles_tall == nc.full_tile_counts(cfg, L, RBF32T_ROWS) != tiles, (rows_tall, tiles_tall)
     assert torch.equal(wave, wave_tall)
 
 

@@ -13,7 +13,6 @@ The one CPU test holds the first-tile table (tools/model_rb_stream.py fill_tile,
 rows a stored row depends on.
 """
 import os
-import re
 import sys
 
 import pytest
@@ -102,34 +101,43 @@ def test_skip_equals_no_skip_bf16(gpu):
     _skip_equals_no_skip(gen, run)
 
 
-PLAN_LINE = re.compile(r"\[rs stamps\] C=128 nd=3 NJ=\d+ k=(\d+) strips=(\d+) len=(\d+)")
-
-
 @gpu_test
 def test_other_plans_same_bits(gpu):
     """RS_C0 moves the strip boundaries, hence the first steps; the planning constant must not show in a single bit.  At T = 24 and B = 1 the grid
     has more slots than strips worth cutting and every RS_C0 plans the same strips, so this case is B = 16, T = 18 (2 160 rows per item, 16 slots per
     item on 256 CUs), where RS_C0 = 2.0 / 3.8 / 6.0 plan 10 + 4 + 2 / 6 + 4 + 5 / 6 + 5 + 5 strips of 2 to 7 steps.  That the plans differ is
-    OBSERVED: from the strips and strip lengths the launch prints under RS_STAMPS."""
+    REPORTED: the strips and strip lengths of the very forwards that are compared (``gen.last_plan()``)."""
     c = nc.Case("v2_48k", 16, 18, 313, nc.STREAM)
     gen, run, tap = _gen(c, gpu)
     outs, plans = [], []
     for c0 in (2.0, 3.8, 6.0):
         gen.set_option("RS_C0", c0)
-        outs.append((run(), tap("stage1")))
-        gen.set_option("RS_STAMPS", 1)
-        with nc.captured_stderr_fd() as printed:
-            wave = run()
-        gen.set_option("RS_STAMPS", None)
-        assert torch.equal(wave, outs[-1][0])
-        plans.append(tuple(sorted(PLAN_LINE.findall(printed[0]))))
-        assert len(plans[-1]) == 3, printed[0]
+        wave = run()
+        r = gen.last_plan()[1]
+        assert (r["path"], r["C"], r["n_rb"]) == ("STREAM", 128, 3), r
+        plans.append(tuple(sorted(zip(r["k"], r["tiles"], r["strip_len"]))))
+        outs.append((wave, tap("stage1")))
     gen.set_option("RS_C0", None)
     assert len(set(plans)) == 3, plans
     assert bool(torch.isfinite(outs[0][0]).all()) and outs[0][0].abs().max() > 0
     for wave, s1 in outs[1:]:
         assert torch.equal(wave, outs[0][0]) and torch.equal(s1, outs[0][1])
     _skip_equals_no_skip(gen, run)
+
+
+@gpu_test
+def test_stamped_forward_same_bits(gpu):
+    """RS_STAMPS = 1 (dev: the kernel's stamped branch, a synchronisation and a printed breakdown per launch) at T = 2 leaves every bit alone"""
+    c = nc.Case("v2_48k", 1, 2, 315, nc.STREAM)
+    gen, run, _ = _gen(c, gpu)
+    wave = run()
+    assert gen.last_plan()[1]["path"] == "STREAM"
+    gen.set_option("RS_STAMPS", 1)
+    try:
+        stamped = run()
+    finally:
+        gen.set_option("RS_STAMPS", None)
+    assert bool(torch.isfinite(wave).all()) and wave.abs().max() > 0 and torch.equal(stamped, wave)
 
 
 @gpu_test

@@ -4,11 +4,11 @@ summation order of the K loop, the liberty tests/nsf_cases.py derived the MFMA l
 the layer oracle, and everything that only changes what the new path executes (fill skip, strips, batch) is held to bit-equality inside it.
 
 All cases are v2_48k with RB_STREAM = 1, RS_SMALL = 1, RS_KL = 2.  T = 24 is 2 880 rows at stage 1 (strips of several steps), T = 1, 2, 3 are single
-strips of one step that starts in front of the sequence (r0 < 0).  Which shape ran is OBSERVED: the launch prints it under RS_STAMPS ("mfma=16").
+strips of one step that starts in front of the sequence (r0 < 0).  Which shape ran is REPORTED by the forward whose output is compared
+(``gen.last_plan()``: ``stream_mfma``).
 """
 import functools
 import os
-import re
 import sys
 
 import pytest
@@ -23,7 +23,6 @@ gpu_test = pytest.mark.gpu
 
 LEAN = dict(RB_STREAM=1, RS_SMALL=1, RS_KL=2)
 LAYERS = ("stage1", "post")  # the stage the kernel computes, and the waveform (conv_post's oracle on the device's last stage)
-SHAPE_LINE = re.compile(r"\[rs stamps\] C=128 nd=3 NJ=6 k=(\d+) strips=(\d+) len=(\d+) mfma=(\d+)")
 
 
 def _case(T, seed, operand="fp16", B=1, **opts):
@@ -38,16 +37,11 @@ def _runner(c, gen, gpu):
 
 
 def _shape_and_plan(gen, run):
-    """-> (the MFMA shape stage 1's launch ran on, its strips per resblock, the waveform of that forward)"""
-    gen.set_option("RS_STAMPS", 1)
-    with nc.captured_stderr_fd() as printed:
-        wave = run()
-    gen.set_option("RS_STAMPS", None)
-    lines = SHAPE_LINE.findall(printed[0])
-    assert len(lines) == 3, printed[0]
-    shapes = {int(l[3]) for l in lines}
-    assert len(shapes) == 1, lines
-    return shapes.pop(), tuple(sorted(l[:3] for l in lines)), wave
+    """-> (the MFMA shape stage 1's launch ran on, its (k, strips, strip length) per resblock, the waveform) of ONE plain forward, as it reports itself"""
+    wave = run()
+    r = gen.last_plan()[1]
+    assert (r["path"], r["C"], r["stream_nj"], r["n_rb"]) == ("STREAM", 128, 6, 3), r
+    return r["stream_mfma"], tuple(sorted(zip(r["k"], r["tiles"], r["strip_len"]))), wave
 
 
 @functools.lru_cache(maxsize=None)
@@ -62,9 +56,10 @@ def _within_bars(c, gpu):
         print("%s %s: rms %.3e (bar %.3e, floor %.3e)  max %.3e (bar %.3e, floor %.3e)" % (
             rec["case"], r["layer"], r["rms"], r["bar_rms"], r["floor_rms"], r["max"], r["bar_max"], r["floor_max"]))
     run, _ = _runner(c, gen, gpu)
+    assert rec["plan"][1]["stream_mfma"] == 16, rec["plan"][1]  # (reported by the forward device_case compared)
     shape, _, wave_s = _shape_and_plan(gen, run)
     assert shape == 16, shape
-    assert torch.equal(wave_s, wave)  # (the forward that printed is the plain forward)
+    assert torch.equal(wave_s, wave)
     assert {r["layer"] for r in rec["layers"]} == set(LAYERS)
     for r in rec["layers"]:
         assert r["within_bars"], r
@@ -113,6 +108,18 @@ def test_fill_skip_same_bits(T, gpu):
 
 
 @gpu_test
+def test_stamped_forward_same_bits(gpu):
+    """RS_STAMPS = 1 (dev: the kernel's stamped branch, a synchronisation and a printed breakdown per launch) leaves every bit of the output alone"""
+    _, wave, gen, run = _within_bars(_case(2, 402), gpu)
+    gen.set_option("RS_STAMPS", 1)
+    try:
+        stamped = run()
+    finally:
+        gen.set_option("RS_STAMPS", None)
+    assert torch.equal(stamped, wave)
+
+
+@gpu_test
 def test_ragged_batch_items_equal_single_calls(gpu):
     """B = 2 with lengths (24, 5): each item bit-equal to its own single call (5 frames = 600 rows at stage 1: one strip)"""
     import rvc_amd
@@ -138,7 +145,7 @@ def test_ragged_batch_items_equal_single_calls(gpu):
 
 @gpu_test
 def test_other_plans_same_bits(gpu):
-    """RS_C0 = 2.0 / 3.8 / 6.0 at B = 16, T = 18 plan different strips (observed from the printed plans, as tests/test_gpu_rb_stream_fill.py does);
+    """RS_C0 = 2.0 / 3.8 / 6.0 at B = 16, T = 18 plan different strips (as each forward reports them, as in tests/test_gpu_rb_stream_fill.py);
     the rows they produce on the 16x16x32 shape are the same bits"""
     import rvc_amd
 

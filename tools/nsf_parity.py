@@ -2,8 +2,7 @@
 
     python tools/nsf_parity.py --out profiles/nsf_parity.json
 
-Per case: the ResBlock path every stage ran on (``paths``: the family from the profiler's kernel names, k_rb_full's tile height from the tile counts it
-prints under DBG = 32, ``full_tiles``; ``paths_observed`` is false where both heights give those counts and the class is plan_stage's rule), and per layer the error of the device's tap against the oracle applied
+Per case: the ResBlock path every stage ran on (``paths``, with ``plan`` the forward's own report of it: ``gen.last_plan()``), and per layer the error of the device's tap against the oracle applied
 to the device's previous tap, the floor (the oracle's float32 evaluation against float64 on the same input), the bars and the ratios.  Needs a GPU.
 """
 import argparse
@@ -49,8 +48,7 @@ def main():
                 share = e[key] / e["bar_" + key]
                 if share > worst.get((k, key), (0.0, None))[0]:
                     worst[(k, key)] = (share, "%s %s" % (rec["case"], e["layer"]))
-    out = {"paths": "family: profiler kernel names; FULL256 / FULL512: the tile height whose ceil(L / (R - 2 halo)) per resblock equals full_tiles, "
-                    "printed by the library; paths_observed false = both heights fit and the class is computed",
+    out = {"paths": "as the compared forward reported them (plan: rvcmi_nsf_last_plan); FULL<n>: k_rb_full with n-row tiles; the profiler's kernel names agree",
            "reference": "oracle/nsf_layer_oracle.Layers, float64, operands and streams rounded where the kernels round; each layer fed the device's own previous tap",
            "floor": "the same layer in float32 against float64 on the same input; bar = FACTOR * floor + one ulp (fp16 or fp32, as the tap is stored) at max |y| "
                     "(over sqrt(n) for RMS); FACTOR = %s" % json.dumps(nc.FACTOR),
