@@ -6,7 +6,9 @@ defaults, ``smoothing_filter`` buffer and ``forward(x, xn=None)``, computed by o
 
 Divergences from the reference: an odd ``n_fft`` raises ``RvcmiError`` (torch accepts it); a ``freq_mask_smooth_hz`` below one bin
 raises the ``ValueError`` the reference means to raise (its message formats the missing ``self._n_fft``, so it raises
-``AttributeError``, torchgate.py:94-96); the DirectML ``STFT`` branch is not reproduced (the input must be a ROCm tensor).
+``AttributeError``, torchgate.py:94-96); the DirectML ``STFT`` branch is not reproduced (the input must be a ROCm tensor).  As
+``torch.istft``, a window / hop pair whose overlap-added squared window falls below 1e-11 inside the kept range (``hop_length >
+win_length``, or hann with ``hop_length = n_fft``) raises, here a ``ValueError`` from the host before anything is launched.
 """
 from __future__ import annotations
 
@@ -45,6 +47,7 @@ class TorchGateHIP(torch.nn.Module):
         self.time_mask_smooth_ms = time_mask_smooth_ms
         self.register_buffer("smoothing_filter", self._generate_mask_smoothing_filter())
         self._windows = {}
+        self._ola_checked = set()
 
     @torch.no_grad()
     def _generate_mask_smoothing_filter(self) -> Union[torch.Tensor, None]:
@@ -76,6 +79,26 @@ class TorchGateHIP(torch.nn.Module):
             w = self._windows[dev] = w.to(dev)
         return w
 
+    def _check_overlap_add(self, L: int) -> None:
+        """torch.istft's check, on the host (no device read-back): the overlap-added squared window of the call's ``1 + L // hop``
+        frames must stay above 1e-11 wherever the output is kept, or the division behind the overlap-add gives inf / NaN.  Away from
+        both ends the sum has period ``hop_length``, so 2 ceil(n_fft / hop) + 2 frames stand for any larger number."""
+        n, hop = self.n_fft, int(self.hop_length)
+        if not 0 < hop <= n or n % 2:
+            return  # the library refuses these with its own message
+        frames = min(1 + L // hop, 2 * -(-n // hop) + 2)
+        if frames in self._ola_checked:
+            return
+        w2 = self._window(torch.device("cpu")) ** 2
+        env = torch.zeros(n + hop * (frames - 1), dtype=torch.float64)
+        for f in range(frames):
+            env[f * hop: f * hop + n] += w2
+        kept = env[n // 2: n // 2 + hop * (frames - 1)]
+        if kept.numel() and float(kept.min()) < 1e-11:
+            raise ValueError("window overlap add min below 1e-11: hann_window(%d) centred in n_fft = %d with hop_length = %d leaves output "
+                             "samples that no frame covers (torch.istft refuses this too)" % (self.win_length, n, hop))
+        self._ola_checked.add(frames)
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor, xn: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [B, L] or [L] (``xn`` shaped alike, or None: the noise statistics come from x) on the GPU -> the gated signal,
@@ -84,6 +107,7 @@ class TorchGateHIP(torch.nn.Module):
             raise _lib.RvcmiError("TorchGateHIP runs on the GPU (got %s); there is no CPU fallback" % x.device)
         squeeze = x.dim() == 1
         x32 = (x[None] if squeeze else x).to(torch.float32).contiguous()
+        self._check_overlap_add(int(x32.shape[-1]))
         xn32 = None
         if xn is not None:
             xn32 = (xn[None] if xn.dim() == 1 else xn).to(torch.float32)

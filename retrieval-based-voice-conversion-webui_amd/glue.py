@@ -541,7 +541,9 @@ def spectral_gate(x: torch.Tensor, xn: Optional[torch.Tensor], n_fft: int, hop: 
     """``TorchGate.forward(x, xn)`` (infer/modules/gui/torchgate.py) in one enqueue-only call: x [B, L] and xn [B, Ln] (or None)
     contiguous float32, ``window`` [n_fft] float64 (the hann window zero-padded to the centre), ``smoothing_filter`` [nf, nt]
     float32 or None.  Returns a new float32 tensor [B, hop * (L // hop)].  STFT, statistics and overlap-add in fp64
-    (rvcmi.h); n_fft must be even and <= 4096."""
+    (rvcmi.h); n_fft must be even and <= 4096.  The overlap-add divides by the summed squared window unchecked: a window / hop pair
+    that leaves a kept sample uncovered (``torch.istft`` refuses those) gives inf / NaN there; that is the caller's to rule out
+    (``TorchGateHIP`` does, on the host)."""
     dev = _lib.on_gpu(x, "x")
     tensors = [(x, "x", torch.float32), (window, "window", torch.float64)]
     if xn is not None:
