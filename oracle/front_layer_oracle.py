@@ -18,7 +18,7 @@ The flow taps are in the DEVICE's channel order.  The Flip in front of every cou
 stream buffer never moves: coupling f runs after n_flows - f flips, and when that count is odd the buffer holds the logical tensor with its channel
 axis reversed.  ``flow`` takes and returns that physical order (n_flows = 4: "flow3" and "flow1" are reversed, "z_p", "flow2" and "flow0" are not).
 
-Where the kernels round (file:line of csrc/; OpT = the operand type; to_op = nsf_kernels.hpp:619-626: RNE, fp16 saturates at +-65504):
+Where the kernels round (file:line of csrc/; OpT = the operand type; to_op = mfma_conv.hpp: to_op: RNE, fp16 saturates at +-65504):
 
   weights      every conv's weights are packed as OpT once, at handle creation (conv_pack.hpp build_conv, called from front.hip:532,546,551,585-593,
                603,615,623,628,637) -- emb_phone, conv_q/k/v/o, the FFN convs, proj, the flow's pre / in_layers / res_skip_layers / post.
@@ -37,7 +37,7 @@ Where the kernels round (file:line of csrc/; OpT = the operand type; to_op = nsf
                b + gc is summed first, in fp32 (:350-353,550-553,670).
 
 fp32 on the device, so never rounded here: biases, the pitch embedding (front.hip:533), LayerNorm (front_kernels.hpp:263-311,1109-1160,1257-1292; eps 1e-5
-inside sqrtf), masks, the residual added in front of every LayerNorm (the UNMASKED fp32 stream), the flow / WN / skip streams, k_cond (nsf_kernels.hpp:129-139),
+inside sqrtf), masks, the residual added in front of every LayerNorm (the UNMASKED fp32 stream), the flow / WN / skip streams, k_cond (nsf_source_kernels.hpp: k_cond),
 the prior sample (expf, the constant 0.66666f; front_kernels.hpp:334-336), the coupling update (:512-513) and k_fr_out (:1295-1314).
 
 Masks, as the kernels apply them: "emb" is masked; the q/k/v conv and conv_o are not (padding keys score -1e4, :869); the FFN's input and hidden rows

@@ -11,32 +11,32 @@
 Tensors are channel-first [B, C, L] as ``debug_tap`` returns them.  ``arith`` = "f64" / "f32" is the dtype everything is evaluated in;
 ``operand`` = "fp16" / "bf16" / None rounds (to nearest even) where the kernels round and NOWHERE else; None is the reference's function.
 
-Where the kernels round (file:line of csrc/, OpT = the operand type, to_op = nsf_kernels.hpp:618-626: RNE, fp16 saturates at 65504):
+Where the kernels round (file:line of csrc/, OpT = the operand type, to_op = mfma_conv.hpp: to_op: RNE, fp16 saturates at 65504):
 
   weights      every conv that runs on the MFMA path has its weights packed as OpT once, at handle creation: conv_pre, ups, resblock convs
                (conv_pack.hpp build_conv, called from nsf.hip:128,190,227), the noise conv where it runs as an MFMA conv (nsf.hip:151, "mfma"
                route) or as one extra k-step of k_ups (nsf.hip:163, "k1" route).  Biases, cond, conv_post and the noise conv of the "valu"
                route (the last stage's 1-tap conv, or a stride the two MFMA forms do not take; nsf.hip:144-145) stay fp32.
-  conv_pre     z is rounded while it is staged, to_op(z) (nsf_kernels.hpp:671,776); fp32 accumulation, + bias + cond in fp32
-               (nsf_kernels.hpp:1072-1098).  The "pre" tap is that fp32 sum (OUT_F32); a real forward stores to_op(lrelu(sum, 0.1)) instead
-               (OUT_ACT, nsf.hip:950-959, nsf_kernels.hpp:1103) -- the very value k_ups computes from the fp32 sum (next line), so ``up(0, pre)`` is
+  conv_pre     z is rounded while it is staged, to_op(z) (conv_kernels.hpp: stage_tile, IN_F32_CF); fp32 accumulation, + bias + cond in fp32
+               (conv_kernels.hpp: conv_mfma_body, epilogue).  The "pre" tap is that fp32 sum (OUT_F32); a real forward stores to_op(lrelu(sum, 0.1)) instead
+               (OUT_ACT, nsf.hip:950-959, conv_kernels.hpp: conv_mfma_body, OUT_ACT store) -- the very value k_ups computes from the fp32 sum (next line), so ``up(0, pre)`` is
                what the real run computes.
-  ups input    to_op(lrelu(div3_exact((a + b) + c), 0.1)) (nsf_kernels.hpp:1649,1655): the three streams are summed in fp32 in that order (as the
-               stage tap sums them, k_sum3h / k_sum3, nsf_kernels.hpp:556-570), div3_exact is the IEEE quotient bit for bit (exact_fp.hpp:31-42).
-  noise conv   "mfma" route (stride % 8 == 0, stride <= 64): to_op(har) (nsf_kernels.hpp:747) x OpT weights, fp32 sum + fp32 bias -> NZ, added in
-               k_ups' epilogue in fp32 (nsf_kernels.hpp:1839,1868).  "k1" route (2..16 taps, even stride): to_op(har) (nsf_kernels.hpp:1772-1775) x
-               OpT weights, one extra MFMA k-step on the transposed conv's accumulator (nsf_kernels.hpp:1807-1823).  "valu" route: fp32 har x fp32
-               weights (nsf_kernels.hpp:1841-1853).  (k_noise_add, nsf_kernels.hpp:247-265, belongs to the fp32 path alone: nothing is rounded.)
-  X0           written as fp32, or -- ``StagePlan.x0_half`` (nsf.hip:845-897) -- as FP16 whatever OpT is (pack4_h, nsf_kernels.hpp:271-276,1873-1878):
+  ups input    to_op(lrelu(div3_exact((a + b) + c), 0.1)) (ups_kernels.hpp: k_ups, convert_store): the three streams are summed in fp32 in that order (as the
+               stage tap sums them, post_kernels.hpp: k_sum3h, k_sum3), div3_exact is the IEEE quotient bit for bit (exact_fp.hpp:31-42).
+  noise conv   "mfma" route (stride % 8 == 0, stride <= 64): to_op(har) (conv_kernels.hpp: stage_tile, IN_HAR) x OpT weights, fp32 sum + fp32 bias -> NZ, added in
+               k_ups' epilogue in fp32 (ups_kernels.hpp: k_ups, addend in the epilogue).  "k1" route (2..16 taps, even stride): to_op(har) (ups_kernels.hpp: k_ups, har16 staging) x
+               OpT weights, one extra MFMA k-step on the transposed conv's accumulator (ups_kernels.hpp: k_ups, nz_k1 k-step).  "valu" route: fp32 har x fp32
+               weights (ups_kernels.hpp: k_ups, VALU noise loop of the epilogue).  (k_noise_add, conv_kernels.hpp, belongs to the fp32 path alone: nothing is rounded.)
+  X0           written as fp32, or -- ``StagePlan.x0_half`` (nsf.hip:845-897) -- as FP16 whatever OpT is (mfma_conv.hpp: pack4_h; ups_kernels.hpp: k_ups, X0 stores):
                k_rb_full's stages under Y_F16 and X0_F16, the streaming kernel's unless X0_F16_NOSTREAM / RS_KL != 2 / RS_SMALL = 0
                (rb_stream.hip:258-261).  The SPLIT and PAIR paths keep fp32.  The "up<i>" tap is X0 as stored (widened).
-  resblock     conv1's input to_op(lrelu(x, 0.1)) (SPLIT nsf_kernels.hpp:714; PAIR :1441; FULL / STREAM pack4_lrelu :1273-1282), the H tile
-               between conv1 and conv2 to_op(lrelu(conv1 + b1, 0.1)) (SPLIT OUT_ACT :1103,1231; fused kernels publish_operand :1286-1301), and
+  resblock     conv1's input to_op(lrelu(x, 0.1)) (SPLIT conv_kernels.hpp: stage_tile, row-major batch; PAIR rb_pair_kernels.hpp: k_rb_pair, step 1; FULL / STREAM mfma_conv.hpp: pack4_lrelu), the H tile
+               between conv1 and conv2 to_op(lrelu(conv1 + b1, 0.1)) (SPLIT conv_kernels.hpp: conv_mfma_body / conv_ks_body, OUT_ACT store; fused kernels mfma_conv.hpp: publish_operand), and
                x <- conv2 + b2 + x with x the fp32 residual stream (it starts as X0 as stored and is never rounded inside a resblock).
   Y streams    a resblock's output is written fp32, or -- ``StagePlan.stage_half`` = option Y_F16 on the FULL and STREAM paths -- as FP16 whatever
-               OpT is (pack4_h: nsf_kernels.hpp:2219,2242; rb_stream_kernels.hpp:499,555).  SPLIT and PAIR write fp32.
+               OpT is (pack4_h: rb_full_kernels.hpp: k_rb_full, fp16 stores; rb_stream_kernels.hpp:499,555).  SPLIT and PAIR write fp32.
   conv_post    nothing is rounded: (a + b) + c, div3_exact, lrelu 0.01, an fp32 fmaf chain over (tap, channel), tanhf
-               (k_post nsf_kernels.hpp:349-361,414-426; k_post_dma :518-543).
+               (post_kernels.hpp: k_post, staging and tap loop; k_post_dma, convert pass and tap loop).
 
 ``variant=`` names a WRONG layer (tests/test_cpu_nsf_layers.py: the bars must reject each); ``perturb=`` a liberty the kernels may take
 against the fp32 evaluation (``reorder``: summation order of the K loop; ``tanh``: tanhf by a few ulp; ``fma``: the one multiply-add of the MFMA layers'
@@ -55,7 +55,7 @@ import torch.nn.functional as F
 
 from .nsf_oracle import GenConfig, get_padding, har_source  # noqa: F401  (har_source: the "har" layer is nsf_oracle's)
 
-TILE_ROW_PERIOD = 128  # variant "tile_row": one output row in every 128 (the SPLIT / PAIR kernels' conv tile, nsf_kernels.hpp RB_ROWS)
+TILE_ROW_PERIOD = 128  # variant "tile_row": one output row in every 128 (the SPLIT / PAIR kernels' conv tile, rb_pair_kernels.hpp RB_ROWS)
 
 
 def dtype_of(arith: str):
@@ -85,7 +85,7 @@ def rounder(operand: Optional[str]):
 
 
 def lrelu(x: torch.Tensor, slope: float) -> torch.Tensor:
-    """v > 0 ? v : v * slope, the slope being the float32 constant the kernels multiply by (nsf_kernels.hpp:28,1264-1270)"""
+    """v > 0 ? v : v * slope, the slope being the float32 constant the kernels multiply by (mfma_conv.hpp: lrelu, lrelu_op)"""
     return torch.where(x > 0, x, x * float(np.float32(slope)))
 
 
@@ -261,7 +261,7 @@ class Layers:
         wp = self.w["conv_post.weight"]
         p = self.perturb or {}
         if self.operand is not None and self.arith == "f32":
-            # both kernels' arithmetic, step for step: ONE fmaf chain per output, taps outer, channels inner (nsf_kernels.hpp:414-425,529-542).  The products
+            # both kernels' arithmetic, step for step: ONE fmaf chain per output, taps outer, channels inner (post_kernels.hpp: k_post / k_post_dma, tap loop).  The products
             # are exact in float64, so rounding the float64 sum to float32 is the fused multiply-add's single rounding.
             xp = F.pad(x, (3, 3)).double()
             L = x.shape[-1]

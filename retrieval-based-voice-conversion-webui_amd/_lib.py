@@ -233,7 +233,7 @@ def build(verbose: bool = True, force: bool = False) -> str:
             # nsf.hip alone, none with this option; the 512-register kernels keep their overflow in AGPRs
             cmd[1:1] = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
         for d_ in os.environ.get("RVCMI_DEFINES", "").split():
-            cmd.insert(1, "-D" + d_)  # dev: geometry experiments, e.g. RVCMI_DEFINES="RB256_NJ=3"
+            cmd.insert(1, "-D" + d_)  # dev: compile-time defaults, e.g. RVCMI_DEFINES="RS_MFMA_DEFAULT=32"
         if os.environ.get("RVCMI_DEV_STAMPS"):
             cmd.insert(1, "-DRVCMI_DEV_STAMPS")  # per-phase s_memtime stamps in the fused kernels (RVCMI_DBG=32)
         if verbose:

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
-#include "nsf_kernels.hpp"
+#include "mfma_conv.hpp"
 #include "split_f16.hpp"
 
 namespace rvcmi {

@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "conv_pack.hpp"
 #include "front_kernels.hpp"
+#include "nsf_source_kernels.hpp"
 #include "front_split_kernels.hpp"
 
 using namespace rvcmi;

@@ -16,7 +16,7 @@
 #pragma once
 #include <type_traits>
 
-#include "nsf_kernels.hpp"
+#include "mfma_conv.hpp"
 
 namespace rvcmi {
 
@@ -518,7 +518,7 @@ static __global__ void __launch_bounds__(64 * NW) k_fr_conv(FrConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// in_layer + gate of one WN layer with the TAPS split over the block's waves (round 6; the K-split idea of conv_ks_body, nsf_kernels.hpp).
+// in_layer + gate of one WN layer with the TAPS split over the block's waves (round 6; the K-split idea of conv_ks_body, conv_kernels.hpp).
 // Measured first (ABAB, B = 1): splitting the layer's CHANNELS over 3x the blocks (FR_GATE epilogue of k_fr_conv + a res_skip launch)
 // changes nothing -- 15.0 + 7.8 us against 22.3 us fused: a wave's K loop runs at the latency of ITS cold weight stream (60 k-steps with
 // 16 in flight = four dependent trips to the far memory side), however few blocks share a CU.  Here block = (time tile, one (tanh, sigmoid)

@@ -10,6 +10,9 @@
 // atomics arrive in, but every id of a segment is unique and the segment is sorted by id before any row is placed, so the final
 // ids array -- and with it the rows, which are gathered BY id -- is a function of (old index, assignment) alone.  No float atomics.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
 
 namespace rvcmi {
 

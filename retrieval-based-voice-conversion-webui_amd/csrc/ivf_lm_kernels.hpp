@@ -16,6 +16,11 @@
 // Why the result IS the exact top-k: at least k rows have S_hat <= t8, hence true distance (minus |q|^2) <= t8 + E, so the true
 // k-th best is <= t8 + E; a true top-k row therefore has S_hat <= true + E <= t8 + 2 E and is among the verified candidates.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "ivf_kernels.hpp"  // CG_S, CG_K, the fp32 MFMA tile of the coarse quantiser
 
 namespace rvcmi {
 

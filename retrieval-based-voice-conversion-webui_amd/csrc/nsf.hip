@@ -10,7 +10,12 @@
 #include <unordered_map>
 
 #include "common.hpp"
-#include "nsf_kernels.hpp"
+#include "nsf_source_kernels.hpp"
+#include "conv_kernels.hpp"
+#include "post_kernels.hpp"
+#include "rb_pair_kernels.hpp"
+#include "ups_kernels.hpp"
+#include "rb_full_kernels.hpp"
 #include "conv_pack.hpp"
 #include "rb_stream.hpp"
 
@@ -84,9 +89,7 @@ namespace rvcmi {
 
 static void set_lds_limits();
 constexpr int RB_KG = 4;  // k-steps per weight-prefetch group inside the fused resblock kernel
-#ifndef RB256_NJ
-#define RB256_NJ 4  // (96-row tiles, 2 blocks per CU, measured the same 0.33 ms at B=1; 128 rows reuse weights better)
-#endif
+constexpr int RB256_NJ = 4;  // (96-row tiles, 2 blocks per CU, measured the same 0.33 ms at B=1; 128 rows reuse weights better)
 static int rb_rows(int C) { return C == 256 ? 32 * RB256_NJ : RB_ROWS; }
 // Resblock stages of at most this many rows (B x L) at C = 256 run conv by conv, split over output channels (run_conv_jobs): a
 // realtime chunk's first stage is 310 rows = 9 fused pair tiles, each pulling 2.9 MB of weights through ONE CU (3 x 70 us).
@@ -522,7 +525,7 @@ static int rbf32_tall_mode(const rvcmi_nsf* h) { return tri_mode(h, "RBF32_TALL"
 static int rb_stream_mode(const rvcmi_nsf* h) { return tri_mode(h, "RB_STREAM"); }
 
 // Option Y_F16 (default 1): the whole-ResBlock kernels (k_rb_stream ND = 3, k_rb_full) write their output streams Ya[j] as fp16
-// and the next stage's k_ups / k_post read them as such (nsf_kernels.hpp pack4_h).  0 = fp32 streams (round 3).
+// and the next stage's k_ups / k_post read them as such (mfma_conv.hpp pack4_h).  0 = fp32 streams (round 3).
 static bool y_f16(const rvcmi_nsf* h) {
     return h->cfg.operand != RVCMI_OPERAND_F32 && h->opt.geti("Y_F16", 1) != 0;
 }
@@ -582,7 +585,7 @@ static void run_conv(rvcmi_nsf* h, const ConvLayer& L, ConvArgs a, int B, const 
 }
 
 // Up to three independent convs of the same shape class (C_in = C_out = 256 or 128) in ONE launch of k_conv_ks_jobs
-// (nsf_kernels.hpp conv_ks_body): 32 NJ rows x 32 channels per block, the four waves split the taps.
+// (conv_kernels.hpp conv_ks_body): 32 NJ rows x 32 channels per block, the four waves split the taps.
 constexpr int conv_ks_nj(int C) { return C == 256 ? 1 : 3; }  // rows per block / 32 (C = 128: 96-row tiles = 396 blocks for a chunk's 3100 rows)
 template <typename OpT, int C>
 static void launch_conv_ks_jobs(const ConvJobs& js, int Lq, int B, size_t smem, hipStream_t st) {
@@ -1350,7 +1353,7 @@ static void tap_stage(const Fwd& f, const Act& x) {
 }
 
 // `lens`: optional device array [B] of valid frames per item (1 <= lens[b] <= T): a ragged batch, every item computed exactly as
-// a separate call of its own length (nsf_kernels.hpp item_rows); the output rows behind an item's end are zero.
+// a separate call of its own length (mfma_conv.hpp item_rows); the output rows behind an item's end are zero.
 static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float* x, const float* f0, const float* g,
                         const float* noise, int n_res, float* out, hipStream_t st, TapRequest* tr) {
     if (!h || !x || (!out && !tr)) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");

@@ -70,13 +70,8 @@ void launch_inst(const RbStreamArgs& a, int nblocks, int B, size_t smem, hipStre
 
 // weight ring of the C = 128 kernel: NB groups of KG k-steps; a group is requested (NB-1)*KG k-steps ahead of its use.
 // (4 groups of 2 k-steps -- the same 32 registers, 6 instead of 4 k-steps of L2 latency covered -- was measured: 47 instead
-// of 37 cycles per MFMA, the group bookkeeping comes twice as often; 0.69 vs 0.62 ms.  RVCMI_DEFINES="RS_KG128=2 RS_NB128=4".)
-#ifndef RS_KG128
-#define RS_KG128 4
-#endif
-#ifndef RS_NB128
-#define RS_NB128 2
-#endif
+// of 37 cycles per MFMA, the group bookkeeping comes twice as often; 0.69 vs 0.62 ms.)
+constexpr int RS128_KG = 4, RS128_NB = 2;
 template <typename OpT>
 void launch_t(int C, int nd, int NJ, const RbStreamArgs& a, int nblocks, int B, size_t smem, hipStream_t st) {
     if (C == 256 && nd == 1 && NJ == 4) return launch_inst<OpT, 256, 2, 4, 4, 1>(a, nblocks, B, smem, st);
@@ -84,13 +79,13 @@ void launch_t(int C, int nd, int NJ, const RbStreamArgs& a, int nblocks, int B, 
     if (C == 128 && nd == 3 && NJ == 8) return launch_inst<OpT, 128, 1, 8, 4, 3>(a, nblocks, B, smem, st);
     // (weight ring 3 / 4 groups deep instead of 2: 65 / 129 spilled registers, 0.70 -> 0.77 / 0.89 ms -- measured, not kept)
     if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4) && (a.flags & 64)) {  // lean K loop on v_mfma_f32_16x16x32: fp16 / fp32 input rows
-        if (a.flags & 16) return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2, 1, 16>(a, nblocks, B, smem, st);
-        return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2, 0, 16>(a, nblocks, B, smem, st);
+        if (a.flags & 16) return launch_inst<OpT, 128, 1, 6, 4, 3, RS128_KG, RS128_NB, 1, 2, 1, 16>(a, nblocks, B, smem, st);
+        return launch_inst<OpT, 128, 1, 6, 4, 3, RS128_KG, RS128_NB, 1, 2, 0, 16>(a, nblocks, B, smem, st);
     }
     if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4) && (a.flags & 16))
-        return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2, 1>(a, nblocks, B, smem, st);  // lean K loop, fp16 input rows
-    if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4)) return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128, 1, 2>(a, nblocks, B, smem, st);  // lean K loop
-    if (C == 128 && nd == 3 && NJ == 6) return launch_inst<OpT, 128, 1, 6, 4, 3, RS_KG128, RS_NB128>(a, nblocks, B, smem, st);
+        return launch_inst<OpT, 128, 1, 6, 4, 3, RS128_KG, RS128_NB, 1, 2, 1>(a, nblocks, B, smem, st);  // lean K loop, fp16 input rows
+    if (C == 128 && nd == 3 && NJ == 6 && (a.flags & 4)) return launch_inst<OpT, 128, 1, 6, 4, 3, RS128_KG, RS128_NB, 1, 2>(a, nblocks, B, smem, st);  // lean K loop
+    if (C == 128 && nd == 3 && NJ == 6) return launch_inst<OpT, 128, 1, 6, 4, 3, RS128_KG, RS128_NB>(a, nblocks, B, smem, st);
     RVCMI_FAIL(RVCMI_ERR_INVALID, "rb_stream: no instantiation for C=%d nd=%d", C, nd);
 }
 

@@ -26,11 +26,11 @@ struct RbStreamArgs {
     int njobs;
     int B;          // utterances; the grid is (sum of nstrips) * B blocks
     int L;
-    const int* lens;  // ragged batch (nsf_kernels.hpp item_rows)
+    const int* lens;  // ragged batch (mfma_conv.hpp item_rows)
     int lmul;
     long bstride;
     int side_rows;  // rows of the side area (max over jobs)
-    int flags;      // bit 2 (4) = lean K loop instantiation; bit 3 (8) = the dst streams are fp16 (pack4_h, nsf_kernels.hpp), same
+    int flags;      // bit 2 (4) = lean K loop instantiation; bit 3 (8) = the dst streams are fp16 (pack4_h, mfma_conv.hpp), same
                     // element layout; bit 4 (16) = the src stream is fp16 (KL = 2 only); bit 5 (32) = a strip's first step skips its
                     // pipeline-fill column tiles (rs_fill_tile); bit 6 (64) = the K loops run on v_mfma_f32_16x16x32 (SH = 16)
     unsigned long long* ts;  // dev only (RVCMI_RS_STAMPS=1): per-wave cycle sums per phase, [block][wave][16]

@@ -21,7 +21,7 @@
 #pragma once
 #include <type_traits>
 
-#include "nsf_kernels.hpp"
+#include "mfma_conv.hpp"
 #include "rb_stream_args.hpp"
 
 namespace rvcmi {
@@ -63,14 +63,14 @@ __device__ __forceinline__ void rs_copy_rows(char* dst, const char* src, int row
     for (int i = threadIdx.x; i < total; i += NT) *(uint4*)(dst + (size_t)i * 16) = *(const uint4*)(src + (size_t)i * 16);
 }
 
-// KL = 2: the lean K loop kconv (nsf_kernels.hpp) instead of conv_prefetch / conv_run
+// KL = 2: the lean K loop kconv (mfma_conv.hpp) instead of conv_prefetch / conv_run
 // XH = 1 (with KL = 2): the src stream is fp16 (a.flags bit 4) -- its own instantiation: as a runtime switch the fp32 and the fp16 row
 // registers of the step prefetch were both live (472 -> 512 registers + 16 spilled)
 // SH: the MFMA shape of the K loops, 32 = v_mfma_f32_32x32x16 (kconv / conv_run), 16 = v_mfma_f32_16x16x32 (kconv16, KL = 2 only).
 // Accumulator, residual and carry tiles are acc_t[MIH][NTL]: tiles of CT channels x TR rows holding NG register quads per lane, each
 // quad four consecutive channels (8 g + half4 of the tile) of the lane's row lrow.
 //   SH = 32: f32x16[MI][NJ], 32 x 32, 4 quads, lrow = lane % 32, half4 = 4 (lane / 32)
-//   SH = 16: f32x4[2 MI][2 NJ], 16 x 16, 1 quad, lrow = mfma16_row(lane % 16), half4 = 4 (lane / 16)   (nsf_kernels.hpp kconv16)
+//   SH = 16: f32x4[2 MI][2 NJ], 16 x 16, 1 quad, lrow = mfma16_row(lane % 16), half4 = 4 (lane / 16)   (mfma_conv.hpp kconv16)
 // The 32-row lag of a pair is LAG = 32 / TR column tiles.
 template <typename OpT, int C, int MI, int NJ, int NCO, int ND, int KG, int NB, int OCC = 1, int KL = 1, int XH = 0, int SH = 32>
 static __global__ void __launch_bounds__(64 * NCO, OCC) k_rb_stream(RbStreamArgs a) {

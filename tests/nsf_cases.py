@@ -25,7 +25,7 @@ Sizes, from the constants of the headers (rows = B x L, L = T x the product of t
   CONV_TILE_SMALL = 32     rows per block of conv_pre and of the SPLIT path at C = 256 for short launches (nsf.hip run_conv nj = 1, conv_ks_nj(256))
   SPLIT_ROWS_128 = 96      rows per block of the SPLIT path at C = 128 (nsf.hip conv_ks_nj(128) x 32)
   UPS_TQ0 = 64             input rows per block of k_ups at C_in = 512 (nsf.hip ups_mfma: nj = 2, four channel waves); 32 at C_in = 256, 64 at 128
-  RB_ROWS = 128            k_rb_pair's tile: 128 - (k - 1) valid rows per tile (nsf_kernels.hpp RB_ROWS, nsf.hip rb_rows)
+  RB_ROWS = 128            k_rb_pair's tile: 128 - (k - 1) valid rows per tile (rb_pair_kernels.hpp RB_ROWS, nsf.hip rb_rows)
   RB_SPLIT_MAX_ROWS = 1024 / RB_SPLIT_MAX_ROWS_128 = 4096: the SPLIT path ends above these rows (nsf.hip plan_stage)
   RBF_SMALL_ROWS = 256     k_rb_full's small tile, 256 - 2 * halo valid rows (halo 60 / 36 / 12 for k = 11 / 7 / 3: 136 / 184 / 232)
   rbf_rows(64) = 512, rbf_rows(32) = rbf_rows(16) = 384: its default tiles, taken from num_cus() / 2 (C = 64) or num_cus() (C = 32) blocks (plan_stage)
@@ -68,9 +68,9 @@ CONV_TILE_SMALL, UPS_TQ0, RB_ROWS = 32, 64, 128
 # because the liberties differ: the MFMA layers (pre, up<i>, stage<i>) reorder their K loop (and may contract the one multiply-add of their fp32 epilogues,
 # see below); conv_post's fp32 evaluation is the kernels' own fmaf chain on a floor of a few fp32 ulps, and tanhf moves it.  Layers whose bar is decided by
 # the additive term (FACTOR * floor < the one-flip term: a handful of flips or none) do not count.
-# FMA contraction: the MFMA layers' fp32 epilogues are additions of already rounded terms (acc + bias + cond, nsf_kernels.hpp:1072-1098; + NZ / + bn, :1866-1869;
+# FMA contraction: the MFMA layers' fp32 epilogues are additions of already rounded terms (acc + bias + cond, conv_kernels.hpp: conv_mfma_body, epilogue; + NZ / + bn, ups_kernels.hpp: k_ups, epilogue;
 # conv2 + b2 + x), lrelu's product feeds a median, not an add, and div3_exact is the IEEE quotient whatever is fused (exact_fp.hpp).  The ONE product that an add
-# follows is the VALU noise conv of the last stage, bias + w * har (nsf_kernels.hpp:1852,1867): ``perturb["fma"]`` rounds it once instead of twice.
+# follows is the VALU noise conv of the last stage, bias + w * har (ups_kernels.hpp: k_ups, VALU noise loop of the epilogue): ``perturb["fma"]`` rounds it once instead of twice.
 PERTURB_WORST = {"mfma": 1.99, "post": 2.29}  # pre of the bf16 case (max-abs): 3.98 -> 4.0; post of v1_32k and v1_48k (RMS): 4.58 -> 5.0
 FACTOR = {"mfma": 4.0, "post": 5.0}
 

@@ -1,4 +1,4 @@
-"""The lane maps of k_rb_stream on v_mfma_f32_16x16x32 (csrc/nsf_kernels.hpp kconv16, csrc/rb_stream_kernels.hpp SH = 16), on the host model
+"""The lane maps of k_rb_stream on v_mfma_f32_16x16x32 (csrc/mfma_conv.hpp kconv16, csrc/rb_stream_kernels.hpp SH = 16), on the host model
 tools/model_rb_stream_mfma16.py: what the K loop multiplies, which LDS slots its B reads touch, and that the lane-held tiles of the step schedule
 (publish, T pick-up and deposit, residual shift by two tiles, two-tile carry, dual write, H tail, fill skip from tile 2 (m + 1)) give ResBlock1's rows."""
 import os

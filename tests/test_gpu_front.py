@@ -409,7 +409,7 @@ def test_fp16_range_headroom_and_saturation_against_the_fp32_reference(gpu, caps
       * G puts the largest tapped activation at ~1/8 of the fp16 range: the error against the reference must be the unscaled run's
         (within 10 %) -- the parity claim does not depend on the absolute scale of a checkpoint's activations;
       * G puts it 1.25-2.5x BEYOND the range (asserted on the oracle's fp32 taps): the publish path converts with SATURATION
-        (`v_med3_f32(x, 0.1 x, 65504)` in pack4_lrelu, `pack4_h` for the streams; csrc/nsf_kernels.hpp), so the clipped peaks cost accuracy
+        (`v_med3_f32(x, 0.1 x, 65504)` in pack4_lrelu, `pack4_h` for the streams; csrc/mfma_conv.hpp), so the clipped peaks cost accuracy
         locally but the waveform stays finite and close to the fp32 reference; an overflowing conversion would produce inf, and inf - inf =
         NaN in the next conv."""
     import rvc_amd

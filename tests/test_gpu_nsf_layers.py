@@ -1,4 +1,4 @@
-"""The generator's kernels (csrc/nsf.hip, nsf_kernels.hpp, rb_stream_kernels.hpp), LAYER BY LAYER against the fp64 oracle that rounds where they round
+"""The generator's kernels (csrc/nsf.hip and the family headers it launches, rb_stream_kernels.hpp), LAYER BY LAYER against the fp64 oracle that rounds where they round
 (oracle/nsf_layer_oracle.py), at the bars tests/nsf_cases.py derives from that oracle's own fp32 noise floor -- an RMS bar and a max-abs bar per layer.
 
 Layer n's oracle is applied to the tap the device itself produced for layer n - 1 ("har", "pre", "up<i>", "stage<i>" of ``debug_tap``; the last layer's

@@ -1,4 +1,4 @@
-"""k_rb_full at C <= 32 (csrc/nsf_kernels.hpp, nsf.hip): two changes of what the kernel executes, neither of what it computes, so every check here is
+"""k_rb_full at C <= 32 (csrc/rb_full_kernels.hpp, nsf.hip): two changes of what the kernel executes, neither of what it computes, so every check here is
 BIT-equality between two code paths on the same device, inputs and handle.
 
 * Real taps only.  A k-group of the K loop holds 2 taps at C = 32 and 4 at C = 16, and k = 11 / 7 / 3 is packed as 12 / 8 / 4 taps; the default loop

@@ -1,4 +1,4 @@
-"""k_rb_stream's lean-K-loop instantiations (C = 128, whole resblocks, 192-row steps) run their K loops on v_mfma_f32_16x16x32 (csrc/nsf_kernels.hpp
+"""k_rb_stream's lean-K-loop instantiations (C = 128, whole resblocks, 192-row steps) run their K loops on v_mfma_f32_16x16x32 (csrc/mfma_conv.hpp
 kconv16, csrc/rb_stream_kernels.hpp SH = 16, option RS_MFMA = 16 / 32).  The hardware then sums 32 products per instruction instead of 16: a permuted
 summation order of the K loop, the liberty tests/nsf_cases.py derived the MFMA layers' bars for (FACTOR 4) -- so the stage is held to the SAME bars against
 the layer oracle, and everything that only changes what the new path executes (fill skip, strips, batch) is held to bit-equality inside it.

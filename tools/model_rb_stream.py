@@ -1,4 +1,4 @@
-"""CPU model of the streaming fused-ResBlock schedule of k_rb_stream (csrc/nsf_kernels.hpp): the SAME buffer layout,
+"""CPU model of the streaming fused-ResBlock schedule of k_rb_stream (csrc/rb_stream_kernels.hpp): the SAME buffer layout,
 row arithmetic, masks, history copies and residual tile shift, in numpy fp32 -- checked against a direct evaluation of
 ResBlock1 (rvc/layers/residuals.py:68-85).  Also the first-step tile table (fill_tile = rs_fill_tile of csrc/rb_stream_kernels.hpp):
 the column tiles of a strip's first step that only fill the pipeline are poisoned here and must not show in the result.

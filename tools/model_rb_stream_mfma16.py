@@ -1,4 +1,4 @@
-"""CPU model of the lane maps of k_rb_stream on v_mfma_f32_16x16x32 (csrc/nsf_kernels.hpp kconv16, csrc/rb_stream_kernels.hpp SH = 16), a sibling of
+"""CPU model of the lane maps of k_rb_stream on v_mfma_f32_16x16x32 (csrc/mfma_conv.hpp kconv16, csrc/rb_stream_kernels.hpp SH = 16), a sibling of
 tools/model_rb_stream.py, whose row-level schedule it re-runs with every register tile held lane by lane.  Three things, each a function a test calls
 (tests/test_cpu_rb_stream_mfma16.py):
 
@@ -58,7 +58,7 @@ def bank_slots(natural=False):
 def kloop_products(k, dil, jt0=0):
     """-> cnt[co 32][row R][ci C][tap k]: how often kconv16 forms the product W[co][ci][tap] * X[row + tap * dil][ci] into output (co, row) of one wave.
     The packed weight buffer holds element (co, tap * C + ci) of the wave's tile at [k_step = (tap * C + ci) // 16][lane = (co % 32) + 32 * ((ci % 16) // 8)][ci % 8]
-    (csrc/nsf_kernels.hpp, "A (weights)"); X row r, channel ci is at LDS byte r * STRIDE + 2 * ci."""
+    (csrc/mfma_conv.hpp, "A (weights)"); X row r, channel ci is at LDS byte r * STRIDE + 2 * ci."""
     cnt = np.zeros((32, R, C, k), np.int32)
     lanes = np.arange(64)
     q, n = lanes >> 4, lanes & 15

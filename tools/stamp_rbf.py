@@ -1,6 +1,6 @@
 """dev: per-phase cycle stamps of k_rb_full on the benchmark clip (needs a library built with RVCMI_DEV_STAMPS=1; RVCMI_LIB selects it):
 RVCMI_LIB=.../librvcmi_stamps.so python tools/stamp_rbf.py
-Prints, per kernel size, the mean cycles between consecutive stamps of a tile (nsf_kernels.hpp k_rb_full: 1 x loaded, 2 X published,
+Prints, per kernel size, the mean cycles between consecutive stamps of a tile (rb_full_kernels.hpp k_rb_full: 1 x loaded, 2 X published,
 3 barrier, 4 conv1, 5 H published, 6 barrier, 7 conv2, 8 X' published, 9 barrier (pair 0), 10 all pairs, 11 stores issued)."""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

@@ -1,10 +1,10 @@
-// Micro-benchmark of the generator's K loop (conv_prefetch / conv_run from nsf_kernels.hpp) in isolation:
+// Micro-benchmark of the generator's K loop (conv_prefetch / conv_run from mfma_conv.hpp) in isolation:
 // one block of 4 waves per CU, each wave runs REPS convs of `k` taps on a resident LDS tile; reports cycles per MFMA.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../../retrieval-based-voice-conversion-webui_amd/csrc/nsf_kernels.hpp"
+#include "../../retrieval-based-voice-conversion-webui_amd/csrc/mfma_conv.hpp"
 using namespace rvcmi;
 #ifndef VARIANT
 #define VARIANT 0
@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(64 * NWV, 1) kloop(const _Float16* w, long ct,
         conv_prefetch<_Float16, C, MI, KG, NB>(A, w + lane * 8, ct, k_p);
         t0 = __builtin_readcyclecounter();
         for (int r = 0; r < reps; ++r) {
-            conv_run<_Float16, C, MI, NJ, KG, NB>(acc, A, xl, w + lane * 8, ct, k_p, 32 - dil * (k_p - 1) / 2, dil, dbg);
+            conv_run<_Float16, C, MI, NJ, KG, NB>(acc, A, xl, w + lane * 8, ct, k_p, 32 - dil * (k_p - 1) / 2, dil);
             conv_prefetch<_Float16, C, MI, KG, NB>(A, w + lane * 8, ct, k_p);
         }
         t1 = __builtin_readcyclecounter();
@@ -76,14 +76,6 @@ void run(int k, int dil, int dbg) {
     hipFree(w); hipFree(out); hipFree(ticks);
 }
 int main() {
-#ifdef RVCMI_KLOOP_V1
-    printf("K loop V1 (round 2: scheduler-ordered reads)\n");
-#else
-    printf("K loop V2 (pinned slot order)\n");
-#endif
-#ifdef RVCMI_KLOOP_ABLATE
-    printf("ABLATE=%d (1: no weight loads, 2: no B reads)\n", RVCMI_KLOOP_ABLATE);
-#endif
     run<128, 1, 6, 4, 2, true, 4, 2>(11, 5, 0);
     run<128, 1, 6, 4, 2, true, 4, 2>(3, 1, 0);
     run<128, 1, 6, 4, 2, true>(3, 1, 0);
