@@ -548,6 +548,57 @@ int rvcmi_glue_envelope_mix_batch(int S, const float* input_dev, int64_t in_stri
 int rvcmi_glue_expand_protect_batch(int S, const float* feats_dev, int64_t nq, int d, int reps, const float* pitchf_dev,
                                     float protect, int64_t p_len, float* out_dev, void* stream);
 
+/* The noise reduction of a bank (rvc_amd.TorchGateBank, RealtimeBank.set_noise_reduce): rvcmi_glue_spectral_gate, stationary with a
+ * noise signal, for S sessions whose noise signal xn is a ROLLING buffer.  Between two calls every xn row moved left by `shift`
+ * samples and its last `tail` samples were rewritten, so most of its Fn = 1 + nn / hop frames hold the samples of frame
+ * f + shift / hop of the call before.  The caller keeps their spectra: ring_dev [S][Fn][K] double2 (K = n_fft / 2 + 1,
+ * rvcmi_glue_spectral_gate_ring_bytes), logical frame f of THIS call in slot (ring_base + f) % Fn, so the caller adds shift / hop to
+ * ring_base per call.  A frame is CLEAN -- kept, not transformed -- iff shift >= 0, shift % hop == 0, tail <= nn and
+ *   shift > 0:   f hop - n_fft / 2 >= 0  and  f hop + n_fft / 2 <= nn - max(tail, shift);
+ *   shift == 0:  tail == 0  or  f hop + n_fft / 2 <= nn - tail          (the frame keeps its slot, zero padding included);
+ * anything else makes every frame dirty (the arithmetic of a cold call, not an error).  rvcmi_glue_gate_ring_plan is that rule.
+ * mode_dev [S] uint8 on the device: 0 = the session is off: its out row, its ring rows and its scratch are not written;
+ * 1 = warm: only the dirty frames are transformed and stored (the caller vouches that the session's ring rows hold the previous
+ * call's spectra under the previous ring_base); 2 = cold: all Fn frames are.  any_cold (host): non-zero when some session is cold;
+ * the launch covers all noise tiles only then (a cold session with any_cold = 0 would be left with stale rows).  Blocks of off
+ * sessions and of a warm session's surplus tiles leave on a branch that is uniform per block.
+ * BIT-EQUALITY: a frame's spectrum is summed in an order that depends on neither its place in a tile nor its slot, and the
+ * statistics pass reads the cache in logical frame order, so every active session's out row is bit-equal to rvcmi_glue_spectral_gate
+ * on contiguous copies of its x and xn rows -- warm or cold, whatever S and whatever the other sessions do.  The launch count (six)
+ * does not depend on S.  x_dev rows of n, xn_dev rows of nn, out_dev rows of hop * (n / hop) samples, each with its row stride.
+ * out_dev MAY ALIAS x_dev (same rows): the overlap-add reads only scratch.  It must not overlap xn_dev.  nonstationary must be 0
+ * (the non-stationary mask ignores xn): RVCMI_ERR_INVALID, as are S outside 1 .. 65535, a stride shorter than its row, an odd n_fft
+ * or one above 4096, and a ring or scratch smaller than the _bytes functions say.  Enqueue-only, no allocation.                  */
+int rvcmi_glue_spectral_gate_ring_batch(int S, const float* x_dev, int64_t x_stride, int64_t n, const float* xn_dev, int64_t xn_stride,
+                                        int64_t nn, float* out_dev, int64_t out_stride, int64_t shift, int64_t tail, void* ring_dev,
+                                        size_t ring_bytes, int64_t ring_base, const uint8_t* mode_dev, int any_cold, int n_fft, int hop,
+                                        const double* window_dev, const float* filter_dev, int nf, int nt, int nonstationary,
+                                        double n_std_thresh, double prop_decrease, void* scratch_dev, size_t scratch_bytes, void* stream);
+/* Bytes of scratch / of the spectrum cache the call above needs; 0 when the arguments are out of range. */
+size_t rvcmi_glue_spectral_gate_ring_scratch_bytes(int S, int64_t n, int n_fft, int hop);
+size_t rvcmi_glue_spectral_gate_ring_bytes(int S, int64_t nn, int n_fft, int hop);
+/* The dirty-frame rule on the host (no device needed): plan_out[6] = { Fn, K, head, back, advance, n_dirty }: the dirty frames are
+ * [0, head) and [back, Fn) (head == back == Fn: all of them), advance = shift / hop is what the caller adds to ring_base before the
+ * call (0 when every frame is dirty).  RVCMI_ERR_INVALID when nn < 1, n_fft is odd or outside [2, 4096] or hop outside [1, n_fft]. */
+int rvcmi_glue_gate_ring_plan(int64_t nn, int n_fft, int hop, int64_t shift, int64_t tail, int* plan_out);
+
+/* The GUI's cross-fade of the gated input block (gui.py:986-990) for the sessions with mode_dev[s] != 0; g_dev rows of
+ * block_frame + Lb samples (the gate's output), Lb <= block_frame:
+ *   g[:Lb] = g[:Lb] * fade_in + nr_buffer * fade_out;   denoise[-block_frame:] = g[:block_frame];   nr_buffer = g[block_frame:]
+ * with three fp32 roundings per faded sample and no fused multiply-add, so the result is bit-equal to torch's three element-wise
+ * statements.  denoise_dev rows of den_len samples; den_prev_dev (or NULL: no roll) rows of den_len - block_frame samples, a COPY of
+ * denoise[block_frame:] taken before the call, written to denoise[: den_len - block_frame] (the roll, per session: a session with
+ * mode 0 keeps its row).  g_dev is not written.                                                                              */
+int rvcmi_glue_nr_stitch_batch(int S, const float* g_dev, int64_t g_stride, int Lb, int64_t block_frame, const float* fade_in_dev,
+                               const float* fade_out_dev, float* nr_buffer_dev, int64_t nr_stride, float* denoise_dev, int64_t den_stride,
+                               int64_t den_len, const float* den_prev_dev, int64_t prev_stride, const uint8_t* mode_dev, void* stream);
+
+/* Per session a copy chosen by mode_dev[s]: non-zero: dst[s][off_a : off_a + na] = a[s][:na]; zero: dst[s][off_b : off_b + nb] =
+ * b[s][:nb], or nothing when b_dev is NULL.  dst_dev rows of dst_len samples.  A range that leaves its row: RVCMI_ERR_INVALID.     */
+int rvcmi_glue_masked_write_batch(int S, float* dst_dev, int64_t dst_stride, int64_t dst_len, const float* a_dev, int64_t a_stride,
+                                  int64_t off_a, int64_t na, const float* b_dev, int64_t b_stride, int64_t off_b, int64_t nb,
+                                  const uint8_t* mode_dev, void* stream);
+
 /* ---- beyond SURVEY.md section 8: the recurrent layer of the RMVPE f0 network -----------------------------------------------
  * Stands in for the `nn.GRU(384, 256, num_layers=1, batch_first=True, bidirectional=True)` of rvc/f0/e2e.py:50-67 (E2E.BiGRU, the
  * first module of E2E.fc), which bench.py --e2e measured at 75-90 % of a whole conversion on PyTorch-ROCm / MIOpen.

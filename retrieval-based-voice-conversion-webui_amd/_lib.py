@@ -137,6 +137,16 @@ SYMBOLS = [
     ("rvcmi_glue_spectral_gate", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                            C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P, _P, C.c_size_t, _P]),
     ("rvcmi_glue_spectral_gate_scratch_bytes", C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    ("rvcmi_glue_spectral_gate_ring_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
+                                                      _P, C.c_size_t, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                                      C.c_double, C.c_double, _P, C.c_size_t, _P]),
+    ("rvcmi_glue_spectral_gate_ring_scratch_bytes", C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    ("rvcmi_glue_spectral_gate_ring_bytes", C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    ("rvcmi_glue_gate_ring_plan", C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int)]),
+    ("rvcmi_glue_nr_stitch_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64,
+                                             _P, _P]),
+    ("rvcmi_glue_masked_write_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64,
+                                                C.c_int64, _P, _P]),
     ("rvcmi_glue_cut_points", C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("rvcmi_glue_cut_points_scratch_bytes", C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
     ("rvcmi_glue_filtfilt", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P,

@@ -6,12 +6,13 @@
 #include "cut_kernels.hpp"
 #include "filt_kernels.hpp"
 #include "gate_kernels.hpp"
+#include "gate_ring.hpp"
 #include "glue_kernels.hpp"
 
 using namespace rvcmi;
 
 static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0},
-    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_sola_b{0}, g_attr_sola_search_b{0}, g_attr_pv_spec_b{0}, g_attr_pv_synth_b{0};
+    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_gate_stft_r{0}, g_attr_gate_idft_r{0}, g_attr_sola_b{0}, g_attr_sola_search_b{0}, g_attr_pv_spec_b{0}, g_attr_pv_synth_b{0};
 
 // The phase-vocoder launches on a device-resident b (b_off: optional device offset into b); out [n] may not alias a or b.
 static void launch_phase_vocoder(const float* a, const float* b, const int* b_off, const float* fade_out, const float* fade_in, int n, float* out,
@@ -24,6 +25,10 @@ static void launch_phase_vocoder(const float* a, const float* b, const int* b_of
     hipLaunchKernelGGL(k_pv_synth, dim3((unsigned)((n + 63) / 64)), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st, a, b, b_off, fade_out,
                        fade_in, n, (const double*)bins, out);
 }
+
+#define RVCMI_BANK_MAX_S 65535  // a session is blockIdx.y (or blockIdx.x of a one-block-per-session launch)
+static_assert(GATE_RING_FT == GATE_FT && GATE_RING_MAX_NFFT == RVCMI_GATE_MAX_NFFT && GATE_RING_MAX_S == RVCMI_BANK_MAX_S,
+              "gate_ring.hpp restates the tile and the limits of the kernels");
 
 // Scratch of rvcmi_glue_spectral_gate, in this order (each part 256-byte aligned):
 //   X [B][F][K] double2 | XN [B][Fn][K] double2 (nn > 0) | xmax, thresh [B][K] double | mask [B][F][K] float | frames [B][F][n_fft] double
@@ -205,6 +210,119 @@ int rvcmi_glue_spectral_gate(const float* x, int B, int64_t n, const float* xn, 
 }
 
 
+size_t rvcmi_glue_spectral_gate_ring_scratch_bytes(int S, int64_t n, int n_fft, int hop) {
+    GateRingLayout g;
+    return gate_ring_layout(S, n, n_fft, hop, &g) ? g.total : 0;
+}
+
+size_t rvcmi_glue_spectral_gate_ring_bytes(int S, int64_t nn, int n_fft, int hop) { return gate_ring_bytes(S, nn, n_fft, hop); }
+
+int rvcmi_glue_gate_ring_plan(int64_t nn, int n_fft, int hop, int64_t shift, int64_t tail, int* plan_out) {
+    return guarded([&] {
+        GateRingPlan p;
+        if (!plan_out) RVCMI_FAIL(RVCMI_ERR_INVALID, "gate_ring_plan: null pointer");
+        if (!gate_ring_plan(nn, n_fft, hop, shift, tail, &p))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "gate_ring_plan: nn = %lld >= 1, n_fft = %d even and in [2, %d], hop = %d in [1, n_fft]", (long long)nn, n_fft,
+                       RVCMI_GATE_MAX_NFFT, hop);
+        plan_out[0] = p.Fn, plan_out[1] = p.K, plan_out[2] = p.head, plan_out[3] = p.back, plan_out[4] = p.advance, plan_out[5] = p.n_dirty;
+    });
+}
+
+int rvcmi_glue_spectral_gate_ring_batch(int S, const float* x, int64_t x_stride, int64_t n, const float* xn, int64_t xn_stride, int64_t nn,
+                                        float* out, int64_t out_stride, int64_t shift, int64_t tail, void* ring, size_t ring_bytes,
+                                        int64_t ring_base, const uint8_t* mode, int any_cold, int n_fft, int hop, const double* window,
+                                        const float* filter, int nf, int nt, int nonstationary, double n_std_thresh, double prop_decrease,
+                                        void* scratch, size_t scratch_bytes, void* stream) {
+    return guarded([&] {
+        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
+        if (!x || !xn || !out || !ring || !mode || !window || !scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: null pointer");
+        if (nonstationary) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: only the stationary gate with a noise signal is served");
+        if (n_fft < 2 || n_fft > RVCMI_GATE_MAX_NFFT || (n_fft & 1))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: n_fft = %d must be even and in [2, %d]", n_fft, RVCMI_GATE_MAX_NFFT);
+        if (hop < 1 || hop > n_fft) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: hop = %d outside [1, n_fft = %d]", hop, n_fft);
+        if (n < 1 || nn < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: empty input");
+        const int64_t Lout = (int64_t)hop * (n / hop);
+        if (x_stride < n || xn_stride < nn || out_stride < Lout)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: row stride %lld / %lld / %lld shorter than the row %lld / %lld / %lld", (long long)x_stride,
+                       (long long)xn_stride, (long long)out_stride, (long long)n, (long long)nn, (long long)Lout);
+        if (filter && (nf < 1 || nt < 1 || (int64_t)nf * nt > (1 << 20)))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: smoothing filter %d x %d", nf, nt);
+        if (!(prop_decrease >= 0.0 && prop_decrease <= 1.0)) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: prop_decrease outside [0, 1]");
+        GateRingLayout g;
+        GateRingPlan p;
+        if (!gate_ring_layout(S, n, n_fft, hop, &g) || !gate_ring_plan(nn, n_fft, hop, shift, tail, &p))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: too many frames");
+        const int tiles_n = any_cold ? p.tiles_cold : p.tiles_dirty;
+        if (g.tiles_x + tiles_n > 65535) RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: too many frames");
+        const size_t need_ring = gate_ring_bytes(S, nn, n_fft, hop);
+        if (scratch_bytes < g.total || ring_bytes < need_ring)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "spectral_gate_ring: scratch of %zu bytes, %zu needed; cache of %zu bytes, %zu needed", scratch_bytes, g.total,
+                       ring_bytes, need_ring);
+        char* s = static_cast<char*>(scratch);
+        double2* X = reinterpret_cast<double2*>(s + g.x);
+        double2* R = static_cast<double2*>(ring);
+        double* xmax = reinterpret_cast<double*>(s + g.xmax);
+        double* thresh = reinterpret_cast<double*>(s + g.thresh);
+        float* mraw = reinterpret_cast<float*>(s + g.mask);
+        double* z = reinterpret_cast<double*>(s + g.frames);
+        const int F = g.F, K = g.K, Fn = p.Fn;
+        const int base = gate_ring_slot(ring_base, 0, Fn);
+        const int lds = gate_lds_bytes(n_fft);
+        hipStream_t st = (hipStream_t)stream;
+        ensure_dyn_lds((const void*)k_gate_stft_ring, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_stft_r);
+        ensure_dyn_lds((const void*)k_gate_idft_ring, gate_lds_bytes(RVCMI_GATE_MAX_NFFT), g_attr_gate_idft_r);
+        hipLaunchKernelGGL(k_gate_stft_ring, dim3((unsigned)((K + 63) / 64), (unsigned)(g.tiles_x + tiles_n), (unsigned)S), dim3(256), (size_t)lds, st,
+                           x, x_stride, n, F, X, xn, xn_stride, nn, Fn, R, g.tiles_x, n_fft, hop, window, mode, p.head, p.back, base);
+        hipLaunchKernelGGL(k_gate_stats_ring, dim3((unsigned)((K + 63) / 64), (unsigned)S), dim3(1024), 0, st, (const double2*)X, F,
+                           (const double2*)R, Fn, K, n_std_thresh, xmax, thresh, base, mode);
+        hipLaunchKernelGGL(k_gate_mask_ring, dim3((unsigned)((K + 255) / 256), (unsigned)F, (unsigned)S), dim3(256), 0, st, (const double2*)X, F, K,
+                           (const double*)xmax, (const double*)thresh, 0, 0.0, 1.0, 1, (float)prop_decrease, mraw, mode);
+        hipLaunchKernelGGL(k_gate_smooth_ring, dim3((unsigned)((K + 255) / 256), (unsigned)F, (unsigned)S), dim3(256), 0, st, X, F, K,
+                           (const float*)mraw, filter, nf, nt, mode);
+        hipLaunchKernelGGL(k_gate_idft_ring, dim3((unsigned)((n_fft + 63) / 64), (unsigned)g.tiles_x, (unsigned)S), dim3(256), (size_t)lds, st,
+                           (const double2*)X, F, n_fft, window, z, mode);
+        if (Lout > 0)
+            hipLaunchKernelGGL(k_gate_ola_ring, dim3((unsigned)((Lout + 255) / 256), (unsigned)S), dim3(256), 0, st, (const double*)z, F, n_fft, hop,
+                               window, Lout, out, out_stride, mode);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_nr_stitch_batch(int S, const float* g, int64_t g_stride, int Lb, int64_t block_frame, const float* fade_in, const float* fade_out,
+                               float* nr_buffer, int64_t nr_stride, float* denoise, int64_t den_stride, int64_t den_len, const float* den_prev,
+                               int64_t prev_stride, const uint8_t* mode, void* stream) {
+    return guarded([&] {
+        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "nr_stitch_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
+        if (!g || !fade_in || !fade_out || !nr_buffer || !denoise || !mode) RVCMI_FAIL(RVCMI_ERR_INVALID, "nr_stitch_batch: null pointer");
+        if (Lb < 1 || block_frame < Lb || den_len < block_frame)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "nr_stitch_batch: 1 <= Lb = %d <= block_frame = %lld <= the rolling buffer's %lld samples", Lb,
+                       (long long)block_frame, (long long)den_len);
+        if (g_stride < block_frame + Lb || nr_stride < Lb || den_stride < den_len || (den_prev && prev_stride < den_len - block_frame))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "nr_stitch_batch: a row stride is shorter than its row");
+        if ((den_len + 255) / 256 > 0x7fffffff) RVCMI_FAIL(RVCMI_ERR_INVALID, "nr_stitch_batch: buffer too long");
+        hipLaunchKernelGGL(k_nr_stitch_batch, dim3((unsigned)((den_len + 255) / 256), (unsigned)S), dim3(256), 0, (hipStream_t)stream, g, g_stride, Lb,
+                           block_frame, fade_in, fade_out, nr_buffer, nr_stride, denoise, den_stride, den_len, den_prev, prev_stride, mode);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_masked_write_batch(int S, float* dst, int64_t dst_stride, int64_t dst_len, const float* a, int64_t a_stride, int64_t off_a, int64_t na,
+                                  const float* b, int64_t b_stride, int64_t off_b, int64_t nb, const uint8_t* mode, void* stream) {
+    return guarded([&] {
+        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "masked_write_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
+        if (!dst || !a || !mode) RVCMI_FAIL(RVCMI_ERR_INVALID, "masked_write_batch: null pointer");
+        if (!b) nb = 0, off_b = 0, b_stride = 0;
+        if (dst_len < 1 || dst_stride < dst_len || na < 1 || nb < 0 || off_a < 0 || off_b < 0 || off_a > dst_len - na || off_b > dst_len - nb ||
+            a_stride < na || b_stride < nb)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "masked_write_batch: a range leaves its row, or a row stride is shorter than its row");
+        const int64_t nmax = na > nb ? na : nb;
+        if ((nmax + 255) / 256 > 0x7fffffff) RVCMI_FAIL(RVCMI_ERR_INVALID, "masked_write_batch: row too long");
+        hipLaunchKernelGGL(k_masked_write_batch, dim3((unsigned)((nmax + 255) / 256), (unsigned)S), dim3(256), 0, (hipStream_t)stream, dst, dst_stride, a,
+                           a_stride, off_a, na, b, b_stride, off_b, nb, mode);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int rvcmi_glue_expand_protect(const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
                               float* out, void* stream) {
     return guarded([&] {
@@ -356,7 +474,6 @@ int rvcmi_glue_resample_poly(const float* x, int64_t n, const float* kernel, int
 }
 
 // ---- the block DSP for a bank of S sessions: the single-stream bodies, session index in the grid (glue_kernels.hpp) --------------------
-#define RVCMI_BANK_MAX_S 65535  // a session is blockIdx.y (or blockIdx.x of a one-block-per-session launch)
 
 int rvcmi_glue_resample_poly_batch(int S, const float* x, int64_t x_stride, int64_t n, const float* kernel, int orig, int new_, int K, int width,
                                    float* out, int64_t out_stride, int64_t n_out, void* stream) {

@@ -122,3 +122,87 @@ class TorchGateHIP(torch.nn.Module):
                                temp_coeff=self.temp_coeff_nonstationary, n_movemean=self.n_movemean_nonstationary,
                                prop_decrease=self.prop_decrease)
         return (y[0] if squeeze else y).to(x.dtype)
+
+
+class TorchGateBank:
+    """``TorchGateHIP.forward(x, xn)`` for a bank of ``sessions`` talkers whose noise signal ``xn`` is a rolling buffer of ``nn`` samples
+    (the realtime GUI's: the whole ``input_wav`` / ``output_buffer``, gui.py:983-985, 1020-1022), with the noise spectra kept from block to
+    block: a block rewrites only the tail of ``xn``, so of its ``1 + nn // hop`` STFT frames only the few ``glue.gate_ring_plan`` calls dirty
+    are transformed again (29 of 282 at the GUI's geometries).  Every active session's result is BIT-equal to ``tg(x[i][None], xn[i][None])``.
+
+        bank = TorchGateBank(tg, sessions=S, nn=input_wav_len)
+        y = bank.forward(x_rows, xn_rows, shift=block_frame, tail=block_frame, active=[True, False, ...])
+
+    It owns the spectrum cache (one ``[S, Fn, K]`` complex128 ring, allocated at the first call with an active session: ``ring_bytes``,
+    4.3 MB per session at 48 kHz), the ring's base, the host mirror of every session's state and the device ``mode`` vector (uploaded only
+    when it changes).  A session is WARM -- only its dirty frames are transformed -- when it was active in the previous ``forward`` and has
+    not been invalidated since; otherwise it is COLD and all its frames are.  The caller vouches that between two ``forward`` calls every
+    warm session's ``xn`` row moved left by ``shift`` samples and only its last ``tail`` samples were rewritten; ``invalidate(i)`` after any
+    other write.  Only the stationary gate is served (``tg.nonstationary`` raises).  ``RVCMI_GATE_RING=0`` (development) makes every
+    active session cold in every call: the same results without the cache."""
+
+    def __init__(self, tg: TorchGateHIP, sessions: int, nn: int):
+        if int(sessions) < 1:
+            raise ValueError("a bank has at least one session (got %d)" % int(sessions))
+        if tg.nonstationary:
+            raise ValueError("TorchGateBank serves the stationary gate only: the non-stationary mask ignores the noise signal")
+        self.tg, self.S, self.nn = tg, int(sessions), int(nn)
+        self.plan0 = glue.gate_ring_plan(self.nn, tg.n_fft, int(tg.hop_length), -1, 0)   # raises on a geometry the library refuses
+        self.Fn = self.plan0["Fn"]
+        self.ring_bytes = int(_lib.lib().rvcmi_glue_spectral_gate_ring_bytes(self.S, self.nn, tg.n_fft, int(tg.hop_length)))
+        self.ring = None
+        self.base = 0
+        self.valid = [False] * self.S        # session i's ring rows hold the previous forward's spectra
+        self._mode_host, self._mode = None, None
+        self._scratch = None
+        self._filt = None
+        self.last_modes = None               # what the last forward ran: a list of 0 / 1 / 2 per session
+        self.mode = None                     # the same on the device (uint8 [S])
+
+    def invalidate(self, i: int) -> None:
+        """Session ``i``'s cached spectra no longer describe its noise buffer: its next active call is cold."""
+        self.valid[int(i)] = False
+
+    def _modes(self, host, dev) -> torch.Tensor:
+        if host != self._mode_host or self._mode is None or self._mode.device != dev:
+            self._mode_host, self._mode = list(host), torch.tensor(host, dtype=torch.uint8, device=dev)
+        return self._mode
+
+    @torch.no_grad()
+    def forward(self, x_rows: torch.Tensor, xn_rows: torch.Tensor, shift: int, tail: int, active, out: Optional[torch.Tensor] = None):
+        """``x_rows`` [S, n], ``xn_rows`` [S, nn] float32 on the GPU (rows may be slices of longer buffers); ``active``: S booleans.
+        -> the gated rows [S, hop * (n // hop)] (``out``, which may be ``x_rows`` itself, or a new tensor whose inactive rows are
+        uninitialised); the device ``mode`` vector of this call is ``self.mode``.  With no active session nothing is launched or
+        uploaded, ``out`` is returned as given and ``self.mode`` is None -- but the call still counts: every session is stale after it."""
+        import os
+
+        active = [bool(a) for a in active]
+        if len(active) != self.S:
+            raise ValueError("active must hold %d values, got %d" % (self.S, len(active)))
+        if xn_rows.dim() != 2 or int(xn_rows.shape[1]) != self.nn:
+            raise ValueError("xn_rows must be [%d, %d], got %s" % (self.S, self.nn, tuple(xn_rows.shape)))
+        tg, dev = self.tg, x_rows.device
+        tg._check_overlap_add(int(x_rows.shape[-1]))
+        use_ring = os.environ.get("RVCMI_GATE_RING", "1") != "0"
+        host = [0 if not a else (1 if (v and use_ring) else 2) for a, v in zip(active, self.valid)]
+        plan = glue.gate_ring_plan(self.nn, tg.n_fft, int(tg.hop_length), shift, tail)
+        self.base = (self.base + plan["advance"]) % self.Fn
+        self.valid = active
+        self.last_modes = host
+        if not any(active):   # nothing is launched or uploaded; the sessions go stale
+            self.mode = None
+            return out
+        self.mode = self._modes(host, dev)
+        if self.ring is None or self.ring.device != dev:
+            self.ring = torch.empty(self.ring_bytes, device=dev, dtype=torch.uint8)
+        L = _lib.lib()
+        nbytes = int(L.rvcmi_glue_spectral_gate_ring_scratch_bytes(self.S, int(x_rows.shape[1]), tg.n_fft, int(tg.hop_length)))
+        if self._scratch is None or self._scratch.numel() < nbytes or self._scratch.device != dev:
+            self._scratch = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+        f = tg.smoothing_filter
+        if f is not None and (self._filt is None or self._filt.device != dev):
+            self._filt = f.reshape(f.shape[-2], f.shape[-1]).to(device=dev, dtype=torch.float32).contiguous()
+        filt = self._filt if f is not None else None
+        return glue.spectral_gate_ring(x_rows, xn_rows, shift, tail, self.ring, self.base, self.mode, 2 in host, tg.n_fft, int(tg.hop_length),
+                                       tg._window(dev), filt, n_std_thresh=tg.n_std_thresh_stationary, prop_decrease=tg.prop_decrease, out=out,
+                                       scratch=self._scratch)

@@ -20,6 +20,8 @@ and their forms for a bank of S realtime sessions (``realtime.RealtimeBank``; pe
 
     retrieve_blend_expand_batch(feats [S, nq, d], index, ..., skip_rows)       one search, the realtime guard per session
     sola_batch(infer_wav [S, n], sola_buffer [S, Lb], ...) / envelope_mix_batch(input_wav [S, .], infer_wav [S, n], zc, rate)
+    spectral_gate_ring(x [S, n], xn [S, nn], shift, tail, ring, ring_base, mode, ...)   the gate over a rolling cache of noise spectra
+    nr_stitch_batch(...) / masked_write_batch(...) / gate_ring_plan(nn, n_fft, hop, shift, tail)   per-session noise reduction (gate.TorchGateBank)
 
 All take and return CUDA (ROCm) tensors and enqueue on the current stream; a CPU tensor raises (no fallback).
 """
@@ -576,3 +578,127 @@ def spectral_gate(x: torch.Tensor, xn: Optional[torch.Tensor], n_fft: int, hop: 
                                               1 if nonstationary else 0, float(n_std_thresh), float(n_thresh_ns), float(temp_coeff),
                                               int(n_movemean), float(prop_decrease), _lib.ptr(out), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
     return out
+
+
+def gate_ring_plan(nn: int, n_fft: int, hop: int, shift: int, tail: int) -> dict:
+    """The dirty-frame rule of ``spectral_gate_ring`` (rvcmi.h, csrc/gate_ring.hpp; host only, no device): of the ``Fn = 1 + nn // hop``
+    frames of a rolling noise buffer that moved left by ``shift`` samples and whose last ``tail`` samples were rewritten, the frames
+    ``[0, head)`` and ``[back, Fn)`` must be transformed again (``head == back == Fn``: all of them); ``advance`` is what the caller adds to
+    its ring base before the call.  -> dict(Fn, K, head, back, advance, n_dirty)."""
+    out = (C.c_int * 6)()
+    _lib.check(_lib.lib().rvcmi_glue_gate_ring_plan(int(nn), int(n_fft), int(hop), int(shift), int(tail), out))
+    return dict(zip(("Fn", "K", "head", "back", "advance", "n_dirty"), (int(v) for v in out)))
+
+
+def _bank_mode(mode: torch.Tensor, S: int, dev) -> None:
+    if mode.dtype != torch.uint8 or mode.dim() != 1 or mode.numel() != S or mode.device != dev or not mode.is_contiguous():
+        raise ValueError("mode must be a contiguous uint8 tensor [%d] on %s" % (S, dev))
+
+
+def _rows_overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Do the memory spans of two row arrays intersect?  (Spans, not elements: interleaved rows of one buffer count as overlapping.)"""
+    def span(t):
+        lo = t.data_ptr()
+        return lo, lo + 4 * ((t.shape[0] - 1) * t.stride(0) + t.shape[1] if t.shape[0] > 1 else t.shape[1])
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def spectral_gate_ring(x: torch.Tensor, xn: torch.Tensor, shift: int, tail: int, ring: torch.Tensor, ring_base: int, mode: torch.Tensor,
+                       any_cold: bool, n_fft: int, hop: int, window: torch.Tensor, smoothing_filter: Optional[torch.Tensor] = None,
+                       n_std_thresh: float = 1.5, prop_decrease: float = 1.0, out: Optional[torch.Tensor] = None,
+                       scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The stationary ``spectral_gate(x, xn)`` for a bank whose noise rows ``xn`` [S, nn] are rolling buffers (rvcmi.h,
+    ``rvcmi_glue_spectral_gate_ring_batch``): ``ring`` (uint8, ``>= rvcmi_glue_spectral_gate_ring_bytes``) keeps every session's noise
+    spectra, ``mode`` uint8 [S] says per session off (0) / warm (1: only the frames ``gate_ring_plan`` calls dirty are transformed) / cold
+    (2), ``any_cold`` whether some session is cold.  Rows of ``x`` [S, n], ``xn`` and ``out`` [S, hop * (n // hop)] may be slices of
+    longer buffers; ``out`` may be ``x`` itself (in place), must not overlap ``xn``, and is allocated when None (rows of off sessions are
+    then uninitialised).  Active rows equal ``spectral_gate`` on contiguous copies bit for bit.  ``TorchGateBank`` keeps the state."""
+    dev = _lib.on_gpu(x, "x")
+    S, n, xs = bank_rows(x, "x")
+    Sn, nn, ns = bank_rows(xn, "xn", dev)
+    if Sn != S:
+        raise ValueError("x has %d sessions, xn %d" % (S, Sn))
+    _bank_mode(mode, S, dev)
+    hop, n_fft = int(hop), int(n_fft)
+    if window.dtype != torch.float64 or window.dim() != 1 or window.numel() != n_fft or not window.is_contiguous() or window.device != dev:
+        raise ValueError("window must be a contiguous float64 tensor of n_fft = %d samples on %s" % (n_fft, dev))
+    if smoothing_filter is not None and (smoothing_filter.dtype != torch.float32 or smoothing_filter.dim() != 2 or not smoothing_filter.is_contiguous()
+                                         or smoothing_filter.device != dev):
+        raise ValueError("smoothing_filter must be a contiguous float32 tensor [nf, nt] on %s" % dev)
+    L = _lib.lib()
+    nbytes, rbytes = int(L.rvcmi_glue_spectral_gate_ring_scratch_bytes(S, n, n_fft, hop)), int(L.rvcmi_glue_spectral_gate_ring_bytes(S, nn, n_fft, hop))
+    if nbytes == 0 or rbytes == 0:
+        raise _lib.RvcmiError("spectral_gate_ring: n_fft = %d (even, <= 4096), hop = %d (1..n_fft) or the shapes %s / %s are out of range"
+                              % (n_fft, hop, tuple(x.shape), tuple(xn.shape)), code=_lib.ERR_INVALID)
+    if ring.dtype != torch.uint8 or ring.device != dev or not ring.is_contiguous() or ring.numel() < rbytes:
+        raise ValueError("ring must be a contiguous uint8 tensor of at least %d bytes on %s" % (rbytes, dev))
+    Lout = hop * (n // hop)
+    if out is None:
+        out = torch.empty(S, Lout, device=dev, dtype=torch.float32)
+    So, no, os_ = bank_rows(out, "out", dev)
+    if So != S or no != Lout:
+        raise ValueError("out must be [%d, %d], got %s" % (S, Lout, tuple(out.shape)))
+    if _rows_overlap(out, xn):
+        raise ValueError("out must not overlap xn")
+    if _rows_overlap(out, x) and not (out.data_ptr() == x.data_ptr() and os_ == xs):
+        raise ValueError("out may be x itself (in place) but must not overlap it otherwise")
+    if S > 1 and os_ < Lout:
+        raise ValueError("the rows of out overlap")
+    if scratch is None:
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    elif scratch.dtype != torch.uint8 or scratch.device != dev or not scratch.is_contiguous() or scratch.numel() < nbytes:
+        raise ValueError("scratch must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    nf, nt = (int(smoothing_filter.shape[0]), int(smoothing_filter.shape[1])) if smoothing_filter is not None else (0, 0)
+    with torch.cuda.device(dev):
+        _lib.check(L.rvcmi_glue_spectral_gate_ring_batch(S, _lib.ptr(x), xs, n, _lib.ptr(xn), ns, nn, _lib.ptr(out), os_, int(shift), int(tail),
+                                                         _lib.ptr(ring), ring.numel(), int(ring_base), _lib.ptr(mode), 1 if any_cold else 0, n_fft, hop,
+                                                         _lib.ptr(window), _lib.ptr(smoothing_filter), nf, nt, 0, float(n_std_thresh),
+                                                         float(prop_decrease), _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(dev)))
+    return out
+
+
+def nr_stitch_batch(g: torch.Tensor, nr_buffer: torch.Tensor, denoise: torch.Tensor, fade_in: torch.Tensor, fade_out: torch.Tensor,
+                    block_frame: int, mode: torch.Tensor, den_prev: Optional[torch.Tensor] = None) -> None:
+    """The GUI's cross-fade of the gated input (gui.py:986-990) for the sessions with ``mode != 0``, in place on ``nr_buffer`` [S, Lb] and
+    ``denoise`` [S, n]: ``g[:Lb] = g[:Lb] * fade_in + nr_buffer * fade_out; denoise[-blk:] = g[:blk]; nr_buffer = g[blk:]`` with ``g``
+    [S, blk + Lb] the gate's output (not written), bit-equal to the torch statements.  ``den_prev`` [S, n - blk]: a copy of
+    ``denoise[:, blk:]`` taken before, written to ``denoise[:, :-blk]`` (the roll, only for those sessions).  One launch."""
+    dev = _lib.on_gpu(g, "g")
+    S, ng, gs = bank_rows(g, "g")
+    Sb, Lb, bs = bank_rows(nr_buffer, "nr_buffer", dev)
+    Sd, nd, ds = bank_rows(denoise, "denoise", dev)
+    blk = int(block_frame)
+    if Sb != S or Sd != S or ng != blk + Lb:
+        raise ValueError("g must be [S, block_frame + Lb] with nr_buffer [S, Lb] and denoise [S, n]")
+    _bank_mode(mode, S, dev)
+    for t, nm in ((fade_in, "fade_in"), (fade_out, "fade_out")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != Lb:
+            raise ValueError("%s must be a contiguous float32 tensor of %d samples on %s" % (nm, Lb, dev))
+    ps = 0
+    if den_prev is not None:
+        Sp, npv, ps = bank_rows(den_prev, "den_prev", dev)
+        if Sp != S or npv != nd - blk or _rows_overlap(den_prev, denoise):
+            raise ValueError("den_prev must be a copy [S, %d] of denoise[:, block_frame:]" % (nd - blk))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_nr_stitch_batch(S, _lib.ptr(g), gs, Lb, blk, _lib.ptr(fade_in), _lib.ptr(fade_out), _lib.ptr(nr_buffer), bs,
+                                                         _lib.ptr(denoise), ds, nd, _lib.ptr(den_prev), ps, _lib.ptr(mode), _lib.stream_ptr(dev)))
+
+
+def masked_write_batch(dst: torch.Tensor, mode: torch.Tensor, a: torch.Tensor, off_a: int, b: Optional[torch.Tensor] = None, off_b: int = 0) -> None:
+    """Per session ``s``: ``dst[s, off_a : off_a + a.shape[1]] = a[s]`` where ``mode[s] != 0``, else ``dst[s, off_b : off_b + b.shape[1]] =
+    b[s]`` (nothing when ``b`` is None).  Rows may be slices of longer buffers; ``a`` / ``b`` must not overlap ``dst``.  One launch."""
+    dev = _lib.on_gpu(dst, "dst")
+    S, nd, ds = bank_rows(dst, "dst")
+    Sa, na, as_ = bank_rows(a, "a", dev)
+    _bank_mode(mode, S, dev)
+    Sb, nb, bs = (S, 0, 0)
+    if b is not None:
+        Sb, nb, bs = bank_rows(b, "b", dev)
+    if Sa != S or Sb != S:
+        raise ValueError("dst, a and b must hold the same number of sessions")
+    if _rows_overlap(dst, a) or (b is not None and _rows_overlap(dst, b)):
+        raise ValueError("a / b must not overlap dst")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_masked_write_batch(S, _lib.ptr(dst), ds, nd, _lib.ptr(a), as_, int(off_a), na, _lib.ptr(b), bs, int(off_b), nb,
+                                                            _lib.ptr(mode), _lib.stream_ptr(dev)))

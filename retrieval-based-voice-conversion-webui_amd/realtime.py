@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, glue
-from .gate import TorchGateHIP
+from .gate import TorchGateBank, TorchGateHIP
 
 
 def f0_extractor_frame(block_frame_16k: int, method: str = "fcpe", window: int = 160) -> int:
@@ -604,7 +604,7 @@ class RealtimeBank:
 
         bank = RealtimeBank(rvc, sessions=S, samplerate=48000, use_pv=True)
         out = bank.process(blocks)     # host float32 [S, block_frame] -> device float32 [S, block_frame]
-        bank.set_key(i, key); bank.set_sid(i, sid); bank.reset(i)
+        bank.set_key(i, key); bank.set_sid(i, sid); bank.set_noise_reduce(i, I=True, O=False); bank.reset(i)
         bank.last_offsets              # device int32 [S]: every session's SOLA offset of the last block
 
     Per block: the input gate (host, per session), ONE host-to-device copy of the ``[S, m]`` block, then on the device the 16 kHz
@@ -614,8 +614,17 @@ class RealtimeBank:
     ``infer_batch(input_wav_res [S, n16], block_frame_16k, skip_head, return_length, f0method, keys, sids)`` method is asked instead
     of ``rvc_infer_batch_hip``.
 
-    Not served, and refused by the constructor: the noise-reduction boxes, the monitor mode ``function="im"``; a formant shift is
-    refused at the first block.  The step is eager: it is not captured into a hipGraph."""
+    The GUI's noise-reduction boxes (gui.py:974-992, 1015-1022) are per session and switchable between blocks: ``set_noise_reduce(i, I,
+    O)``.  The gate of all ticked sessions is one ``TorchGateBank`` call per box (six launches whatever ``S``) that keeps every session's
+    noise spectra from block to block and transforms only the frames the block rewrote; the cross-fade, the rolling ``input_wav_denoise`` /
+    ``nr_buffer`` / ``output_buffer`` rows and the 16 kHz write-back are masked per session, so each session equals a ``RealtimeStream``
+    with its boxes bit for bit.  The launch count depends on whether any session has I and whether any has O ticked, never on ``S`` or on
+    which sessions they are; with no box ticked the step issues exactly the launches it issues without this feature.  The spectrum caches
+    are allocated at the first block that needs them: ``TorchGateBank.ring_bytes``, 4.3 MB per session and box at 48 kHz.
+
+    Not served, and refused by the constructor: bank-wide ``I_noise_reduce`` / ``O_noise_reduce`` arguments (the boxes are per session),
+    the monitor mode ``function="im"``; a formant shift is refused at the first block.  The step is eager: it is not captured into a
+    hipGraph."""
 
     def __init__(self, rvc, sessions: int, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05,
                  extra_time: float = 2.5, threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe",
@@ -623,7 +632,8 @@ class RealtimeBank:
         if int(sessions) < 1:
             raise ValueError("a bank has at least one session (got %d)" % int(sessions))
         if I_noise_reduce or O_noise_reduce:
-            raise ValueError("RealtimeBank does not serve noise reduction (I_noise_reduce / O_noise_reduce); use RealtimeStream")
+            raise ValueError("RealtimeBank does not serve noise reduction (I_noise_reduce / O_noise_reduce) bank-wide: tick the boxes per session "
+                             "with set_noise_reduce(i, I, O)")
         if function != "vc":
             raise ValueError("RealtimeBank serves function=\"vc\" only (got %r); the monitor mode is RealtimeStream's" % (function,))
         if rvc is None:
@@ -651,6 +661,14 @@ class RealtimeBank:
         self.fade_out_window = (1 - fade_in).to(self.device)
         self.resampler = SincResample(self.samplerate, 16000, self.device)
         self.resampler2 = SincResample(self.tgt_sr, self.samplerate, self.device) if self.tgt_sr != self.samplerate else None
+        # gui.py:825, 835-836, per session: kept whatever the boxes say, updated only while they are ticked
+        self.input_wav_denoise = torch.zeros_like(self.input_wav)
+        self.nr_buffer = torch.zeros_like(self.sola_buffer)
+        self.output_buffer = torch.zeros_like(self.input_wav)
+        self.I_noise_reduce, self.O_noise_reduce = [False] * S, [False] * S
+        self.tg = TorchGateHIP(sr=self.samplerate, n_fft=4 * self.zc, prop_decrease=0.9).to(self.device)   # gui.py:869-871
+        self.gate_I = self.gate_O = None   # the boxes' TorchGateBank (spectrum cache + session states), made when a box is first ticked
+        self._masks = {}
         self.keys = [getattr(rvc, "f0_up_key", 0)] * S
         self.sids = [0] * S
         self.vc = None            # the sessions' RealtimeVCBatch (pitch caches), made at the first block of a real rvc object
@@ -662,13 +680,43 @@ class RealtimeBank:
     def set_sid(self, i: int, sid: int) -> None:
         self.sids[int(i)] = int(sid)
 
-    def reset(self, i: int) -> None:
-        """Session ``i``'s state back to zeros (a new talker takes the slot); the other sessions are not touched."""
+    def set_noise_reduce(self, i: int, I: Optional[bool] = None, O: Optional[bool] = None) -> None:
+        """Session ``i``'s noise-reduction boxes (``None`` leaves a box as it is); takes effect at the next block.  A session whose box was
+        not ticked in the previous block starts from a full transform of its noise buffer (cold); after that only the rewritten frames are."""
         i = int(i)
         if not 0 <= i < self.S:
             raise IndexError("session %d of %d" % (i, self.S))
-        for t in (self.input_wav, self.input_wav_res, self.sola_buffer):
+        if I is not None:
+            if I and self.block_frame < self.sola_buffer_frame:
+                raise ValueError("the bank's input gate needs block_frame = %d >= sola_buffer_frame = %d (a block shorter than the cross-fade); "
+                                 "use RealtimeStream" % (self.block_frame, self.sola_buffer_frame))
+            self.I_noise_reduce[i] = bool(I)
+            if I and self.gate_I is None:
+                self.gate_I = TorchGateBank(self.tg, self.S, self.input_wav_len)
+        if O is not None:
+            self.O_noise_reduce[i] = bool(O)
+            if O and self.gate_O is None:
+                self.gate_O = TorchGateBank(self.tg, self.S, self.input_wav_len)
+
+    def _mask(self, name: str, flags) -> torch.Tensor:
+        """The device copy of a box's per-session flags (uint8 [S]), uploaded when they change."""
+        host, t = self._masks.get(name, (None, None))
+        if host != flags:
+            host, t = list(flags), torch.tensor([1 if f else 0 for f in flags], dtype=torch.uint8, device=self.device)
+            self._masks[name] = (host, t)
+        return t
+
+    def reset(self, i: int) -> None:
+        """Session ``i``'s state back to zeros (a new talker takes the slot); the other sessions are not touched.  The session's
+        noise-reduction boxes stay as they are; its cached noise spectra are dropped."""
+        i = int(i)
+        if not 0 <= i < self.S:
+            raise IndexError("session %d of %d" % (i, self.S))
+        for t in (self.input_wav, self.input_wav_res, self.sola_buffer, self.input_wav_denoise, self.nr_buffer, self.output_buffer):
             t[i].zero_()
+        for g in (self.gate_I, self.gate_O):
+            if g is not None:
+                g.invalidate(i)
         self.rms_buffer[i] = 0
         if self.vc is not None:
             self.vc.reset(i)
@@ -695,7 +743,22 @@ class RealtimeBank:
         self.input_wav[:, :-blk] = self.input_wav[:, blk:].clone()
         self.input_wav[:, -m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)   # the block's one host-to-device copy
         self.input_wav_res[:, :-blk16] = self.input_wav_res[:, blk16:].clone()
-        self.input_wav_res[:, -160 * (m // zc + 1):] = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
+        Lb = self.sola_buffer_frame
+        any_I, any_O = any(self.I_noise_reduce), any(self.O_noise_reduce)
+        if self.gate_I is not None:                                                      # gui.py:974-992, the ticked sessions only
+            den_prev = self.input_wav_denoise[:, blk:].clone() if any_I else None
+            gated = self.gate_I.forward(self.input_wav[:, -Lb - blk:], self.input_wav, blk, m, self.I_noise_reduce)
+        if any_I:
+            mask_I = self.gate_I.mode
+            glue.nr_stitch_batch(gated, self.nr_buffer, self.input_wav_denoise, self.fade_in_window, self.fade_out_window, blk, mask_I, den_prev=den_prev)
+            # both resamples go to staging; each session's own range is written from its own source (the ranges differ when the host input
+            # gate is on: m = blk + 2 zc)
+            res_I = self.resampler.batch(self.input_wav_denoise[:, -blk - 2 * zc:])[:, 160:]
+            res = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
+            n16 = self.input_wav_res_len
+            glue.masked_write_batch(self.input_wav_res, mask_I, res_I, n16 - int(res_I.shape[1]), res, n16 - int(res.shape[1]))
+        else:
+            self.input_wav_res[:, -160 * (m // zc + 1):] = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
         infer_wav = self._infer()
         if infer_wav.dim() != 2 or infer_wav.shape[0] != self.S:
             raise ValueError("the model returned %s for %d sessions" % (tuple(infer_wav.shape), self.S))
@@ -705,9 +768,21 @@ class RealtimeBank:
             infer_wav = self.resampler2.batch(infer_wav if infer_wav.stride(1) == 1 else infer_wav.contiguous())
         if not infer_wav.is_contiguous():
             infer_wav = infer_wav.contiguous()
+        if any_O:                                                                        # gui.py:1015-1022, in place on the ticked sessions' rows
+            n = int(infer_wav.shape[1])
+            if n % zc or n < blk:
+                raise ValueError("the bank's output gate needs a converted block of a whole number of hops (got %d samples, hop %d)" % (n, zc))
+            rolled = torch.cat((self.output_buffer[:, blk:], infer_wav[:, -blk:]), 1)
+            glue.masked_write_batch(self.output_buffer, self._mask("O", self.O_noise_reduce), rolled, 0)
+        if self.gate_O is not None:
+            self.gate_O.forward(infer_wav, self.output_buffer, blk, blk, self.O_noise_reduce, out=infer_wav if any_O else None)
         if self.rms_mix_rate < 1:
             n = int(infer_wav.shape[1])
-            glue.envelope_mix_batch(self.input_wav[:, self.extra_frame: self.extra_frame + n], infer_wav, zc, self.rms_mix_rate)
+            src = self.input_wav[:, self.extra_frame: self.extra_frame + n]
+            if any_I:   # the envelope's source is per session: the denoised input where I is ticked
+                src = src.clone()
+                glue.masked_write_batch(src, mask_I, self.input_wav_denoise[:, self.extra_frame: self.extra_frame + n], 0)
+            glue.envelope_mix_batch(src, infer_wav, zc, self.rms_mix_rate)
         out, self.last_offsets = glue.sola_batch(infer_wav, self.sola_buffer, self.fade_in_window, self.fade_out_window, blk,
                                                  self.sola_search_frame, use_pv=self.use_pv)
         return out
