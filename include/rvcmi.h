@@ -374,7 +374,8 @@ int rvcmi_ivf_profile_read(rvcmi_ivf* h, rvcmi_kernel_stat* stats, int capacity,
 /* ------------------------------------------------------------------------------------------- */
 
 /* The x2 interpolation + protect mix of pipeline.py:140-159 when NO index is used (index_rate == 0):
- * out[t] = feats[t/reps] (* pf + feats[t/reps] * (1 - pf) when pitchf_dev != NULL).                */
+ * out[t] = feats[t/reps] (* pf + feats[t/reps] * (1 - pf) when pitchf_dev != NULL).
+ * The bank form (rvcmi_glue_expand_protect_batch) at S = 1.                                        */
 int rvcmi_glue_expand_protect(const float* feats_dev, int64_t nq, int d, int reps, const float* pitchf_dev,
                               float protect, int64_t p_len, float* out_dev, void* stream);
 
@@ -411,7 +412,8 @@ int rvcmi_glue_scale_int16_range(float* audio_dev, int64_t n, float* scratch_dev
 /* SOLA chunk stitching of the realtime path (gui.py:1057-1090): normalised cross-correlation
  * of infer_wav[: Lb + Ls] with sola_buffer [Lb] over offsets 0..Ls, argmax (first maximum), cut, cross-fade with the
  * sin^2 windows, out_block_dev [block_frame] <- result, sola_buffer_dev <- the next tail (in place).
- * offset_out_dev (optional) receives the chosen offset.  Needs Ls + block_frame + Lb <= n.            */
+ * offset_out_dev (optional) receives the chosen offset.  Needs Ls + block_frame + Lb <= n.
+ * The bank form (rvcmi_glue_sola_batch) at S = 1 with contiguous rows: the same kernel, checks and limits. */
 int rvcmi_glue_sola(const float* infer_wav_dev, int64_t n, float* sola_buffer_dev, int Lb, int Ls,
                     const float* fade_in_dev, const float* fade_out_dev, int block_frame, float* out_block_dev,
                     int* offset_out_dev, void* stream);
@@ -422,14 +424,15 @@ int rvcmi_glue_sola(const float* infer_wav_dev, int64_t n, float* sola_buffer_de
  *   out[t] = a fade_out^2 + b fade_in^2 + w / n * sum_k absab[k] cos((2 pi k + d[k]) t / n + angle(Fa)[k]).
  * Spectrum and synthesis in fp64 (an O(n * (n/2+1)) sum, not an inverse DFT).  A bin whose real and imaginary parts are both
  * exactly zero has phase 0.  n <= 4096, else RVCMI_ERR_INVALID.  scratch_dev: 3 * (n/2 + 1) doubles.
- * out_dev may not alias the inputs.                                                                                         */
+ * out_dev may not alias the inputs.  The two vocoder launches of rvcmi_glue_sola_pv_batch at S = 1, without an offset.         */
 int rvcmi_glue_phase_vocoder(const float* a_dev, const float* b_dev, const float* fade_out_dev, const float* fade_in_dev, int n,
                              float* out_dev, double* scratch_dev, void* stream);
 
 /* rvcmi_glue_sola with the GUI's use_pv branch (gui.py:1076-1087): the same search (first maximum), then
  * infer_wav[off : off + Lb] is cross-faded with sola_buffer by rvcmi_glue_phase_vocoder instead of the sin^2 fade; out_block_dev
  * and the new tail (sola_buffer_dev, in place) are cut from the result as in rvcmi_glue_sola, block_frame < Lb included.  The
- * offset stays on the device.  Lb <= 4096.  scratch_dev: 3 * (Lb/2 + 1) + Lb/2 + 1 doubles.                                  */
+ * offset stays on the device.  Lb <= 4096.  scratch_dev: 3 * (Lb/2 + 1) + Lb/2 + 1 doubles.
+ * The bank form (rvcmi_glue_sola_pv_batch) at S = 1 with contiguous rows.                                                    */
 int rvcmi_glue_sola_pv(const float* infer_wav_dev, int64_t n, float* sola_buffer_dev, int Lb, int Ls,
                        const float* fade_in_dev, const float* fade_out_dev, int block_frame, float* out_block_dev,
                        int* offset_out_dev, double* scratch_dev, void* stream);
@@ -438,7 +441,8 @@ int rvcmi_glue_sola_pv(const float* infer_wav_dev, int64_t n, float* sola_buffer
  *   rms1, rms2 = frame RMS of input_dev[:n] and wav_dev (librosa.feature.rms, frame_length 4 zc, hop zc, centred, zero padded),
  *   both linearly interpolated with align_corners=True to n + 1 points, the last dropped;  rms2 = max(rms2, 1e-3);
  *   wav *= pow(rms1 / rms2, float32(1 - rate)).
- * scratch_dev: 2 * (1 + n / zc) floats.  Not the offline change_rms (half-second frames, align_corners=False, 1e-6).           */
+ * scratch_dev: 2 * (1 + n / zc) floats.  Not the offline change_rms (half-second frames, align_corners=False, 1e-6).
+ * The bank form (rvcmi_glue_envelope_mix_batch) at S = 1 with contiguous rows.                                                 */
 int rvcmi_glue_envelope_mix(const float* input_dev, float* wav_dev, int64_t n, int zc, double rate, float* scratch_dev,
                             void* stream);
 
@@ -507,14 +511,15 @@ size_t rvcmi_glue_filtfilt_scratch_bytes(int B, int64_t total, int order);
  * new_freq = tgt_sr / 100)): out[j * new + p] = sum_{k < K} kernel[p][k] * xpad[j * orig + k], xpad = x with `width` zeros in
  * front and zeros behind; orig / new already divided by their gcd; kernel_dev [new][K] (K = 2 * width + orig) is torchaudio's
  * windowed-sinc table (rvc_amd.realtime.sinc_resample_kernel restates its published formula: hann window, lowpass_filter_width 6,
- * rolloff 0.99).  n_out = ceil(new * n / orig) for the whole signal.  PARITY UNPINNED: torchaudio is not installable offline. */
+ * rolloff 0.99).  n_out = ceil(new * n / orig) for the whole signal.  PARITY UNPINNED: torchaudio is not installable offline.
+ * The bank form (rvcmi_glue_resample_poly_batch) at S = 1 with contiguous rows.                                               */
 int rvcmi_glue_resample_poly(const float* x_dev, int64_t n, const float* kernel_dev, int orig, int new_, int K, int width,
                              float* out_dev, int64_t n_out, void* stream);
 
 /* ---- the realtime block for a bank of S sessions (rvc_amd.RealtimeBank) ----------------------------------------------------
- * Each call below is its single-stream namesake applied to S signals at once: the same device code per session (the kernels
- * share their bodies), so session s's results equal a single-stream call on its row bit for bit, and the number of launches
- * does not depend on S.  Every per-session array is given with a ROW STRIDE in elements (`*_stride`): session s's row starts
+ * Each call below is its single-stream namesake applied to S signals at once: the same kernels and the same launch recipe (the
+ * single-stream entry IS this one at S = 1), so session s's results equal a single-stream call on its row bit for bit, and the
+ * number of launches does not depend on S.  Every per-session array is given with a ROW STRIDE in elements (`*_stride`): session s's row starts
  * at base + s * stride, and a row may be a slice of a longer rolling buffer (stride >= the row's length, else
  * RVCMI_ERR_INVALID).  Rows of one output array must not overlap.  1 <= S <= 65535.  Tables (resample kernel, fades) are shared. */
 

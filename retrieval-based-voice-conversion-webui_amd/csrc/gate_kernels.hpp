@@ -12,7 +12,7 @@
 //   k_gate_idft     per frame: window * irfft(Y)          k_gate_ola: overlap-add / sum of squared windows, centre trim
 //
 // The transforms are direct DFTs in fp64 with an LDS table of the n twiddles and exact integer argument reduction (k m) mod n,
-// as k_pv_spectrum does: any even n_fft <= 4096 (the GUI's are 880..1920, none a power of two), no plan, no workspace beyond
+// as k_pv_spectrum_batch does: any even n_fft <= 4096 (the GUI's are 880..1920, none a power of two), no plan, no workspace beyond
 // the spectra.  A block owns 64 bins (or 64 samples) of GATE_FT consecutive frames; its 4 waves split the inner sum, staged
 // through LDS in chunks, and add their partial sums in a fixed order, so every output depends only on its own row's data.
 //

@@ -11,20 +11,9 @@
 
 using namespace rvcmi;
 
+// one once-flag per kernel that needs more dynamic LDS than the default
 static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0},
-    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_gate_stft_r{0}, g_attr_gate_idft_r{0}, g_attr_sola_b{0}, g_attr_sola_search_b{0}, g_attr_pv_spec_b{0}, g_attr_pv_synth_b{0};
-
-// The phase-vocoder launches on a device-resident b (b_off: optional device offset into b); out [n] may not alias a or b.
-static void launch_phase_vocoder(const float* a, const float* b, const int* b_off, const float* fade_out, const float* fade_in, int n, float* out,
-                                 double* bins, hipStream_t st) {
-    const int nb = n / 2 + 1;
-    ensure_dyn_lds((const void*)k_pv_spectrum, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec);
-    ensure_dyn_lds((const void*)k_pv_synth, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth);
-    hipLaunchKernelGGL(k_pv_spectrum, dim3((unsigned)std::min(256, (nb + 3) / 4)), dim3(256), (size_t)32 * n, st, a, b, b_off, fade_out,
-                       fade_in, n, bins);
-    hipLaunchKernelGGL(k_pv_synth, dim3((unsigned)((n + 63) / 64)), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st, a, b, b_off, fade_out,
-                       fade_in, n, (const double*)bins, out);
-}
+    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_gate_stft_r{0}, g_attr_gate_idft_r{0};
 
 #define RVCMI_BANK_MAX_S 65535  // a session is blockIdx.y (or blockIdx.x of a one-block-per-session launch)
 static_assert(GATE_RING_FT == GATE_FT && GATE_RING_MAX_NFFT == RVCMI_GATE_MAX_NFFT && GATE_RING_MAX_S == RVCMI_BANK_MAX_S,
@@ -323,18 +312,6 @@ int rvcmi_glue_masked_write_batch(int S, float* dst, int64_t dst_stride, int64_t
     });
 }
 
-int rvcmi_glue_expand_protect(const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
-                              float* out, void* stream) {
-    return guarded([&] {
-        if (!feats || !out || nq < 0 || d < 1 || reps < 1 || p_len < 0 || p_len > nq * reps)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "expand_protect: bad argument (nq %lld d %d reps %d p_len %lld)", (long long)nq, d, reps, (long long)p_len);
-        if (!nq || !p_len) return;
-        hipLaunchKernelGGL(k_blend_expand, dim3((unsigned)nq), dim3(256), 0, (hipStream_t)stream, feats, nullptr, nullptr, nullptr, d, 0,
-                           (int64_t)0, 0.f, 0.f, nullptr, 0, pitchf, protect, p_len, reps, out);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
 int rvcmi_glue_rmvpe_f0(const float* salience, int n, int nbins, float thred, int p_len, int f0_up_key, double* scratch,
                         int64_t* pitch, float* pitchf, void* stream) {
     return rvcmi_glue_rmvpe_f0_key(salience, n, nbins, thred, p_len, (double)f0_up_key, scratch, pitch, pitchf, stream);
@@ -393,21 +370,123 @@ int rvcmi_glue_scale_int16_range(float* audio, int64_t n, float* scratch256, voi
     });
 }
 
-int rvcmi_glue_sola(const float* infer_wav, int64_t n, float* sola_buffer, int Lb, int Ls, const float* fade_in,
-                    const float* fade_out, int block_frame, float* out_block, int* offset_out, void* stream) {
+// ---- the block DSP: ONE recipe per step, for a bank of S sessions (session index in the grid, every per-session array with a row
+// stride; glue_kernels.hpp).  The single-stream entry of a step is the same recipe at S = 1 with strides equal to the row lengths;
+// `who` is the entry's name in its messages. ---------------------------------------------------------------------------------------------
+
+static void check_sessions(const char* who, int S) {
+    if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: S = %d outside [1, %d]", who, S, RVCMI_BANK_MAX_S);
+}
+
+static void expand_protect_rows(const char* who, int S, const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect,
+                                int64_t p_len, float* out, hipStream_t st) {
+    check_sessions(who, S);
+    if (!feats || !out || nq < 0 || d < 1 || reps < 1 || p_len < 0 || p_len > nq * reps)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument (nq %lld d %d reps %d p_len %lld)", who, (long long)nq, d, reps, (long long)p_len);
+    if (!nq || !p_len) return;
+    hipLaunchKernelGGL(k_blend_expand_batch, dim3((unsigned)nq, (unsigned)S), dim3(256), 0, st, feats, nullptr, nullptr, nullptr, d, 0, (int64_t)0,
+                       0.f, 0.f, nullptr, 0, nq, (int64_t)0, pitchf, protect, p_len, reps, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+int rvcmi_glue_expand_protect(const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
+                              float* out, void* stream) {
+    return guarded([&] { expand_protect_rows("expand_protect", 1, feats, nq, d, reps, pitchf, protect, p_len, out, (hipStream_t)stream); });
+}
+
+// The bank's retrieval-free expansion (index_rate == 0 / no index).
+int rvcmi_glue_expand_protect_batch(int S, const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
+                                    float* out, void* stream) {
+    return guarded([&] { expand_protect_rows("expand_protect_batch", S, feats, nq, d, reps, pitchf, protect, p_len, out, (hipStream_t)stream); });
+}
+
+static void resample_rows(const char* who, int S, const float* x, int64_t x_stride, int64_t n, const float* kernel, int orig, int new_, int K,
+                          int width, float* out, int64_t out_stride, int64_t n_out, hipStream_t st) {
+    check_sessions(who, S);
+    if (!x || !kernel || !out || n < 1 || orig < 1 || new_ < 1 || K < 1 || width < 0 || n_out < 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
+    if (x_stride < n || out_stride < n_out)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: row stride %lld / %lld shorter than the row %lld / %lld", who, (long long)x_stride, (long long)out_stride,
+                   (long long)n, (long long)n_out);
+    if (n_out == 0) return;
+    hipLaunchKernelGGL(k_resample_poly_batch, dim3((unsigned)((n_out + 255) / 256), (unsigned)S), dim3(256), 0, st, x, x_stride, n, kernel, orig, new_,
+                       K, width, out, out_stride, n_out);
+    HIP_CHECK(hipGetLastError());
+}
+
+int rvcmi_glue_resample_poly(const float* x, int64_t n, const float* kernel, int orig, int new_, int K, int width, float* out, int64_t n_out,
+                             void* stream) {
+    return guarded([&] { resample_rows("resample", 1, x, n, n, kernel, orig, new_, K, width, out, n_out, n_out, (hipStream_t)stream); });
+}
+
+int rvcmi_glue_resample_poly_batch(int S, const float* x, int64_t x_stride, int64_t n, const float* kernel, int orig, int new_, int K, int width,
+                                   float* out, int64_t out_stride, int64_t n_out, void* stream) {
     return guarded([&] {
-        if (!infer_wav || !sola_buffer || !fade_in || !fade_out || !out_block || Lb < 1 || Ls < 0 || block_frame < 1)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "sola: bad argument");
-        if ((int64_t)Ls + block_frame + Lb > n)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "sola: chunk of %lld samples is shorter than search %d + block %d + buffer %d", (long long)n, Ls,
-                       block_frame, Lb);
-        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
-        if (smem > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "sola: buffer + search window too large");
-        ensure_dyn_lds((const void*)k_sola, 150 * 1024, g_attr_sola);  // + 2 KB static
-        hipLaunchKernelGGL(k_sola, dim3(1), dim3(256), smem, (hipStream_t)stream, infer_wav, sola_buffer, Lb, Ls, fade_in, fade_out,
-                           block_frame, out_block, offset_out);
-        HIP_CHECK(hipGetLastError());
+        resample_rows("resample_batch", S, x, x_stride, n, kernel, orig, new_, K, width, out, out_stride, n_out, (hipStream_t)stream);
     });
+}
+
+// What both stitches check, in this order (rest_ok: the caller's further pointers are non-null); the LDS limit (2 Lb + Ls floats of
+// dynamic LDS <= 150 KB, + 2 KB static) comes last, after the phase vocoder's size limit.
+static void check_sola_rows(const char* who, int S, const float* infer_wav, int64_t wav_stride, int64_t n, const float* sola_buffer, int64_t buf_stride,
+                            int Lb, int Ls, const float* fade_in, const float* fade_out, int block_frame, const float* out_block, int64_t out_stride,
+                            bool rest_ok) {
+    check_sessions(who, S);
+    if (!infer_wav || !sola_buffer || !fade_in || !fade_out || !out_block || !rest_ok || Lb < 1 || Ls < 0 || block_frame < 1)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
+    if ((int64_t)Ls + block_frame + Lb > n)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: chunk of %lld samples is shorter than search %d + block %d + buffer %d", who, (long long)n, Ls, block_frame, Lb);
+    if (wav_stride < n || buf_stride < Lb || out_stride < block_frame)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a row stride (%lld, %lld, %lld) is shorter than its row (%lld, %d, %d)", who, (long long)wav_stride,
+                   (long long)buf_stride, (long long)out_stride, (long long)n, Lb, block_frame);
+}
+static size_t sola_lds_bytes(const char* who, int Lb, int Ls) {
+    const size_t smem = (size_t)(2 * (int64_t)Lb + Ls) * sizeof(float);
+    if (smem > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "%s: buffer + search window too large", who);
+    return smem;
+}
+
+// One block per session; offset_out [S] contiguous, or null.
+static void sola_rows(const char* who, int S, const float* infer_wav, int64_t wav_stride, int64_t n, float* sola_buffer, int64_t buf_stride, int Lb,
+                      int Ls, const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
+                      hipStream_t st) {
+    check_sola_rows(who, S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block, out_stride, true);
+    const size_t smem = sola_lds_bytes(who, Lb, Ls);
+    ensure_dyn_lds((const void*)k_sola_batch, 150 * 1024, g_attr_sola);
+    hipLaunchKernelGGL(k_sola_batch, dim3((unsigned)S), dim3(256), smem, st, infer_wav, wav_stride, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out,
+                       block_frame, out_block, out_stride, offset_out);
+    HIP_CHECK(hipGetLastError());
+}
+
+int rvcmi_glue_sola(const float* infer_wav, int64_t n, float* sola_buffer, int Lb, int Ls, const float* fade_in, const float* fade_out,
+                    int block_frame, float* out_block, int* offset_out, void* stream) {
+    return guarded([&] {
+        sola_rows("sola", 1, infer_wav, n, n, sola_buffer, Lb, Lb, Ls, fade_in, fade_out, block_frame, out_block, block_frame, offset_out,
+                  (hipStream_t)stream);
+    });
+}
+
+int rvcmi_glue_sola_batch(int S, const float* infer_wav, int64_t wav_stride, int64_t n, float* sola_buffer, int64_t buf_stride, int Lb, int Ls,
+                          const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
+                          void* stream) {
+    return guarded([&] {
+        sola_rows("sola_batch", S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block, out_stride,
+                  offset_out, (hipStream_t)stream);
+    });
+}
+
+// The phase vocoder's two launches on device-resident rows: out row s <- phase_vocoder(a row s, b row s at its offset).  b_off: the rows'
+// device offsets into b, off_stride ints apart, or null (offset 0; off_stride = 0 then).  bins: 3 (n/2 + 1) doubles per row.  out may not
+// alias a or b.
+static void launch_pv_rows(int S, const float* a, int64_t a_stride, const float* b, int64_t b_stride, const int* b_off, int64_t off_stride,
+                           const float* fade_out, const float* fade_in, int n, double* bins, int64_t bins_stride, float* out, int64_t out_stride,
+                           hipStream_t st) {
+    const int nb = n / 2 + 1;
+    ensure_dyn_lds((const void*)k_pv_spectrum_batch, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec);
+    ensure_dyn_lds((const void*)k_pv_synth_batch, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth);
+    hipLaunchKernelGGL(k_pv_spectrum_batch, dim3((unsigned)std::min(256, (nb + 3) / 4), (unsigned)S), dim3(256), (size_t)32 * n, st, a, a_stride, b,
+                       b_stride, b_off, off_stride, fade_out, fade_in, n, bins, bins_stride);
+    hipLaunchKernelGGL(k_pv_synth_batch, dim3((unsigned)((n + 63) / 64), (unsigned)S), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st, a, a_stride, b,
+                       b_stride, b_off, off_stride, fade_out, fade_in, n, (const double*)bins, bins_stride, out, out_stride);
 }
 
 int rvcmi_glue_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out, double* scratch,
@@ -415,107 +494,41 @@ int rvcmi_glue_phase_vocoder(const float* a, const float* b, const float* fade_o
     return guarded([&] {
         if (!a || !b || !fade_out || !fade_in || !out || !scratch || n < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "phase_vocoder: bad argument");
         if (n > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "phase_vocoder: n = %d exceeds %d", n, RVCMI_PV_MAX_N);
-        launch_phase_vocoder(a, b, nullptr, fade_out, fade_in, n, out, scratch, (hipStream_t)stream);
+        launch_pv_rows(1, a, n, b, n, nullptr, 0, fade_out, fade_in, n, scratch, 3 * (n / 2 + 1), out, n, (hipStream_t)stream);
         HIP_CHECK(hipGetLastError());
     });
+}
+
+// Four launches: search -> pv spectrum -> pv synthesis (into scratch) -> stitch.
+// scratch: S slices of P = 3 nb + Lb/2 + 1 doubles (nb = Lb/2 + 1), session s at s * P, each laid out as
+//   bins [3 nb] doubles | pv result [Lb] floats | offset (one int, used when offset_out is null)
+static void sola_pv_rows(const char* who, int S, const float* infer_wav, int64_t wav_stride, int64_t n, float* sola_buffer, int64_t buf_stride, int Lb,
+                         int Ls, const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
+                         double* scratch, hipStream_t st) {
+    check_sola_rows(who, S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block, out_stride,
+                    scratch != nullptr);
+    if (Lb > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: cross-fade buffer of %d samples exceeds %d", who, Lb, RVCMI_PV_MAX_N);
+    const size_t smem = sola_lds_bytes(who, Lb, Ls);
+    const int nb = Lb / 2 + 1;
+    const int64_t per = 3 * (int64_t)nb + Lb / 2 + 1;
+    float* pv = reinterpret_cast<float*>(scratch + 3 * nb);
+    int* off = offset_out ? offset_out : reinterpret_cast<int*>(pv + Lb);
+    const int64_t off_stride = offset_out ? 1 : 2 * per;  // in ints
+    ensure_dyn_lds((const void*)k_sola_search_batch, 150 * 1024, g_attr_sola_search);
+    hipLaunchKernelGGL(k_sola_search_batch, dim3((unsigned)S), dim3(256), smem, st, infer_wav, wav_stride, (const float*)sola_buffer, buf_stride, Lb, Ls,
+                       off, off_stride);
+    // a = the session's sola_buffer row, b = its chunk at its own offset, which never leaves the device
+    launch_pv_rows(S, sola_buffer, buf_stride, infer_wav, wav_stride, off, off_stride, fade_out, fade_in, Lb, scratch, per, pv, 2 * per, st);
+    hipLaunchKernelGGL(k_sola_pv_stitch_batch, dim3((unsigned)((block_frame + Lb + 255) / 256), (unsigned)S), dim3(256), 0, st, infer_wav, wav_stride,
+                       (const int*)off, off_stride, (const float*)pv, 2 * per, Lb, block_frame, out_block, out_stride, sola_buffer, buf_stride);
+    HIP_CHECK(hipGetLastError());
 }
 
 int rvcmi_glue_sola_pv(const float* infer_wav, int64_t n, float* sola_buffer, int Lb, int Ls, const float* fade_in, const float* fade_out,
                        int block_frame, float* out_block, int* offset_out, double* scratch, void* stream) {
     return guarded([&] {
-        if (!infer_wav || !sola_buffer || !fade_in || !fade_out || !out_block || !scratch || Lb < 1 || Ls < 0 || block_frame < 1)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv: bad argument");
-        if ((int64_t)Ls + block_frame + Lb > n)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv: chunk of %lld samples is shorter than search %d + block %d + buffer %d", (long long)n, Ls,
-                       block_frame, Lb);
-        if (Lb > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv: cross-fade buffer of %d samples exceeds %d", Lb, RVCMI_PV_MAX_N);
-        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
-        if (smem > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "sola_pv: buffer + search window too large");
-        // scratch: bins [3 * (Lb/2 + 1)] doubles | pv result [Lb] floats | offset (when offset_out is NULL)
-        const int nb = Lb / 2 + 1;
-        float* pv = reinterpret_cast<float*>(scratch + 3 * nb);
-        int* off = offset_out ? offset_out : reinterpret_cast<int*>(pv + Lb);
-        hipStream_t st = (hipStream_t)stream;
-        ensure_dyn_lds((const void*)k_sola_search, 150 * 1024, g_attr_sola_search);
-        hipLaunchKernelGGL(k_sola_search, dim3(1), dim3(256), smem, st, infer_wav, (const float*)sola_buffer, Lb, Ls, off);
-        launch_phase_vocoder(sola_buffer, infer_wav, off, fade_out, fade_in, Lb, pv, scratch, st);
-        hipLaunchKernelGGL(k_sola_pv_stitch, dim3((unsigned)((block_frame + Lb + 255) / 256)), dim3(256), 0, st, infer_wav, (const int*)off,
-                           (const float*)pv, Lb, block_frame, out_block, sola_buffer);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-int rvcmi_glue_envelope_mix(const float* input, float* wav, int64_t n, int zc, double rate, float* scratch, void* stream) {
-    return guarded([&] {
-        if (!input || !wav || !scratch || n < 1 || zc < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix: bad argument");
-        const int64_t nf64 = 1 + n / zc;
-        if (nf64 > (1 << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix: too many frames");
-        const int nf = (int)nf64;
-        hipStream_t st = (hipStream_t)stream;
-        hipLaunchKernelGGL(k_frame_rms, dim3(nf), dim3(256), 0, st, input, n, 4 * zc, zc, nf, scratch);
-        hipLaunchKernelGGL(k_frame_rms, dim3(nf), dim3(256), 0, st, (const float*)wav, n, 4 * zc, zc, nf, scratch + nf);
-        // torch.pow(rms1 / rms2, torch.tensor(1 - rate)): the exponent is the python double rounded to float32
-        const float e = (float)(1.0 - rate);
-        hipLaunchKernelGGL(k_envelope_mix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wav, n, (const float*)scratch,
-                           (const float*)(scratch + nf), nf, e);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-int rvcmi_glue_resample_poly(const float* x, int64_t n, const float* kernel, int orig, int new_, int K, int width, float* out, int64_t n_out,
-                             void* stream) {
-    return guarded([&] {
-        if (!x || !kernel || !out || n < 1 || orig < 1 || new_ < 1 || K < 1 || width < 0 || n_out < 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "resample: bad argument");
-        if (n_out == 0) return;
-        hipLaunchKernelGGL(k_resample_poly, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n, kernel, orig, new_, K,
-                           width, out, n_out);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// ---- the block DSP for a bank of S sessions: the single-stream bodies, session index in the grid (glue_kernels.hpp) --------------------
-
-int rvcmi_glue_resample_poly_batch(int S, const float* x, int64_t x_stride, int64_t n, const float* kernel, int orig, int new_, int K, int width,
-                                   float* out, int64_t out_stride, int64_t n_out, void* stream) {
-    return guarded([&] {
-        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "resample_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
-        if (!x || !kernel || !out || n < 1 || orig < 1 || new_ < 1 || K < 1 || width < 0 || n_out < 0)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "resample_batch: bad argument");
-        if (x_stride < n || out_stride < n_out)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "resample_batch: row stride %lld / %lld shorter than the row %lld / %lld", (long long)x_stride,
-                       (long long)out_stride, (long long)n, (long long)n_out);
-        if (n_out == 0) return;
-        hipLaunchKernelGGL(k_resample_poly_batch, dim3((unsigned)((n_out + 255) / 256), (unsigned)S), dim3(256), 0, (hipStream_t)stream, x, x_stride,
-                           n, kernel, orig, new_, K, width, out, out_stride, n_out);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// what rvcmi_glue_sola and rvcmi_glue_sola_pv check, plus the bank's own arguments
-static void check_sola_batch(const char* who, int S, const float* infer_wav, int64_t wav_stride, int64_t n, const float* sola_buffer,
-                             int64_t buf_stride, int Lb, int Ls, const float* fade_in, const float* fade_out, int block_frame, const float* out_block,
-                             int64_t out_stride) {
-    if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: S = %d outside [1, %d]", who, S, RVCMI_BANK_MAX_S);
-    if (!infer_wav || !sola_buffer || !fade_in || !fade_out || !out_block || Lb < 1 || Ls < 0 || block_frame < 1)
-        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
-    if ((int64_t)Ls + block_frame + Lb > n)
-        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: chunk of %lld samples is shorter than search %d + block %d + buffer %d", who, (long long)n, Ls, block_frame, Lb);
-    if (wav_stride < n || buf_stride < Lb || out_stride < block_frame)
-        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a row stride (%lld, %lld, %lld) is shorter than its row (%lld, %d, %d)", who, (long long)wav_stride,
-                   (long long)buf_stride, (long long)out_stride, (long long)n, Lb, block_frame);
-    if ((size_t)(2 * (int64_t)Lb + Ls) * sizeof(float) > 150 * 1024) RVCMI_FAIL(RVCMI_ERR_NOMEM, "%s: buffer + search window too large", who);
-}
-
-int rvcmi_glue_sola_batch(int S, const float* infer_wav, int64_t wav_stride, int64_t n, float* sola_buffer, int64_t buf_stride, int Lb, int Ls,
-                          const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
-                          void* stream) {
-    return guarded([&] {
-        check_sola_batch("sola_batch", S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block, out_stride);
-        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
-        ensure_dyn_lds((const void*)k_sola_batch, 150 * 1024, g_attr_sola_b);  // + 2 KB static
-        hipLaunchKernelGGL(k_sola_batch, dim3((unsigned)S), dim3(256), smem, (hipStream_t)stream, infer_wav, wav_stride, sola_buffer, buf_stride, Lb, Ls,
-                           fade_in, fade_out, block_frame, out_block, out_stride, offset_out);
-        HIP_CHECK(hipGetLastError());
+        sola_pv_rows("sola_pv", 1, infer_wav, n, n, sola_buffer, Lb, Lb, Ls, fade_in, fade_out, block_frame, out_block, block_frame, offset_out, scratch,
+                     (hipStream_t)stream);
     });
 }
 
@@ -523,71 +536,39 @@ int rvcmi_glue_sola_pv_batch(int S, const float* infer_wav, int64_t wav_stride, 
                              const float* fade_in, const float* fade_out, int block_frame, float* out_block, int64_t out_stride, int* offset_out,
                              double* scratch, void* stream) {
     return guarded([&] {
-        check_sola_batch("sola_pv_batch", S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block,
-                         out_stride);
-        if (!scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv_batch: bad argument");
-        if (Lb > RVCMI_PV_MAX_N) RVCMI_FAIL(RVCMI_ERR_INVALID, "sola_pv_batch: cross-fade buffer of %d samples exceeds %d", Lb, RVCMI_PV_MAX_N);
-        const size_t smem = (size_t)(2 * Lb + Ls) * sizeof(float);
-        // scratch: S slices of P = 3 * (Lb/2 + 1) + Lb/2 + 1 doubles, session s at s * P, each laid out as rvcmi_glue_sola_pv's:
-        //   bins [3 * (Lb/2 + 1)] doubles | pv result [Lb] floats | offset (when offset_out is NULL)
-        const int nb = Lb / 2 + 1;
-        const int64_t per = 3 * (int64_t)nb + Lb / 2 + 1;
-        float* pv = reinterpret_cast<float*>(scratch + 3 * nb);
-        const int* off = offset_out ? offset_out : reinterpret_cast<int*>(pv + Lb);
-        const int64_t off_stride = offset_out ? 1 : 2 * per;  // in ints
-        hipStream_t st = (hipStream_t)stream;
-        ensure_dyn_lds((const void*)k_sola_search_batch, 150 * 1024, g_attr_sola_search_b);
-        ensure_dyn_lds((const void*)k_pv_spectrum_batch, 32 * RVCMI_PV_MAX_N, g_attr_pv_spec_b);
-        ensure_dyn_lds((const void*)k_pv_synth_batch, 8 * (3 * (RVCMI_PV_MAX_N / 2 + 1) + 16 * 64), g_attr_pv_synth_b);
-        hipLaunchKernelGGL(k_sola_search_batch, dim3((unsigned)S), dim3(256), smem, st, infer_wav, wav_stride, (const float*)sola_buffer, buf_stride, Lb,
-                           Ls, const_cast<int*>(off), off_stride);
-        // a = the session's sola_buffer row, b = its chunk at its own offset (launch_phase_vocoder's two launches, session in grid.y)
-        hipLaunchKernelGGL(k_pv_spectrum_batch, dim3((unsigned)std::min(256, (nb + 3) / 4), (unsigned)S), dim3(256), (size_t)32 * Lb, st,
-                           (const float*)sola_buffer, buf_stride, infer_wav, wav_stride, off, off_stride, fade_out, fade_in, Lb, scratch, per);
-        hipLaunchKernelGGL(k_pv_synth_batch, dim3((unsigned)((Lb + 63) / 64), (unsigned)S), dim3(1024), (size_t)8 * (3 * nb + 16 * 64), st,
-                           (const float*)sola_buffer, buf_stride, infer_wav, wav_stride, off, off_stride, fade_out, fade_in, Lb, (const double*)scratch,
-                           per, pv, 2 * per);
-        hipLaunchKernelGGL(k_sola_pv_stitch_batch, dim3((unsigned)((block_frame + Lb + 255) / 256), (unsigned)S), dim3(256), 0, st, infer_wav, wav_stride,
-                           off, off_stride, (const float*)pv, 2 * per, Lb, block_frame, out_block, out_stride, sola_buffer, buf_stride);
-        HIP_CHECK(hipGetLastError());
+        sola_pv_rows("sola_pv_batch", S, infer_wav, wav_stride, n, sola_buffer, buf_stride, Lb, Ls, fade_in, fade_out, block_frame, out_block, out_stride,
+                     offset_out, scratch, (hipStream_t)stream);
     });
+}
+
+// scratch [S][2][nf] floats, nf = 1 + n / zc: session s's input envelope, then its output envelope.
+static void envelope_mix_rows(const char* who, int S, const float* input, int64_t in_stride, float* wav, int64_t wav_stride, int64_t n, int zc,
+                              double rate, float* scratch, hipStream_t st) {
+    check_sessions(who, S);
+    if (!input || !wav || !scratch || n < 1 || zc < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
+    if (in_stride < n || wav_stride < n)
+        RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: row stride %lld / %lld shorter than the row %lld", who, (long long)in_stride, (long long)wav_stride,
+                   (long long)n);
+    const int64_t nf64 = 1 + n / zc;
+    if (nf64 > (1 << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: too many frames", who);
+    const int nf = (int)nf64;
+    hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf, (unsigned)S), dim3(256), 0, st, input, in_stride, n, 4 * zc, zc, nf, scratch, (int64_t)2 * nf);
+    hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf, (unsigned)S), dim3(256), 0, st, (const float*)wav, wav_stride, n, 4 * zc, zc, nf, scratch + nf,
+                       (int64_t)2 * nf);
+    // torch.pow(rms1 / rms2, torch.tensor(1 - rate)): the exponent is the python double rounded to float32
+    const float e = (float)(1.0 - rate);
+    hipLaunchKernelGGL(k_envelope_mix_batch, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, st, wav, wav_stride, n,
+                       (const float*)scratch, nf, e);
+    HIP_CHECK(hipGetLastError());
+}
+
+int rvcmi_glue_envelope_mix(const float* input, float* wav, int64_t n, int zc, double rate, float* scratch, void* stream) {
+    return guarded([&] { envelope_mix_rows("envelope_mix", 1, input, n, wav, n, n, zc, rate, scratch, (hipStream_t)stream); });
 }
 
 int rvcmi_glue_envelope_mix_batch(int S, const float* input, int64_t in_stride, float* wav, int64_t wav_stride, int64_t n, int zc, double rate,
                                   float* scratch, void* stream) {
-    return guarded([&] {
-        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
-        if (!input || !wav || !scratch || n < 1 || zc < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: bad argument");
-        if (in_stride < n || wav_stride < n)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: row stride %lld / %lld shorter than the row %lld", (long long)in_stride,
-                       (long long)wav_stride, (long long)n);
-        const int64_t nf64 = 1 + n / zc;
-        if (nf64 > (1 << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "envelope_mix_batch: too many frames");
-        const int nf = (int)nf64;
-        hipStream_t st = (hipStream_t)stream;
-        // scratch [S][2][nf]: session s's input envelope, then its output envelope
-        hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf, (unsigned)S), dim3(256), 0, st, input, in_stride, n, 4 * zc, zc, nf, scratch, (int64_t)2 * nf);
-        hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf, (unsigned)S), dim3(256), 0, st, (const float*)wav, wav_stride, n, 4 * zc, zc, nf, scratch + nf,
-                           (int64_t)2 * nf);
-        const float e = (float)(1.0 - rate);
-        hipLaunchKernelGGL(k_envelope_mix_batch, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, st, wav, wav_stride, n,
-                           (const float*)scratch, nf, e);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// The bank's retrieval-free expansion (index_rate == 0 / no index): rvcmi_glue_expand_protect per session, one launch.
-int rvcmi_glue_expand_protect_batch(int S, const float* feats, int64_t nq, int d, int reps, const float* pitchf, float protect, int64_t p_len,
-                                    float* out, void* stream) {
-    return guarded([&] {
-        if (S < 1 || S > RVCMI_BANK_MAX_S) RVCMI_FAIL(RVCMI_ERR_INVALID, "expand_protect_batch: S = %d outside [1, %d]", S, RVCMI_BANK_MAX_S);
-        if (!feats || !out || nq < 0 || d < 1 || reps < 1 || p_len < 0 || p_len > nq * reps)
-            RVCMI_FAIL(RVCMI_ERR_INVALID, "expand_protect_batch: bad argument (nq %lld d %d reps %d p_len %lld)", (long long)nq, d, reps, (long long)p_len);
-        if (!nq || !p_len) return;
-        hipLaunchKernelGGL(k_blend_expand_batch, dim3((unsigned)nq, (unsigned)S), dim3(256), 0, (hipStream_t)stream, feats, nullptr, nullptr, nullptr, d,
-                           0, (int64_t)0, 0.f, 0.f, nullptr, 0, nq, (int64_t)0, pitchf, protect, p_len, reps, out);
-        HIP_CHECK(hipGetLastError());
-    });
+    return guarded([&] { envelope_mix_rows("envelope_mix_batch", S, input, in_stride, wav, wav_stride, n, zc, rate, scratch, (hipStream_t)stream); });
 }
 
 int rvcmi_glue_change_rms(const float* data1, int64_t n1, int sr1, float* data2, int64_t n2, int sr2, float rate, float* scratch,
@@ -597,8 +578,9 @@ int rvcmi_glue_change_rms(const float* data1, int64_t n1, int sr1, float* data2,
         const int h1 = sr1 / 2, h2 = sr2 / 2;
         const int nf1 = 1 + (int)(n1 / h1), nf2 = 1 + (int)(n2 / h2);
         hipStream_t st = (hipStream_t)stream;
-        hipLaunchKernelGGL(k_frame_rms, dim3(nf1), dim3(256), 0, st, data1, n1, 2 * h1, h1, nf1, scratch);
-        hipLaunchKernelGGL(k_frame_rms, dim3(nf2), dim3(256), 0, st, (const float*)data2, n2, 2 * h2, h2, nf2, scratch + nf1);
+        hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf1, 1), dim3(256), 0, st, data1, n1, n1, 2 * h1, h1, nf1, scratch, (int64_t)nf1);
+        hipLaunchKernelGGL(k_frame_rms_batch, dim3(nf2, 1), dim3(256), 0, st, (const float*)data2, n2, n2, 2 * h2, h2, nf2, scratch + nf1,
+                           (int64_t)nf2);
         // torch.pow(rms, torch.tensor(1 - rate)): the exponent is the python double rounded to float32
         const float e1 = (float)(1.0 - (double)rate), e2 = (float)((double)rate - 1.0);
         hipLaunchKernelGGL(k_change_rms, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, data2, n2, scratch, nf1, scratch + nf1, nf2, e1, e2);

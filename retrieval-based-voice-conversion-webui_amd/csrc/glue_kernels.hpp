@@ -23,7 +23,7 @@ namespace rvcmi {
 // One block per QUERY row (both of its output frames): the blended row is computed once, in registers.
 // P == nullptr: no retrieval (index_rate == 0 / no index): the row is the input row.
 // The body: query row qi of feats [nq, d] -> output frames qi * reps .. of out [p_len, d]; D / P are the row's own k results (read
-// only when blend).  Shared by k_blend_expand and k_blend_expand_batch: one arithmetic, whoever launches it.
+// only when blend).  The body of k_blend_expand_batch; a single stream is that kernel at S = 1.
 __device__ __forceinline__ void blend_expand_row(const float* __restrict__ feats, const float* __restrict__ D, const int64_t* __restrict__ P,
                                                  const float* __restrict__ vecs, int d, int k, int64_t pos_last, float rate, float omr,
                                                  bool blend, const float* __restrict__ pitchf, float protect, int64_t p_len, int reps,
@@ -71,18 +71,6 @@ __device__ __forceinline__ void blend_expand_row(const float* __restrict__ feats
     }
 }
 
-static __global__ void __launch_bounds__(256) k_blend_expand(const float* __restrict__ feats, const float* __restrict__ D,
-                                                             const int64_t* __restrict__ P, const float* __restrict__ vecs,
-                                                             int d, int k, int64_t pos_last, float rate, float omr,
-                                                             const int* __restrict__ any_short, int skip_if_short,
-                                                             const float* __restrict__ pitchf, float protect, int64_t p_len,
-                                                             int reps, float* __restrict__ out) {
-    const int64_t qi = blockIdx.x;
-    const bool blend = P != nullptr && !(skip_if_short && *any_short);
-    blend_expand_row(feats, blend ? D + qi * k : nullptr, blend ? P + qi * k : nullptr, vecs, d, k, pos_last, rate, omr, blend, pitchf,
-                     protect, p_len, reps, out, qi);
-}
-
 // The realtime guard per SESSION (rtrvc.py:172-180 is a per-call condition; in a bank a call is one session's block):
 // flags[s] = 1 when any of session s's m * k result ids is negative.  One block per session.
 static __global__ void __launch_bounds__(256) k_session_short(const int64_t* __restrict__ I, int64_t per_session, int* __restrict__ flags) {
@@ -107,7 +95,7 @@ static __global__ void __launch_bounds__(256) k_gather_tail_rows(const float* __
     for (int e = threadIdx.x; e < d; e += 256) dst[e] = src[e];
 }
 
-// k_blend_expand for a bank: grid (nq, S).  Row qi < skip of a session is expanded un-blended; row qi >= skip uses result row
+// blend_expand_row per session: grid (nq, S); S = 1, skip = 0 is the single-stream form (result row qi, flags[0]).  Row qi < skip of a session is expanded un-blended; row qi >= skip uses result row
 // s * (nq - skip) + qi - skip of the one search and blends unless the session's flag is set (skip_if_short).  P == nullptr: no
 // retrieval at all.  feats [S, nq, d], pitchf [S, p_len] or nullptr, out [S, p_len, d].
 static __global__ void __launch_bounds__(256) k_blend_expand_batch(const float* __restrict__ feats, const float* __restrict__ D,
@@ -307,7 +295,7 @@ static __global__ void __launch_bounds__(256) k_scale_int16_range(float* __restr
 // The two sums are accumulated in fp64 and rounded once (the reference's F.conv1d leaves the fp32 summation order to the
 // backend); everything after the argmax is the reference's fp32 expression, unfused.  One block.
 //
-// The offset search shared by k_sola and k_sola_search (256 threads): xs [Lb + Ls] and bs [Lb] staged in LDS, rv / ri 256
+// The offset search of k_sola_batch and k_sola_search_batch (256 threads): xs [Lb + Ls] and bs [Lb] staged in LDS, rv / ri 256
 // entries of LDS for the block's argmax.  Every thread gets the offset.
 __device__ __forceinline__ int sola_search(const float* xs, const float* bs, int Lb, int Ls, float* rv, int* ri) {
 #pragma clang fp contract(off)
@@ -343,7 +331,7 @@ __device__ __forceinline__ int sola_search(const float* xs, const float* bs, int
     return ri[0];
 }
 
-// One block's whole stitch of one signal (sl: the dynamic LDS, 2 Lb + Ls floats): the body of k_sola and k_sola_batch.
+// One block's whole stitch of one signal (sl: the dynamic LDS, 2 Lb + Ls floats): the body of k_sola_batch.
 __device__ __forceinline__ void sola_block(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
                                            const float* __restrict__ fade_in, const float* __restrict__ fade_out, int block,
                                            float* __restrict__ out, int* __restrict__ offset_out, float* sl, float* rv, int* ri) {
@@ -363,17 +351,9 @@ __device__ __forceinline__ void sola_block(const float* __restrict__ x, float* _
     for (int i = threadIdx.x; i < Lb; i += 256) buf[i] = y(block + i);  // old tail is in LDS: safe to overwrite
 }
 
-static __global__ void __launch_bounds__(256) k_sola(const float* __restrict__ x, float* __restrict__ buf, int Lb, int Ls,
-                                                     const float* __restrict__ fade_in, const float* __restrict__ fade_out,
-                                                     int block, float* __restrict__ out, int* __restrict__ offset_out) {
-    extern __shared__ float sl[];
-    __shared__ float rv[256];
-    __shared__ int ri[256];
-    sola_block(x, buf, Lb, Ls, fade_in, fade_out, block, out, offset_out, sl, rv, ri);
-}
-
 // A bank of S signals, one block per session (blockIdx.x); every per-session array has a row stride in elements (a row may be a
-// slice of a longer rolling buffer).  fade_in / fade_out are shared.  offset_out [S] (optional).
+// slice of a longer rolling buffer).  fade_in / fade_out are shared.  offset_out [S] (optional).  A single stream is S = 1 with
+// strides equal to the row lengths -- here and in every _batch kernel below; there is no other form.
 static __global__ void __launch_bounds__(256) k_sola_batch(const float* __restrict__ x, int64_t x_stride, float* __restrict__ buf,
                                                            int64_t buf_stride, int Lb, int Ls, const float* __restrict__ fade_in,
                                                            const float* __restrict__ fade_out, int block, float* __restrict__ out,
@@ -401,14 +381,6 @@ __device__ __forceinline__ void sola_search_block(const float* __restrict__ x, c
     if (threadIdx.x == 0) *offset_out = off;
 }
 
-static __global__ void __launch_bounds__(256) k_sola_search(const float* __restrict__ x, const float* __restrict__ buf, int Lb, int Ls,
-                                                            int* __restrict__ offset_out) {
-    extern __shared__ float sl[];
-    __shared__ float rv[256];
-    __shared__ int ri[256];
-    sola_search_block(x, buf, Lb, Ls, offset_out, sl, rv, ri);
-}
-
 // One block per session (blockIdx.x), rows by stride; offset_out [S].
 static __global__ void __launch_bounds__(256) k_sola_search_batch(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ buf,
                                                                   int64_t buf_stride, int Lb, int Ls, int* __restrict__ offset_out,
@@ -429,11 +401,6 @@ __device__ __forceinline__ void sola_pv_stitch_at(const float* __restrict__ x, c
     const float v = i < Lb ? pv[i] : x[off + i];
     if (i < block) out[i] = v;
     else buf[i - block] = v;
-}
-
-static __global__ void __launch_bounds__(256) k_sola_pv_stitch(const float* __restrict__ x, const int* __restrict__ offset, const float* __restrict__ pv,
-                                                               int Lb, int block, float* __restrict__ out, float* __restrict__ buf) {
-    sola_pv_stitch_at(x, offset, pv, Lb, block, out, buf, blockIdx.x * 256 + threadIdx.x);
 }
 
 // Session blockIdx.y; pv and offset live in the session's slice of the scratch (strides in floats / ints).
@@ -462,7 +429,7 @@ static __global__ void __launch_bounds__(256) k_sola_pv_stitch_batch(const float
 // Spectrum: one wave per bin (grid-strided), lanes over samples.  LDS: the twiddle table (cos, sin)(2 pi m / n) built with
 // sincospi (the quarter points are exact) and the windowed inputs, 32 n bytes.  bins: absab [nb] | phia [nb] | d / n [nb].
 // b_off (optional): b is read at b + *b_off (the SOLA offset, which never leaves the device).
-// (bx, gx: the block's index and the block count over the bins of ONE signal -- blockIdx.x / gridDim.x in both launch forms)
+// (bx, gx: the block's index and the block count over the bins of ONE signal -- blockIdx.x / gridDim.x)
 __device__ __forceinline__ void pv_spectrum_block(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
                                                   const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
                                                   double* __restrict__ bins, double* pv_sm, int bx, int gx) {
@@ -512,14 +479,8 @@ __device__ __forceinline__ void pv_spectrum_block(const float* __restrict__ a, c
     }
 }
 
-static __global__ void __launch_bounds__(256) k_pv_spectrum(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
-                                                            const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
-                                                            double* __restrict__ bins) {
-    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
-    pv_spectrum_block(a, b, b_off, fade_out, fade_in, n, bins, pv_sm, blockIdx.x, gridDim.x);
-}
-
 // Session blockIdx.y: a / b rows by stride, b_off and bins in the session's slice of the scratch (strides in ints / doubles).
+// The stand-alone vocoder has no offset: b_off = nullptr with off_stride = 0 at S = 1 (nullptr + 0; the body reads offset 0).
 static __global__ void __launch_bounds__(256) k_pv_spectrum_batch(const float* __restrict__ a, int64_t a_stride, const float* __restrict__ b,
                                                                   int64_t b_stride, const int* __restrict__ b_off, int64_t off_stride,
                                                                   const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
@@ -569,13 +530,6 @@ __device__ __forceinline__ void pv_synth_block(const float* __restrict__ a, cons
     }
 }
 
-static __global__ void __launch_bounds__(1024) k_pv_synth(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ b_off,
-                                                          const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
-                                                          const double* __restrict__ bins, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double pv_sm[];
-    pv_synth_block(a, b, b_off, fade_out, fade_in, n, bins, out, pv_sm, blockIdx.x);
-}
-
 static __global__ void __launch_bounds__(1024) k_pv_synth_batch(const float* __restrict__ a, int64_t a_stride, const float* __restrict__ b,
                                                                 int64_t b_stride, const int* __restrict__ b_off, int64_t off_stride,
                                                                 const float* __restrict__ fade_out, const float* __restrict__ fade_in, int n,
@@ -589,7 +543,7 @@ static __global__ void __launch_bounds__(1024) k_pv_synth_batch(const float* __r
 
 // ------------------------------------------------------------------------------------------------
 // The realtime GUI's envelope mix (gui.py:1023-1056), in place on wav [n]:
-//   rms1, rms2 = librosa.feature.rms(input[:n] / wav, frame_length = 4 zc, hop_length = zc)   (k_frame_rms below)
+//   rms1, rms2 = librosa.feature.rms(input[:n] / wav, frame_length = 4 zc, hop_length = zc)   (k_frame_rms_batch below)
 //   both -> F.interpolate(linear, align_corners=True, size=n+1)[:-1];  rms2 = max(rms2, 1e-3);
 //   wav *= pow(rms1 / rms2, float32(1 - rate))
 // The interpolation is torch's CPU kernel: scale = (in-1)/(out-1) in fp32, src = scale * o, floor, clamp.
@@ -612,11 +566,6 @@ __device__ __forceinline__ void envelope_mix_at(float* __restrict__ wav, int64_t
     const float r1 = interp_linear_ac(rms1, nf, n + 1, t);
     const float r2 = fmaxf(interp_linear_ac(rms2, nf, n + 1, t), 1e-3f);
     wav[t] = mul_rn(wav[t], powf(div_rn(r1, r2), e));
-}
-
-static __global__ void __launch_bounds__(256) k_envelope_mix(float* __restrict__ wav, int64_t n, const float* __restrict__ rms1,
-                                                             const float* __restrict__ rms2, int nf, float e) {
-    envelope_mix_at(wav, n, rms1, rms2, nf, e, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // Session blockIdx.y: wav rows by stride; rms [S][2][nf] (the session's two envelopes side by side).
@@ -655,12 +604,6 @@ __device__ __forceinline__ void frame_rms_block(const float* __restrict__ y, int
         __syncthreads();
     }
     if (threadIdx.x == 0) rms[f] = sqrtf((float)(red[0] / (double)frame));
-}
-
-static __global__ void __launch_bounds__(256) k_frame_rms(const float* __restrict__ y, int64_t n, int frame, int hop, int nframes,
-                                                          float* __restrict__ rms) {
-    __shared__ double red[256];
-    frame_rms_block(y, n, frame, hop, nframes, rms, red, blockIdx.x);
 }
 
 // Session blockIdx.y: y rows by stride, rms rows by rms_stride floats.
@@ -713,11 +656,6 @@ __device__ __forceinline__ void resample_poly_at(const float* __restrict__ x, in
         acc = fmaf(wp[k], xv, acc);
     }
     out[i] = acc;
-}
-
-static __global__ void __launch_bounds__(256) k_resample_poly(const float* __restrict__ x, int64_t n, const float* __restrict__ w, int of, int nf,
-                                                       int K, int width, float* __restrict__ out, int64_t n_out) {
-    resample_poly_at(x, n, w, of, nf, K, width, out, n_out, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // Session blockIdx.y: x and out rows by stride, one coefficient table.

@@ -648,9 +648,10 @@ int rvcmi_ivf_search_blend_expand(rvcmi_ivf* h, int64_t nq, const float* feats, 
         const int d = h->hdr.d;
         const float rate = index_rate, omr = (float)(1.0 - (double)index_rate);
         h->prof.launch("ivf_blend_x2", 2.0 * nq * k * d, (double)nq * d * 4 * (1 + k) + (double)p_len * d * 4, st, [&] {
-            hipLaunchKernelGGL(k_blend_expand, dim3((unsigned)nq), dim3(256), 0, st, feats, h->Dtmp.as<float>(), h->P.as<int64_t>(),
-                               h->vecs(), d, k, h->hdr.pos_last, rate, omr, h->flag.as<int>(), skip_if_short, pitchf, protect,
-                               p_len, 2, out);
+            // one session, no skipped rows: result row qi, flags[0] = the search's any_short
+            hipLaunchKernelGGL(k_blend_expand_batch, dim3((unsigned)nq, 1), dim3(256), 0, st, feats, (const float*)h->Dtmp.as<float>(),
+                               (const int64_t*)h->P.as<int64_t>(), h->vecs(), d, k, h->hdr.pos_last, rate, omr, (const int*)h->flag.as<int>(),
+                               skip_if_short, nq, (int64_t)0, pitchf, protect, p_len, 2, out);
         });
         HIP_CHECK(hipGetLastError());
     });

@@ -16,7 +16,9 @@ and of the realtime GUI's block (gui.py:934-1090, assembled by ``realtime.Realti
     phase_vocoder(a, b, fade_out, fade_in)                                    gui.py:27-49
     spectral_gate(x, xn, n_fft, hop, window, smoothing_filter, ...)           torchgate.py (gui.py:974-992, 1015-1022)
 
-and their forms for a bank of S realtime sessions (``realtime.RealtimeBank``; per session bit-equal, launch count independent of S):
+and their forms for a bank of S realtime sessions (``realtime.RealtimeBank``; launch count independent of S).  The library has one
+kernel and one launch recipe per step: a single-stream call above is the bank form at S = 1 with contiguous rows, so a session's
+results are bit-equal to a single-stream call on its row:
 
     retrieve_blend_expand_batch(feats [S, nq, d], index, ..., skip_rows)       one search, the realtime guard per session
     sola_batch(infer_wav [S, n], sola_buffer [S, Lb], ...) / envelope_mix_batch(input_wav [S, .], infer_wav [S, n], zc, rate)

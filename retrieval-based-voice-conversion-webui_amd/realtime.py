@@ -289,7 +289,7 @@ def stream_geometry(samplerate: int, block_time: float = 0.25, crossfade_time: f
 
 def frame_rms_np(y: np.ndarray, frame_length: int, hop_length: int) -> np.ndarray:
     """``librosa.feature.rms(y=y, frame_length, hop_length)[0]`` (librosa >= 0.10.2: centred, zero padding) in numpy; the float32
-    squares are summed in float64 and the mean rounded to float32, as the device's k_frame_rms does."""
+    squares are summed in float64 and the mean rounded to float32, as the device's k_frame_rms_batch does."""
     y = np.asarray(y, dtype=np.float32)
     pad = frame_length // 2
     yp = np.pad(y, (pad, pad), mode="constant")

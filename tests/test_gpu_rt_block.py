@@ -70,6 +70,39 @@ def test_sola_pv_is_the_search_plus_the_phase_vocoder(blk, Lb, Ls, true_off, gpu
 
 
 @pytest.mark.gpu
+def test_sola_without_an_offset_pointer_equals_the_call_with_one(gpu):
+    """offset_out = NULL at the C entries: the fade call drops the offset, the pv call keeps it in its scratch; block and new tail are
+    the same bits either way.  The bank test's smallest geometry; the odd Lb gives the vocoder its odd bin count."""
+    from rvc_amd import _lib
+
+    blk, Lb, Ls = 100, 33, 10
+    n = Ls + blk + Lb
+    gen = torch.Generator().manual_seed(5)
+    wav = torch.randn(n, generator=gen).to(gpu)
+    buf = (0.9 * wav[7: 7 + Lb].cpu() + 0.01 * torch.randn(Lb, generator=gen)).to(gpu)
+    fi, fo = (w.to(gpu) for w in _fades(Lb))
+    L, p, st = _lib.lib(), _lib.ptr, _lib.stream_ptr(gpu)
+    got = {}
+    for pv in (False, True):
+        for with_off in (True, False):
+            b, out = buf.clone(), torch.full((blk,), -7.0, device=gpu)
+            off = torch.full((1,), -7, dtype=torch.int32, device=gpu)
+            scratch = torch.zeros(3 * (Lb // 2 + 1) + Lb // 2 + 1, dtype=torch.float64, device=gpu)
+            args = (p(wav), n, p(b), Lb, Ls, p(fi), p(fo), blk, p(out), p(off) if with_off else None)
+            with torch.cuda.device(gpu):
+                rc = L.rvcmi_glue_sola_pv(*args, p(scratch), st) if pv else L.rvcmi_glue_sola(*args, st)
+            torch.cuda.synchronize(gpu)
+            assert rc == 0
+            got[pv, with_off] = (out, b, int(off.item()))
+    for pv in (False, True):
+        (out_o, buf_o, off_o), (out_n, buf_n, off_n) = got[pv, True], got[pv, False]
+        assert 0 <= off_o <= Ls and off_n == -7
+        assert torch.equal(out_n, out_o) and torch.equal(buf_n, buf_o)
+        assert not bool((out_o == -7.0).any()) and not torch.equal(buf_o, buf)
+    assert got[True, True][2] == got[False, True][2]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("rate", [0.0, 0.25, 0.8])
 @pytest.mark.parametrize("zc,n", [(400, 12000), (480, 7200), (441, 6174)])
 def test_envelope_mix_matches_the_gui_expression(rate, zc, n, gpu):
