@@ -28,6 +28,7 @@ from typing import Tuple
 import numpy as np
 
 FLT_MAX = np.float32(3.4028234663852886e38)
+C_MAX_PROBES = 64  # oracle/ivf_scan.c: ``int64_t lists[64]`` per query
 
 
 def coarse_assign(index: dict, q: np.ndarray, nprobe: int) -> np.ndarray:
@@ -93,6 +94,9 @@ def search_c(index: dict, q: np.ndarray, k: int = 8, nprobe: int | None = None, 
     lib = _c_lib()
     q = np.ascontiguousarray(q, dtype=np.float32)
     nprobe = int(index.get("nprobe", 1) if nprobe is None else nprobe)
+    if min(nprobe, int(index["nlist"])) > C_MAX_PROBES:  # ivf_scan.c would silently probe the nearest 64 only
+        raise ValueError("search_c: min(nprobe, nlist) = %d, oracle/ivf_scan.c probes at most %d lists (lists[64]); use search()"
+                         % (min(nprobe, int(index["nlist"])), C_MAX_PROBES))
     nq, d = q.shape
     D = np.empty((nq, k), np.float32)
     I = np.empty((nq, k), np.int64)
