@@ -130,6 +130,18 @@ int rvcmi_nsf_forward(rvcmi_nsf* h, int B, int T, const int* lengths_dev, const 
                       const float* g_dev, const float* noise_dev, int n_res, float* out_dev,
                       void* stream);
 
+/* rvcmi_nsf_forward with a realtime resample target PER ITEM (the bank's formant shift per session: return_length2 of rtrvc.py:191
+ * differs between the sessions of one batch).
+ *   n_res_dev  int32 [B] on the device, 1 <= n_res[b] <= n_res_max; the caller vouches for the values (they are not read back)
+ *   out_dev    [B, n_res_max * upp] fp32
+ * Item b is computed exactly as rvcmi_nsf_forward(h, 1, T, NULL, x[b], f0[b], g[b], noise[b], n_res[b], ...) computes it: the
+ * excitation over all T input frames, then it and x interpolated to n_res[b] frames (an item with n_res[b] == T is not
+ * interpolated, as there), the layers behind as a ragged item of n_res[b] frames.  Output samples [n_res[b] * upp, n_res_max * upp)
+ * of item b are zero.  n_res_max > max_T: RVCMI_ERR_NOMEM; B < 1, n_res_max < 1, a null n_res_dev: RVCMI_ERR_INVALID.  No
+ * allocation, no synchronisation, no host read of n_res_dev.  Serves no debug tap. */
+int rvcmi_nsf_forward_nres(rvcmi_nsf* h, int B, int T, int n_res_max, const int* n_res_dev, const float* x_dev, const float* f0_dev,
+                           const float* g_dev, const float* noise_dev, float* out_dev, void* stream);
+
 int rvcmi_nsf_upp(const rvcmi_nsf* h);               /* prod(upsample_rates)                    */
 size_t rvcmi_nsf_workspace_bytes(const rvcmi_nsf* h);
 
@@ -526,6 +538,23 @@ int rvcmi_glue_resample_poly(const float* x_dev, int64_t n, const float* kernel_
 /* rvcmi_glue_resample_poly per row: x_dev rows of n samples -> out_dev rows of n_out samples. */
 int rvcmi_glue_resample_poly_batch(int S, const float* x_dev, int64_t x_stride, int64_t n, const float* kernel_dev, int orig,
                                    int new_, int K, int width, float* out_dev, int64_t out_stride, int64_t n_out, void* stream);
+
+/* rvcmi_glue_resample_poly_batch with a ratio PER ROW (the bank's formant shift per session, rtrvc.py:248-259): ONE launch, row s
+ * resampled by its own descriptor rows_dev[s] -- its table kernels_dev + w_off ([new_][K], as rvcmi_glue_resample_poly takes it), its
+ * reduced orig / new_, K, width, and the n <= n_max samples of the row it reads -- to n_out samples, bit-equal to
+ * rvcmi_glue_resample_poly on that row with that table.  A row with orig == new_ is not resampled: its first n_out samples are copied
+ * (zeros behind n).  kernels_dev holds kernels_floats floats, the tables of all distinct ratios back to back; a descriptor that points
+ * outside it yields a row of zeros (the descriptors live on the device and are not read back).  x_stride < n_max, out_stride < n_out,
+ * S < 1: RVCMI_ERR_INVALID. */
+typedef struct {
+    int64_t w_off;   /* first float of the row's table in kernels_dev */
+    int64_t n;       /* input samples of the row                      */
+    int orig, new_;  /* rates divided by their gcd                    */
+    int K, width;    /* K = 2 * width + orig                          */
+} rvcmi_resample_row;
+int rvcmi_glue_resample_poly_ragged(int S, const float* x_dev, int64_t x_stride, int64_t n_max, const float* kernels_dev,
+                                    int64_t kernels_floats, const rvcmi_resample_row* rows_dev, float* out_dev, int64_t out_stride,
+                                    int64_t n_out, void* stream);
 
 /* rvcmi_glue_sola per session: one offset search per session (one block each, the chunk head and the previous tail staged in
  * LDS: 2 Lb + Ls floats <= 150 KB), sola_buffer_dev [S rows of Lb] updated in place, out_block_dev [S rows of block_frame],

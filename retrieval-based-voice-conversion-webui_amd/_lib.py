@@ -50,6 +50,11 @@ class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
 
+class ResampleRow(C.Structure):
+    """rvcmi_resample_row: one row's descriptor of rvcmi_glue_resample_poly_ragged."""
+    _fields_ = [("w_off", C.c_int64), ("n", C.c_int64), ("orig", C.c_int), ("new_", C.c_int), ("K", C.c_int), ("width", C.c_int)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -72,6 +77,7 @@ SYMBOLS = [
     ("rvcmi_nsf_create", C.c_int, [C.POINTER(NsfConfig), C.POINTER(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     ("rvcmi_nsf_destroy", C.c_int, [_P]),
     ("rvcmi_nsf_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    ("rvcmi_nsf_forward_nres", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     ("rvcmi_nsf_upp", C.c_int, [_P]),
     ("rvcmi_nsf_workspace_bytes", C.c_size_t, [_P]),
     ("rvcmi_nsf_debug_forward", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_char_p, _P, C.c_size_t,
@@ -129,6 +135,7 @@ SYMBOLS = [
     ("rvcmi_glue_sola_pv", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     ("rvcmi_glue_envelope_mix", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P]),
     ("rvcmi_glue_resample_poly_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int64, _P]),
+    ("rvcmi_glue_resample_poly_ragged", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P]),
     ("rvcmi_glue_sola_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P, _P]),
     ("rvcmi_glue_sola_pv_batch", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P, _P,
                                            _P]),
@@ -193,7 +200,7 @@ class RvcmiError(RuntimeError):
         self.code = code
 
 
-ERR_INVALID, ERR_IO = -1, -3
+ERR_INVALID, ERR_IO, ERR_NOMEM = -1, -3, -4
 
 
 _lib = None

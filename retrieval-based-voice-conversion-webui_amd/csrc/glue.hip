@@ -425,6 +425,23 @@ int rvcmi_glue_resample_poly_batch(int S, const float* x, int64_t x_stride, int6
     });
 }
 
+int rvcmi_glue_resample_poly_ragged(int S, const float* x, int64_t x_stride, int64_t n_max, const float* kernels, int64_t kernels_floats,
+                                    const rvcmi_resample_row* rows, float* out, int64_t out_stride, int64_t n_out, void* stream) {
+    return guarded([&] {
+        const char* who = "resample_ragged";
+        check_sessions(who, S);
+        if (!x || !kernels || !rows || !out || n_max < 1 || kernels_floats < 1 || n_out < 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
+        if (x_stride < n_max || out_stride < n_out)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: row stride %lld / %lld shorter than the row %lld / %lld", who, (long long)x_stride, (long long)out_stride,
+                       (long long)n_max, (long long)n_out);
+        if (n_out == 0) return;
+        hipStream_t st = (hipStream_t)stream;
+        hipLaunchKernelGGL(k_resample_poly_ragged, dim3((unsigned)((n_out + 255) / 256), (unsigned)S), dim3(256), 0, st, x, x_stride, kernels,
+                           kernels_floats, rows, n_max, out, out_stride, n_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 // What both stitches check, in this order (rest_ok: the caller's further pointers are non-null); the LDS limit (2 Lb + Ls floats of
 // dynamic LDS <= 150 KB, + 2 KB static) comes last, after the phase vocoder's size limit.
 static void check_sola_rows(const char* who, int S, const float* infer_wav, int64_t wav_stride, int64_t n, const float* sola_buffer, int64_t buf_stride,

@@ -15,6 +15,8 @@
 #include "exact_fp.hpp"
 #include <stdint.h>
 
+#include "../../include/rvcmi.h"  // rvcmi_resample_row
+
 namespace rvcmi {
 
 // feats = blend(search) per query row i (pipeline.py:129-138, see k_blend), then for output frame t < p_len:
@@ -664,6 +666,27 @@ static __global__ void __launch_bounds__(256) k_resample_poly_batch(const float*
                                                                     float* __restrict__ out, int64_t out_stride, int64_t n_out) {
     const int64_t s = blockIdx.y;
     resample_poly_at(x + s * x_stride, n, w, of, nf, K, width, out + s * out_stride, n_out, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// Session blockIdx.y resamples with ITS OWN ratio (the bank's formant shift per session, rtrvc.py:248-259): row s's table starts at
+// w + desc[s].w_off, its reduced rates / K / width and the samples n it reads are the descriptor's; the output is dense, n_out per row.
+// A row whose descriptor says of == nf is the head copy of its input (the reference does not resample it).  Same arithmetic per sample
+// as k_resample_poly_batch (resample_poly_at), so a row equals that kernel with the row's table bit for bit.
+static __global__ void __launch_bounds__(256) k_resample_poly_ragged(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ w,
+                                                                     int64_t w_floats, const rvcmi_resample_row* __restrict__ desc, int64_t n_max,
+                                                                     float* __restrict__ out, int64_t out_stride, int64_t n_out) {
+    const int64_t s = blockIdx.y;
+    const rvcmi_resample_row d = desc[s];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = d.n < 0 ? 0 : (d.n < n_max ? d.n : n_max);  // (never past the n_max samples the host checked the row stride for)
+    const bool copy = d.orig == d.new_;
+    // a descriptor that does not describe a table inside the buffer (the host cannot read it: it lives on the device) yields a row of zeros
+    const bool ok = copy || (d.orig >= 1 && d.new_ >= 1 && d.K >= 1 && d.width >= 0 && d.w_off >= 0 && d.w_off + (int64_t)d.new_ * d.K <= w_floats);
+    if (copy || !ok) {
+        if (i < n_out) out[s * out_stride + i] = (ok && i < n) ? x[s * x_stride + i] : 0.f;
+        return;
+    }
+    resample_poly_at(x + s * x_stride, n, w + d.w_off, d.orig, d.new_, d.K, d.width, out + s * out_stride, n_out, i);
 }
 
 }  // namespace rvcmi

@@ -718,6 +718,8 @@ struct Fwd {
     rvcmi_nsf* h;
     int op, B, Te;       // Te: frames after the realtime interpolation (n_res)
     const int* lens;     // ragged batch: valid frames per item (device [B]) or nullptr
+    const int* nres;     // rvcmi_nsf_forward_nres: interpolation target per item (device [B], <= Te) or nullptr.  The excitation runs over all T
+                         // input frames of every item whatever it says; behind the interpolation it is the layers' `lens`
     const float* har;    // excitation [B][Te * upp] (use_f0)
     hipStream_t st;
     TapRequest* tr;
@@ -896,7 +898,7 @@ static bool excitation(Fwd& f, int T, const float* f0, const float* noise) {
     const rvcmi_nsf_config& c = h->cfg;
     const int B = f.B, Te = f.Te, upp = h->upp;
     hipStream_t st = f.st;
-    const int* lens = f.lens;
+    const int* lens = f.nres ? nullptr : f.lens;  // (per-item n_res: every item's source covers its T input frames, nsf.py:152-154)
     h->prof.launch("phase_scan", 0, (double)B * T * 8, st, [&] {
         hipLaunchKernelGGL(k_phase_scan, dim3(B), dim3(256), 0, st, f0, h->phase.as<float>(), T, (float)c.sr, (float)upp, lens);
     });
@@ -906,7 +908,12 @@ static bool excitation(Fwd& f, int T, const float* f0, const float* noise) {
                            h->phase.as<float>(), noise, h->har.as<float>(), T, upp, (float)c.sr, h->lin_w, h->lin_b, total);
     });
     f.har = h->har.as<float>();
-    if (Te != T) {  // nsf.py:155-159
+    if (f.nres) {  // nsf.py:155-159 with a target per item; the row stride becomes Te * upp
+        const size_t tot2 = (size_t)B * Te * upp;
+        hipLaunchKernelGGL(k_interp_linear_ragged, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, st, f.har, h->har2.as<float>(), f.nres,
+                           1, upp, T * upp, Te * upp, tot2);
+        f.har = h->har2.as<float>();
+    } else if (Te != T) {  // nsf.py:155-159
         const size_t tot2 = (size_t)B * Te * upp;
         hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, st, f.har,
                            h->har2.as<float>(), T * upp, Te * upp, tot2);
@@ -930,7 +937,12 @@ static Act conv_pre(const Fwd& f, const float* x, int T, const float* g) {
     const rvcmi_nsf_config& c = h->cfg;
     const int B = f.B, Te = f.Te, inter = c.inter_channels, C0 = h->C0;
     hipStream_t st = f.st;
-    if (Te != T) {  // nsf.py:160-162 / generators.py:76-79
+    if (f.nres) {  // nsf.py:160-162 / generators.py:76-79 with a target per item
+        const size_t tot = (size_t)B * inter * Te;
+        hipLaunchKernelGGL(k_interp_linear_ragged, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, h->x2.as<float>(), f.nres, inter, 1,
+                           T, Te, tot);
+        x = h->x2.as<float>();
+    } else if (Te != T) {  // nsf.py:160-162 / generators.py:76-79
         const size_t tot = (size_t)B * inter * Te;
         hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, h->x2.as<float>(), T, Te, tot);
         x = h->x2.as<float>();
@@ -1354,10 +1366,13 @@ static void tap_stage(const Fwd& f, const Act& x) {
 
 // `lens`: optional device array [B] of valid frames per item (1 <= lens[b] <= T): a ragged batch, every item computed exactly as
 // a separate call of its own length (mfma_conv.hpp item_rows); the output rows behind an item's end are zero.
+// `nres`: optional device array [B] of interpolation targets per item (1 <= nres[b] <= n_res, which is then their upper bound and the
+// output's frame count): item b is interpolated to nres[b] frames and decoded as a ragged item of that length.
 static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float* x, const float* f0, const float* g,
-                        const float* noise, int n_res, float* out, hipStream_t st, TapRequest* tr) {
+                        const float* noise, int n_res, float* out, hipStream_t st, TapRequest* tr, const int* nres = nullptr) {
     if (!h || !x || (!out && !tr)) RVCMI_FAIL(RVCMI_ERR_INVALID, "null argument");
     if (lens && n_res >= 0) RVCMI_FAIL(RVCMI_ERR_INVALID, "lengths and n_res (the realtime interpolation) cannot be combined");
+    if (nres && (n_res < 1 || tr)) RVCMI_FAIL(RVCMI_ERR_INVALID, "per-item n_res needs n_res_max >= 1 and serves no debug tap");
     const rvcmi_nsf_config& c = h->cfg;
     if (c.use_f0 && !f0) RVCMI_FAIL(RVCMI_ERR_INVALID, "f0 is required for an NSF (use_f0) generator");
     if (B < 1 || T < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "B and T must be positive");
@@ -1367,9 +1382,10 @@ static void nsf_forward(rvcmi_nsf* h, int B, int T, const int* lens, const float
         RVCMI_FAIL(RVCMI_ERR_NOMEM, "shape B=%d T=%d n_res=%d exceeds handle limits (max_B=%d max_T=%d)", B, T, n_res,
                    h->max_B, h->max_T);
     HIP_CHECK(hipSetDevice(h->device));
-    Fwd f{h, c.operand, B, Te, lens, nullptr, st, tr, nullptr};
+    Fwd f{h, c.operand, B, Te, lens, nres, nullptr, st, tr, nullptr};
     h->n_plan = 0;
     if (c.use_f0 && excitation(f, T, f0, noise)) return;
+    if (nres) f.lens = nres;  // from conv_pre on, item b is a ragged item of nres[b] frames in rows of Te
     Act a = conv_pre(f, x, T, g);
     if (f.want("pre")) return copy_tap_cl(h, a.y[0], B, Te, h->C0, tr, st);
     char nm[48];
@@ -1420,6 +1436,13 @@ int rvcmi_nsf_destroy(rvcmi_nsf* h) {
 int rvcmi_nsf_forward(rvcmi_nsf* h, int B, int T, const int* lengths, const float* x, const float* f0, const float* g,
                       const float* noise, int n_res, float* out, void* stream) {
     return guarded([&] { nsf_forward(h, B, T, lengths, x, f0, g, noise, n_res, out, (hipStream_t)stream, nullptr); });
+}
+int rvcmi_nsf_forward_nres(rvcmi_nsf* h, int B, int T, int n_res_max, const int* n_res, const float* x, const float* f0, const float* g,
+                           const float* noise, float* out, void* stream) {
+    return guarded([&] {
+        if (!n_res || n_res_max < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "forward_nres: n_res_dev is null or n_res_max = %d < 1", n_res_max);
+        nsf_forward(h, B, T, nullptr, x, f0, g, noise, n_res_max, out, (hipStream_t)stream, nullptr, n_res);
+    });
 }
 int rvcmi_nsf_upp(const rvcmi_nsf* h) { return h ? h->upp : RVCMI_ERR_INVALID; }
 size_t rvcmi_nsf_workspace_bytes(const rvcmi_nsf* h) { return h ? h->ws_bytes : 0; }

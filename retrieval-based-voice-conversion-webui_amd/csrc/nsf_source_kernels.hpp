@@ -80,12 +80,8 @@ static __global__ void __launch_bounds__(256) k_sine_source(const float* __restr
 
 // F.interpolate(mode="linear", align_corners=False) along the last axis of [rows][Lin] -> [rows][Lout]
 // (nsf.py:155-162, generators.py:76-79).
-static __global__ void __launch_bounds__(256) k_interp_linear(const float* __restrict__ in, float* __restrict__ out,
-                                                       int Lin, int Lout, size_t total) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    size_t row = i / (size_t)Lout;
-    int o = (int)(i - row * Lout);
+// Output sample o of one row r[Lin] -> [Lout]: the arithmetic both kernels below share, so that a row comes out the same bits from either.
+__device__ __forceinline__ float interp_linear_at(const float* __restrict__ r, int Lin, int Lout, int o) {
     float scale = (float)Lin / (float)Lout;
     float src = scale * ((float)o + 0.5f) - 0.5f;
     if (src < 0.f) src = 0.f;
@@ -94,8 +90,33 @@ static __global__ void __launch_bounds__(256) k_interp_linear(const float* __res
     int i1 = i0 + (i0 < Lin - 1 ? 1 : 0);
     float l1 = src - (float)i0;
     float l0 = 1.f - l1;
+    return l0 * r[i0] + l1 * r[i1];
+}
+
+static __global__ void __launch_bounds__(256) k_interp_linear(const float* __restrict__ in, float* __restrict__ out,
+                                                       int Lin, int Lout, size_t total) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    size_t row = i / (size_t)Lout;
+    int o = (int)(i - row * Lout);
+    out[i] = interp_linear_at(in + row * (size_t)Lin, Lin, Lout, o);
+}
+
+// The same with a target length PER ITEM (rvcmi_nsf_forward_nres): rows [B * rows_per_item][Lin] -> [B * rows_per_item][Lmax], a row of
+// item b interpolated to n_res[b] * mul samples exactly as k_interp_linear does it for Lout = n_res[b] * mul, zeros behind them.  An item
+// whose target is Lin is copied: the single-item forward does not interpolate then (nsf.py:155, generators.py:76).
+static __global__ void __launch_bounds__(256) k_interp_linear_ragged(const float* __restrict__ in, float* __restrict__ out,
+                                                              const int* __restrict__ n_res, int rows_per_item, int mul, int Lin,
+                                                              int Lmax, size_t total) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    size_t row = i / (size_t)Lmax;
+    int o = (int)(i - row * Lmax);
+    const int Lout = item_rows(n_res, (int)(row / (size_t)rows_per_item), mul, Lmax);  // (clamped to [mul, Lmax]: nothing is read or written outside the rows)
     const float* r = in + row * (size_t)Lin;
-    out[i] = l0 * r[i0] + l1 * r[i1];
+    float v = 0.f;
+    if (o < Lout) v = Lout == Lin ? r[o] : interp_linear_at(r, Lin, Lout, o);
+    out[i] = v;
 }
 
 // cond(g): a 1x1 conv over a length-1 sequence = one GEMV per utterance (nsf.py:165-166).

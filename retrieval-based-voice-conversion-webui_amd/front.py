@@ -175,7 +175,19 @@ def infer_hip(net_g, front: FrontHIP, phone, phone_lengths, sid, pitch=None, pit
 
     ``ragged=True`` (not in the reference): the batch items are independent utterances of ``phone_lengths`` frames and each one
     must come out as a SEPARATE call would produce it -- the generator is told the lengths (every conv zero-pads behind the item's
-    own end).  The reference's padded batch, ``ragged=False``, lets the rows behind a short item leak into its last frames."""
+    own end).  The reference's padded batch, ``ragged=False``, lets the rows behind a short item leak into its last frames.
+
+    ``return_length2`` may also be a sequence of ``B`` ints (not in the reference; only with ``skip_head`` / ``return_length``, never
+    with ``ragged=True``): item ``b`` is decoded to ``return_length2[b]`` frames as its own call would decode it, in rows of
+    ``max(return_length2) * upp`` samples with zeros behind its end."""
+    from .nsf import _per_item
+
+    if _per_item(return_length2):
+        # one return_length2 per item (not in the reference: a bank's formant shift per session) goes to the generator as a per-item n_res
+        if skip_head is None or return_length is None:
+            raise ValueError("a return_length2 per item needs skip_head / return_length (the realtime partial decode)")
+        if len(return_length2) != phone.shape[0]:
+            raise ValueError("return_length2 must hold %d values, got %d" % (phone.shape[0], len(return_length2)))
     g = net_g.emb_g(sid).unsqueeze(-1)
     T = phone.shape[1]
     if skip_head is not None and return_length is not None:

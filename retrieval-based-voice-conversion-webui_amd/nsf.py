@@ -70,6 +70,13 @@ def _operand_code(operand: str) -> int:
     return _lib.OPERANDS[operand]
 
 
+def _per_item(n_res) -> bool:
+    """``n_res`` names one target per batch item (a sequence or a tensor with an axis), not the reference's single int."""
+    if torch.is_tensor(n_res) or isinstance(n_res, np.ndarray):
+        return n_res.ndim >= 1
+    return isinstance(n_res, (list, tuple))
+
+
 class _HipGenerator(torch.nn.Module):
     """Shared implementation; see NSFGeneratorHIP / GeneratorHIP."""
 
@@ -166,6 +173,21 @@ class _HipGenerator(torch.nn.Module):
             gf = g.to(dev, torch.float32).reshape(B, -1).contiguous()
             if gf.shape[1] != self.cfg.get("gin_channels", 0):
                 raise ValueError("g must carry %d channels" % self.cfg.get("gin_channels", 0))
+        nrs = None
+        if _per_item(n_res):
+            # one resample target per item (rvcmi_nsf_forward_nres): item b = a separate call with n_res[b].  The values are host values
+            # (a device tensor is read back here); their device copy is kept until they change
+            if lengths is not None or tap is not None:
+                raise ValueError("a per-item n_res cannot be combined with lengths / debug taps")
+            host = tuple(int(v) for v in (n_res.tolist() if hasattr(n_res, "tolist") else n_res))
+            if len(host) != B:
+                raise ValueError("n_res must hold %d values, got %d" % (B, len(host)))
+            self._ensure(B, T)
+            if min(host) < 1 or max(host) > self._max_T:
+                raise ValueError("every n_res must lie in [1, max_T = %d] (got %s); reserve(max_B, max_T) sizes the workspace" % (self._max_T, list(host)))
+            if getattr(self, "_nres_dev", (None, None))[0] != host:
+                self._nres_dev = (host, torch.tensor(host, dtype=torch.int32, device=dev))
+            nrs, n_res = self._nres_dev[1], max(host)
         Te = T if n_res is None else int(n_res)
         ln = None
         if lengths is not None:
@@ -186,6 +208,9 @@ class _HipGenerator(torch.nn.Module):
         with torch.cuda.device(dev):
             if tap is None:
                 out = torch.empty(B, 1, Te * self.upp, device=dev, dtype=torch.float32)
+                if nrs is not None:
+                    _lib.check(L.rvcmi_nsf_forward_nres(self._handle, B, T, Te, ptr(nrs), ptr(xf), ptr(f0f), ptr(gf), ptr(nf), ptr(out), stream))
+                    return out.to(out_dtype)
                 _lib.check(L.rvcmi_nsf_forward(self._handle, B, T, ptr(ln), ptr(xf), ptr(f0f), ptr(gf), ptr(nf), nr, ptr(out), stream))
                 return out.to(out_dtype)
             cap = B * max(self.cfg["upsample_initial_channel"] * Te, Te * self.upp * 256)
@@ -245,7 +270,9 @@ class NSFGeneratorHIP(_HipGenerator):
     def forward(self, x: torch.Tensor, f0: torch.Tensor, g: Optional[torch.Tensor] = None,
                 n_res: Optional[int] = None, *, noise: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
         """``lengths`` (keyword, not in the reference's signature): [B] valid frames per item -- a ragged batch whose items come
-        out exactly as separate calls of those lengths would (segments of a long file, utterances of a folder, in one launch)."""
+        out exactly as separate calls of those lengths would (segments of a long file, utterances of a folder, in one launch).
+        ``n_res``: the reference's int, or (not in the reference) a sequence / tensor of ``B`` ints -- item ``b`` comes out as a separate
+        call with ``n_res[b]`` would, in rows of ``max(n_res) * upp`` samples with zeros behind its end (a bank's formant shift per session)."""
         return self._run(x, f0, g, n_res, noise, lengths=lengths)
 
     def debug_tap(self, what: str, x, f0, g=None, n_res=None, noise=None) -> torch.Tensor:

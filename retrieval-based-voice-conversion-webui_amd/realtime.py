@@ -94,6 +94,96 @@ class SincResample:
         return out
 
 
+def formant_geometry(shift: float, return_length: int, tgt_sr: int):
+    """What a formant shift of ``shift`` semitones makes of a realtime block (rtrvc.py:190-191, 248; no device needed) ->
+    ``(factor, return_length2, upp_res)``: the generator decodes ``return_length2`` frames instead of ``return_length``, and their first
+    ``return_length * upp_res`` samples are resampled from ``upp_res`` to ``tgt_sr // 100`` samples per frame (not at all when the two
+    are equal).  The reference's own expressions, so that every caller rounds as it does."""
+    factor = pow(2, shift / 12)                                                           # :190
+    return_length2 = int(np.ceil(return_length * factor))                                 # :191
+    upp_res = int(np.floor(factor * tgt_sr // 100))                                       # :248
+    return factor, return_length2, upp_res
+
+
+class SincResampleRagged:
+    """``SincResample(orig_s, new_freq)`` for ``S`` rows with a rate ``orig_s`` of their own, in ONE launch
+    (``rvcmi_glue_resample_poly_ragged``): row ``s`` of ``wav`` [S, >= frames * orig_s] -> row ``s`` of [S, frames * new_freq], bit-equal
+    to ``SincResample(orig_s, new_freq)`` on its first ``frames * orig_s`` samples; a row with ``orig_s == new_freq`` is the first
+    ``frames * new_freq`` samples of its input.  The bank's formant shift per session (rtrvc.py:248-259): ``orig_s`` is the session's
+    ``upp_res``.
+
+    The filter tables (``sinc_resample_kernel``) are kept per distinct ``orig``; the concatenated device buffer and the per-row descriptors
+    are rebuilt only when the tuple of the rows' rates (or ``frames``) changes -- nothing is uploaded per block.  ``plan`` is the host part
+    and needs no device."""
+
+    def __init__(self, new_freq: int, device=None):
+        self.new_freq = int(new_freq)
+        self.device = None if device is None else torch.device(device)
+        self._tables = {}     # orig -> (kernel [nf, K] CPU, width, of, nf)
+        self.key = None       # (the rows' rates, frames) of the current plan
+        self.rows = []        # per row: dict(w_off, n, orig, new, K, width), the fields of rvcmi_resample_row
+        self.offsets = {}     # orig -> first float of its table in the concatenated buffer
+        self.table_floats = 0
+        self.rebuilds = 0
+        self._dev = None      # (tables, descriptors) on the device
+
+    def plan(self, origs, frames: int) -> bool:
+        """Lay out the tables and descriptors for rows of rates ``origs`` and ``frames`` frames each; -> whether anything changed."""
+        key = (tuple(int(o) for o in origs), int(frames))
+        if key == self.key:
+            return False
+        if not key[0] or min(key[0]) < 1 or key[1] < 1:
+            raise ValueError("SincResampleRagged needs at least one row, positive rates and frames >= 1 (got %s)" % (key,))
+        self.offsets, self.rows, off = {}, [], 0
+        for o in key[0]:
+            if o != self.new_freq and o not in self.offsets:   # equal rates share one table; an un-resampled row has none
+                if o not in self._tables:
+                    self._tables[o] = sinc_resample_kernel(o, self.new_freq)
+                k = self._tables[o][0]
+                self.offsets[o] = off
+                off += int(k.numel())
+        self.table_floats = off
+        for o in key[0]:
+            if o == self.new_freq:
+                self.rows.append(dict(w_off=0, n=key[1] * o, orig=1, new=1, K=0, width=0))
+            else:
+                k, width, of, nf = self._tables[o]
+                self.rows.append(dict(w_off=self.offsets[o], n=key[1] * o, orig=of, new=nf, K=int(k.shape[1]), width=width))
+        self.key, self._dev = key, None
+        self.rebuilds += 1
+        return True
+
+    def _upload(self):
+        import ctypes as C
+
+        tabs = [self._tables[o][0].reshape(-1) for o in sorted(self.offsets, key=self.offsets.get)]
+        table = torch.cat(tabs) if tabs else torch.zeros(1)
+        desc = (_lib.ResampleRow * len(self.rows))(*[_lib.ResampleRow(r["w_off"], r["n"], r["orig"], r["new"], r["K"], r["width"]) for r in self.rows])
+        raw = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8)
+        self._dev = (table.to(self.device), raw.to(self.device), C.sizeof(desc))
+        return self._dev
+
+    def __call__(self, wav: torch.Tensor, origs, frames: int) -> torch.Tensor:
+        if wav.device.type != "cuda":
+            raise _lib.RvcmiError("SincResampleRagged input must live on the GPU (no CPU fallback)")
+        if self.device is None:
+            self.device = wav.device
+        S, n, stride = glue.bank_rows(wav, "wav")
+        self.plan(origs, frames)
+        if len(self.rows) != S:
+            raise ValueError("%d rates for %d rows" % (len(self.rows), S))
+        n_max = max(r["n"] for r in self.rows)
+        if n_max > n:
+            raise ValueError("a row needs %d input samples, wav has %d" % (n_max, n))
+        table, desc, _ = self._dev or self._upload()
+        n_out = int(frames) * self.new_freq
+        out = torch.empty(S, n_out, device=wav.device, dtype=torch.float32)
+        with torch.cuda.device(wav.device):
+            _lib.check(_lib.lib().rvcmi_glue_resample_poly_ragged(S, _lib.ptr(wav), stride, n_max, _lib.ptr(table), int(table.numel()), _lib.ptr(desc),
+                                                                  _lib.ptr(out), n_out, n_out, _lib.stream_ptr(wav.device)))
+        return out
+
+
 class PitchCache:
     """``cache_pitch`` / ``cache_pitchf`` of rtrvc.py:63-66 and their per-block update (rtrvc.py:213-217)."""
 
@@ -193,14 +283,19 @@ class RealtimeVCBatch:
     retrieval call (``glue.retrieve_blend_expand_batch``: one search over all sessions' new frames, the realtime guard per
     session) and one ``net_g.infer`` at batch ``S``.  The launch count does not depend on ``S``.
 
-    ``formant_shift`` must be 0: a shift changes ``return_length2`` per session, i.e. asks for a ragged partial decode."""
+    The formant shift is per session: ``set_session_formant(i, shift)`` (or ``infer(..., formants=[...])``), kept in ``formants``.  A
+    shifted bank decodes every session to its own ``return_length2`` in one ``net_g.infer`` (``return_length2`` = the list: a ragged
+    partial decode) and brings the rows back to ``return_length * (tgt_sr // 100)`` samples with one ``SincResampleRagged`` launch; with
+    every shift zero it issues exactly the launches it issues without the feature.  The bank-wide forms -- the constructor's
+    ``formant_shift`` and the one-argument ``set_formant`` -- serve 0 only."""
 
     def __init__(self, net_g, sessions: int, index=None, index_rate: float = 0.0, device="cuda:0", if_f0: int = 1, tgt_sr: int = 48000,
                  formant_shift: float = 0.0, window: int = 160, cache_size: int = 1024):
         if int(sessions) < 1:
             raise ValueError("a bank has at least one session (got %d)" % int(sessions))
         if formant_shift != 0:
-            raise ValueError("RealtimeVCBatch serves formant_shift = 0 only (got %r): a shift makes return_length2 differ per session" % (formant_shift,))
+            raise ValueError("RealtimeVCBatch takes no bank-wide formant_shift (got %r): the formant shift is per session, set_session_formant(i, shift)"
+                             % (formant_shift,))
         self.net_g, self.index, self.index_rate = net_g, index, float(index_rate)
         self.S, self.device = int(sessions), torch.device(device)
         self.if_f0, self.tgt_sr, self.window = int(if_f0), int(tgt_sr), int(window)
@@ -208,13 +303,25 @@ class RealtimeVCBatch:
         self.pitchf = torch.zeros(self.S, cache_size, device=self.device, dtype=torch.float32)
         self._sid_host, self._sid = None, None
         self._lengths = {}
+        self.formants = [0.0] * self.S   # semitones per session (the GUI's slider: -2 .. 2)
+        self._rl2_host, self._rl2 = None, None
+        self._resample = SincResampleRagged(self.tgt_sr // 100, self.device)
 
     def set_index_rate(self, new_index_rate):
         self.index_rate = float(new_index_rate)
 
     def set_formant(self, new_formant):
         if new_formant != 0:
-            raise ValueError("RealtimeVCBatch serves formant_shift = 0 only (got %r)" % (new_formant,))
+            raise ValueError("RealtimeVCBatch takes no bank-wide formant shift (got %r): use set_session_formant(i, shift)" % (new_formant,))
+
+    def set_session_formant(self, i: int, shift: float) -> None:
+        """Session ``i``'s formant shift in semitones (rtrvc.py:128-129 per session); takes effect at the next block."""
+        i = int(i)
+        if not 0 <= i < self.S:
+            raise IndexError("session %d of %d" % (i, self.S))
+        if not math.isfinite(float(shift)):
+            raise ValueError("formant shift must be finite (got %r)" % (shift,))
+        self.formants[i] = shift
 
     def reset(self, i: int) -> None:
         """Session ``i``'s pitch cache back to zeros (a new talker takes the slot)."""
@@ -230,15 +337,28 @@ class RealtimeVCBatch:
         return self._sid
 
     def infer(self, feats: torch.Tensor, n_input_samples: int, block_frame_16k: int, skip_head: int, return_length: int,
-              pitch: Optional[torch.Tensor] = None, pitchf: Optional[torch.Tensor] = None, protect: float = 1.0, sid=0) -> torch.Tensor:
+              pitch: Optional[torch.Tensor] = None, pitchf: Optional[torch.Tensor] = None, protect: float = 1.0, sid=0,
+              formants=None) -> torch.Tensor:
         """``feats`` [S, n, d] (HuBERT of every session's rolling window), ``pitch`` / ``pitchf`` [S, m] (the estimator's output per
-        session; ``None`` for a model without f0), ``sid``: one id or ``S`` of them.  Returns the block's waveforms [S, L]; row ``i``
-        is what ``RealtimeVC.infer`` gives session ``i`` alone, to the batch invariance of ``net_g.infer``."""
+        session; ``None`` for a model without f0), ``sid``: one id or ``S`` of them, ``formants``: ``S`` shifts that replace
+        ``self.formants`` (``None`` keeps them).  Returns the block's waveforms [S, L]; row ``i`` is what ``RealtimeVC.infer`` gives
+        session ``i`` alone (with ``formant_shift = formants[i]``), to the batch invariance of ``net_g.infer``.  A session
+        whose shift leaves ``upp_res == tgt_sr // 100`` (32 kHz, +0.05) gets the first ``L`` samples of the longer block the solo object returns."""
         if feats.dim() != 3 or feats.shape[0] != self.S:
             raise ValueError("feats must be [%d, n, d], got %s" % (self.S, tuple(feats.shape)))
+        if formants is not None:
+            if len(formants) != self.S:
+                raise ValueError("formants must hold %d values, got %d" % (self.S, len(formants)))
+            self.formants = list(formants)
         feats = torch.cat((feats, feats[:, -1:, :]), 1)                                   # rtrvc.py:163
         p_len = int(n_input_samples) // self.window                                       # :189
+        shifted = any(f != 0 for f in self.formants)
         return_length2 = int(return_length)                                               # :190-191 at formant_shift 0
+        if shifted:                                                                       # :190-191, 248 per session
+            geo = [formant_geometry(f, return_length, self.tgt_sr) for f in self.formants]
+            rl2s, upp_res = [g[1] for g in geo], [g[2] for g in geo]
+            if rl2s != self._rl2_host:   # uploaded when a session's slider moves, not per block
+                self._rl2_host, self._rl2 = rl2s, torch.tensor(rl2s, dtype=torch.float32, device=self.device)[:, None]
         pf = pitchf if (protect < 0.5 and pitch is not None and pitchf is not None) else None   # :224
         if pf is not None and (pf.dim() != 2 or pf.shape[1] != p_len):
             raise RuntimeError("protect < 0.5 needs pitchf of exactly p_len = %d frames per session (got %s), as the reference's broadcast at "
@@ -258,7 +378,9 @@ class RealtimeVCBatch:
                 self.pitchf[:, :-shift] = self.pitchf[:, shift:].clone()
             self.pitch[:, 4 - n:] = pitch[:, 3:-1].to(self.device, torch.long)
             self.pitchf[:, 4 - n:] = pitchf[:, 3:-1].to(self.device, torch.float32)
-            cache_pitch, cache_pitchf = self.pitch[:, -p_len:], self.pitchf[:, -p_len:] * return_length2 / return_length   # :216-219
+            # :216-219; per session the same float32 product and quotient as the solo object's python scalars
+            cache_pitch = self.pitch[:, -p_len:]
+            cache_pitchf = self.pitchf[:, -p_len:] * (self._rl2 if shifted else return_length2) / return_length
         use_index = self.index is not None and self.index_rate > 0                        # :167
         phone = glue.retrieve_blend_expand_batch(feats, self.index if use_index else None, self.index_rate if use_index else 0.0,
                                                  pf, protect if pf is not None else 1.0, p_len, realtime_guard=True,
@@ -268,8 +390,11 @@ class RealtimeVCBatch:
             lengths = self._lengths[p_len] = torch.full((self.S,), p_len, dtype=torch.long, device=self.device)
         with torch.no_grad():
             audio = self.net_g.infer(phone, lengths, self._sids(sid), pitch=cache_pitch, pitchf=cache_pitchf, skip_head=skip_head,
-                                     return_length=return_length, return_length2=return_length2)   # :236-247
-        return audio.squeeze(1).float()
+                                     return_length=return_length, return_length2=rl2s if shifted else return_length2)   # :236-247
+        audio = audio.squeeze(1).float()
+        if shifted:                                                                       # :248-259: [S, max(rl2) * upp] -> [S, return_length * tgt_sr // 100]
+            audio = self._resample(audio, upp_res, int(return_length))
+        return audio
 
 
 def stream_geometry(samplerate: int, block_time: float = 0.25, crossfade_time: float = 0.05, extra_time: float = 2.5) -> dict:
@@ -526,12 +651,14 @@ def rvc_infer_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, ret
 
 
 def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, return_length, f0method, protect: float = 1.0,
-                        keys=None, sids=None, rt: Optional[RealtimeVCBatch] = None) -> torch.Tensor:
+                        keys=None, sids=None, rt: Optional[RealtimeVCBatch] = None, formants=None) -> torch.Tensor:
     """``rvc_infer_hip`` for ``S`` sessions of one voice: ``input_wav`` [S, n16] (every session's rolling 16 kHz window) -> [S, L].
     HuBERT runs once on the ``[S, n16]`` batch (equal lengths: the padding mask is all-false), the RMVPE network once on the
     ``[S, .]`` f0 windows; only the salience decode is per session, with that session's key (``keys``, default the object's
     ``f0_up_key``; ``sids`` default 0).  ``rt``: the ``RealtimeVCBatch`` that holds the sessions' pitch caches (default: one kept on
-    the object).  Not served, and refused: a precomputed ``(pitch, pitchf)`` tuple, an index object that is not ours, a formant shift."""
+    the object).  ``formants``: a formant shift per session (default: the ones ``rt`` holds); session ``s``'s f0 key is then
+    ``keys[s] - formants[s]`` (rtrvc.py:208) and ``rt.infer`` decodes and resamples it by its own factor.  Not served, and refused: a
+    precomputed ``(pitch, pitchf)`` tuple, an index object that is not ours, a bank-wide ``formant_shift`` on the object."""
     from .ivf import IVFFlatHIP
 
     index = getattr(self, "index", None)
@@ -540,7 +667,8 @@ def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_hea
     if input_wav.dim() != 2 or input_wav.shape[0] < 1:
         raise ValueError("input_wav must be [S, n16] with S >= 1, got %s" % (tuple(input_wav.shape),))
     if getattr(self, "formant_shift", 0) != 0:
-        raise ValueError("a bank serves formant_shift = 0 only (got %r)" % (self.formant_shift,))
+        raise ValueError("a bank takes no bank-wide formant_shift (got %r on the rvc object): pass formants= per session / RealtimeBank.set_formant(i, shift)"
+                         % (self.formant_shift,))
     S = int(input_wav.shape[0])
     keys = [self.f0_up_key] * S if keys is None else list(keys)
     sids = [0] * S if sids is None else list(sids)
@@ -554,6 +682,10 @@ def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_hea
     elif rt.S != S:
         raise ValueError("the RealtimeVCBatch holds %d sessions, input_wav %d" % (rt.S, S))
     rt.index, rt.index_rate = index, float(self.index_rate)
+    formants = list(rt.formants) if formants is None else list(formants)
+    if len(formants) != S:
+        raise ValueError("formants must hold one value per session (%d)" % S)
+    keys = [k - f if f != 0 else k for k, f in zip(keys, formants)]   # rtrvc.py:208: f0_up_key - formant_shift, per session
     with torch.no_grad():                                           # rtrvc.py:142-162, all sessions at once
         feats = input_wav.half() if self.is_half else input_wav.float()
         feats = feats.to(self.device)
@@ -594,17 +726,17 @@ def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_hea
         pitch = torch.cat([g[0].to(self.device) for g in got], 0)
         pitchf = torch.cat([g[1].to(self.device) for g in got], 0)
     return rt.infer(feats, int(input_wav.shape[1]), block_frame_16k, skip_head, return_length, pitch=pitch, pitchf=pitchf, protect=protect,
-                    sid=sids)
+                    sid=sids, formants=formants)
 
 
 class RealtimeBank:
     """``S`` live streams of ONE voice in one pass per block: a bank of ``RealtimeStream`` sessions that share the model, the index,
     the sample rate and the block geometry.  Each session has its own rolling buffers, SOLA tail, input gate, pitch cache, speaker
-    id and pitch key:
+    id, pitch key and formant shift:
 
         bank = RealtimeBank(rvc, sessions=S, samplerate=48000, use_pv=True)
         out = bank.process(blocks)     # host float32 [S, block_frame] -> device float32 [S, block_frame]
-        bank.set_key(i, key); bank.set_sid(i, sid); bank.set_noise_reduce(i, I=True, O=False); bank.reset(i)
+        bank.set_key(i, key); bank.set_sid(i, sid); bank.set_formant(i, shift); bank.set_noise_reduce(i, I=True, O=False); bank.reset(i)
         bank.last_offsets              # device int32 [S]: every session's SOLA offset of the last block
 
     Per block: the input gate (host, per session), ONE host-to-device copy of the ``[S, m]`` block, then on the device the 16 kHz
@@ -623,8 +755,13 @@ class RealtimeBank:
     are allocated at the first block that needs them: ``TorchGateBank.ring_bytes``, 4.3 MB per session and box at 48 kHz.
 
     Not served, and refused by the constructor: bank-wide ``I_noise_reduce`` / ``O_noise_reduce`` arguments (the boxes are per session),
-    the monitor mode ``function="im"``; a formant shift is refused at the first block.  The step is eager: it is not captured into a
-    hipGraph."""
+    the monitor mode ``function="im"``; a bank-wide formant shift (``rvc.formant_shift != 0``) is refused at the first block.  The step
+    is eager: it is not captured into a hipGraph.
+
+    The formant slider is per session and switchable between blocks like the key: ``set_formant(i, shift)``.  A shifted bank decodes each
+    session to its own length in the one ``net_g.infer`` and resamples all rows in one launch (``RealtimeVCBatch``); that adds three
+    launches to the block whatever ``S`` and however many distinct shifts there are, and with every shift zero the step issues exactly the
+    launches it issues without this feature.  A custom ``rvc.infer_batch`` is passed ``formants=`` only while some session's shift is non-zero."""
 
     def __init__(self, rvc, sessions: int, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05,
                  extra_time: float = 2.5, threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe",
@@ -671,6 +808,7 @@ class RealtimeBank:
         self._masks = {}
         self.keys = [getattr(rvc, "f0_up_key", 0)] * S
         self.sids = [0] * S
+        self.formants = [0.0] * S
         self.vc = None            # the sessions' RealtimeVCBatch (pitch caches), made at the first block of a real rvc object
         self.last_offsets = None  # device int32 [S]
 
@@ -679,6 +817,16 @@ class RealtimeBank:
 
     def set_sid(self, i: int, sid: int) -> None:
         self.sids[int(i)] = int(sid)
+
+    def set_formant(self, i: int, shift: float) -> None:
+        """Session ``i``'s formant shift in semitones (the GUI's slider, -2 .. 2); takes effect at the next block.  ``reset(i)`` leaves it
+        as it is, as it leaves the key."""
+        i = int(i)
+        if not 0 <= i < self.S:
+            raise IndexError("session %d of %d" % (i, self.S))
+        if not math.isfinite(float(shift)):
+            raise ValueError("formant shift must be finite (got %r)" % (shift,))
+        self.formants[i] = shift
 
     def set_noise_reduce(self, i: int, I: Optional[bool] = None, O: Optional[bool] = None) -> None:
         """Session ``i``'s noise-reduction boxes (``None`` leaves a box as it is); takes effect at the next block.  A session whose box was
@@ -724,13 +872,15 @@ class RealtimeBank:
     def _infer(self) -> torch.Tensor:
         args = (self.input_wav_res, self.block_frame_16k, self.skip_head, self.return_length, self.f0method)
         if hasattr(self.rvc, "infer_batch"):
-            return self.rvc.infer_batch(*args, keys=list(self.keys), sids=list(self.sids))
+            fm = {"formants": list(self.formants)} if any(f != 0 for f in self.formants) else {}
+            return self.rvc.infer_batch(*args, keys=list(self.keys), sids=list(self.sids), **fm)
         if self.vc is None or self.vc.net_g is not self.rvc.net_g:
             if getattr(self.rvc, "formant_shift", 0) != 0:
-                raise ValueError("a bank serves formant_shift = 0 only (got %r)" % (self.rvc.formant_shift,))
+                raise ValueError("a bank takes no bank-wide formant_shift (got %r on the rvc object): the formant shift is per session, "
+                                 "set_formant(i, shift)" % (self.rvc.formant_shift,))
             self.vc = RealtimeVCBatch(self.rvc.net_g, self.S, index=getattr(self.rvc, "index", None), index_rate=self.rvc.index_rate,
                                       device=self.device, if_f0=self.rvc.if_f0, tgt_sr=self.tgt_sr, window=getattr(self.rvc, "window", 160))
-        return rvc_infer_batch_hip(self.rvc, *args, protect=self.protect, keys=self.keys, sids=self.sids, rt=self.vc)
+        return rvc_infer_batch_hip(self.rvc, *args, protect=self.protect, keys=self.keys, sids=self.sids, rt=self.vc, formants=self.formants)
 
     def process(self, blocks) -> torch.Tensor:
         x = np.asarray(blocks, dtype=np.float32)
