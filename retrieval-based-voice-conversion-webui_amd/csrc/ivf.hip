@@ -487,7 +487,9 @@ static void ivf_build_impl(int d, int64_t n, const float* x_host, int64_t nlist,
         HIP_CHECK(hipMemcpyAsync(cent.data(), Cd.p, cent.size() * 4, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         kmeans_split_empty(cent.data(), nlist, d, off.data());
-        // relocation (kmeans_relocate), while settling iterations remain: its inputs are computed here on the device
+        // relocation (kmeans_relocate), while settling iterations remain: its inputs are computed here on the device, from the device's copy of
+        // the new means -- the split above touched the host copy only (an empty list still holds its previous centre in Cd), while the costs
+        // inside kmeans_relocate are taken on the host centres after the split.  oracle/ivf_build_oracle.py restates exactly this.
         if (it + 3 < niter && nlist >= 2) {
             hipLaunchKernelGGL(k_assigned_dist, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, X.as<float>(), Cd.as<float>(), As.as<int64_t>(), n, d,
                                Dist.as<double>());  // distance of every row to ITS new mean
@@ -510,7 +512,9 @@ static void ivf_build_impl(int d, int64_t n, const float* x_host, int64_t nlist,
             kmeans_relocate(x_host, d, nlist, dist.data(), nn2.data(), off.data(), order.data(), cent.data());
         }
     }
-    if (centroids_out) {  // every centre is valid: a cluster that lost all its points was re-seeded by splitting the largest one
+    // every centre is finite and usable: a cluster that lost all its points was re-seeded by splitting the largest one.  Not every centre is
+    // distinct or has points: an all-zero centre cannot be split, and more lists than distinct rows leave duplicates of the seeds' rows
+    if (centroids_out) {
         memcpy(centroids_out, cent.data(), cent.size() * 4);
         return;
     }

@@ -1,6 +1,6 @@
 // Host steps of the k-means behind the index build (web.py:544-563: index.train), as plain functions over host arrays (no HIP):
 // ivf_build_impl in ivf.hip owns the device buffers, the launches and the loop, and calls one of these per step.  Every step is
-// deterministic: the built index is a function of (x, nlist, niter, seed).
+// deterministic: the built index is a function of (x, nlist, niter, seed) -- the one oracle/ivf_build_oracle.py restates step by step.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -37,7 +37,9 @@ inline void kmeans_lists(const int64_t* assign, int64_t n, int64_t nlist, std::v
 }
 
 // empty lists: split the currently largest one (faiss' split_clusters idea, deterministic choice): copy its
-// centroid and nudge the two copies apart by 1/1024 in alternating coordinates
+// centroid and nudge the two copies apart by 1/1024 in alternating coordinates.  The nudge is relative: an all-zero centre cannot be
+// split (v * (1 +- 1/1024) is 0), the re-seeded list stays its duplicate and stays empty -- legal for retrieval (ties go to the lower
+// list), and pinned as it is by tests/ivf_build_cases.py "zero_rows".  The running sizes make the next empty list split what is largest then.
 inline void kmeans_split_empty(float* cent, int64_t nlist, int d, const int64_t* off) {
     std::vector<int64_t> sz(nlist);
     for (int64_t l = 0; l < nlist; ++l) sz[l] = off[l + 1] - off[l];
@@ -61,7 +63,8 @@ inline void kmeans_split_empty(float* cent, int64_t nlist, int d, const int64_t*
 // deletion costs least -- every point of cluster j re-assigned to j's nearest other centre i costs at most n_j |c_j - c_i|^2 --
 // moves to the farthest point p of the cluster with the largest distortion, if the EXACT gain of a centre at p for that
 // cluster's own points, sum max(0, |x - c_o|^2 - |x - p|^2), exceeds that cost: the objective of the next assignment cannot
-// go up (the build's objective stays non-increasing).  Deterministic; at most nlist / 20 moves per iteration; on rows without
+// go up (the build's objective stays non-increasing over every iteration that splits no empty list; kmeans_split_empty does nudge a
+// centre off its mean, so an iteration that splits may raise it).  Deterministic; at most nlist / 20 moves per iteration; on rows without
 // cluster structure no move passes the test and the iterations are the plain ones.
 //   dist: [n] squared distance of every row to the mean of its list;  nn2: [nlist][2] the two nearest centres of every centre (itself
 //   among them);  off / order: the lists (kmeans_lists);  cent: [nlist][d], moved centres are overwritten.

@@ -363,7 +363,7 @@ def reduce_features(big_npy: np.ndarray, n_clusters: int = 10000, threshold: flo
 def kmeans(x: np.ndarray, k: int, niter: int = 10, seed: int = 1234, device="cuda:0") -> np.ndarray:
     """``k`` k-means centres of the rows of ``x`` (``rvcmi_kmeans``): the Lloyd iterations of :meth:`IVFFlatHIP.train` without the
     index -- no ``add`` pass over the N rows, no list-major copy in HBM.  A cluster that loses all its points is re-seeded by
-    splitting the largest one, so all ``k`` rows returned are valid centres."""
+    splitting the largest one, so all ``k`` rows returned are usable centres (not necessarily distinct: an all-zero centre cannot be split)."""
     dev = _cuda(device)
     x = np.ascontiguousarray(x, dtype=np.float32)
     if x.ndim != 2:

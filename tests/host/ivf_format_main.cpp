@@ -5,6 +5,9 @@
 //   prefixes IN TMP    every proper prefix of IN (written to TMP) must be refused with RVCMI_ERR_IO and a "truncated" message
 //   reject FILE        FILE must be refused with RVCMI_ERR_IO (prints the message)
 //   kmeans             the host steps of k-means on n = 64, d = 8
+//   steps IN OUT       one update of the build loop on the rows, assignment and previous centres of IN (layout below): kmeans_lists ->
+//                      fp64 means -> kmeans_split_empty -> kmeans_relocate; OUT = the centres and the moves
+//   seeds N NLIST SEED prints kmeans_seed_rows(N, NLIST, SEED), one row per line
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -202,12 +205,80 @@ static int kmeans() {
     return 0;
 }
 
+// ---- one update of the build loop, as ivf_build_impl strings the host steps together, on inputs a test wrote ----
+// IN:  int64 n, d, nlist; float x[n][d]; int64 assign[n]; float prev[nlist][d] (the centres before the update: an empty list keeps its own)
+// OUT: float cent[nlist][d]; int64 nmoves; int64 (centre, row)[nmoves]
+// The distances of the rows and the two nearest centres are computed here on the host by plain loops, from the means BEFORE the split (what
+// the build's device copy holds at that point); kmeans_relocate then works on the centres after the split.
+static int steps(const char* in, const char* out) {
+    FILE* f = fopen(in, "rb");
+    CHECK(f);
+    int64_t hdr[3];
+    CHECK(fread(hdr, 8, 3, f) == 3);
+    const int64_t n = hdr[0], nlist = hdr[2];
+    const int d = (int)hdr[1];
+    CHECK(n >= 1 && n <= (1 << 20) && d >= 1 && d <= 4096 && nlist >= 1 && nlist <= n);
+    std::vector<float> x((size_t)n * d), cent((size_t)nlist * d);
+    std::vector<int64_t> assign(n);
+    CHECK(fread(x.data(), 4, x.size(), f) == x.size());
+    CHECK(fread(assign.data(), 8, assign.size(), f) == assign.size());
+    CHECK(fread(cent.data(), 4, cent.size(), f) == cent.size());
+    fclose(f);
+    for (int64_t i = 0; i < n; ++i) CHECK(assign[i] >= 0 && assign[i] < nlist);
+    std::vector<int64_t> off, order;
+    kmeans_lists(assign.data(), n, nlist, off, order);
+    for (int64_t l = 0; l < nlist; ++l) {  // the Lloyd update of k_list_mean: ascending ids, fp64, one division
+        if (off[l + 1] == off[l]) continue;
+        for (int e = 0; e < d; ++e) {
+            double acc = 0.0;
+            for (int64_t p = off[l]; p < off[l + 1]; ++p) acc += (double)x[(size_t)order[p] * d + e];
+            cent[(size_t)l * d + e] = (float)(acc / (double)(off[l + 1] - off[l]));
+        }
+    }
+    auto d2 = [&](const float* a, const float* b) {
+        double s = 0.0;
+        for (int e = 0; e < d; ++e) s += ((double)a[e] - (double)b[e]) * ((double)a[e] - (double)b[e]);
+        return s;
+    };
+    std::vector<double> dist(n);
+    for (int64_t i = 0; i < n; ++i) dist[i] = d2(&x[(size_t)i * d], &cent[(size_t)assign[i] * d]);
+    std::vector<int64_t> nn2((size_t)nlist * 2, -1);
+    for (int64_t l = 0; l < nlist; ++l)
+        for (int s = 0; s < 2 && s < nlist; ++s) {
+            int64_t best = -1;
+            for (int64_t c = 0; c < nlist; ++c)
+                if (!(s == 1 && c == nn2[l * 2]) && (best < 0 || d2(&cent[(size_t)l * d], &cent[(size_t)c * d]) < d2(&cent[(size_t)l * d], &cent[(size_t)best * d])))
+                    best = c;
+            nn2[l * 2 + s] = best;
+        }
+    kmeans_split_empty(cent.data(), nlist, d, off.data());
+    std::vector<std::pair<int64_t, int64_t>> moves;
+    if (nlist >= 2) moves = kmeans_relocate(x.data(), d, nlist, dist.data(), nn2.data(), off.data(), order.data(), cent.data());
+    f = fopen(out, "wb");
+    CHECK(f);
+    CHECK(fwrite(cent.data(), 4, cent.size(), f) == cent.size());
+    const int64_t nm = (int64_t)moves.size();
+    CHECK(fwrite(&nm, 8, 1, f) == 1);
+    for (const auto& m : moves) {
+        const int64_t pr[2] = {m.first, m.second};
+        CHECK(fwrite(pr, 8, 2, f) == 2);
+    }
+    CHECK(fclose(f) == 0);
+    printf("steps ok: n=%lld d=%d nlist=%lld moves=%lld\n", (long long)n, d, (long long)nlist, (long long)nm);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const std::string cmd = argc > 1 ? argv[1] : "";
     if (cmd == "roundtrip" && argc == 4) return roundtrip(argv[2], argv[3]);
     if (cmd == "prefixes" && argc == 4) return prefixes(argv[2], argv[3]);
     if (cmd == "reject" && argc == 3) return reject(argv[2]);
     if (cmd == "kmeans" && argc == 2) return kmeans();
-    fprintf(stderr, "usage: %s roundtrip IN OUT | prefixes IN TMP | reject FILE | kmeans\n", argv[0]);
+    if (cmd == "steps" && argc == 4) return steps(argv[2], argv[3]);
+    if (cmd == "seeds" && argc == 5) {
+        for (int64_t r : kmeans_seed_rows(atoll(argv[2]), atoll(argv[3]), strtoull(argv[4], nullptr, 10))) printf("%lld\n", (long long)r);
+        return 0;
+    }
+    fprintf(stderr, "usage: %s roundtrip IN OUT | prefixes IN TMP | reject FILE | kmeans | steps IN OUT | seeds N NLIST SEED\n", argv[0]);
     return 2;
 }

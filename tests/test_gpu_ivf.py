@@ -470,6 +470,10 @@ def test_index_build_kmeans_lists_and_roundtrip(gpu, tmp_path):
 
 
 def test_index_build_handles_empty_lists_and_is_deterministic(gpu):
+    """Two builds of rows with few distinct values give the same bytes, and every distinct row finds itself.  Despite the name, seed 1 draws
+    rows of 15 distinct points for the 15 lists (oracle/ivf_build_oracle.py: no iteration splits anything), so no list ever empties here:
+    empty lists and kmeans_split_empty are tested by tests/ivf_build_cases.py (dup_nlist40, dup_nlist14, zero_rows, ...) in
+    tests/test_gpu_ivf_build.py."""
     import rvc_amd
 
     rng = np.random.default_rng(4)
