@@ -409,6 +409,33 @@ int rvcmi_glue_rmvpe_f0_key(const float* salience_dev, int n, int nbins, float t
                             double* scratch_dev, int64_t* pitch_dev, float* pitchf_dev, void* stream);
 int rvcmi_glue_f0_post_key(const double* f0_dev, int n, double f0_up_key, int64_t* pitch_dev, float* pitchf_dev,
                            void* stream);
+/* The key factor of the entries above, pow(2, key / 12) in fp64 as the host evaluates it there (they call this function): what a caller
+ * of rvcmi_glue_rmvpe_f0_ragged puts into rvcmi_f0_row.key_mul.  A key that is not finite: NaN, which that entry refuses.             */
+double rvcmi_glue_f0_key_mul(double f0_up_key);
+
+/* rvcmi_glue_rmvpe_f0_key for MANY sequences whose salience rows lie packed in one array [R, nbins] (rvcmi_gru_forward_ragged's layout;
+ * rows between items are allowed and ignored), in TWO launches whatever nseq: the per-frame decode over all R rows, then one block per
+ * item for resize + interpolation + post_process.  Item i is described by rows[i] and equals rvcmi_glue_rmvpe_f0_key on its rows
+ * alone bit for bit, with key_mul = rvcmi_glue_f0_key_mul(its key).  The descriptors are given twice, as rvcmi_gru_forward_ragged takes
+ * its offsets: rows_host is checked before anything is launched, rows_dev (the same bytes in device memory) is what the kernel reads.
+ * scratch_dev: R doubles.  pitch_dev / pitchf_dev: out_len elements, item i at [out_off, out_off + p_len).
+ * Work arrays: dynamic LDS sized for the largest item when (n + p_len) * 8 <= 160 KiB for EVERY item; otherwise every item works in
+ * global memory, its rows of scratch_dev in place and its slice of pitch_dev -- the aliasing of the single call beyond 10240 frames.
+ * Enqueue-only: no allocation, no synchronisation, no device memory read by the host.
+ * RVCMI_ERR_INVALID, nothing launched: nseq < 1, an item with n < 1 or p_len < 1, a key_mul that is not finite and positive, source rows
+ * outside [0, R), source ranges of two items that overlap (the global mode marks unvoiced frames in place), output ranges that overlap
+ * or leave [0, out_len).                                                                                                              */
+typedef struct {
+    int64_t out_off;  /* first element of the item in pitch_dev / pitchf_dev */
+    double key_mul;   /* rvcmi_glue_f0_key_mul(the item's key)               */
+    int first_row;    /* first packed salience row of the item               */
+    int n;            /* its frames (salience rows)                          */
+    int p_len;        /* frames to return                                    */
+    int reserved_;    /* 0                                                   */
+} rvcmi_f0_row;
+int rvcmi_glue_rmvpe_f0_ragged(const float* salience_dev, int64_t R, int nbins, int nseq, const rvcmi_f0_row* rows_host,
+                               const rvcmi_f0_row* rows_dev, float thred, double* scratch_dev, int64_t* pitch_dev, float* pitchf_dev,
+                               int64_t out_len, void* stream);
 
 /* change_rms (infer/modules/vc/pipeline.py:26-46, called at :351 when rms_mix_rate != 1): mixes the loudness envelope of the
  * input (data1 at sr1 = 16000) into the converted audio data2 (sr2 = tgt_sr), IN PLACE on data2:
@@ -632,6 +659,23 @@ int rvcmi_glue_nr_stitch_batch(int S, const float* g_dev, int64_t g_stride, int 
 int rvcmi_glue_masked_write_batch(int S, float* dst_dev, int64_t dst_stride, int64_t dst_len, const float* a_dev, int64_t a_stride,
                                   int64_t off_a, int64_t na, const float* b_dev, int64_t b_stride, int64_t off_b, int64_t nb,
                                   const uint8_t* mode_dev, void* stream);
+
+/* The realtime GUI's input gate (gui.py:950-963) per session, on the device: with x = rms_buffer | block (4 zc + blk samples),
+ *   rms = librosa.feature.rms(x, frame_length 4 zc, hop zc)[2:]  (blk / zc + 3 centred frames, zero padded; the arithmetic of
+ *         rvcmi_glue_envelope_mix's frame RMS: float32 squares, fp64 sum, the mean rounded to float32, sqrtf),
+ *   frame i is quiet iff librosa.amplitude_to_db(rms)[i] < threhold,
+ *   dst[j] = x[2 zc + j] for j < blk + 2 zc, zero iff frame (j + zc / 2) / zc (integer divisions) is quiet;  rms_buffer <- x[-4 zc:].
+ * No logarithm is evaluated here: the decision is monotone in the float32 RMS, so the caller passes two float32 cutoffs derived on the
+ * host from the threshold (rvc_amd.realtime.input_gate_cutoffs): quiet iff rms[i] < cut_a and max_i rms[i] < cut_b (the 80 dB clip under
+ * the loudest frame); a NaN among the frames makes no frame quiet.
+ * block_dev rows of blk samples, rms_buffer_dev rows of 4 zc (in / out), dst_dev rows of blk + 2 zc (the tail of a rolling buffer: a row
+ * stride in elements each).  scratch_dev: S * rvcmi_glue_input_gate_scratch_floats(zc, blk) floats (per session the staged x, then its
+ * frame RMS); x is read from there, never from a buffer being written.  Three launches whatever S.
+ * RVCMI_ERR_INVALID: blk % zc != 0, blk < zc, zc < 1, S outside [1, 65535], a row stride shorter than its row.                        */
+size_t rvcmi_glue_input_gate_scratch_floats(int zc, int blk);
+int rvcmi_glue_input_gate_batch(int S, const float* block_dev, int64_t block_stride, float* rms_buffer_dev, int64_t rms_stride,
+                                float* dst_dev, int64_t dst_stride, int zc, int blk, float cut_a, float cut_b, float* scratch_dev,
+                                void* stream);
 
 /* ---- beyond SURVEY.md section 8: the recurrent layer of the RMVPE f0 network -----------------------------------------------
  * Stands in for the `nn.GRU(384, 256, num_layers=1, batch_first=True, bidirectional=True)` of rvc/f0/e2e.py:50-67 (E2E.BiGRU, the

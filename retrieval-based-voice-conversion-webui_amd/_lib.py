@@ -55,6 +55,11 @@ class ResampleRow(C.Structure):
     _fields_ = [("w_off", C.c_int64), ("n", C.c_int64), ("orig", C.c_int), ("new_", C.c_int), ("K", C.c_int), ("width", C.c_int)]
 
 
+class F0Row(C.Structure):
+    """rvcmi_f0_row: one item's descriptor of rvcmi_glue_rmvpe_f0_ragged."""
+    _fields_ = [("out_off", C.c_int64), ("key_mul", C.c_double), ("first_row", C.c_int), ("n", C.c_int), ("p_len", C.c_int), ("reserved_", C.c_int)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -127,6 +132,10 @@ SYMBOLS = [
     ("rvcmi_glue_f0_post", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     ("rvcmi_glue_rmvpe_f0_key", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, _P, _P, _P, _P]),
     ("rvcmi_glue_f0_post_key", C.c_int, [_P, C.c_int, C.c_double, _P, _P, _P]),
+    ("rvcmi_glue_f0_key_mul", C.c_double, [C.c_double]),
+    ("rvcmi_glue_rmvpe_f0_ragged", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, C.c_int64, _P]),
+    ("rvcmi_glue_input_gate_scratch_floats", C.c_size_t, [C.c_int, C.c_int]),
+    ("rvcmi_glue_input_gate_batch", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
     ("rvcmi_glue_change_rms", C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
     ("rvcmi_glue_scale_int16_range", C.c_int, [_P, C.c_int64, _P, _P]),
     ("rvcmi_glue_resample_poly", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),

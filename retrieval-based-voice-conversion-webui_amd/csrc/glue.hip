@@ -4,6 +4,7 @@
 
 #include "common.hpp"
 #include "cut_kernels.hpp"
+#include "f0_rows.hpp"
 #include "filt_kernels.hpp"
 #include "gate_kernels.hpp"
 #include "gate_ring.hpp"
@@ -13,7 +14,7 @@ using namespace rvcmi;
 
 // one once-flag per kernel that needs more dynamic LDS than the default
 static std::atomic<unsigned long long> g_attr_f0{0}, g_attr_sola{0}, g_attr_sola_search{0}, g_attr_pv_spec{0}, g_attr_pv_synth{0},
-    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_gate_stft_r{0}, g_attr_gate_idft_r{0};
+    g_attr_gate_stft{0}, g_attr_gate_idft{0}, g_attr_gate_stft_r{0}, g_attr_gate_idft_r{0}, g_attr_f0_ragged{0};
 
 #define RVCMI_BANK_MAX_S 65535  // a session is blockIdx.y (or blockIdx.x of a one-block-per-session launch)
 static_assert(GATE_RING_FT == GATE_FT && GATE_RING_MAX_NFFT == RVCMI_GATE_MAX_NFFT && GATE_RING_MAX_S == RVCMI_BANK_MAX_S,
@@ -312,6 +313,13 @@ int rvcmi_glue_masked_write_batch(int S, float* dst, int64_t dst_stride, int64_t
     });
 }
 
+// np.multiply(f0, pow(2, f0_up_key / 12)) (rvc/f0/gen.py:18): the python expression in fp64 (an integral key: the same double as
+// (double)int / 12.0).  The one place the factor is computed, for the single entries and for the descriptors of the ragged one.
+double rvcmi_glue_f0_key_mul(double f0_up_key) {
+    if (!std::isfinite(f0_up_key)) return std::nan("");
+    return std::pow(2.0, f0_up_key / 12.0);
+}
+
 int rvcmi_glue_rmvpe_f0(const float* salience, int n, int nbins, float thred, int p_len, int f0_up_key, double* scratch,
                         int64_t* pitch, float* pitchf, void* stream) {
     return rvcmi_glue_rmvpe_f0_key(salience, n, nbins, thred, p_len, (double)f0_up_key, scratch, pitch, pitchf, stream);
@@ -325,13 +333,13 @@ int rvcmi_glue_rmvpe_f0_key(const float* salience, int n, int nbins, float thred
             RVCMI_FAIL(RVCMI_ERR_INVALID, "rmvpe_f0: bad argument");
         // work arrays: LDS when (n + p_len) doubles fit, else global (scratch in place + the pitch buffer) -- no length limit
         size_t smem = (size_t)(n + p_len) * sizeof(double);
-        const bool in_lds = smem <= 160 * 1024;
+        const bool in_lds = smem <= F0_LDS_BYTES;
         if (!in_lds) smem = 0;
         hipStream_t st = (hipStream_t)stream;
         hipLaunchKernelGGL(k_rmvpe_decode, dim3((n + 3) / 4), dim3(256), 0, st, salience, n, nbins, thred, scratch);
-        ensure_dyn_lds((const void*)k_f0_post, 160 * 1024, g_attr_f0);
+        ensure_dyn_lds((const void*)k_f0_post, (int)F0_LDS_BYTES, g_attr_f0);
         // the host evaluates the scalars exactly as the reference does (python floats / math.log, rvc/f0/gen.py:18, 70-73)
-        const double key_mul = std::pow(2.0, f0_up_key / 12.0);  // (an integral key: the same double as (double)int / 12.0)
+        const double key_mul = rvcmi_glue_f0_key_mul(f0_up_key);
         const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
         hipLaunchKernelGGL(k_f0_post, dim3(1), dim3(256), smem, st, scratch, n, p_len, 1, 1, key_mul, mel_min, mel_max, pitch, pitchf,
                            in_lds ? nullptr : scratch, in_lds ? nullptr : reinterpret_cast<double*>(pitch));
@@ -347,13 +355,31 @@ int rvcmi_glue_f0_post_key(const double* f0, int n, double f0_up_key, int64_t* p
     return guarded([&] {
         if (!f0 || !pitch || !pitchf || n < 1 || !std::isfinite(f0_up_key)) RVCMI_FAIL(RVCMI_ERR_INVALID, "f0_post: bad argument");
         size_t smem = (size_t)(2 * n) * sizeof(double);
-        const bool in_lds = smem <= 160 * 1024;
+        const bool in_lds = smem <= F0_LDS_BYTES;
         if (!in_lds) smem = 0;
-        ensure_dyn_lds((const void*)k_f0_post, 160 * 1024, g_attr_f0);
-        const double key_mul = std::pow(2.0, f0_up_key / 12.0);
+        ensure_dyn_lds((const void*)k_f0_post, (int)F0_LDS_BYTES, g_attr_f0);
+        const double key_mul = rvcmi_glue_f0_key_mul(f0_up_key);
         const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
         hipLaunchKernelGGL(k_f0_post, dim3(1), dim3(256), smem, (hipStream_t)stream, f0, n, n, 0, 0, key_mul, mel_min, mel_max, pitch, pitchf,
                            (double*)nullptr, in_lds ? nullptr : reinterpret_cast<double*>(pitch));
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int rvcmi_glue_rmvpe_f0_ragged(const float* salience, int64_t R, int nbins, int nseq, const rvcmi_f0_row* rows_host, const rvcmi_f0_row* rows_dev,
+                               float thred, double* scratch, int64_t* pitch, float* pitchf, int64_t out_len, void* stream) {
+    return guarded([&] {
+        if (!salience || !rows_host || !rows_dev || !scratch || !pitch || !pitchf || nbins < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "rmvpe_f0_ragged: bad argument");
+        F0RowsPlan plan;
+        if (const char* why = f0_rows_check(rows_host, nseq, R, out_len, &plan)) RVCMI_FAIL(RVCMI_ERR_INVALID, "rmvpe_f0_ragged: %s", why);
+        hipStream_t st = (hipStream_t)stream;
+        // launch 1: the decode is per frame and knows nothing of items; rows between items decode to values nobody reads
+        hipLaunchKernelGGL(k_rmvpe_decode, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, salience, (int)R, nbins, thred, scratch);
+        ensure_dyn_lds((const void*)k_f0_post_ragged, (int)F0_LDS_BYTES, g_attr_f0_ragged);
+        const double mel_min = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
+        // launch 2: one block per item
+        hipLaunchKernelGGL(k_f0_post_ragged, dim3((unsigned)nseq), dim3(256), plan.lds_doubles * sizeof(double), st, scratch, R, rows_dev,
+                           plan.use_global ? 1 : 0, (int)plan.lds_doubles, mel_min, mel_max, pitch, pitchf, out_len);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -586,6 +612,37 @@ int rvcmi_glue_envelope_mix(const float* input, float* wav, int64_t n, int zc, d
 int rvcmi_glue_envelope_mix_batch(int S, const float* input, int64_t in_stride, float* wav, int64_t wav_stride, int64_t n, int zc, double rate,
                                   float* scratch, void* stream) {
     return guarded([&] { envelope_mix_rows("envelope_mix_batch", S, input, in_stride, wav, wav_stride, n, zc, rate, scratch, (hipStream_t)stream); });
+}
+
+size_t rvcmi_glue_input_gate_scratch_floats(int zc, int blk) {
+    if (zc < 1 || blk < zc || blk % zc || zc > (1 << 20) || blk > (1 << 28)) return 0;
+    return (size_t)4 * zc + blk + blk / zc + 5;
+}
+
+// Per session in scratch: x = rms_buffer | block [4 zc + blk], then its blk / zc + 5 frame RMS values (the gate reads frames 2 ..).
+int rvcmi_glue_input_gate_batch(int S, const float* block, int64_t block_stride, float* rms_buffer, int64_t rms_stride, float* dst,
+                                int64_t dst_stride, int zc, int blk, float cut_a, float cut_b, float* scratch, void* stream) {
+    return guarded([&] {
+        const char* who = "input_gate_batch";
+        check_sessions(who, S);
+        if (!block || !rms_buffer || !dst || !scratch) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: null pointer", who);
+        const size_t per = rvcmi_glue_input_gate_scratch_floats(zc, blk);
+        if (!per) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a block of %d samples must be a whole number (>= 1) of hops of zc = %d >= 1 samples", who, blk, zc);
+        if (cut_a != cut_a || cut_b != cut_b || cut_a < 0.f || cut_b < 0.f) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: the cutoffs are RMS values (>= 0, not NaN)", who);
+        if (block_stride < blk || rms_stride < 4 * (int64_t)zc || dst_stride < (int64_t)blk + 2 * zc)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a row stride (%lld, %lld, %lld) is shorter than its row (%d, %d, %d)", who, (long long)block_stride,
+                       (long long)rms_stride, (long long)dst_stride, blk, 4 * zc, blk + 2 * zc);
+        const int nx = 4 * zc + blk, nfr = blk / zc + 5, nout = std::max(blk + 2 * zc, 4 * zc);
+        float* rms = scratch + nx;
+        hipStream_t st = (hipStream_t)stream;
+        hipLaunchKernelGGL(k_gate_stage_batch, dim3((unsigned)((nx + 255) / 256), (unsigned)S), dim3(256), 0, st, block, block_stride,
+                           (const float*)rms_buffer, rms_stride, zc, blk, scratch, (int64_t)per);
+        hipLaunchKernelGGL(k_frame_rms_batch, dim3((unsigned)nfr, (unsigned)S), dim3(256), 0, st, (const float*)scratch, (int64_t)per, (int64_t)nx,
+                           4 * zc, zc, nfr, rms, (int64_t)per);
+        hipLaunchKernelGGL(k_input_gate_batch, dim3((unsigned)((nout + 255) / 256), (unsigned)S), dim3(256), 0, st, (const float*)scratch, (int64_t)per,
+                           (const float*)rms, (int64_t)per, zc, blk, cut_a, cut_b, dst, dst_stride, rms_buffer, rms_stride);
+        HIP_CHECK(hipGetLastError());
+    });
 }
 
 int rvcmi_glue_change_rms(const float* data1, int64_t n1, int sr1, float* data2, int64_t n2, int sr2, float rate, float* scratch,

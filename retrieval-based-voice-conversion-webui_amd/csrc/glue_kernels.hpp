@@ -15,7 +15,7 @@
 #include "exact_fp.hpp"
 #include <stdint.h>
 
-#include "../../include/rvcmi.h"  // rvcmi_resample_row
+#include "../../include/rvcmi.h"  // rvcmi_resample_row, rvcmi_f0_row
 
 namespace rvcmi {
 
@@ -170,13 +170,12 @@ static __global__ void __launch_bounds__(256) k_rmvpe_decode(const float* __rest
 // buffers ga / gr -- a whole file's f0 is computed in ONE call by the reference (pipeline.py:260-266; a 3-minute song is
 // ~36k frames), so there must be no length limit.  ga may alias src (in-place NaN marking); gr may be the `pitch` output
 // buffer itself (same size: the last loop reads r[i] and writes pitch[i] from the same thread).
-static __global__ void __launch_bounds__(256) k_f0_post(const double* src, int n, int p_len, int do_resize,
-                                                        int do_interp, double key_mul, double mel_min, double mel_max,
-                                                        int64_t* pitch, float* __restrict__ pitchf, double* ga, double* gr) {
+// The body: one block's whole chain for one sequence, work arrays a [n] (source with NaN for unvoiced) and r [p_len] given by the caller.
+// Shared by k_f0_post and k_f0_post_ragged, so an item of a ragged call equals the single call on it bit for bit.
+__device__ __forceinline__ void f0_post_block(const double* src, int n, int p_len, int do_resize, int do_interp, double key_mul,
+                                              double mel_min, double mel_max, int64_t* pitch, float* __restrict__ pitchf, double* a,
+                                              double* r) {
 #pragma clang fp contract(off)
-    extern __shared__ double sm[];
-    double* a = ga ? ga : sm;           // [n]   source with NaN for unvoiced
-    double* r = gr ? gr : sm + n;       // [p_len]
     const double NaN = __longlong_as_double(0x7ff8000000000000LL);
     if (do_resize) {
         for (int i = threadIdx.x; i < n; i += 256) {
@@ -254,6 +253,32 @@ static __global__ void __launch_bounds__(256) k_f0_post(const double* src, int n
         pitch[i] = (int64_t)rint(mel);
         pitchf[i] = (float)f;
     }
+}
+
+static __global__ void __launch_bounds__(256) k_f0_post(const double* src, int n, int p_len, int do_resize,
+                                                        int do_interp, double key_mul, double mel_min, double mel_max,
+                                                        int64_t* pitch, float* __restrict__ pitchf, double* ga, double* gr) {
+    extern __shared__ double sm[];
+    f0_post_block(src, n, p_len, do_resize, do_interp, key_mul, mel_min, mel_max, pitch, pitchf, ga ? ga : sm, gr ? gr : sm + n);
+}
+
+// k_f0_post (resize + interpolate) for MANY sequences, one block per item: item blockIdx.x's descriptor says where its decoded rows start in
+// f0 [R] (the packed output of ONE k_rmvpe_decode over all rows), how many there are, its p_len, its factor and where its results go in the
+// packed pitch / pitchf [out_len].  use_global == 0: work arrays in dynamic LDS (lds_doubles of it, sized by the host for the largest
+// item); else every item works in global memory as the single call does beyond 10240 frames: its own slice of f0 in place and its own
+// slice of `pitch` as the r array.  The descriptors live on the device; the host has checked its copy, and an item whose device
+// descriptor leaves the buffers all the same is skipped rather than followed out of bounds.
+static __global__ void __launch_bounds__(256) k_f0_post_ragged(double* f0, int64_t R, const rvcmi_f0_row* __restrict__ desc, int use_global,
+                                                               int lds_doubles, double mel_min, double mel_max, int64_t* pitch,
+                                                               float* __restrict__ pitchf, int64_t out_len) {
+    extern __shared__ double sm[];
+    const rvcmi_f0_row d = desc[blockIdx.x];
+    if (d.n < 1 || d.p_len < 1 || d.first_row < 0 || (int64_t)d.first_row + d.n > R || d.out_off < 0 || d.out_off + d.p_len > out_len) return;
+    if (!use_global && (int64_t)d.n + d.p_len > lds_doubles) return;
+    double* src = f0 + d.first_row;
+    int64_t* p = pitch + d.out_off;
+    f0_post_block(src, d.n, d.p_len, 1, 1, d.key_mul, mel_min, mel_max, p, pitchf + d.out_off, use_global ? src : sm,
+                  use_global ? reinterpret_cast<double*>(p) : sm + d.n);
 }
 
 // audio_max = abs(audio).max() / 0.99; max_int16 = 32768; if audio_max > 1: max_int16 /= audio_max; audio *= max_int16
@@ -637,6 +662,59 @@ static __global__ void __launch_bounds__(256) k_change_rms(float* __restrict__ d
     float r2 = interp_linear_1d(rms2, nf2, n2, t);
     r2 = fmaxf(r2, 1e-6f);
     data2[t] = mul_rn(data2[t], mul_rn(powf(r1, e1), powf(r2, e2)));
+}
+
+// ------------------------------------------------------------------------------------------------
+// The realtime GUI's input gate (gui.py:950-963) for a bank, session blockIdx.y.  Three launches:
+//   k_gate_stage_batch     x = rms_buffer | block  (4 zc + blk samples) into the session's staging row
+//   k_frame_rms_batch      the frame RMS of x, frame 4 zc, hop zc (all blk / zc + 5 centred frames; the gate reads frames 2 ..)
+//   k_input_gate_batch     out[j] = x[2 zc + j] for j < blk + 2 zc, zero where frame (j + zc / 2) / zc is quiet; rms_buffer <- x[-4 zc:]
+// librosa.amplitude_to_db(rms)[i] < threhold is decided WITHOUT a logarithm: it is monotone in the float32 RMS, so the host derives the
+// two float32 cutoffs (realtime.input_gate_cutoffs) and frame i is quiet iff rms[i] < cut_a and max(rms) < cut_b (the 80 dB clip under the
+// loudest frame); a NaN among the frames makes no frame quiet, as numpy's max propagates it.
+static __global__ void __launch_bounds__(256) k_gate_stage_batch(const float* __restrict__ block, int64_t block_stride,
+                                                                 const float* __restrict__ rbuf, int64_t rbuf_stride, int zc, int blk,
+                                                                 float* __restrict__ x, int64_t x_stride) {
+    const int64_t s = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 4 * zc + blk) return;
+    x[s * x_stride + i] = i < 4 * zc ? rbuf[s * rbuf_stride + i] : block[s * block_stride + (i - 4 * zc)];
+}
+
+// rms: the session's blk / zc + 5 frames as k_frame_rms_batch wrote them (rms_stride floats apart); the gate's frame i is rms[2 + i].
+static __global__ void __launch_bounds__(256) k_input_gate_batch(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ rms,
+                                                                 int64_t rms_stride, int zc, int blk, float cut_a, float cut_b,
+                                                                 float* __restrict__ dst, int64_t dst_stride, float* __restrict__ rbuf,
+                                                                 int64_t rbuf_stride) {
+    __shared__ float red[256];
+    __shared__ int has_nan;
+    const int64_t s = blockIdx.y;
+    const float* r = rms + s * rms_stride + 2;
+    const int nf = blk / zc + 3;
+    if (threadIdx.x == 0) has_nan = 0;
+    __syncthreads();
+    float m = 0.f;  // an RMS is never negative
+    int nan = 0;
+    for (int i = threadIdx.x; i < nf; i += 256) {
+        const float v = r[i];
+        nan |= v != v ? 1 : 0;
+        m = fmaxf(m, v);
+    }
+    red[threadIdx.x] = m;
+    if (nan) atomicOr(&has_nan, 1);
+    __syncthreads();
+    for (int s2 = 128; s2 >= 1; s2 >>= 1) {
+        if ((int)threadIdx.x < s2) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
+        __syncthreads();
+    }
+    const bool may = !has_nan && red[0] < cut_b;
+    const float* xs = x + s * x_stride;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < blk + 2 * zc) {
+        const bool quiet = may && r[(j + zc / 2) / zc] < cut_a;
+        dst[s * dst_stride + j] = quiet ? 0.f : xs[2 * zc + j];
+    }
+    if (j < 4 * zc) rbuf[s * rbuf_stride + j] = xs[blk + j];
 }
 
 // Polyphase FIR resampling as torchaudio.transforms.Resample applies it (rtrvc.py:248-259: the formant-shifted block comes out

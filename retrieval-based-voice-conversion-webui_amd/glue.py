@@ -24,12 +24,15 @@ results are bit-equal to a single-stream call on its row:
     sola_batch(infer_wav [S, n], sola_buffer [S, Lb], ...) / envelope_mix_batch(input_wav [S, .], infer_wav [S, n], zc, rate)
     spectral_gate_ring(x [S, n], xn [S, nn], shift, tail, ring, ring_base, mode, ...)   the gate over a rolling cache of noise spectra
     nr_stitch_batch(...) / masked_write_batch(...) / gate_ring_plan(nn, n_fft, hop, shift, tail)   per-session noise reduction (gate.TorchGateBank)
+    rmvpe_f0_ragged(salience [R, 360], ((first_row, n, p_len, key), ...))     rmvpe_f0 of many packed sequences, a key each, in two launches
+    input_gate_batch(block [S, blk], rms_buffer [S, 4 zc], dst [S, blk + 2 zc], zc, cut_a, cut_b)   the GUI's input gate (gui.py:950-963)
 
 All take and return CUDA (ROCm) tensors and enqueue on the current stream; a CPU tensor raises (no fallback).
 """
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from typing import Optional, Tuple
 
 import numpy as np
@@ -137,6 +140,11 @@ def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.0
     dev = _lib.on_gpu(salience, "salience")
     if salience.dim() != 2:
         raise ValueError("salience must be [n, bins]")
+    open_blocks = getattr(_F0_GATHER, "blocks", None)
+    if open_blocks:   # inside ``with _f0_gather(...)`` (this thread's): rows of its packed salience are noted, decoded when the block ends
+        got = open_blocks[-1].add(salience, p_len, f0_up_key, thred)
+        if got is not None:
+            return got
     s = salience.to(torch.float32).contiguous()
     n, nb = int(s.shape[0]), int(s.shape[1])
     scratch = torch.empty(n, device=dev, dtype=torch.float64)
@@ -146,6 +154,124 @@ def rmvpe_f0(salience: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.0
         _lib.check(_lib.lib().rvcmi_glue_rmvpe_f0_key(_lib.ptr(s), n, nb, float(thred), int(p_len), float(f0_up_key), _lib.ptr(scratch), _lib.ptr(pitch),
                                                       _lib.ptr(pitchf), _lib.stream_ptr(dev)))
     return pitch.unsqueeze(0), pitchf.unsqueeze(0)
+
+
+_F0_ROWS: dict = {}     # (device index, rows) -> (host descriptors, their device copy, total p_len): kept until the tuple of rows changes
+_F0_ROWS_KEEP = 8       # distinct row tuples remembered (a bank's step, a folder's batch); the oldest goes first
+f0_rows_uploads = 0     # how often descriptors went to the device (tests read it)
+
+
+def f0_rows(rows, dev):
+    """The descriptors of ``rmvpe_f0_ragged`` for ``rows`` = ((first_row, n, p_len, key), ...): -> (host array of ``rvcmi_f0_row``, the same
+    bytes on ``dev``, total output length).  Item ``i``'s output starts at the sum of the ``p_len`` before it; its factor is
+    ``rvcmi_glue_f0_key_mul(key)``, the double the single entry uses.  Cached per tuple of rows: an unchanged bank step uploads nothing."""
+    global f0_rows_uploads
+    key = (_lib.device_index(dev), tuple((int(r), int(n), int(p), float(k)) for r, n, p, k in rows))
+    hit = _F0_ROWS.get(key)
+    if hit is None:
+        L = _lib.lib()
+        desc, off = (_lib.F0Row * len(key[1]))(), 0
+        for d, (r, n, p, k) in zip(desc, key[1]):
+            d.out_off, d.key_mul, d.first_row, d.n, d.p_len = off, L.rvcmi_glue_f0_key_mul(k), r, n, p
+            off += max(p, 0)
+        raw = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8) if len(desc) else torch.zeros(0, dtype=torch.uint8)
+        while len(_F0_ROWS) >= _F0_ROWS_KEEP:
+            _F0_ROWS.pop(next(iter(_F0_ROWS)))
+        hit = _F0_ROWS[key] = (desc, raw.to(dev), off)
+        f0_rows_uploads += 1
+    return hit
+
+
+def rmvpe_f0_ragged_packed(salience: torch.Tensor, rows, thred: float = 0.03, out=None):
+    """``rmvpe_f0_ragged`` without the views: -> (pitch int64 [sum p_len], pitchf float32 [sum p_len]), item ``i`` behind the items before it.
+    ``out``: a (pitch, pitchf) pair of contiguous device tensors of exactly that length to write into."""
+    dev = _lib.on_gpu(salience, "salience")
+    if salience.dim() != 2 or salience.dtype != torch.float32 or not salience.is_contiguous():
+        raise ValueError("salience must be a contiguous float32 tensor [R, bins]")
+    rows = list(rows)
+    R, nb = int(salience.shape[0]), int(salience.shape[1])
+    desc, desc_dev, total = f0_rows(rows, dev)
+    scratch = torch.empty(max(R, 1), device=dev, dtype=torch.float64)
+    if out is None:
+        pitch = torch.empty(max(total, 1), device=dev, dtype=torch.int64)
+        pitchf = torch.empty(max(total, 1), device=dev, dtype=torch.float32)
+    else:
+        pitch, pitchf = out
+        if (pitch.dtype != torch.int64 or pitchf.dtype != torch.float32 or pitch.device != dev or pitchf.device != dev or pitch.dim() != 1 or pitchf.dim() != 1
+                or pitch.numel() != total or pitchf.numel() != total or not pitch.is_contiguous() or not pitchf.is_contiguous() or total < 1):
+            raise ValueError("out must be (int64 [%d], float32 [%d]) contiguous on %s" % (total, total, dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_rmvpe_f0_ragged(_lib.ptr(salience), R, nb, len(rows), C.cast(desc, C.c_void_p), _lib.ptr(desc_dev), float(thred),
+                                                         _lib.ptr(scratch), _lib.ptr(pitch), _lib.ptr(pitchf), total, _lib.stream_ptr(dev)))
+    return pitch[:total], pitchf[:total]
+
+
+def rmvpe_f0_ragged(salience: torch.Tensor, rows, thred: float = 0.03):
+    """``rmvpe_f0`` for many sequences whose salience rows lie packed in ``salience`` [R, 360] (contiguous float32), in TWO launches whatever
+    their number: ``rows`` is a sequence of ``(first_row, n, p_len, key)``.  -> a list of ``(pitch int64 [1, p_len_i], pitchf float32
+    [1, p_len_i])``, views of two packed tensors; item ``i`` equals ``rmvpe_f0(salience[first_row : first_row + n], p_len, key, thred)``
+    bit for bit.  Rows between items are allowed; items must not share rows (``RvcmiError`` with ``ERR_INVALID``, as for ``p_len < 1`` or
+    a key that is not finite, before anything is launched)."""
+    rows = list(rows)
+    pitch, pitchf = rmvpe_f0_ragged_packed(salience, rows, thred)
+    out, off = [], 0
+    for _, _, p, _ in rows:
+        out.append((pitch[off: off + int(p)].unsqueeze(0), pitchf[off: off + int(p)].unsqueeze(0)))
+        off += int(p)
+    return out
+
+
+_F0_GATHER = threading.local()   # .blocks: this thread's open _f0_gather blocks, innermost last
+
+
+class _f0_gather:
+    """Private to the package (``rvc_infer_batch_hip``): ``rmvpe_f0`` calls of one block, decoded together:
+
+        with glue._f0_gather(salience_packed, total_p_len, thred) as g:
+            pairs = [glue.rmvpe_f0(salience_packed[r: r + n], p_len, key, thred) for r, n, p_len, key in ...]   # nothing is launched here
+        g.pitch, g.pitchf                                                   # packed [total_p_len], filled by ONE rmvpe_f0_ragged call
+
+    Inside the block a ``rmvpe_f0`` call whose salience is a run of whole rows of ``salience_packed`` (a view of it, same ``thred``) launches
+    nothing: it is noted as an item and gets views of the packed outputs, which the two launches at the end of the block fill -- item for
+    item the bits the call alone would have produced.  UNTIL THE BLOCK EXITS THE RETURNED VIEWS ARE UNDEFINED (nothing has written them yet):
+    the caller must not read them inside the block, and after an exception they are never filled.  Any other ``rmvpe_f0`` call inside the block runs at once, as outside.  The caller
+    keeps calling ``rmvpe_f0`` per sequence, each with its own key, and the launch count does not depend on how many there are."""
+
+    def __init__(self, salience: torch.Tensor, total_p_len: int, thred: float = 0.03):
+        _lib.on_gpu(salience, "salience")
+        if salience.dim() != 2 or salience.dtype != torch.float32 or not salience.is_contiguous():
+            raise ValueError("salience must be a contiguous float32 tensor [R, bins]")
+        self.salience, self.thred, self.total = salience, float(thred), int(total_p_len)
+        self.pitch = torch.empty(max(self.total, 1), device=salience.device, dtype=torch.int64)[: self.total]
+        self.pitchf = torch.empty(max(self.total, 1), device=salience.device, dtype=torch.float32)[: self.total]
+        self.rows, self.used = [], 0
+
+    def add(self, sal: torch.Tensor, p_len: int, key, thred: float):
+        """-> views of the packed outputs for this item, or None when ``sal`` is not a run of rows of the packed salience."""
+        base, nb = self.salience, int(self.salience.shape[1])
+        off = sal.storage_offset() - base.storage_offset()
+        if (sal.dtype != torch.float32 or sal.device != base.device or sal.untyped_storage().data_ptr() != base.untyped_storage().data_ptr()
+                or not sal.is_contiguous() or sal.shape[1] != nb or sal.shape[0] < 1 or off < 0 or off % nb
+                or off // nb + sal.shape[0] > base.shape[0] or float(thred) != self.thred):
+            return None
+        p_len = int(p_len)
+        if p_len < 1 or self.used + p_len > self.total:
+            raise ValueError("_f0_gather: %d output frames were announced, item %d asks for %d more than are left" % (self.total, len(self.rows), p_len))
+        self.rows.append((off // nb, int(sal.shape[0]), p_len, float(key)))
+        lo, self.used = self.used, self.used + p_len
+        return self.pitch[lo: lo + p_len].unsqueeze(0), self.pitchf[lo: lo + p_len].unsqueeze(0)
+
+    def __enter__(self):
+        if not hasattr(_F0_GATHER, "blocks"):
+            _F0_GATHER.blocks = []
+        _F0_GATHER.blocks.append(self)
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        _F0_GATHER.blocks.remove(self)
+        if exc_type is None and self.rows:
+            rmvpe_f0_ragged_packed(self.salience, self.rows, self.thred, out=(self.pitch, self.pitchf))
+        return False
 
 
 def f0_post(f0: torch.Tensor, f0_up_key=0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -500,6 +626,43 @@ def envelope_mix_batch(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int
         _lib.check(_lib.lib().rvcmi_glue_envelope_mix_batch(S, _lib.ptr(input_wav), ins, _lib.ptr(infer_wav), ws, n, zc, float(rms_mix_rate),
                                                             _lib.ptr(scratch), _lib.stream_ptr(dev)))
     return infer_wav
+
+
+def input_gate_scratch_floats(zc: int, blk: int) -> int:
+    """Floats of scratch per session of ``input_gate_batch`` (0: the geometry is refused)."""
+    return int(_lib.lib().rvcmi_glue_input_gate_scratch_floats(int(zc), int(blk)))
+
+
+def input_gate_batch(block: torch.Tensor, rms_buffer: torch.Tensor, dst: torch.Tensor, zc: int, cut_a: float, cut_b: float,
+                     scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``realtime.input_gate`` (gui.py:950-963) for a bank, on the device: ``block`` [S, blk] (the raw block), ``rms_buffer`` [S, 4 zc]
+    (updated in place), ``dst`` [S, blk + 2 zc] (written: the gated samples; its rows are usually the tails of the rolling ``input_wav``),
+    ``cut_a`` / ``cut_b`` = ``realtime.input_gate_cutoffs(threhold)``.  Rows of all three may be views into longer buffers.  Session ``s``
+    equals ``input_gate`` on its rows bit for bit; three launches whatever ``S``.  ``scratch``: float32, at least ``S *
+    input_gate_scratch_floats(zc, blk)`` elements (allocated when None).  Returns ``dst``."""
+    dev = _lib.on_gpu(block, "block")
+    S, blk, bs = bank_rows(block, "block")
+    Sr, nr, rs = bank_rows(rms_buffer, "rms_buffer", dev)
+    Sd, nd, ds = bank_rows(dst, "dst", dev)
+    zc = int(zc)
+    if Sr != S or Sd != S:
+        raise ValueError("block, rms_buffer and dst must hold the same number of sessions")
+    per = input_gate_scratch_floats(zc, blk)
+    if per == 0:
+        raise _lib.RvcmiError("input_gate_batch: a block of %d samples must be a whole number (>= 1) of hops of zc = %d >= 1 samples" % (blk, zc),
+                              code=_lib.ERR_INVALID)
+    if nr != 4 * zc or nd != blk + 2 * zc:
+        raise ValueError("rms_buffer must be [S, %d] and dst [S, %d], got %s / %s" % (4 * zc, blk + 2 * zc, tuple(rms_buffer.shape), tuple(dst.shape)))
+    if S > 1 and (rs < nr or ds < nd):
+        raise ValueError("the rows of rms_buffer / dst overlap")
+    if scratch is None:
+        scratch = torch.empty(S * per, device=dev, dtype=torch.float32)
+    elif scratch.dtype != torch.float32 or scratch.device != dev or not scratch.is_contiguous() or scratch.numel() < S * per:
+        raise ValueError("scratch must be a contiguous float32 tensor of at least %d elements on %s" % (S * per, dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_input_gate_batch(S, _lib.ptr(block), bs, _lib.ptr(rms_buffer), rs, _lib.ptr(dst), ds, zc, blk, float(cut_a),
+                                                          float(cut_b), _lib.ptr(scratch), _lib.stream_ptr(dev)))
+    return dst
 
 
 def phase_vocoder(a: torch.Tensor, b: torch.Tensor, fade_out: torch.Tensor, fade_in: torch.Tensor) -> torch.Tensor:

@@ -448,6 +448,64 @@ def input_gate(indata: np.ndarray, rms_buffer: np.ndarray, zc: int, threhold: fl
     return x[zc // 2:]
 
 
+_GATE_CUTOFFS: dict = {}
+
+
+def _first_true(pred) -> np.float32:
+    """The smallest non-negative float32 ``r`` (+inf included) with ``pred(r)``, for a ``pred`` that is monotone in ``r`` (false, then
+    true): bisection over the bit patterns 0 .. 0x7f800000, which order like the values.  +inf when there is none."""
+    bits = lambda b: np.array([b], np.uint32).view(np.float32)[0]  # noqa: E731
+    lo, hi = 0, 0x7F800000
+    if not pred(bits(hi)):
+        return np.float32(np.inf)
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if pred(bits(mid)):
+            hi = mid
+        else:
+            lo = mid + 1
+    return bits(lo)
+
+
+def input_gate_cutoffs(threhold: float):
+    """The gate's decision ``amplitude_to_db(rms)[i] < threhold`` (``input_gate``) as two float32 RMS cutoffs, for the device gate
+    (``glue.input_gate_batch``), which evaluates no logarithm: ``amplitude_to_db`` is monotone in the RMS, and with the 80 dB clip
+    ``db[i] = max(db1(rms[i]), db1(max rms) - 80)``, so
+
+        frame i is quiet  iff  rms[i] < cut_a  and  max_i rms[i] < cut_b
+
+    with ``cut_a`` the smallest float32 ``r >= 0`` for which ``db1(r) < threhold`` is false and ``cut_b`` the smallest for which
+    ``float32(db1(r) - float32(80)) < threhold`` is false; ``db1`` is ``amplitude_to_db`` itself on the single value.  Both are found by
+    bisection over float32 bit patterns and cached per threshold; no device is needed.  The ends: a threshold at or below the floor of
+    ``db1`` (-100 dB, the ``amin`` of 1e-5) gives ``cut_a == 0`` -- no frame is ever quiet; a threshold above every level a finite
+    ``rms ** 2`` reaches (385.3 dB) puts a cutoff where the float32 square overflows (1.8447e19), or at +inf if not even that level
+    fails the comparison.  -> (cut_a, cut_b) as python floats that are exact float32 values."""
+    t = float(threhold)
+    hit = _GATE_CUTOFFS.get(t)
+    if hit is None:
+        db1 = lambda r: amplitude_to_db(np.array([r], np.float32))  # noqa: E731  (arrays, so that `< threhold` promotes as in input_gate)
+        with np.errstate(over="ignore", invalid="ignore"):
+            cut_a = _first_true(lambda r: not bool((db1(r) < t)[0]))
+            cut_b = _first_true(lambda r: not bool(((db1(r) - np.float32(80.0)).astype(np.float32) < t)[0]))
+        if len(_GATE_CUTOFFS) > 256:
+            _GATE_CUTOFFS.clear()
+        hit = _GATE_CUTOFFS[t] = (float(cut_a), float(cut_b))
+    return hit
+
+
+BANK_DEVICE_GATE = True      # RealtimeBank(device_gate=None); RVCMI_RT_DEVICE_GATE=1 / =0 overrides both defaults.  Decided by tools/rt_bank_gate_time.py
+STREAM_DEVICE_GATE = True    # RealtimeStream(device_gate=None)                          (profiles/rt_bank_gate_time.json: the device gate's range lies below the host gate's)
+
+
+def _device_gate(arg, default: bool) -> bool:
+    import os
+
+    if arg is not None:
+        return bool(arg)
+    env = os.environ.get("RVCMI_RT_DEVICE_GATE")
+    return default if env in (None, "") else env != "0"
+
+
 class RealtimeStream:
     """The per-block audio path of the realtime GUI (``audio_infer``, gui.py:934-1090) around any ``rtrvc.RVC``-like object
     (``.tgt_sr`` and ``.infer(input_wav_res, block_frame_16k, skip_head, return_length, f0method)``; the reference's own after
@@ -456,7 +514,8 @@ class RealtimeStream:
         rt = RealtimeStream(rvc, samplerate=48000, use_pv=True)
         out = rt.process(block)        # host float32 [block_frame] or [block_frame, channels] -> device float32 [block_frame]
 
-    Per block: the input gate (host, when ``threhold > -60``), rolling ``input_wav`` / ``input_wav_res`` buffers and the 16 kHz
+    Per block: the input gate (when ``threhold > -60``; on the host, or with ``device_gate=True`` on the device: ``glue.input_gate_batch`` at
+    ``S = 1``, bit-equal; ``None`` reads ``RVCMI_RT_DEVICE_GATE``, else ``STREAM_DEVICE_GATE``), rolling ``input_wav`` / ``input_wav_res`` buffers and the 16 kHz
     resample, ``rvc.infer``, the ``tgt_sr -> samplerate`` resample, the envelope mix (``rms_mix_rate < 1``) and the SOLA stitch
     (sin^2 or phase-vocoder fade), all on the device: one host-to-device copy (the block), none back.  The keyword names are the
     GUI's ``GUIConfig`` fields; ``samplerate=None`` is the model rate.  ``I_noise_reduce`` / ``O_noise_reduce`` (the GUI's
@@ -466,8 +525,9 @@ class RealtimeStream:
 
     def __init__(self, rvc, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05, extra_time: float = 2.5,
                  threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe", device=None,
-                 I_noise_reduce: bool = False, O_noise_reduce: bool = False, function: str = "vc"):
+                 I_noise_reduce: bool = False, O_noise_reduce: bool = False, function: str = "vc", device_gate: Optional[bool] = None):
         self.rvc = rvc
+        self.device_gate = _device_gate(device_gate, STREAM_DEVICE_GATE)
         if rvc is None and samplerate is None:
             raise ValueError("RealtimeStream without an rvc object (the \"im\" mode) needs samplerate")
         self.tgt_sr = int(rvc.tgt_sr) if rvc is not None else int(samplerate)
@@ -485,7 +545,9 @@ class RealtimeStream:
             setattr(self, k, v)
         self.input_wav = torch.zeros(self.input_wav_len, device=self.device, dtype=torch.float32)
         self.input_wav_res = torch.zeros(self.input_wav_res_len, device=self.device, dtype=torch.float32)
-        self.rms_buffer = np.zeros(4 * self.zc, dtype="float32")
+        # the input gate's 4 zc samples of history: on the host with the host gate, on the device with the device gate
+        self.rms_buffer = torch.zeros(4 * self.zc, device=self.device, dtype=torch.float32) if self.device_gate else np.zeros(4 * self.zc, dtype="float32")
+        self._gate_scratch = None
         self.sola_buffer = torch.zeros(self.sola_buffer_frame, device=self.device, dtype=torch.float32)
         # gui.py:825, 835-836: kept whatever the noise-reduction boxes say, updated only while they are ticked
         self.input_wav_denoise = self.input_wav.clone()
@@ -506,12 +568,19 @@ class RealtimeStream:
             x = np.mean(x.T, axis=0)       # librosa.to_mono(indata.T)
         if x.shape[0] != self.block_frame:
             raise ValueError("a block has %d samples, got %d" % (self.block_frame, x.shape[0]))
-        if self.threhold > -60:
-            x = input_gate(x, self.rms_buffer, self.zc, self.threhold)
-        m = int(x.shape[0])
         blk, blk16 = self.block_frame, self.block_frame_16k
+        on_device = self.threhold > -60 and self.device_gate
+        if self.threhold > -60 and not on_device:
+            x = input_gate(x, self.rms_buffer, self.zc, self.threhold)
+        m = blk + 2 * self.zc if on_device else int(x.shape[0])
         self.input_wav[:-blk] = self.input_wav[blk:].clone()
-        self.input_wav[-m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        if on_device:   # the bank's entry at S = 1: the raw block goes up, the gate writes the tail of input_wav
+            if self._gate_scratch is None:
+                self._gate_scratch = torch.empty(glue.input_gate_scratch_floats(self.zc, blk), device=self.device, dtype=torch.float32)
+            glue.input_gate_batch(torch.from_numpy(np.ascontiguousarray(x)).to(self.device)[None], self.rms_buffer[None], self.input_wav[None, -m:],
+                                  self.zc, *input_gate_cutoffs(self.threhold), scratch=self._gate_scratch)
+        else:
+            self.input_wav[-m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         self.input_wav_res[:-blk16] = self.input_wav_res[blk16:].clone()
         Lb = self.sola_buffer_frame
         if self.I_noise_reduce:                                                          # gui.py:974-992
@@ -654,8 +723,8 @@ def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_hea
                         keys=None, sids=None, rt: Optional[RealtimeVCBatch] = None, formants=None) -> torch.Tensor:
     """``rvc_infer_hip`` for ``S`` sessions of one voice: ``input_wav`` [S, n16] (every session's rolling 16 kHz window) -> [S, L].
     HuBERT runs once on the ``[S, n16]`` batch (equal lengths: the padding mask is all-false), the RMVPE network once on the
-    ``[S, .]`` f0 windows; only the salience decode is per session, with that session's key (``keys``, default the object's
-    ``f0_up_key``; ``sids`` default 0).  ``rt``: the ``RealtimeVCBatch`` that holds the sessions' pitch caches (default: one kept on
+    ``[S, .]`` f0 windows, and the salience decode of all sessions in one ``glue.rmvpe_f0_ragged`` call, each with its own key (``keys``,
+    default the object's ``f0_up_key``; ``sids`` default 0).  ``rt``: the ``RealtimeVCBatch`` that holds the sessions' pitch caches (default: one kept on
     the object).  ``formants``: a formant shift per session (default: the ones ``rt`` holds); session ``s``'s f0 key is then
     ``keys[s] - formants[s]`` (rtrvc.py:208) and ``rt.infer`` decodes and resamples it by its own factor.  Not served, and refused: a
     precomputed ``(pitch, pitchf)`` tuple, an index object that is not ours, a bank-wide ``formant_shift`` on the object."""
@@ -707,24 +776,33 @@ def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_hea
         r = _torch_rmvpe(self) if (f0method == "rmvpe" and getattr(self, "f0_gen", None) is not None) else None
         if r is not None:
             hip = for_generator(self.f0_gen, r) if rmvpe_on() else None
-            if hip is not None:
-                sal = hip.salience_batch([w[s].float().to(hip.device) for s in range(S)])
+            if hip is not None:   # the packed rows of the ragged pass, as they lie (no clone per session)
+                sal, off, frames = hip._salience_ragged(hip._wavs([w[s].float().to(hip.device) for s in range(S)]))
+                rows = [(off[s], frames[s], m, keys[s]) for s in range(S)]
             else:
                 from .gru import accelerate_f0_rmvpe
 
                 accelerate_f0_rmvpe(r)
                 with torch.no_grad():
                     hidden = r._mel2hidden(r.mel_extractor(w.float().to(r.device), center=True))
-                sal = [hidden[s].float() for s in range(S)]
-            got = [glue.rmvpe_f0(sal[s], m, keys[s] if (hip is not None or not float(keys[s]).is_integer()) else int(keys[s]), RMVPE_THRED)
-                   for s in range(S)]                              # the only S-proportional launches of the block
+                T = int(hidden.shape[1])
+                sal = hidden.float().contiguous().view(S * T, int(hidden.shape[2]))   # [S, T, 360] seen as [S * T, 360]
+                rows = [(s * T, T, m, keys[s]) for s in range(S)]
+            # every session asks glue.rmvpe_f0 for its rows with its own key, as before; inside glue._f0_gather the calls launch nothing and the
+            # block ends in ONE rvcmi_glue_rmvpe_f0_ragged: two launches whatever S, each row the bits of the call alone
+            with glue._f0_gather(sal, S * m, RMVPE_THRED) as gathered:
+                for r0, nr, p, k in rows:
+                    glue.rmvpe_f0(sal[r0: r0 + nr], p, k if (hip is not None or not float(k).is_integer()) else int(k), RMVPE_THRED)
+            if len(gathered.rows) != S:   # (a glue.rmvpe_f0 that did not recognise its rows would have decoded alone: never quietly)
+                raise _lib.RvcmiError("rvc_infer_batch_hip: %d of %d sessions' decodes were gathered" % (len(gathered.rows), S))
+            pitch, pitchf = gathered.pitch.view(S, m).to(self.device), gathered.pitchf.view(S, m).to(self.device)
         else:
             got = []
             for s in range(S):
                 p, pf = self._get_f0(input_wav[s, -n:], keys[s], method=f0method)
                 got.append((p.reshape(1, -1), pf.reshape(1, -1)))
-        pitch = torch.cat([g[0].to(self.device) for g in got], 0)
-        pitchf = torch.cat([g[1].to(self.device) for g in got], 0)
+            pitch = torch.cat([g[0].to(self.device) for g in got], 0)
+            pitchf = torch.cat([g[1].to(self.device) for g in got], 0)
     return rt.infer(feats, int(input_wav.shape[1]), block_frame_16k, skip_head, return_length, pitch=pitch, pitchf=pitchf, protect=protect,
                     sid=sids, formants=formants)
 
@@ -739,7 +817,9 @@ class RealtimeBank:
         bank.set_key(i, key); bank.set_sid(i, sid); bank.set_formant(i, shift); bank.set_noise_reduce(i, I=True, O=False); bank.reset(i)
         bank.last_offsets              # device int32 [S]: every session's SOLA offset of the last block
 
-    Per block: the input gate (host, per session), ONE host-to-device copy of the ``[S, m]`` block, then on the device the 16 kHz
+    Per block: the input gate (when ``threhold > -60``: on the host per session, or with ``device_gate=True`` one
+    ``glue.input_gate_batch`` for all sessions, bit-equal; ``None`` reads ``RVCMI_RT_DEVICE_GATE``, else ``BANK_DEVICE_GATE``), ONE
+    host-to-device copy of the block (``[S, m]`` gated, or raw ``[S, block_frame]`` with the device gate), then on the device the 16 kHz
     resample, ``rvc_infer_batch_hip`` (HuBERT, f0, retrieval and ``net_g.infer`` at batch ``S``), the ``tgt_sr -> samplerate`` resample,
     the envelope mix and the SOLA stitch, each as ONE set of launches for all sessions (``rvcmi_glue_*_batch``).  Nothing is read back.
     Every DSP step is bit-equal, per session, to ``RealtimeStream``'s.  ``rvc`` is an ``rtrvc.RVC``-like object; one that has an
@@ -765,7 +845,8 @@ class RealtimeBank:
 
     def __init__(self, rvc, sessions: int, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05,
                  extra_time: float = 2.5, threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe",
-                 device=None, I_noise_reduce: bool = False, O_noise_reduce: bool = False, function: str = "vc", protect: float = 1.0):
+                 device=None, I_noise_reduce: bool = False, O_noise_reduce: bool = False, function: str = "vc", protect: float = 1.0,
+                 device_gate: Optional[bool] = None):
         if int(sessions) < 1:
             raise ValueError("a bank has at least one session (got %d)" % int(sessions))
         if I_noise_reduce or O_noise_reduce:
@@ -791,7 +872,10 @@ class RealtimeBank:
         S, f32 = self.S, torch.float32
         self.input_wav = torch.zeros(S, self.input_wav_len, device=self.device, dtype=f32)
         self.input_wav_res = torch.zeros(S, self.input_wav_res_len, device=self.device, dtype=f32)
-        self.rms_buffer = np.zeros((S, 4 * self.zc), dtype="float32")
+        self.device_gate = _device_gate(device_gate, BANK_DEVICE_GATE)
+        # the input gate's 4 zc samples of history per session: host rows with the host gate, a device tensor with the device gate
+        self.rms_buffer = torch.zeros(S, 4 * self.zc, device=self.device, dtype=f32) if self.device_gate else np.zeros((S, 4 * self.zc), dtype="float32")
+        self._gate_scratch = None
         self.sola_buffer = torch.zeros(S, self.sola_buffer_frame, device=self.device, dtype=f32)
         fade_in = torch.sin(0.5 * np.pi * torch.linspace(0.0, 1.0, steps=self.sola_buffer_frame, dtype=torch.float32)) ** 2   # gui.py:841-855
         self.fade_in_window = fade_in.to(self.device)
@@ -865,7 +949,7 @@ class RealtimeBank:
         for g in (self.gate_I, self.gate_O):
             if g is not None:
                 g.invalidate(i)
-        self.rms_buffer[i] = 0
+        self.rms_buffer[i] = 0   # (a host row or a device row)
         if self.vc is not None:
             self.vc.reset(i)
 
@@ -886,12 +970,19 @@ class RealtimeBank:
         x = np.asarray(blocks, dtype=np.float32)
         if x.ndim != 2 or x.shape != (self.S, self.block_frame):
             raise ValueError("a bank block is [%d, %d] (sessions, samples), got %s" % (self.S, self.block_frame, x.shape))
-        if self.threhold > -60:   # the input gate stays on the host, per session (gui.py:950-963)
-            x = np.stack([input_gate(x[s], self.rms_buffer[s], self.zc, self.threhold) for s in range(self.S)])
-        m = int(x.shape[1])
         blk, blk16, zc = self.block_frame, self.block_frame_16k, self.zc
+        on_device = self.threhold > -60 and self.device_gate
+        if self.threhold > -60 and not on_device:   # the host gate, per session (gui.py:950-963)
+            x = np.stack([input_gate(x[s], self.rms_buffer[s], self.zc, self.threhold) for s in range(self.S)])
+        m = blk + 2 * zc if on_device else int(x.shape[1])
         self.input_wav[:, :-blk] = self.input_wav[:, blk:].clone()
-        self.input_wav[:, -m:] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)   # the block's one host-to-device copy
+        xd = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)                       # the block's one host-to-device copy
+        if on_device:   # the raw block went up; the gate of all sessions writes the gated blk + 2 zc samples (three launches whatever S)
+            if self._gate_scratch is None:
+                self._gate_scratch = torch.empty(self.S * glue.input_gate_scratch_floats(zc, blk), device=self.device, dtype=torch.float32)
+            glue.input_gate_batch(xd, self.rms_buffer, self.input_wav[:, -m:], zc, *input_gate_cutoffs(self.threhold), scratch=self._gate_scratch)
+        else:
+            self.input_wav[:, -m:] = xd
         self.input_wav_res[:, :-blk16] = self.input_wav_res[:, blk16:].clone()
         Lb = self.sola_buffer_frame
         any_I, any_O = any(self.I_noise_reduce), any(self.O_noise_reduce)

@@ -223,8 +223,9 @@ class RMVPEHIP:
         return xs
 
     def _salience_ragged(self, xs: List[torch.Tensor], mark=None) -> Tuple[torch.Tensor, List[int], List[int]]:
-        """-> (packed salience [R, 360] fp32, row offsets, frame counts).  Mel per sequence into its own rows (its own reflection pad, its own
-        zero pad frames), then ONE ragged U-Net, ONE ragged GRU and ONE head launch over the R packed rows.  ``mark(stage)``: called after each
+        """-> (packed salience [R, 360] fp32, row offsets, frame counts).  Mel of every sequence into its own rows (its own reflection pad,
+        its own zero pad frames): ONE batched launch when all sequences have the same sample count -- one sequence included, so that a bank
+        of one session issues the launches a larger bank issues -- else one launch per sequence; then ONE ragged U-Net, ONE ragged GRU and ONE head launch over the R packed rows.  ``mark(stage)``: called after each
         stage has been enqueued (tools/rmvpe_batch_time.py puts a synchronising clock there)."""
         mark = mark or (lambda stage: None)
         L = _lib.lib()
@@ -246,9 +247,16 @@ class RMVPEHIP:
             y = torch.empty(R, 2 * self.gru.hidden_size, device=dev, dtype=f32)
             sal = torch.empty(R, N_CLASS, device=dev, dtype=f32)
             st, half = _lib.stream_ptr(self.device), 1 if self.is_half else 0
-            for i, x in enumerate(xs):
-                _lib.check(L.rvcmi_mel_forward(self._h, 1, int(x.shape[1]), _lib.ptr(x), half, off[i + 1] - off[i],
-                                               C.c_void_p(mel.data_ptr() + 4 * N_MELS * off[i]), st))
+            if len({int(x.shape[1]) for x in xs}) == 1:
+                # equal lengths (a bank's f0 windows): every sequence has the same T_pad, so the packed rows ARE the dense
+                # [B, T_pad, 128] layout of one batched call (k_rmvpe_logmel writes out[b][t][m] and tiles the frames per b from 0).
+                # The stacked copy is a temporary: freeing it when this statement ends is safe only because `st` is torch's current
+                # stream, the one its caching allocator orders the block's reuse on.
+                _lib.check(L.rvcmi_mel_forward(self._h, nseq, int(xs[0].shape[1]), _lib.ptr(torch.cat(xs)), half, off[1] - off[0], _lib.ptr(mel), st))
+            else:
+                for i, x in enumerate(xs):
+                    _lib.check(L.rvcmi_mel_forward(self._h, 1, int(x.shape[1]), _lib.ptr(x), half, off[i + 1] - off[i],
+                                                   C.c_void_p(mel.data_ptr() + 4 * N_MELS * off[i]), st))
             mark("mel")
             _lib.check(L.rvcmi_unet_forward_ragged(self.unet._h, nseq, off_host, _lib.ptr(off_dev), _lib.ptr(mel), _lib.ptr(feat), _lib.ptr(ws), st))
             mark("unet")
@@ -261,17 +269,23 @@ class RMVPEHIP:
 
     def salience_batch(self, wavs) -> List[torch.Tensor]:
         """A list of 1-D waveforms of ANY lengths -> their saliences ``[T_i, 360]`` fp32 from ONE pass over the packed batch; each is what
-        ``salience`` of that waveform alone returns, to the summation order of the U-Net layers that split their K loop by launch size."""
+        ``salience`` of that waveform alone returns, to the summation order of the U-Net layers that split their K loop by launch size.
+        The results are VIEWS of one packed tensor that belongs to this call alone (no copy per sequence: the launch count does not depend
+        on the number of waveforms); ``.clone()`` one to keep it without the rest of the batch, or before writing into it."""
         sal, off, frames = self._salience_ragged(self._wavs(wavs))
-        return [sal[o: o + t].clone() for o, t in zip(off, frames)]
+        return [sal[o: o + t] for o, t in zip(off, frames)]   # views of the call's own packed tensor: no copy per sequence
 
     def f0_batch(self, wavs, p_lens, f0_up_key=0, thred: float = 0.03) -> List[Tuple[torch.Tensor, torch.Tensor]]:
-        """-> per waveform (pitch int64 [1, p_len_i], pitchf float32 [1, p_len_i]): ``glue.rmvpe_f0`` of its rows of ``salience_batch``."""
+        """-> per waveform (pitch int64 [1, p_len_i], pitchf float32 [1, p_len_i]): ``glue.rmvpe_f0`` of its rows of ``salience_batch``, for
+        all waveforms in ONE ``glue.rmvpe_f0_ragged`` call on the packed salience (two launches).  ``f0_up_key``: one key, or one per waveform."""
         xs = self._wavs(wavs)
         if not isinstance(p_lens, (list, tuple)) or len(p_lens) != len(xs) or any(int(p) < 1 for p in p_lens):
             raise _lib.RvcmiError("RMVPEHIP.f0_batch: one positive p_len per waveform", code=_lib.ERR_INVALID)
+        keys = list(f0_up_key) if isinstance(f0_up_key, (list, tuple)) else [f0_up_key] * len(xs)
+        if len(keys) != len(xs):
+            raise _lib.RvcmiError("RMVPEHIP.f0_batch: one key, or one per waveform (%d keys for %d waveforms)" % (len(keys), len(xs)), code=_lib.ERR_INVALID)
         sal, off, frames = self._salience_ragged(xs)
-        return [glue.rmvpe_f0(sal[o: o + t], int(p), f0_up_key, thred) for o, t, p in zip(off, frames, p_lens)]
+        return glue.rmvpe_f0_ragged(sal, [(o, t, int(p), k) for o, t, p, k in zip(off, frames, p_lens, keys)], thred)
 
     def f0(self, wav: torch.Tensor, p_len: int, f0_up_key=0, thred: float = 0.03) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (pitch int64 [1, p_len], pitchf float32 [1, p_len]) as ``glue.rmvpe_f0`` returns them; ``f0_up_key`` may be fractional."""
