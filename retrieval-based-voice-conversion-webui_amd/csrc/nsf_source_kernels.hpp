@@ -18,8 +18,11 @@ namespace rvcmi {
 
 // phase[b][t] = fmod(float(sum_{tau<t} w_tau), 1), w_tau = fmod(f0/sr*upp + 0.5, 1) - 0.5.
 // torch's CPU cumsum accumulates fp32 inputs in DOUBLE and rounds each prefix to fp32
-// (verified against torch 2.10); a wave-level scan in fp64 reproduces that to the last bit except
-// on exact rounding boundaries.  One block of 256 threads per utterance (the frames' slow fmod / divide chain is spread
+// (verified against torch 2.10); a wave-level scan in fp64 reproduces that to the last bit, unconditionally:
+// every w is a multiple of 2^-25 (rad + 0.5 >= 0.5 has an ulp of 2^-24 or more, fmodf and the subtraction are exact),
+// so every partial sum is an exact fp64 number in any order and the one rounding to fp32 is the same everywhere
+// (tests/test_cpu_source.py holds this partition, torch's cumsum and exact integer prefix sums against each other bit for
+// bit).  One block of 256 threads per utterance (the frames' slow fmod / divide chain is spread
 // over 4 waves: 15 -> ~5 us for a 10 s clip; the block-level scan goes through LDS).
 static __global__ void __launch_bounds__(256) k_phase_scan(const float* __restrict__ f0, float* __restrict__ phase,
                                                    int T, float sr, float upp, const int* __restrict__ lens) {
