@@ -359,6 +359,33 @@ int rvcmi_ivf_search_blend_expand_batch(rvcmi_ivf* h, int S, int64_t nq, int64_t
                                         float index_rate, int k, int skip_if_short, const float* pitchf_dev, float protect,
                                         int64_t p_len, float* out_dev, void* stream);
 
+/* rvcmi_ivf_search_blend_expand_batch with the four retrieval controls PER SESSION (the GUI's index_rate slider and RVC.infer's protect,
+ * gui.py:676-679, rtrvc.py:167-185, 221-233).  Session s is described by sess[s]:
+ *   index_rate   its blend weight;   slot   >= 0: the session is searched and blended, and this is its position among the sessions
+ *   that are (they count up from 0 in session order); -1: it is not -- its rows are expanded un-blended, the BITS of its input rows
+ *   (never acc * 0 + 1 * f: a -0.0 stays -0.0, and nothing of the index reaches it);   protect / protect_on   the protect mix of the
+ *   session, applied iff protect_on (then pitchf_dev must not be NULL); protect_on == 0 gives o = x, as a NULL pitchf_dev does.
+ * Only the sessions with a slot contribute rows to the ONE search: their rows [skip_rows, nq) are packed by slot, the realtime guard
+ * (skip_if_short) is reduced per packed slot, and the blend maps session -> slot.  With no such session nothing is searched.  Row s of
+ * out_dev equals rvcmi_ivf_search_blend_expand_batch at S = 1 on session s's rows with its values (or rvcmi_glue_expand_protect_batch
+ * for a session without a slot) bit for bit: the same device bodies.  The launch count depends on neither S nor on which sessions
+ * blend.  h may be NULL -- a bank without an index that has a protect per session: then every slot must be -1, and d is the feature
+ * width; with a handle d must be the index's.  The values are given twice, as rvcmi_glue_rmvpe_f0_ragged takes its rows: sess_host is
+ * checked (and the search planned from it) before anything is launched, sess_dev -- the same bytes in device memory -- is what the
+ * kernels read.  Enqueue-only: no allocation beyond the handle's grow-on-demand buffers, no synchronisation, no device memory read by
+ * the host.  RVCMI_ERR_INVALID, nothing launched: S outside [1, 65535], nq < 1, skip_rows outside [0, nq], p_len outside [0, 2 nq], a
+ * value that is not finite, slots that do not count up, a slot without a handle, protect_on without pitchf_dev, d != the index's.
+ * The `ivf_blend_x2` profile record carries flops = 2 * rows * k * d with rows = the rows actually searched.                          */
+typedef struct {
+    float index_rate;    /* the session's blend weight                                            */
+    float protect;       /* the session's protect (used iff protect_on)                           */
+    int32_t slot;        /* packed position among the blending sessions, or -1                    */
+    int32_t protect_on;  /* 0 / 1: the protect mix applies                                        */
+} rvcmi_session_blend;
+int rvcmi_ivf_search_blend_expand_sessions(rvcmi_ivf* h, int S, int64_t nq, int d, int64_t skip_rows, const float* feats_dev,
+                                           const rvcmi_session_blend* sess_host, const rvcmi_session_blend* sess_dev, int k,
+                                           int skip_if_short, const float* pitchf_dev, int64_t p_len, float* out_dev, void* stream);
+
 /* index.reconstruct_n(i0, n) -> out_host [n,d] rows in id order (pipeline.py:215).             */
 int rvcmi_ivf_reconstruct_n(const rvcmi_ivf* h, int64_t i0, int64_t n, float* out_host);
 
@@ -676,6 +703,39 @@ size_t rvcmi_glue_input_gate_scratch_floats(int zc, int blk);
 int rvcmi_glue_input_gate_batch(int S, const float* block_dev, int64_t block_stride, float* rms_buffer_dev, int64_t rms_stride,
                                 float* dst_dev, int64_t dst_stride, int zc, int blk, float cut_a, float cut_b, float* scratch_dev,
                                 void* stream);
+
+/* rvcmi_glue_envelope_mix_batch and rvcmi_glue_input_gate_batch with their control PER SESSION (the GUI's rms_mix_rate and threhold sliders, gui.py:1024-1056, 950-963), for a
+ * bank whose talkers move them independently.  The values are given twice, as rvcmi_glue_rmvpe_f0_ragged takes its rows: sess_host is
+ * checked before anything is launched, sess_dev (the same bytes in device memory) is what the kernels read.  The kernels call the
+ * device bodies of the _batch kernels, so an active session's arithmetic is the same instructions in the same order; the blocks of
+ * an inactive session leave on a branch that is uniform per block.  Enqueue-only, no allocation; the launch count (three) depends on
+ * neither S nor on which sessions are active (with none active: rvcmi_glue_envelope_mix_sessions launches nothing,
+ * rvcmi_glue_input_gate_sessions its last kernel alone).  RVCMI_ERR_INVALID, nothing launched: S outside [1, 65535], an `on` that is
+ * not 0 / 1, an exponent that is not finite, a cutoff that is negative or NaN, a row stride shorter than its row, and what the
+ * _batch calls refuse.
+ *
+ * rvcmi_glue_envelope_mix_sessions: session s is mixed with the exponent sess[s].exponent = float32(1 - rate), computed on the host in
+ * double and rounded once (as rvcmi_glue_envelope_mix_batch does with its scalar), iff sess[s].on; the wav row and the scratch of a
+ * session that is off are not written.
+ *
+ * rvcmi_glue_input_gate_sessions: session s is gated with its own cutoffs iff sess[s].on.  A session that is off (threhold <= -60)
+ * ends as the stream that does not call the gate: the last blk samples of its dst row are the raw block, the 2 zc samples in front of
+ * them and its rms_buffer row are not touched (the reference leaves the buffer stale while the slider is at or below -60).          */
+typedef struct {
+    float exponent;  /* float32(1 - rms_mix_rate) */
+    int32_t on;      /* 0 / 1                     */
+} rvcmi_session_mix;
+typedef struct {
+    float cut_a, cut_b;  /* rvc_amd.realtime.input_gate_cutoffs(the session's threhold) */
+    int32_t on;          /* 0 / 1                                                       */
+    int32_t reserved_;   /* 0                                                           */
+} rvcmi_session_gate;
+int rvcmi_glue_envelope_mix_sessions(int S, const float* input_dev, int64_t in_stride, float* wav_dev, int64_t wav_stride, int64_t n,
+                                     int zc, const rvcmi_session_mix* sess_host, const rvcmi_session_mix* sess_dev, float* scratch_dev,
+                                     void* stream);
+int rvcmi_glue_input_gate_sessions(int S, const float* block_dev, int64_t block_stride, float* rms_buffer_dev, int64_t rms_stride,
+                                   float* dst_dev, int64_t dst_stride, int zc, int blk, const rvcmi_session_gate* sess_host,
+                                   const rvcmi_session_gate* sess_dev, float* scratch_dev, void* stream);
 
 /* ---- beyond SURVEY.md section 8: the recurrent layer of the RMVPE f0 network -----------------------------------------------
  * Stands in for the `nn.GRU(384, 256, num_layers=1, batch_first=True, bidirectional=True)` of rvc/f0/e2e.py:50-67 (E2E.BiGRU, the

@@ -21,12 +21,12 @@ from .synthesizer import accelerate_synthesizer, get_synthesizer, load_synthesiz
 from . import dist
 from .install import install, uninstall
 from .gate import TorchGateBank, TorchGateHIP
-from .realtime import PitchCache, RealtimeBank, RealtimeStream, RealtimeVC, RealtimeVCBatch, SincResample, SincResampleRagged, f0_extractor_frame, formant_geometry, sinc_resample_kernel, stream_geometry
+from .realtime import PitchCache, RealtimeBank, RealtimeStream, RealtimeVC, RealtimeVCBatch, SessionSliders, SincResample, SincResampleRagged, f0_extractor_frame, formant_geometry, sinc_resample_kernel, stream_geometry
 
 __all__ = [
     "RvcmiError", "build", "IVFFlatHIP", "read_index", "write_index", "train_index", "reduce_features", "kmeans", "index_factory", "extract_index_ivf", "GeneratorHIP", "NSFGeneratorHIP",
     "config_from_reference", "FrontHIP", "front_config_from_reference", "infer_hip", "retrieve_blend", "accelerate_synthesizer", "get_synthesizer", "load_synthesizer", "dist", "glue", "install", "uninstall", "RealtimeVC", "PitchCache", "f0_extractor_frame", "SincResample", "SincResampleRagged", "formant_geometry", "sinc_resample_kernel", "GRUHIP", "accelerate_rmvpe",
     "UNetHIP", "accelerate_rmvpe_unet", "restore_rmvpe_unet", "RMVPEHIP", "HubertFrontHIP", "accelerate_hubert", "restore_hubert", "hubert_on", "hubert_batch_on", "batch_capable", "extract_features_batch",
     "frame_mask", "sample_mask", "plan_groups", "HubertEncoderHIP", "HubertLayerHIP", "accelerate_hubert_layers", "restore_hubert_layers", "supported_layer", "hubert_enc_on",
-    "RealtimeStream", "RealtimeBank", "RealtimeVCBatch", "stream_geometry", "TorchGateHIP", "TorchGateBank", "cut_points", "cut_count", "filtfilt", "highpass16k",
+    "RealtimeStream", "RealtimeBank", "RealtimeVCBatch", "SessionSliders", "stream_geometry", "TorchGateHIP", "TorchGateBank", "cut_points", "cut_count", "filtfilt", "highpass16k",
 ]

@@ -60,6 +60,21 @@ class F0Row(C.Structure):
     _fields_ = [("out_off", C.c_int64), ("key_mul", C.c_double), ("first_row", C.c_int), ("n", C.c_int), ("p_len", C.c_int), ("reserved_", C.c_int)]
 
 
+class SessionBlend(C.Structure):
+    """rvcmi_session_blend: one session's retrieval controls of rvcmi_ivf_search_blend_expand_sessions."""
+    _fields_ = [("index_rate", C.c_float), ("protect", C.c_float), ("slot", C.c_int32), ("protect_on", C.c_int32)]
+
+
+class SessionMix(C.Structure):
+    """rvcmi_session_mix: one session's envelope-mix exponent of rvcmi_glue_envelope_mix_sessions."""
+    _fields_ = [("exponent", C.c_float), ("on", C.c_int32)]
+
+
+class SessionGate(C.Structure):
+    """rvcmi_session_gate: one session's cutoffs of rvcmi_glue_input_gate_sessions."""
+    _fields_ = [("cut_a", C.c_float), ("cut_b", C.c_float), ("on", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -119,6 +134,8 @@ SYMBOLS = [
     ("rvcmi_ivf_search_blend_expand", C.c_int, [_P, C.c_int64, _P, C.c_float, C.c_int, C.c_int, _P, C.c_float, C.c_int64, _P, _P]),
     ("rvcmi_ivf_search_blend_expand_batch", C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_float, C.c_int, C.c_int, _P, C.c_float,
                                                       C.c_int64, _P, _P]),
+    ("rvcmi_ivf_search_blend_expand_sessions", C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int64,
+                                                         _P, _P]),
     ("rvcmi_ivf_reconstruct_n", C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     ("rvcmi_ivf_blob", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     ("rvcmi_ivf_centroids", C.c_int, [_P, _P]),
@@ -136,6 +153,8 @@ SYMBOLS = [
     ("rvcmi_glue_rmvpe_f0_ragged", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, C.c_int64, _P]),
     ("rvcmi_glue_input_gate_scratch_floats", C.c_size_t, [C.c_int, C.c_int]),
     ("rvcmi_glue_input_gate_batch", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
+    ("rvcmi_glue_input_gate_sessions", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
+    ("rvcmi_glue_envelope_mix_sessions", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P]),
     ("rvcmi_glue_change_rms", C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
     ("rvcmi_glue_scale_int16_range", C.c_int, [_P, C.c_int64, _P, _P]),
     ("rvcmi_glue_resample_poly", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),

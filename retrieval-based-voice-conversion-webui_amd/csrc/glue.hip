@@ -9,6 +9,7 @@
 #include "gate_kernels.hpp"
 #include "gate_ring.hpp"
 #include "glue_kernels.hpp"
+#include "session_rows.hpp"
 
 using namespace rvcmi;
 
@@ -641,6 +642,63 @@ int rvcmi_glue_input_gate_batch(int S, const float* block, int64_t block_stride,
                            4 * zc, zc, nfr, rms, (int64_t)per);
         hipLaunchKernelGGL(k_input_gate_batch, dim3((unsigned)((nout + 255) / 256), (unsigned)S), dim3(256), 0, st, (const float*)scratch, (int64_t)per,
                            (const float*)rms, (int64_t)per, zc, blk, cut_a, cut_b, dst, dst_stride, rms_buffer, rms_stride);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// envelope_mix_rows with the exponent and an on / off flag per session (session_rows.hpp checks the host copy; the kernels read the device
+// copy).  The same scratch layout; a session that is off has neither its wav row nor its scratch written.
+int rvcmi_glue_envelope_mix_sessions(int S, const float* input, int64_t in_stride, float* wav, int64_t wav_stride, int64_t n, int zc,
+                                     const rvcmi_session_mix* sess_host, const rvcmi_session_mix* sess_dev, float* scratch, void* stream) {
+    return guarded([&] {
+        const char* who = "envelope_mix_sessions";
+        int active = 0;
+        if (const char* why = session_mix_check(sess_host, S, &active)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: %s", who, why);
+        if (!input || !wav || !scratch || !sess_dev || n < 1 || zc < 1) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: bad argument", who);
+        if (in_stride < n || wav_stride < n)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: row stride %lld / %lld shorter than the row %lld", who, (long long)in_stride, (long long)wav_stride,
+                       (long long)n);
+        const int64_t nf64 = 1 + n / zc;
+        if (nf64 > (1 << 30)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: too many frames", who);
+        if (!active) return;
+        const int nf = (int)nf64;
+        hipStream_t st = (hipStream_t)stream;
+        hipLaunchKernelGGL(k_frame_rms_sessions<rvcmi_session_mix>, dim3(nf, (unsigned)S), dim3(256), 0, st, input, in_stride, n, 4 * zc, zc, nf,
+                           scratch, (int64_t)2 * nf, sess_dev);
+        hipLaunchKernelGGL(k_frame_rms_sessions<rvcmi_session_mix>, dim3(nf, (unsigned)S), dim3(256), 0, st, (const float*)wav, wav_stride, n, 4 * zc,
+                           zc, nf, scratch + nf, (int64_t)2 * nf, sess_dev);
+        hipLaunchKernelGGL(k_envelope_mix_sessions, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, st, wav, wav_stride, n,
+                           (const float*)scratch, nf, sess_dev);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// rvcmi_glue_input_gate_batch with the cutoffs and an on / off flag per session; the same scratch layout per session.
+int rvcmi_glue_input_gate_sessions(int S, const float* block, int64_t block_stride, float* rms_buffer, int64_t rms_stride, float* dst,
+                                   int64_t dst_stride, int zc, int blk, const rvcmi_session_gate* sess_host, const rvcmi_session_gate* sess_dev,
+                                   float* scratch, void* stream) {
+    return guarded([&] {
+        const char* who = "input_gate_sessions";
+        int active = 0;
+        if (const char* why = session_gate_check(sess_host, S, &active)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: %s", who, why);
+        if (!block || !rms_buffer || !dst || !scratch || !sess_dev) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: null pointer", who);
+        const size_t per = rvcmi_glue_input_gate_scratch_floats(zc, blk);
+        if (!per) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a block of %d samples must be a whole number (>= 1) of hops of zc = %d >= 1 samples", who, blk, zc);
+        if (block_stride < blk || rms_stride < 4 * (int64_t)zc || dst_stride < (int64_t)blk + 2 * zc)
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: a row stride (%lld, %lld, %lld) is shorter than its row (%d, %d, %d)", who, (long long)block_stride,
+                       (long long)rms_stride, (long long)dst_stride, blk, 4 * zc, blk + 2 * zc);
+        const int nx = 4 * zc + blk, nfr = blk / zc + 5, nout = std::max(blk + 2 * zc, 4 * zc);
+        float* rms = scratch + nx;
+        hipStream_t st = (hipStream_t)stream;
+        if (active) {
+            hipLaunchKernelGGL(k_gate_stage_sessions, dim3((unsigned)((nx + 255) / 256), (unsigned)S), dim3(256), 0, st, block, block_stride,
+                               (const float*)rms_buffer, rms_stride, zc, blk, scratch, (int64_t)per, sess_dev);
+            hipLaunchKernelGGL(k_frame_rms_sessions<rvcmi_session_gate>, dim3((unsigned)nfr, (unsigned)S), dim3(256), 0, st, (const float*)scratch,
+                               (int64_t)per, (int64_t)nx, 4 * zc, zc, nfr, rms, (int64_t)per, sess_dev);
+        }
+        hipLaunchKernelGGL(k_input_gate_sessions, dim3((unsigned)((nout + 255) / 256), (unsigned)S), dim3(256), 0, st, (const float*)scratch,
+                           (int64_t)per, (const float*)rms, (int64_t)per, zc, blk, sess_dev, block, block_stride, dst, dst_stride, rms_buffer,
+                           rms_stride);
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -113,6 +113,42 @@ static __global__ void __launch_bounds__(256) k_blend_expand_batch(const float* 
                      pitchf ? pitchf + s * p_len : nullptr, protect, p_len, reps, out + s * p_len * d, qi);
 }
 
+// ---- the same three steps with the retrieval controls per session (rvcmi_ivf_search_blend_expand_sessions): sess [S] on the device; a
+// session with slot in [0, active) is searched and blended, its rows packed at that slot; any other leaves on a branch that is uniform
+// per block (the session is blockIdx.y).  `active` is the host's count: a device copy that disagrees cannot take a block out of the
+// packed buffers.
+static __global__ void __launch_bounds__(256) k_gather_session_rows(const float* __restrict__ feats, int64_t nq, int64_t skip, int d,
+                                                                    const rvcmi_session_blend* __restrict__ sess, int active,
+                                                                    float* __restrict__ q) {
+    const int64_t m = nq - skip;
+    const int64_t r = blockIdx.x, s = blockIdx.y;
+    const int slot = sess[s].slot;
+    if (slot < 0 || slot >= active) return;
+    const float* src = feats + (s * nq + skip + r) * d;
+    float* dst = q + ((int64_t)slot * m + r) * d;
+    for (int e = threadIdx.x; e < d; e += 256) dst[e] = src[e];
+}
+
+// blend_expand_row per session with the session's own rate and protect: grid (nq, S).  flags [active]: k_session_short over the packed
+// slots.  A session without a slot (or with P == nullptr: nothing was searched) is expanded un-blended: x = f, the bits of the input.
+// pitchf [S, p_len] or nullptr; a session whose protect_on is 0 gets o = x, as a null pitchf gives.  omr is the double difference rounded
+// once, as the host computes it for the scalar entry.
+static __global__ void __launch_bounds__(256) k_blend_expand_sessions(const float* __restrict__ feats, const float* __restrict__ D,
+                                                                      const int64_t* __restrict__ P, const float* __restrict__ vecs, int d,
+                                                                      int k, int64_t pos_last, const rvcmi_session_blend* __restrict__ sess,
+                                                                      int active, const int* __restrict__ flags, int skip_if_short,
+                                                                      int64_t nq, int64_t skip, const float* __restrict__ pitchf,
+                                                                      int64_t p_len, int reps, float* __restrict__ out) {
+    const int64_t qi = blockIdx.x, s = blockIdx.y;
+    const rvcmi_session_blend c = sess[s];
+    const bool has_slot = P != nullptr && c.slot >= 0 && c.slot < active;
+    const bool blend = has_slot && qi >= skip && !(skip_if_short && flags[c.slot]);
+    const int64_t ri = blend ? (int64_t)c.slot * (nq - skip) + (qi - skip) : 0;
+    const float omr = (float)(1.0 - (double)c.index_rate);
+    blend_expand_row(feats + s * nq * d, blend ? D + ri * k : nullptr, blend ? P + ri * k : nullptr, vecs, d, k, pos_last, c.index_rate, omr,
+                     blend, (pitchf && c.protect_on) ? pitchf + s * p_len : nullptr, c.protect, p_len, reps, out + s * p_len * d, qi);
+}
+
 // RMVPE._to_local_average_cents + _decode (rmvpe.py:119-164): one wave per frame.
 //   center = argmax(salience[f]) (first maximum); 9-bin window, zero-padded salience AND zero-padded cents table;
 //   cents = sum(sal*cm) / sum(sal)   product in float64, weight sum in float32 (numpy's pairwise order for n = 9);
@@ -641,6 +677,29 @@ static __global__ void __launch_bounds__(256) k_frame_rms_batch(const float* __r
     frame_rms_block(y + s * y_stride, n, frame, hop, nframes, rms + s * rms_stride, red, blockIdx.x);
 }
 
+// The same for the sessions that are on (Sess: rvcmi_session_mix or rvcmi_session_gate, on the device); the blocks of the others leave
+// before the body, uniformly per block, and write nothing.
+template <typename Sess>
+static __global__ void __launch_bounds__(256) k_frame_rms_sessions(const float* __restrict__ y, int64_t y_stride, int64_t n, int frame, int hop,
+                                                                   int nframes, float* __restrict__ rms, int64_t rms_stride,
+                                                                   const Sess* __restrict__ sess) {
+    __shared__ double red[256];
+    const int64_t s = blockIdx.y;
+    if (!sess[s].on) return;
+    frame_rms_block(y + s * y_stride, n, frame, hop, nframes, rms + s * rms_stride, red, blockIdx.x);
+}
+
+// k_envelope_mix_batch with the exponent per session; a session that is off keeps its row.
+static __global__ void __launch_bounds__(256) k_envelope_mix_sessions(float* __restrict__ wav, int64_t wav_stride, int64_t n,
+                                                                      const float* __restrict__ rms, int nf,
+                                                                      const rvcmi_session_mix* __restrict__ sess) {
+    const int64_t s = blockIdx.y;
+    const rvcmi_session_mix c = sess[s];
+    if (!c.on) return;
+    const float* r = rms + s * 2 * nf;
+    envelope_mix_at(wav + s * wav_stride, n, r, r + nf, nf, c.exponent, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
 __device__ __forceinline__ float interp_linear_1d(const float* __restrict__ r, int nin, int64_t nout, int64_t o) {
     // F.interpolate(mode="linear", align_corners=False): src = scale*(o+0.5)-0.5 clamped at 0, scale = nin/nout (fp32)
     const float scale = (float)nin / (float)nout;
@@ -681,17 +740,12 @@ static __global__ void __launch_bounds__(256) k_gate_stage_batch(const float* __
     x[s * x_stride + i] = i < 4 * zc ? rbuf[s * rbuf_stride + i] : block[s * block_stride + (i - 4 * zc)];
 }
 
-// rms: the session's blk / zc + 5 frames as k_frame_rms_batch wrote them (rms_stride floats apart); the gate's frame i is rms[2 + i].
-static __global__ void __launch_bounds__(256) k_input_gate_batch(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ rms,
-                                                                 int64_t rms_stride, int zc, int blk, float cut_a, float cut_b,
-                                                                 float* __restrict__ dst, int64_t dst_stride, float* __restrict__ rbuf,
-                                                                 int64_t rbuf_stride) {
-    __shared__ float red[256];
-    __shared__ int has_nan;
-    const int64_t s = blockIdx.y;
-    const float* r = rms + s * rms_stride + 2;
+// The gate of ONE session (the body of k_input_gate_batch and k_input_gate_sessions; every thread of the block calls it): xs its staged x,
+// r its gate frames (the frame RMS from frame 2 on), dst / rbuf its rows; red [256] and has_nan in LDS.
+__device__ __forceinline__ void input_gate_block(const float* __restrict__ xs, const float* __restrict__ r, int zc, int blk, float cut_a,
+                                                 float cut_b, float* __restrict__ dst, float* __restrict__ rbuf, float* red, int* has_nan) {
     const int nf = blk / zc + 3;
-    if (threadIdx.x == 0) has_nan = 0;
+    if (threadIdx.x == 0) *has_nan = 0;
     __syncthreads();
     float m = 0.f;  // an RMS is never negative
     int nan = 0;
@@ -701,20 +755,64 @@ static __global__ void __launch_bounds__(256) k_input_gate_batch(const float* __
         m = fmaxf(m, v);
     }
     red[threadIdx.x] = m;
-    if (nan) atomicOr(&has_nan, 1);
+    if (nan) atomicOr(has_nan, 1);
     __syncthreads();
     for (int s2 = 128; s2 >= 1; s2 >>= 1) {
         if ((int)threadIdx.x < s2) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
         __syncthreads();
     }
-    const bool may = !has_nan && red[0] < cut_b;
-    const float* xs = x + s * x_stride;
+    const bool may = !*has_nan && red[0] < cut_b;
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < blk + 2 * zc) {
         const bool quiet = may && r[(j + zc / 2) / zc] < cut_a;
-        dst[s * dst_stride + j] = quiet ? 0.f : xs[2 * zc + j];
+        dst[j] = quiet ? 0.f : xs[2 * zc + j];
     }
-    if (j < 4 * zc) rbuf[s * rbuf_stride + j] = xs[blk + j];
+    if (j < 4 * zc) rbuf[j] = xs[blk + j];
+}
+
+// rms: the session's blk / zc + 5 frames as k_frame_rms_batch wrote them (rms_stride floats apart); the gate's frame i is rms[2 + i].
+static __global__ void __launch_bounds__(256) k_input_gate_batch(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ rms,
+                                                                 int64_t rms_stride, int zc, int blk, float cut_a, float cut_b,
+                                                                 float* __restrict__ dst, int64_t dst_stride, float* __restrict__ rbuf,
+                                                                 int64_t rbuf_stride) {
+    __shared__ float red[256];
+    __shared__ int has_nan;
+    const int64_t s = blockIdx.y;
+    input_gate_block(x + s * x_stride, rms + s * rms_stride + 2, zc, blk, cut_a, cut_b, dst + s * dst_stride, rbuf + s * rbuf_stride, red,
+                     &has_nan);
+}
+
+// The stage and the gate with the cutoffs per session (rvcmi_glue_input_gate_sessions).  A session that is off is not staged; the gate
+// kernel copies its raw block to the last blk samples of its dst row and touches neither the 2 zc samples in front nor its rms_buffer row
+// (the stream that does not call the gate).  Both branches are uniform per block.
+static __global__ void __launch_bounds__(256) k_gate_stage_sessions(const float* __restrict__ block, int64_t block_stride,
+                                                                    const float* __restrict__ rbuf, int64_t rbuf_stride, int zc, int blk,
+                                                                    float* __restrict__ x, int64_t x_stride,
+                                                                    const rvcmi_session_gate* __restrict__ sess) {
+    const int64_t s = blockIdx.y;
+    if (!sess[s].on) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 4 * zc + blk) return;
+    x[s * x_stride + i] = i < 4 * zc ? rbuf[s * rbuf_stride + i] : block[s * block_stride + (i - 4 * zc)];
+}
+
+static __global__ void __launch_bounds__(256) k_input_gate_sessions(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ rms,
+                                                                    int64_t rms_stride, int zc, int blk,
+                                                                    const rvcmi_session_gate* __restrict__ sess,
+                                                                    const float* __restrict__ block, int64_t block_stride,
+                                                                    float* __restrict__ dst, int64_t dst_stride, float* __restrict__ rbuf,
+                                                                    int64_t rbuf_stride) {
+    __shared__ float red[256];
+    __shared__ int has_nan;
+    const int64_t s = blockIdx.y;
+    const rvcmi_session_gate c = sess[s];
+    if (!c.on) {
+        const int j = blockIdx.x * 256 + threadIdx.x;
+        if (j < blk) dst[s * dst_stride + 2 * zc + j] = block[s * block_stride + j];
+        return;
+    }
+    input_gate_block(x + s * x_stride, rms + s * rms_stride + 2, zc, blk, c.cut_a, c.cut_b, dst + s * dst_stride, rbuf + s * rbuf_stride, red,
+                     &has_nan);
 }
 
 // Polyphase FIR resampling as torchaudio.transforms.Resample applies it (rtrvc.py:248-259: the formant-shifted block comes out

@@ -27,6 +27,7 @@
 #include "ivf_kernels.hpp"
 #include "ivf_lm_kernels.hpp"
 #include "ivf_add_kernels.hpp"
+#include "session_rows.hpp"
 
 using namespace rvcmi;
 
@@ -693,6 +694,56 @@ int rvcmi_ivf_search_blend_expand_batch(rvcmi_ivf* h, int S, int64_t nq, int64_t
             hipLaunchKernelGGL(k_blend_expand_batch, dim3((unsigned)nq, (unsigned)S), dim3(256), 0, st, feats, (const float*)h->Dtmp.as<float>(),
                                rows > 0 ? (const int64_t*)h->P.as<int64_t>() : nullptr, h->vecs(), d, k, h->hdr.pos_last, rate, omr,
                                (const int*)h->bank_flags.as<int>(), skip_if_short, nq, skip_rows, pitchf, protect, p_len, 2, out);
+        });
+        HIP_CHECK(hipGetLastError());
+    });
+}
+// The batch entry with the controls per session: only the sessions with a slot are gathered (packed by slot) and searched; the guard is
+// reduced per slot; the blend maps session -> slot.  Without a handle (no index): the expansion and the per-session protect mix alone.
+int rvcmi_ivf_search_blend_expand_sessions(rvcmi_ivf* h, int S, int64_t nq, int d, int64_t skip_rows, const float* feats,
+                                           const rvcmi_session_blend* sess_host, const rvcmi_session_blend* sess_dev, int k, int skip_if_short,
+                                           const float* pitchf, int64_t p_len, float* out, void* stream) {
+    return guarded([&] {
+        const char* who = "search_blend_expand_sessions";
+        if (!feats || !out || !sess_dev) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: null argument", who);
+        if (h && (h->hdr.magic != kMagic || !h->blob)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: not an rvcmi IVF index", who);
+        if (d < 1 || (h && d != h->hdr.d)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: d = %d, the index has %d", who, d, h ? h->hdr.d : 0);
+        SessionBlendPlan plan = {0, 0, 0};
+        if (const char* why = session_blend_check(sess_host, S, nq, skip_rows, p_len, h != nullptr, pitchf != nullptr, &plan))
+            RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: %s", who, why);
+        if (plan.rows > 0 && (k < 1 || k > 8)) RVCMI_FAIL(RVCMI_ERR_INVALID, "%s: k = %d outside [1, 8]", who, k);
+        if (p_len == 0) return;
+        hipStream_t st = (hipStream_t)stream;
+        const int64_t m = nq - skip_rows, rows = plan.rows;
+        auto expand = [&](const float* D, const int64_t* P, const float* vecs, int64_t pos_last, const int* flags) {
+            hipLaunchKernelGGL(k_blend_expand_sessions, dim3((unsigned)nq, (unsigned)S), dim3(256), 0, st, feats, D, P, vecs, d, k, pos_last,
+                               sess_dev, plan.active, flags, skip_if_short, nq, skip_rows, pitchf, p_len, 2, out);
+        };
+        if (!h) {  // no index: every session is expanded un-blended, on the caller's current device
+            expand(nullptr, nullptr, nullptr, 0, nullptr);
+            HIP_CHECK(hipGetLastError());
+            return;
+        }
+        DeviceGuard dg(h->device);
+        if (rows > 0) {
+            reserve(h, rows);
+            if (rows > h->bank_cap_rows) {
+                h->bank_q.alloc((size_t)rows * d * 4);
+                h->bank_cap_rows = rows;
+            }
+            if (plan.active > h->bank_cap_S) {
+                h->bank_flags.alloc((size_t)plan.active * 4);
+                h->bank_cap_S = plan.active;
+            }
+            hipLaunchKernelGGL(k_gather_session_rows, dim3((unsigned)m, (unsigned)S), dim3(256), 0, st, feats, nq, skip_rows, d, sess_dev, plan.active,
+                               h->bank_q.as<float>());
+            search(h, rows, h->bank_q.as<float>(), k, h->Dtmp.as<float>(), h->Itmp.as<int64_t>(), st);
+            hipLaunchKernelGGL(k_session_short, dim3((unsigned)plan.active), dim3(256), 0, st, (const int64_t*)h->Itmp.as<int64_t>(), m * k,
+                               h->bank_flags.as<int>());
+        }
+        h->prof.launch("ivf_blend_x2", 2.0 * rows * k * d, (double)rows * d * 4 * (1 + k) + (double)S * p_len * d * 4, st, [&] {
+            expand((const float*)h->Dtmp.as<float>(), rows > 0 ? (const int64_t*)h->P.as<int64_t>() : nullptr, h->vecs(), h->hdr.pos_last,
+                   (const int*)h->bank_flags.as<int>());
         });
         HIP_CHECK(hipGetLastError());
     });

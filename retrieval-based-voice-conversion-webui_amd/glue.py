@@ -26,6 +26,8 @@ results are bit-equal to a single-stream call on its row:
     nr_stitch_batch(...) / masked_write_batch(...) / gate_ring_plan(nn, n_fft, hop, shift, tail)   per-session noise reduction (gate.TorchGateBank)
     rmvpe_f0_ragged(salience [R, 360], ((first_row, n, p_len, key), ...))     rmvpe_f0 of many packed sequences, a key each, in two launches
     input_gate_batch(block [S, blk], rms_buffer [S, 4 zc], dst [S, blk + 2 zc], zc, cut_a, cut_b)   the GUI's input gate (gui.py:950-963)
+    retrieve_blend_expand_sessions(feats, index, index_rates, pitchf, protects, p_len, skip_rows) / envelope_mix_sessions(..., rates) /
+    input_gate_sessions(..., threholds)                                        the same three with their control per session
 
 All take and return CUDA (ROCm) tensors and enqueue on the current stream; a CPU tensor raises (no fallback).
 """
@@ -662,6 +664,182 @@ def input_gate_batch(block: torch.Tensor, rms_buffer: torch.Tensor, dst: torch.T
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().rvcmi_glue_input_gate_batch(S, _lib.ptr(block), bs, _lib.ptr(rms_buffer), rs, _lib.ptr(dst), ds, zc, blk, float(cut_a),
                                                           float(cut_b), _lib.ptr(scratch), _lib.stream_ptr(dev)))
+    return dst
+
+
+# ---- the realtime controls per session (RealtimeBank's index_rate / protect / rms_mix_rate / threhold sliders) ----------------------------
+# Each entry takes its per-session values twice (rvcmi.h): a host array that the library checks, and the same bytes on the device that the
+# kernels read.  The plans below are pure host functions; the device copy of a plan is kept until the values change (the pattern of
+# RealtimeBank._mask), so an unchanged bank step uploads nothing.
+
+def session_blend_plan(index_rates, protects, has_index: bool, has_pitchf: bool):
+    """Per session ``(index_rate, protect, slot, protect_on)`` of ``retrieve_blend_expand_sessions``: a session is searched and blended iff
+    there is an index and its rate is not 0 (``retrieve_blend_expand``'s rule), and then ``slot`` is its position among those that are (else
+    -1); its protect mix applies iff there is a pitchf and its protect is below 0.5.  No device needed."""
+    rates, protects = [float(r) for r in index_rates], [float(p) for p in protects]
+    if len(rates) != len(protects) or not rates:
+        raise ValueError("index_rates and protects must hold one value per session (got %d / %d)" % (len(rates), len(protects)))
+    out, nxt = [], 0
+    for r, p in zip(rates, protects):
+        if not (np.isfinite(r) and np.isfinite(p)):
+            raise ValueError("index_rate / protect must be finite (got %r / %r)" % (r, p))
+        blend, on = bool(has_index) and r != 0, bool(has_pitchf) and p < 0.5
+        out.append((r if blend else 0.0, p if on else 1.0, nxt if blend else -1, 1 if on else 0))
+        nxt += 1 if blend else 0
+    return out
+
+
+def session_mix_plan(rms_mix_rates):
+    """Per session ``(exponent, on)`` of ``envelope_mix_sessions``: ``float32(1 - rate)`` computed in double and rounded once, as the scalar
+    entry does, and on iff ``rate < 1`` (gui.py:1024)."""
+    out = []
+    for r in rms_mix_rates:
+        r = float(r)
+        if not np.isfinite(r):
+            raise ValueError("rms_mix_rate must be finite (got %r)" % (r,))
+        out.append((float(np.float32(1.0 - r)), 1 if r < 1 else 0))
+    if not out:
+        raise ValueError("rms_mix_rates must hold one value per session")
+    return out
+
+
+def session_gate_plan(threholds):
+    """Per session ``(cut_a, cut_b, on)`` of ``input_gate_sessions``: on iff ``threhold > -60`` (gui.py:950), the cutoffs those of
+    ``realtime.input_gate_cutoffs`` (0, 0 for a session that is off)."""
+    from .realtime import input_gate_cutoffs
+
+    out = []
+    for t in threholds:
+        t = float(t)
+        if not np.isfinite(t):
+            raise ValueError("threhold must be finite (got %r)" % (t,))
+        out.append(input_gate_cutoffs(t) + (1,) if t > -60 else (0.0, 0.0, 0))
+    if not out:
+        raise ValueError("threholds must hold one value per session")
+    return out
+
+
+_SESSION_ROWS: dict = {}   # (device index, struct, plan) -> (host array, its bytes on the device)
+_SESSION_ROWS_KEEP = 16
+session_rows_uploads = 0   # how often a plan went to the device (tests read it)
+
+
+def _session_rows(struct, plan, dev):
+    """``plan`` (a list of per-session field tuples) as an array of ``struct`` on the host and the same bytes on ``dev``; cached per plan."""
+    global session_rows_uploads
+    key = (_lib.device_index(dev), struct.__name__, tuple(plan))
+    hit = _SESSION_ROWS.get(key)
+    if hit is None:
+        arr = (struct * len(plan))(*[struct(*row) for row in plan])
+        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+        while len(_SESSION_ROWS) >= _SESSION_ROWS_KEEP:
+            _SESSION_ROWS.pop(next(iter(_SESSION_ROWS)))
+        hit = _SESSION_ROWS[key] = (arr, raw.to(dev))
+        session_rows_uploads += 1
+    return hit
+
+
+def retrieve_blend_expand_sessions(feats: torch.Tensor, index, index_rates, pitchf: Optional[torch.Tensor] = None, protects=None,
+                                   p_len: Optional[int] = None, realtime_guard: bool = True, skip_rows: int = 0) -> torch.Tensor:
+    """``retrieve_blend_expand_batch`` with an ``index_rate`` and a ``protect`` per session: ``feats`` [S, nq, d] -> [S, p_len, d].  Row ``s``
+    equals ``retrieve_blend_expand(feats[s:s+1], index, index_rates[s], pitchf[s], protects[s], p_len, realtime_guard, skip_rows)`` bit for
+    bit.  Only the sessions whose rate is not 0 contribute rows to the one search (none: no search); a session whose rate is 0 comes out as
+    the bits of its input rows; the guard stays per session.  ``index`` may be None (a protect per session without an index).  The launch
+    count depends on neither ``S`` nor on which sessions blend."""
+    dev = _lib.on_gpu(feats, "feats")
+    if feats.dim() != 3 or feats.shape[0] < 1:
+        raise ValueError("feats must be [S, nq, d] with S >= 1")
+    S, nq, d = int(feats.shape[0]), int(feats.shape[1]), int(feats.shape[2])
+    p_len = 2 * nq if p_len is None else min(int(p_len), 2 * nq)
+    protects = [1.0] * S if protects is None else list(protects)
+    index_rates = list(index_rates)
+    if len(index_rates) != S or len(protects) != S:
+        raise ValueError("index_rates / protects must hold %d values, got %d / %d" % (S, len(index_rates), len(protects)))
+    f = feats.to(torch.float32).contiguous()
+    plan = session_blend_plan(index_rates, protects, index is not None, pitchf is not None)
+    pf = None
+    if any(row[3] for row in plan):
+        if pitchf.dim() != 2 or pitchf.shape[0] != S or pitchf.shape[1] < p_len:
+            raise ValueError("pitchf must be [%d, >= %d], got %s" % (S, p_len, tuple(pitchf.shape)))
+        pf = pitchf[:, :p_len].to(dev, torch.float32).contiguous()
+    active = sum(1 for row in plan if row[2] >= 0)
+    h = max(0, min(int(skip_rows), nq))
+    host, on_dev = _session_rows(_lib.SessionBlend, plan, dev)
+    out = torch.empty(S, p_len, d, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        handle = None
+        if index is not None:
+            if d != index.d:
+                raise ValueError("index mistatch")  # the reference's message (pipeline.py:128)
+            if _lib.device_index(index.device) != _lib.device_index(dev):
+                raise _lib.RvcmiError("the index lives on %s, the features on %s: read the index on the pipeline's device "
+                                      "(read_index(path, device=...))" % (index.device, dev))
+            if active:
+                index.reserve(active * (nq - h))
+            handle = index._h
+        _lib.check(_lib.lib().rvcmi_ivf_search_blend_expand_sessions(handle, S, nq, d, h, _lib.ptr(f), C.cast(host, C.c_void_p), _lib.ptr(on_dev), 8,
+                                                                     1 if realtime_guard else 0, _lib.ptr(pf), p_len, _lib.ptr(out),
+                                                                     _lib.stream_ptr(dev)))
+    return out.to(feats.dtype)
+
+
+def envelope_mix_sessions(input_wav: torch.Tensor, infer_wav: torch.Tensor, zc: int, rms_mix_rates) -> torch.Tensor:
+    """``envelope_mix_batch`` with a ``rms_mix_rate`` per session, IN PLACE on ``infer_wav`` [S, n] (returned): row ``s`` equals
+    ``envelope_mix`` with its own rate bit for bit; the row of a session whose rate is 1 or more is not written.  Three launches whatever
+    ``S`` and whichever sessions mix (none when no session does)."""
+    dev = _lib.on_gpu(infer_wav, "infer_wav")
+    S, n, ws = bank_rows(infer_wav, "infer_wav")
+    Si, ni, ins = bank_rows(input_wav, "input_wav", dev)
+    if Si != S:
+        raise ValueError("infer_wav has %d sessions, input_wav %d" % (S, Si))
+    if ni < n:
+        raise ValueError("input_wav has %d samples, infer_wav %d" % (ni, n))
+    zc = int(zc)
+    if zc < 1:
+        raise ValueError("zc must be positive")
+    plan = session_mix_plan(rms_mix_rates)
+    if len(plan) != S:
+        raise ValueError("rms_mix_rates must hold %d values, got %d" % (S, len(plan)))
+    host, on_dev = _session_rows(_lib.SessionMix, plan, dev)
+    scratch = torch.empty(S * 2 * (1 + n // zc), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_envelope_mix_sessions(S, _lib.ptr(input_wav), ins, _lib.ptr(infer_wav), ws, n, zc, C.cast(host, C.c_void_p),
+                                                               _lib.ptr(on_dev), _lib.ptr(scratch), _lib.stream_ptr(dev)))
+    return infer_wav
+
+
+def input_gate_sessions(block: torch.Tensor, rms_buffer: torch.Tensor, dst: torch.Tensor, zc: int, threholds,
+                        scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``input_gate_batch`` with a ``threhold`` per session (the arguments are its: ``block`` [S, blk], ``rms_buffer`` [S, 4 zc], ``dst``
+    [S, blk + 2 zc]).  A session with ``threhold > -60`` equals ``realtime.input_gate`` with its own threshold bit for bit.  A session at or
+    below -60 ends as the stream that does not call the gate: the last ``blk`` samples of its ``dst`` row are the raw block, the ``2 zc`` in
+    front of them and its ``rms_buffer`` row are not touched.  Three launches whatever ``S`` and whichever sessions gate.  Returns ``dst``."""
+    dev = _lib.on_gpu(block, "block")
+    S, blk, bs = bank_rows(block, "block")
+    Sr, nr, rs = bank_rows(rms_buffer, "rms_buffer", dev)
+    Sd, nd, ds = bank_rows(dst, "dst", dev)
+    zc = int(zc)
+    if Sr != S or Sd != S:
+        raise ValueError("block, rms_buffer and dst must hold the same number of sessions")
+    per = input_gate_scratch_floats(zc, blk)
+    if per == 0:
+        raise _lib.RvcmiError("input_gate_sessions: a block of %d samples must be a whole number (>= 1) of hops of zc = %d >= 1 samples" % (blk, zc),
+                              code=_lib.ERR_INVALID)
+    if nr != 4 * zc or nd != blk + 2 * zc:
+        raise ValueError("rms_buffer must be [S, %d] and dst [S, %d], got %s / %s" % (4 * zc, blk + 2 * zc, tuple(rms_buffer.shape), tuple(dst.shape)))
+    if S > 1 and (rs < nr or ds < nd):
+        raise ValueError("the rows of rms_buffer / dst overlap")
+    plan = session_gate_plan(threholds)
+    if len(plan) != S:
+        raise ValueError("threholds must hold %d values, got %d" % (S, len(plan)))
+    host, on_dev = _session_rows(_lib.SessionGate, [row + (0,) for row in plan], dev)
+    if scratch is None:
+        scratch = torch.empty(S * per, device=dev, dtype=torch.float32)
+    elif scratch.dtype != torch.float32 or scratch.device != dev or not scratch.is_contiguous() or scratch.numel() < S * per:
+        raise ValueError("scratch must be a contiguous float32 tensor of at least %d elements on %s" % (S * per, dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rvcmi_glue_input_gate_sessions(S, _lib.ptr(block), bs, _lib.ptr(rms_buffer), rs, _lib.ptr(dst), ds, zc, blk,
+                                                             C.cast(host, C.c_void_p), _lib.ptr(on_dev), _lib.ptr(scratch), _lib.stream_ptr(dev)))
     return dst
 
 

@@ -277,6 +277,35 @@ class RealtimeVC:
         return audio.squeeze()
 
 
+class SessionSliders:
+    """The hot-update controls a bank keeps per session (gui.py:666-681): for each name a list [S] whose entries are a session's own value
+    or ``None`` (the session follows the bank-wide value).  Host only: no device, no library."""
+
+    NAMES = ("index_rate", "protect", "rms_mix_rate", "threhold")
+
+    def __init__(self, sessions: int, names=NAMES):
+        self.S = int(sessions)
+        self.own = {n: [None] * self.S for n in names}
+
+    def set(self, name: str, i: int, v) -> None:
+        """``IndexError`` for a session outside the bank, ``ValueError`` for a value that is not finite; ``None`` returns the session to the
+        bank-wide value."""
+        i = int(i)
+        if not 0 <= i < self.S:
+            raise IndexError("session %d of %d" % (i, self.S))
+        if v is not None and not math.isfinite(float(v)):
+            raise ValueError("%s must be finite (got %r)" % (name, v))
+        self.own[name][i] = None if v is None else float(v)
+
+    def values(self, name: str, bank_value) -> list:
+        """Every session's effective value under the bank-wide ``bank_value``."""
+        return [bank_value if v is None else v for v in self.own[name]]
+
+    def differs(self, name: str, bank_value) -> bool:
+        """Does some session's effective value differ from the bank-wide one?  (Only then does a bank leave its bank-wide code path.)"""
+        return any(v is not None and v != bank_value for v in self.own[name])
+
+
 class RealtimeVCBatch:
     """``RealtimeVC`` for a bank of ``S`` live sessions that share the model, the index, ``index_rate`` and ``protect``; each has its
     own pitch cache and speaker id.  One ``infer`` is one block of EVERY session: one roll of the ``[S, 1024]`` caches, one
@@ -287,7 +316,11 @@ class RealtimeVCBatch:
     shifted bank decodes every session to its own ``return_length2`` in one ``net_g.infer`` (``return_length2`` = the list: a ragged
     partial decode) and brings the rows back to ``return_length * (tgt_sr // 100)`` samples with one ``SincResampleRagged`` launch; with
     every shift zero it issues exactly the launches it issues without the feature.  The bank-wide forms -- the constructor's
-    ``formant_shift`` and the one-argument ``set_formant`` -- serve 0 only."""
+    ``formant_shift`` and the one-argument ``set_formant`` -- serve 0 only.
+
+    ``index_rate`` and ``protect`` may also be set per session: ``set_session_index_rate(i, rate)`` / ``set_session_protect(i, protect)`` (or
+    ``infer(..., index_rates=[...], protects=[...])``); a session without its own value follows the bank-wide one, and while none differs
+    ``infer`` issues the calls it issues without the feature."""
 
     def __init__(self, net_g, sessions: int, index=None, index_rate: float = 0.0, device="cuda:0", if_f0: int = 1, tgt_sr: int = 48000,
                  formant_shift: float = 0.0, window: int = 160, cache_size: int = 1024):
@@ -306,9 +339,27 @@ class RealtimeVCBatch:
         self.formants = [0.0] * self.S   # semitones per session (the GUI's slider: -2 .. 2)
         self._rl2_host, self._rl2 = None, None
         self._resample = SincResampleRagged(self.tgt_sr // 100, self.device)
+        self.sliders = SessionSliders(self.S, ("index_rate", "protect"))   # a session's own index_rate / protect; None follows the bank-wide value
 
     def set_index_rate(self, new_index_rate):
         self.index_rate = float(new_index_rate)
+
+    def set_session_index_rate(self, i: int, rate) -> None:
+        """Session ``i``'s ``index_rate`` (rtrvc.py:130-132 per session; ``None``: follow the bank-wide one); takes effect at the next block.
+        The session is searched and blended iff there is an index and its rate is above 0, the rule ``RealtimeVC`` applies to its scalar."""
+        self.sliders.set("index_rate", i, rate)
+
+    def set_session_protect(self, i: int, protect) -> None:
+        """Session ``i``'s ``protect`` (``None``: follow the ``protect`` argument of ``infer``); its protect mix applies iff it is below 0.5
+        and the model has f0 (rtrvc.py:224)."""
+        self.sliders.set("protect", i, protect)
+
+    def session_controls(self, protect: float):
+        """-> (index_rates, protects, differs): every session's effective values under the bank-wide ``index_rate`` and ``protect``, and whether
+        any of them is not the bank-wide one (only then does ``infer`` leave ``glue.retrieve_blend_expand_batch``)."""
+        sl = self.sliders
+        return (sl.values("index_rate", self.index_rate), sl.values("protect", float(protect)),
+                sl.differs("index_rate", self.index_rate) or sl.differs("protect", float(protect)))
 
     def set_formant(self, new_formant):
         if new_formant != 0:
@@ -338,10 +389,13 @@ class RealtimeVCBatch:
 
     def infer(self, feats: torch.Tensor, n_input_samples: int, block_frame_16k: int, skip_head: int, return_length: int,
               pitch: Optional[torch.Tensor] = None, pitchf: Optional[torch.Tensor] = None, protect: float = 1.0, sid=0,
-              formants=None) -> torch.Tensor:
+              formants=None, index_rates=None, protects=None) -> torch.Tensor:
         """``feats`` [S, n, d] (HuBERT of every session's rolling window), ``pitch`` / ``pitchf`` [S, m] (the estimator's output per
         session; ``None`` for a model without f0), ``sid``: one id or ``S`` of them, ``formants``: ``S`` shifts that replace
-        ``self.formants`` (``None`` keeps them).  Returns the block's waveforms [S, L]; row ``i`` is what ``RealtimeVC.infer`` gives
+        ``self.formants`` (``None`` keeps them); ``index_rates`` / ``protects`` likewise replace the sessions' own values (an entry that is
+        ``None`` follows the bank-wide ``index_rate`` / ``protect``).  While no session differs from the bank-wide values the retrieval is
+        the one ``glue.retrieve_blend_expand_batch`` call; else ``glue.retrieve_blend_expand_sessions``, which searches only the sessions
+        that blend.  Returns the block's waveforms [S, L]; row ``i`` is what ``RealtimeVC.infer`` gives
         session ``i`` alone (with ``formant_shift = formants[i]``), to the batch invariance of ``net_g.infer``.  A session
         whose shift leaves ``upp_res == tgt_sr // 100`` (32 kHz, +0.05) gets the first ``L`` samples of the longer block the solo object returns."""
         if feats.dim() != 3 or feats.shape[0] != self.S:
@@ -350,6 +404,13 @@ class RealtimeVCBatch:
             if len(formants) != self.S:
                 raise ValueError("formants must hold %d values, got %d" % (self.S, len(formants)))
             self.formants = list(formants)
+        for name, got in (("index_rates", index_rates), ("protects", protects)):
+            if got is not None:
+                if len(got) != self.S:
+                    raise ValueError("%s must hold %d values, got %d" % (name, self.S, len(got)))
+                for i, v in enumerate(got):
+                    self.sliders.set(name[:-1], i, v)
+        rates, prots, per_session = self.session_controls(protect)
         feats = torch.cat((feats, feats[:, -1:, :]), 1)                                   # rtrvc.py:163
         p_len = int(n_input_samples) // self.window                                       # :189
         shifted = any(f != 0 for f in self.formants)
@@ -359,7 +420,7 @@ class RealtimeVCBatch:
             rl2s, upp_res = [g[1] for g in geo], [g[2] for g in geo]
             if rl2s != self._rl2_host:   # uploaded when a session's slider moves, not per block
                 self._rl2_host, self._rl2 = rl2s, torch.tensor(rl2s, dtype=torch.float32, device=self.device)[:, None]
-        pf = pitchf if (protect < 0.5 and pitch is not None and pitchf is not None) else None   # :224
+        pf = pitchf if (min(prots) < 0.5 and pitch is not None and pitchf is not None) else None   # :224 (some session's protect applies)
         if pf is not None and (pf.dim() != 2 or pf.shape[1] != p_len):
             raise RuntimeError("protect < 0.5 needs pitchf of exactly p_len = %d frames per session (got %s), as the reference's broadcast at "
                                "infer/lib/rtrvc.py:229 does" % (p_len, tuple(pf.shape)))
@@ -381,10 +442,15 @@ class RealtimeVCBatch:
             # :216-219; per session the same float32 product and quotient as the solo object's python scalars
             cache_pitch = self.pitch[:, -p_len:]
             cache_pitchf = self.pitchf[:, -p_len:] * (self._rl2 if shifted else return_length2) / return_length
-        use_index = self.index is not None and self.index_rate > 0                        # :167
-        phone = glue.retrieve_blend_expand_batch(feats, self.index if use_index else None, self.index_rate if use_index else 0.0,
-                                                 pf, protect if pf is not None else 1.0, p_len, realtime_guard=True,
-                                                 skip_rows=int(skip_head) // 2)            # :167-185, 221-233
+        if per_session:   # :167-185, 221-233 with each session's own scalars: it blends iff index and rate > 0, protect-mixes iff protect < 0.5 and f0
+            phone = glue.retrieve_blend_expand_sessions(feats, self.index, [r if r > 0 else 0.0 for r in rates], pf,
+                                                        prots if pf is not None else [1.0] * self.S, p_len, realtime_guard=True,
+                                                        skip_rows=int(skip_head) // 2)
+        else:
+            use_index = self.index is not None and self.index_rate > 0                    # :167
+            phone = glue.retrieve_blend_expand_batch(feats, self.index if use_index else None, self.index_rate if use_index else 0.0,
+                                                     pf, protect if pf is not None else 1.0, p_len, realtime_guard=True,
+                                                     skip_rows=int(skip_head) // 2)        # :167-185, 221-233
         lengths = self._lengths.get(p_len)
         if lengths is None:
             lengths = self._lengths[p_len] = torch.full((self.S,), p_len, dtype=torch.long, device=self.device)
@@ -720,13 +786,16 @@ def rvc_infer_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, ret
 
 
 def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_head, return_length, f0method, protect: float = 1.0,
-                        keys=None, sids=None, rt: Optional[RealtimeVCBatch] = None, formants=None) -> torch.Tensor:
+                        keys=None, sids=None, rt: Optional[RealtimeVCBatch] = None, formants=None, index_rates=None,
+                        protects=None) -> torch.Tensor:
     """``rvc_infer_hip`` for ``S`` sessions of one voice: ``input_wav`` [S, n16] (every session's rolling 16 kHz window) -> [S, L].
     HuBERT runs once on the ``[S, n16]`` batch (equal lengths: the padding mask is all-false), the RMVPE network once on the
     ``[S, .]`` f0 windows, and the salience decode of all sessions in one ``glue.rmvpe_f0_ragged`` call, each with its own key (``keys``,
     default the object's ``f0_up_key``; ``sids`` default 0).  ``rt``: the ``RealtimeVCBatch`` that holds the sessions' pitch caches (default: one kept on
     the object).  ``formants``: a formant shift per session (default: the ones ``rt`` holds); session ``s``'s f0 key is then
-    ``keys[s] - formants[s]`` (rtrvc.py:208) and ``rt.infer`` decodes and resamples it by its own factor.  Not served, and refused: a
+    ``keys[s] - formants[s]`` (rtrvc.py:208) and ``rt.infer`` decodes and resamples it by its own factor.  ``index_rates`` / ``protects``: an
+    ``index_rate`` / ``protect`` per session (default: the ones ``rt`` holds; an entry that is ``None`` follows the object's ``index_rate`` /
+    the ``protect`` argument), handed to ``rt.infer``.  Not served, and refused: a
     precomputed ``(pitch, pitchf)`` tuple, an index object that is not ours, a bank-wide ``formant_shift`` on the object."""
     from .ivf import IVFFlatHIP
 
@@ -804,7 +873,7 @@ def rvc_infer_batch_hip(self, input_wav: torch.Tensor, block_frame_16k, skip_hea
             pitch = torch.cat([g[0].to(self.device) for g in got], 0)
             pitchf = torch.cat([g[1].to(self.device) for g in got], 0)
     return rt.infer(feats, int(input_wav.shape[1]), block_frame_16k, skip_head, return_length, pitch=pitch, pitchf=pitchf, protect=protect,
-                    sid=sids, formants=formants)
+                    sid=sids, formants=formants, index_rates=index_rates, protects=protects)
 
 
 class RealtimeBank:
@@ -841,7 +910,16 @@ class RealtimeBank:
     The formant slider is per session and switchable between blocks like the key: ``set_formant(i, shift)``.  A shifted bank decodes each
     session to its own length in the one ``net_g.infer`` and resamples all rows in one launch (``RealtimeVCBatch``); that adds three
     launches to the block whatever ``S`` and however many distinct shifts there are, and with every shift zero the step issues exactly the
-    launches it issues without this feature.  A custom ``rvc.infer_batch`` is passed ``formants=`` only while some session's shift is non-zero."""
+    launches it issues without this feature.  A custom ``rvc.infer_batch`` is passed ``formants=`` only while some session's shift is non-zero.
+
+    The GUI's remaining hot-update sliders are per session too: ``set_index_rate(i, rate)``, ``set_protect(i, protect)``,
+    ``set_rms_mix_rate(i, rate)`` and ``set_threhold(i, db)`` (``SessionSliders``), each effective at the next block and ``None`` to return to
+    the bank-wide value (``rvc.index_rate`` and the constructor's ``protect`` / ``rms_mix_rate`` / ``threhold``).  While no session differs
+    from the bank-wide value of a control, its step is the bank-wide one above, launch for launch.  Otherwise the step reads the sessions'
+    values from device memory (``glue.input_gate_sessions``, ``glue.envelope_mix_sessions``, ``glue.retrieve_blend_expand_sessions``; uploaded
+    when a slider moves, not per block): gated sessions get ``blk + 2 zc`` gated samples and their own 16 kHz range, the others their raw
+    ``blk``; only the sessions whose ``index_rate`` is above 0 are searched.  The launch count depends on neither ``S`` nor on which sessions
+    are active.  What stays the bank's: the sample rate, the block geometry, ``use_pv``, the model and the index."""
 
     def __init__(self, rvc, sessions: int, samplerate: Optional[int] = None, block_time: float = 0.25, crossfade_time: float = 0.05,
                  extra_time: float = 2.5, threhold: float = -60, rms_mix_rate: float = 0.0, use_pv: bool = False, f0method: str = "rmvpe",
@@ -893,8 +971,29 @@ class RealtimeBank:
         self.keys = [getattr(rvc, "f0_up_key", 0)] * S
         self.sids = [0] * S
         self.formants = [0.0] * S
+        # the GUI's hot-update sliders per session (gui.py:666-681); None follows the bank-wide value (rvc.index_rate, protect, rms_mix_rate, threhold)
+        self.sliders = SessionSliders(S)
         self.vc = None            # the sessions' RealtimeVCBatch (pitch caches), made at the first block of a real rvc object
         self.last_offsets = None  # device int32 [S]
+
+    def set_index_rate(self, i: int, rate) -> None:
+        """Session ``i``'s ``index_rate`` (gui.py:676-679); ``None``: back to the bank-wide ``rvc.index_rate``.  Takes effect at the next block;
+        ``reset(i)`` leaves it as it is, as it leaves the key.  A session blends iff there is an index and its rate is above 0."""
+        self.sliders.set("index_rate", i, rate)
+
+    def set_protect(self, i: int, protect) -> None:
+        """Session ``i``'s ``protect`` (rtrvc.py:221-233); ``None``: back to the bank's ``protect``.  Applies iff below 0.5 and the model has f0."""
+        self.sliders.set("protect", i, protect)
+
+    def set_rms_mix_rate(self, i: int, rate) -> None:
+        """Session ``i``'s ``rms_mix_rate`` (gui.py:1024-1056); ``None``: back to the bank-wide one.  The envelope mix runs for the sessions
+        whose rate is below 1."""
+        self.sliders.set("rms_mix_rate", i, rate)
+
+    def set_threhold(self, i: int, db) -> None:
+        """Session ``i``'s input-gate threshold in dB (gui.py:950-963); ``None``: back to the bank-wide one.  At or below -60 the session is
+        not gated (and its ``rms_buffer`` row stays as it is, as the reference leaves it)."""
+        self.sliders.set("threhold", i, db)
 
     def set_key(self, i: int, key) -> None:
         self.keys[int(i)] = key
@@ -955,8 +1054,13 @@ class RealtimeBank:
 
     def _infer(self) -> torch.Tensor:
         args = (self.input_wav_res, self.block_frame_16k, self.skip_head, self.return_length, self.f0method)
+        sl, bank_rate = self.sliders, getattr(self.rvc, "index_rate", 0.0)
         if hasattr(self.rvc, "infer_batch"):
             fm = {"formants": list(self.formants)} if any(f != 0 for f in self.formants) else {}
+            if sl.differs("index_rate", bank_rate):   # handed on only while some session differs, as formants= is
+                fm["index_rates"] = sl.values("index_rate", bank_rate)
+            if sl.differs("protect", self.protect):
+                fm["protects"] = sl.values("protect", self.protect)
             return self.rvc.infer_batch(*args, keys=list(self.keys), sids=list(self.sids), **fm)
         if self.vc is None or self.vc.net_g is not self.rvc.net_g:
             if getattr(self.rvc, "formant_shift", 0) != 0:
@@ -964,23 +1068,43 @@ class RealtimeBank:
                                  "set_formant(i, shift)" % (self.rvc.formant_shift,))
             self.vc = RealtimeVCBatch(self.rvc.net_g, self.S, index=getattr(self.rvc, "index", None), index_rate=self.rvc.index_rate,
                                       device=self.device, if_f0=self.rvc.if_f0, tgt_sr=self.tgt_sr, window=getattr(self.rvc, "window", 160))
-        return rvc_infer_batch_hip(self.rvc, *args, protect=self.protect, keys=self.keys, sids=self.sids, rt=self.vc, formants=self.formants)
+        return rvc_infer_batch_hip(self.rvc, *args, protect=self.protect, keys=self.keys, sids=self.sids, rt=self.vc, formants=self.formants,
+                                   index_rates=sl.own["index_rate"], protects=sl.own["protect"])
 
     def process(self, blocks) -> torch.Tensor:
         x = np.asarray(blocks, dtype=np.float32)
         if x.ndim != 2 or x.shape != (self.S, self.block_frame):
             raise ValueError("a bank block is [%d, %d] (sessions, samples), got %s" % (self.S, self.block_frame, x.shape))
         blk, blk16, zc = self.block_frame, self.block_frame_16k, self.zc
-        on_device = self.threhold > -60 and self.device_gate
-        if self.threhold > -60 and not on_device:   # the host gate, per session (gui.py:950-963)
+        # the threshold per session: None while every session follows the bank-wide one (then the step is the bank-wide one below), else
+        # which sessions gate (threhold > -60, gui.py:950); a bank whose sessions differ but none of which gates is the ungated bank
+        thr = self.sliders.values("threhold", self.threhold) if self.sliders.differs("threhold", self.threhold) else None
+        gates = None if thr is None or not any(t > -60 for t in thr) else [t > -60 for t in thr]
+        bank_gate = self.threhold > -60 if thr is None else False
+        on_device = bank_gate and self.device_gate
+        if bank_gate and not on_device:   # the host gate, per session (gui.py:950-963)
             x = np.stack([input_gate(x[s], self.rms_buffer[s], self.zc, self.threhold) for s in range(self.S)])
-        m = blk + 2 * zc if on_device else int(x.shape[1])
+        elif gates is not None and not self.device_gate:   # ... with a threshold each: gated rows are blk + 2 zc samples, the others their raw blk
+            rows = np.zeros((self.S, blk + 2 * zc), np.float32)
+            for s in range(self.S):
+                if gates[s]:
+                    rows[s] = input_gate(x[s], self.rms_buffer[s], zc, thr[s])
+                else:
+                    rows[s, 2 * zc:] = x[s]
+            x = rows
+        m = blk + 2 * zc if (on_device or gates is not None) else int(x.shape[1])   # (with a mix of sessions: the gated ones' m)
         self.input_wav[:, :-blk] = self.input_wav[:, blk:].clone()
         xd = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)                       # the block's one host-to-device copy
-        if on_device:   # the raw block went up; the gate of all sessions writes the gated blk + 2 zc samples (three launches whatever S)
+        if on_device or (gates is not None and self.device_gate):
+            # the raw block went up; the gate of all sessions writes the gated blk + 2 zc samples (three launches whatever S)
             if self._gate_scratch is None:
                 self._gate_scratch = torch.empty(self.S * glue.input_gate_scratch_floats(zc, blk), device=self.device, dtype=torch.float32)
-            glue.input_gate_batch(xd, self.rms_buffer, self.input_wav[:, -m:], zc, *input_gate_cutoffs(self.threhold), scratch=self._gate_scratch)
+            if gates is None:
+                glue.input_gate_batch(xd, self.rms_buffer, self.input_wav[:, -m:], zc, *input_gate_cutoffs(self.threhold), scratch=self._gate_scratch)
+            else:   # a threshold each; a session that does not gate gets its raw blk samples and keeps its rms_buffer row
+                glue.input_gate_sessions(xd, self.rms_buffer, self.input_wav[:, -m:], zc, thr, scratch=self._gate_scratch)
+        elif gates is not None:   # gated on the host: blk + 2 zc samples for the gated sessions, the last blk for the others
+            glue.masked_write_batch(self.input_wav, self._mask("gated", gates), xd, self.input_wav_len - m, xd[:, 2 * zc:], self.input_wav_len - blk)
         else:
             self.input_wav[:, -m:] = xd
         self.input_wav_res[:, :-blk16] = self.input_wav_res[:, blk16:].clone()
@@ -997,7 +1121,19 @@ class RealtimeBank:
             res_I = self.resampler.batch(self.input_wav_denoise[:, -blk - 2 * zc:])[:, 160:]
             res = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
             n16 = self.input_wav_res_len
-            glue.masked_write_batch(self.input_wav_res, mask_I, res_I, n16 - int(res_I.shape[1]), res, n16 - int(res.shape[1]))
+            if gates is None:
+                glue.masked_write_batch(self.input_wav_res, mask_I, res_I, n16 - int(res_I.shape[1]), res, n16 - int(res.shape[1]))
+            else:   # three ranges: the gated sessions' m + 2 zc, the ungated ones' blk + 2 zc, and over either the ticked sessions' denoised one
+                res_u = self.resampler.batch(self.input_wav[:, -blk - 2 * zc:])[:, 160:]
+                long_ = self._mask("gated_not_I", [g and not i for g, i in zip(gates, self.I_noise_reduce)])
+                glue.masked_write_batch(self.input_wav_res, long_, res, n16 - int(res.shape[1]), res_u, n16 - int(res_u.shape[1]))
+                glue.masked_write_batch(self.input_wav_res, mask_I, res_I, n16 - int(res_I.shape[1]))
+        elif gates is not None:   # the 16 kHz range differs per session with m: both resamples, each session's own range written (also when every
+            # session gates: the launches do not depend on which sessions do)
+            res = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
+            res_u = self.resampler.batch(self.input_wav[:, -blk - 2 * zc:])[:, 160:]
+            n16 = self.input_wav_res_len
+            glue.masked_write_batch(self.input_wav_res, self._mask("gated", gates), res, n16 - int(res.shape[1]), res_u, n16 - int(res_u.shape[1]))
         else:
             self.input_wav_res[:, -160 * (m // zc + 1):] = self.resampler.batch(self.input_wav[:, -m - 2 * zc:])[:, 160:]
         infer_wav = self._infer()
@@ -1017,13 +1153,17 @@ class RealtimeBank:
             glue.masked_write_batch(self.output_buffer, self._mask("O", self.O_noise_reduce), rolled, 0)
         if self.gate_O is not None:
             self.gate_O.forward(infer_wav, self.output_buffer, blk, blk, self.O_noise_reduce, out=infer_wav if any_O else None)
-        if self.rms_mix_rate < 1:
+        mix = self.sliders.values("rms_mix_rate", self.rms_mix_rate) if self.sliders.differs("rms_mix_rate", self.rms_mix_rate) else None
+        if self.rms_mix_rate < 1 if mix is None else any(r < 1 for r in mix):
             n = int(infer_wav.shape[1])
             src = self.input_wav[:, self.extra_frame: self.extra_frame + n]
             if any_I:   # the envelope's source is per session: the denoised input where I is ticked
                 src = src.clone()
                 glue.masked_write_batch(src, mask_I, self.input_wav_denoise[:, self.extra_frame: self.extra_frame + n], 0)
-            glue.envelope_mix_batch(src, infer_wav, zc, self.rms_mix_rate)
+            if mix is None:
+                glue.envelope_mix_batch(src, infer_wav, zc, self.rms_mix_rate)
+            else:   # a rate each: the sessions at 1 or above keep their rows
+                glue.envelope_mix_sessions(src, infer_wav, zc, mix)
         out, self.last_offsets = glue.sola_batch(infer_wav, self.sola_buffer, self.fade_in_window, self.fade_out_window, blk,
                                                  self.sola_search_frame, use_pv=self.use_pv)
         return out
